@@ -32,6 +32,31 @@ if ROOT not in sys.path:
 
 FP64_MATRIX_PEAK_TFLOPS = 78.6   # MI355X FP64 vector/matrix peak
 HBM_PEAK_GBS = 8000.0            # /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: at most this much on disk in all (.npy headers included)
+
+
+def dump_outputs(d, sol, res):
+    """--dump-outputs: what the last timed step handed its caller — the optimised map (`solve_resident` + `download`) and its
+    Result — as float64 DIR/<name>.npy. Wall-clock fields of the Result are left out: they differ from run to run. If the arrays
+    exceed DUMP_BUDGET_BYTES together, the largest keep a fixed, seeded sample of their rows (ascending row order)."""
+    n = min(int(res.iterations), len(res.cost_trace))
+    arrays = {"kf_pose": sol.kf_pose, "kf_speed_bias": sol.kf_speed_bias, "lm_pos": sol.lm_pos,
+              "cost_trace": np.array(res.cost_trace[:n]), "radius_trace": np.array(res.radius_trace[:n]),
+              "accepted_trace": np.array(res.accepted_trace[:n]),
+              "result": np.array([res.iterations, res.accepted, res.termination, res.initial_cost, res.final_cost])}
+    arrays = {k: np.ascontiguousarray(v, np.float64) for k, v in arrays.items()}
+    excess = sum(a.nbytes + 4096 for a in arrays.values()) - DUMP_BUDGET_BYTES   # (4 KiB: an upper bound of one file's header)
+    for k in sorted(arrays, key=lambda k: -arrays[k].nbytes):
+        if excess <= 0:
+            break
+        a = arrays[k]
+        row = a.nbytes // max(len(a), 1)
+        keep = max(len(a) - -(-excess // row), 0)
+        arrays[k] = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        excess -= a.nbytes - arrays[k].nbytes
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, f"{k}.npy"), a)
 
 
 def cpu_baseline(prob, strategy: int, iterations: int, truth_xyz, reps: int = 3):
@@ -204,7 +229,11 @@ def main():
                     "configuration the north star names for the scaling curve; ~70 s of map generation + upload, 3 + 1 steps)")
     ap.add_argument("--sustain-s", type=float, default=8.0, help="after the timed region, repeat the same steps back to back for about this many seconds, "
                     "un-timed in `value` and reported as `sustained`: long enough for an external GPU-utilisation sampler to see the device busy (0: off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (optimised poses, "
+                    "speed-bias, landmarks, cost trace, result) as float64 DIR/<name>.npy, at most 64 MB in all; the inputs are the same on every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: launch the ranks ourselves, exactly as the driver does (one process per GPU over RCCL)
@@ -256,6 +285,25 @@ def main():
     dt = time.perf_counter() - t0
     dt, iters_all = distrib.aggregate(dt, iters, ctx, sharded)
     shard_stats = ctx.shard_stats()
+    shard = prob
+
+    def assemble(s, store):
+        """The optimised full map from this rank's download (sharded: the ranks' pieces gathered through `store` and merged)."""
+        if not sharded:
+            return s
+        pieces = distrib.gather_solutions(s, rank, world, store) if world > 1 else [(s.kf_pose, s.kf_speed_bias, s.lm_pos)]
+        parts = []
+        for r, (kp, ks, lp) in enumerate(pieces):
+            q = distrib.shard_problem(full, plan, r) if r != rank else shard
+            q = q.copy(); q.kf_pose[:] = kp; q.kf_speed_bias[:] = ks; q.lm_pos[:] = lp
+            parts.append(q)
+        return distrib.merge_solution(full, plan, parts)
+
+    if args.dump_outputs:   # the last timed step's solution, before any other step runs on the context (own store keys: gathered again below)
+        from torch.distributed import PrefixStore
+        sol_timed = assemble(ctx.download(), PrefixStore("timed/", keep[0]) if world > 1 else None)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, sol_timed, res)
     # sustained leg (not `value`): the same step repeated for --sustain-s seconds, so that a sampler outside this process (rocm-smi every
     # few seconds) sees the GPU busy — the timed region above is 20 steps x ~35 ms and falls between two samples
     sustained = None
@@ -275,15 +323,8 @@ def main():
     prof = ctx.profile()
     ctx.set_profiling(False)
     lay = ctx.layout()
-    sol = ctx.download()
-    if sharded:  # assemble the optimised map from the ranks' pieces (small: poses, speed-bias, landmark positions)
-        pieces = distrib.gather_solutions(sol, rank, world, keep[0]) if world > 1 else [(sol.kf_pose, sol.kf_speed_bias, sol.lm_pos)]
-        parts = []
-        for r, (kp, ks, lp) in enumerate(pieces):
-            q = distrib.shard_problem(full, plan, r) if r != rank else prob
-            q = q.copy(); q.kf_pose[:] = kp; q.kf_speed_bias[:] = ks; q.lm_pos[:] = lp
-            parts.append(q)
-        sol = distrib.merge_solution(full, plan, parts)
+    # sharded: assemble the optimised map from the ranks' pieces (small: poses, speed-bias, landmark positions)
+    sol = assemble(ctx.download(), keep[0] if world > 1 else None)
     prob = full
 
     if rank == 0:
