@@ -30,7 +30,7 @@ class Options(C.Structure):
         ("min_relative_decrease", C.c_double), ("function_tolerance", C.c_double),
         ("parameter_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
         ("sigma_a", C.c_double), ("sigma_g", C.c_double), ("sigma_aw", C.c_double), ("sigma_gw", C.c_double),
-        ("gravity", C.c_double), ("verbose", C.c_int32), ("reserved", C.c_int32),
+        ("gravity", C.c_double), ("verbose", C.c_int32), ("shard_policy", C.c_int32),
     ]
 
 
@@ -224,6 +224,8 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("shard_plan", [OP, PP, C.c_int32, C.POINTER(C.c_void_p), _ip, _ip, _ip], C.c_int32)
         d("nd_plan_owner", [C.c_void_p, _ip, _ip], None)
         d("nd_plan_ranks", [C.c_void_p, _ip], None)
+        d("nd_plan_rank_flops", [C.c_void_p, _dp], C.c_int32)
+        d("nd_plan_exchange", [C.c_void_p, C.POINTER(C.c_int64)], None)
         d("group_create", [C.c_int32, C.POINTER(C.c_void_p)])
         d("group_destroy", [C.c_void_p], None)
         d("group_abort", [C.c_void_p], None)

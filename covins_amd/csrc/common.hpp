@@ -359,6 +359,21 @@ struct DenseBatch {
 };
 void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int npad, hipStream_t st, CholAux& ax, int tstop = -1,
                               bool solve = true, DenseBatch bt = DenseBatch());  // tstop >= 0 (even): eliminate tile columns [0, tstop) only
+// Partial factorisation of a batch of DISTRIBUTED top fronts (shard policy 1, k_front.hip): every front is the sum of the ranks' copies. Per
+// 256-column panel P, on the one stream `st`: exchange(P) (the caller's pack -> all-reduce -> unpack of the panel's column block and right-hand-
+// side rows), the panel's factorisation and the substitution of every row below (redundant: the same kernels and the same data on every rank;
+// the right-hand-side update below the panel on the lead rank only), then the rank-256 trailing update of the tiles this rank owns
+// (tri[P]: tile list in GemmArgs::tri form, relative to tile t0 + 2). No look-ahead, no second stream: nothing waits across the all-reduce.
+struct DistPanels {
+  int np = 0;                                  // panels with an exchange and an update list
+  const int* const* tri = nullptr;             // [np] device tile lists (nullptr: nothing owned)
+  const int* tri_cnt = nullptr;                // [np] host: entries (incl. the XCD padding)
+  bool lead = false;                           // applies the right-hand-side update below the panel
+  void (*exchange)(void* ctx, int P) = nullptr;
+  void* ctx = nullptr;
+};
+void dense_cholesky_dist(double* S, double* b, double* Linv, int* flag, int npad, hipStream_t st, CholAux& ax, int tstop, DenseBatch bt,
+                         const DistPanels& d);
 int bwd_pipe_min_tiles();    // fronts of at least this many interior tiles: backward substitution as one pipelined launch (k_chol.hip)
 int bwd_front_max_tiles();   // fronts of at most this many interior tiles: backward substitution in one launch (k_chol.hip)
 void dense_backward_solve(double* S, double* b, double* Linv, int npad, hipStream_t st, int tfact, int tend, DenseBatch bt = DenseBatch());
@@ -449,6 +464,10 @@ struct NdLevel {
   int ext_countA = 0;                     // ... of which the first ext_countA tiles lie in the fronts' first 256 rows (first panel)
   int split_ta = 0;                       // border tiles (128) of this level's fronts that reach their parents' first 256 columns (max)
   int ext2_first = 0, ext2_count = 0, ext2_countA = 0;   // ... for their TOP children (top levels of a sharded solve only)
+  // shard policy 1 (distributed top), per 256-column panel of a top level: its exchange entries in NdDev::dist_ent (first entry, column tiles,
+  // right-hand-side segments of 256 rows) and the trailing-update tiles this rank owns in NdDev::dist_tri (first, count incl. the XCD padding)
+  std::vector<int> dx_first, dx_nt, dx_nr, dt_first, dt_cnt;
+  std::vector<const int*> dt_dev;                // device addresses of the owned-tile lists (set at upload)
 };
 struct NdDev {
   bool active = false;
@@ -489,6 +508,13 @@ struct NdDev {
   std::vector<int> h_vnode, h_voff, h_vord, h_vown, h_ndepth, h_nI, h_abase, h_fidx, h_own_dims, h_st_dims, h_own_g, h_st_g, h_gidx, h_cptr, h_cidx, h_cptr2,
       h_cidx2, h_inv_off, h_inv, h_rhs_node, h_ext, h_top_var, h_top_r, h_top_g, h_bb_off, h_bb;
   std::vector<long long> h_ntab;
+  // shard policy 1 (distributed top): exchange entries {front, tile row | first row, tile column | rows, 0 tile | 1 right-hand side} per panel, the
+  // owned trailing-update tiles per panel, the reduce buffer (largest panel), what one linear solve all-reduces, and whether this rank leads
+  // (adds the damping of the top unknowns and the right-hand-side updates below the panels once)
+  bool dist = false, dist_lead = false;
+  int* dist_ent = nullptr; int* dist_tri = nullptr; double* dist_buf = nullptr;
+  std::vector<int> h_dist_ent, h_dist_tri;
+  size_t dist_buf_elems = 0, dist_solve_elems = 0;
   size_t M_elems = 0, rhs_elems = 0, linv_elems = 0;
   double plan_flops = 0;                   // flops of one factorisation of the plan's fronts (NdHostPlan::flops: dense count on the real sizes)
 };

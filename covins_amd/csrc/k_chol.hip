@@ -973,6 +973,43 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
   dense_backward_solve(S, b, Linv, npad, st, T, T, bt);
 }
 
+// Distributed top fronts (shard policy 1; common.hpp: DistPanels). One stream, panel after panel: exchange -> factorisation of the panel's
+// diagonal block (+ y_P) -> substitution of every row below (the right-hand-side rows below on the lead rank only: the others' copies keep
+// their part of the sum) -> rank-256 update of the owned trailing tiles. The same kernels and the same K ranges as dense_cholesky_solve_raw.
+void dense_cholesky_dist(double* S, double* b, double* Linv, int* flag, int npad, hipStream_t st, CholAux& ax, int tstop, DenseBatch bt,
+                         const DistPanels& d) {
+  const int nbt = bt.n > 0 ? bt.n : 1;
+  const int T = npad / kTile;
+  const size_t ld = (size_t)npad;
+  const size_t lds_gemm = (size_t)2 * kTile * LDT * sizeof(double);
+  static std::atomic<unsigned long long> attr_seen{0};
+  if (first_use_on_device(attr_seen)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_abt<MODE_SYRK_TRI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gemm);
+  ax.init();
+  const int NP = (T + 1) / 2;
+  const int Pstop = std::min((tstop >= 0 && tstop < T) ? tstop / 2 : NP, d.np);
+  auto kd = [&](int Pp) {
+    const int full = std::min(2, T - 2 * Pp) * kTile;
+    if (bt.own_max <= 0) return full;
+    return std::max(0, std::min(full, ((bt.own_max - 2 * Pp * kTile + 31) / 32) * 32));
+  };
+  for (int P = 0; P < Pstop; ++P) {
+    const int t0 = 2 * P, w = (T - t0 >= 2) ? 2 : 1, tb = t0 + 2;
+    ax.mark(st, P);
+    if (d.exchange != nullptr) d.exchange(d.ctx, P);
+    const int nbp = bt.own_max > 0 ? std::max(0, std::min(8 * w, (bt.own_max - t0 * kTile + 15) / 16)) : -1;
+    if (bt.plist != nullptr) launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, st, bt.tab, nbp, bt.own_dims, bt.plist, bt.pbig_h[P], bt.psmall_h[P]);
+    else launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, st, bt.tab, nbp);
+    if (T > tb) launch_trsm_sub(S, ld, t0, w, tb, T, Linv, d.lead ? b : nullptr, npad, nbt, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, st, true, bt.tab, nbp, bt.own_dims);
+    const int count = d.tri_cnt[P];
+    if (T > tb && kd(P) > 0 && count > 0 && d.tri[P] != nullptr) {
+      GemmArgs g{S, ld, t0 * kTile, kd(P), tb * kTile, tb * kTile, tb * kTile, T - tb, nullptr, nullptr, nullptr, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, nullptr, bt.tab, bt.own_dims};
+      g.tri = d.tri[P];
+      if (count <= kQuarterMax) hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_TRI, 64, 64>), dim3(count, 1, 4), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), st, g);
+      else hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(count, 1), dim3(256), lds_gemm, st, g);
+    }
+  }
+}
+
 // Fronts of at most this many interior tiles run their whole backward substitution in ONE launch (k_bwd_front: the last workgroup solves the
 // interior tiles one after the other). Measured in round 5 on the corrected 5-agent map, whose upper levels hold fronts of 5-6 tiles: the
 // serial part costs ~15 us per tile (dependent loads of one workgroup), a launch per tile 8.6 — 4: 212.8 it/s, 8: 211.8, 16: 200.0.

@@ -314,6 +314,71 @@ void nd_tables(const NdHostPlan& hp, const int* pos_kf, int D, int rank, NdDev& 
         for (int i = dev.lev[l].first; i < dev.lev[l].first + dev.lev[l].n; ++i)
           for (int q = 0; q < dev.h_own_dims[i]; ++q) dev.h_tree_fill.push_back(dev.h_gidx[dev.h_own_g[i] + q]);
   }
+  // ---- shard policy 1 (distributed top): per panel of every top level, what is exchanged and which trailing-update tiles this rank applies
+  dev.dist = sh && hp.shard_policy == 1;
+  dev.dist_lead = rank == 0;
+  dev.h_dist_ent.clear(); dev.h_dist_tri.clear(); dev.dist_buf_elems = 0; dev.dist_solve_elems = 0;
+  if (dev.dist) {
+    const int world = std::max(hp.world, 1);
+    for (int l = Hs; l < nlev; ++l) {
+      NdLevel& L = dev.lev[l];
+      const int np = L.nI / 256, T = L.ntot / kTile, tI = L.nI / kTile;
+      L.dx_first.assign(np, 0); L.dx_nt.assign(np, 0); L.dx_nr.assign(np, 0); L.dt_first.assign(np, 0); L.dt_cnt.assign(np, 0);
+      for (int P = 0; P < np; ++P) {
+        const int t0 = 2 * P, tb = t0 + 2;
+        // exchange: the live tiles of the panel's real tile columns, from the diagonal down, then 256 right-hand-side rows, of every front whose
+        // interior reaches the panel (the others hold identity padding there, the same on every rank)
+        L.dx_first[P] = (int)dev.h_dist_ent.size() / 4;
+        for (int pass = 0; pass < 2; ++pass)
+          for (int k = 0; k < L.n; ++k) {
+            const int i = L.first + k, nIr = L.live_h[2 * k], nO = L.live_h[2 * k + 1], Tn = ld[i] / kTile;
+            if (t0 >= nIr) continue;
+            auto live = [&](int t) { return t < nIr || (t >= tI && t - tI < nO); };
+            if (pass == 1) {
+              const int rows = std::min(256, ld[i] - t0 * kTile);
+              dev.h_dist_ent.insert(dev.h_dist_ent.end(), {i, t0 * kTile, rows, 1});
+              ++L.dx_nr[P];
+              continue;
+            }
+            for (int c = t0; c < std::min(t0 + 2, nIr); ++c)
+              for (int t = c; t < Tn; ++t)
+                if (live(t)) { dev.h_dist_ent.insert(dev.h_dist_ent.end(), {i, t, c, 0}); ++L.dx_nt[P]; }
+          }
+        const size_t elems = (size_t)L.dx_nt[P] * kTile * kTile + (size_t)L.dx_nr[P] * 256;
+        dev.dist_buf_elems = std::max(dev.dist_buf_elems, elems);
+        dev.dist_solve_elems += elems;
+        // owned trailing-update tiles (i, j), j <= i, relative to tile tb: tile row owner by nd_tile_owner on the front's compact rows (real interior
+        // tiles, then border tiles); XCD-balanced as k_chol.hip's build_list (whole 8x8 supertiles of a front to the shortest of 8 queues, interleaved)
+        std::vector<int> q[8];
+        for (int k = 0; k < L.n; ++k) {
+          const int i = L.first + k, nIr = L.live_h[2 * k], nO = L.live_h[2 * k + 1], node = order[i];
+          if (t0 >= nIr) continue;
+          auto live = [&](int t) { return t < nIr || (t >= tI && t - tI < nO); };
+          auto mine = [&](int t) { return nd_tile_owner(node, t < tI ? t : nIr + (t - tI), world) == rank; };
+          const int nt = T - tb, Ts = (nt + 7) / 8;
+          for (int si = 0; si < Ts; ++si)
+            for (int sj = 0; sj <= si; ++sj) {
+              std::vector<int> grp;
+              for (int a = 8 * si; a < std::min(nt, 8 * si + 8); ++a) {
+                if (!live(tb + a) || !mine(tb + a)) continue;
+                for (int b = 8 * sj; b < std::min(a + 1, 8 * sj + 8); ++b) if (live(tb + b)) grp.push_back((k << 20) | (a << 10) | b);
+              }
+              if (grp.empty()) continue;
+              int best = 0;
+              for (int x = 1; x < 8; ++x) if (q[x].size() < q[best].size()) best = x;
+              q[best].insert(q[best].end(), grp.begin(), grp.end());
+            }
+        }
+        size_t longest = 0;
+        for (int x = 0; x < 8; ++x) longest = std::max(longest, q[x].size());
+        L.dt_first[P] = (int)dev.h_dist_tri.size();
+        L.dt_cnt[P] = (int)(8 * longest);
+        dev.h_dist_tri.resize(dev.h_dist_tri.size() + 8 * longest, -1);
+        for (int x = 0; x < 8; ++x) for (size_t e = 0; e < q[x].size(); ++e) dev.h_dist_tri[L.dt_first[P] + 8 * e + x] = q[x][e];
+      }
+    }
+    dev.dist_solve_elems += 2 * dev.h_top_g.size();   // gradient and diag(J^T J) of the top unknowns
+  }
   dev.active = true;
 }
 
@@ -576,16 +641,45 @@ __global__ __launch_bounds__(256) void k_nd_top_pack(DevProblem P, const int* __
   }
 }
 // sharded solve: trust-region damping of the top unknowns, applied to the all-reduced top fronts with the all-reduced
-// diag(J^T J) (k_finalize_diag leaves them out: every rank holds only its part of their rows before the exchange)
+// diag(J^T J) (k_finalize_diag leaves them out: every rank holds only its part of their rows before the exchange).
+// Distributed top (shard policy 1): the fronts are still sums over the ranks' copies — the lead rank adds the damping, the others
+// clear the row of an unknown without any observation (the lead's 1 on the diagonal is then the sum)
 __global__ __launch_bounds__(256) void k_nd_top_damp(DevProblem P, const int* __restrict__ top_var, const int* __restrict__ top_r,
-                                                      const int* __restrict__ top_g, int ntop, const int* __restrict__ rhs_off, double mu) {
+                                                      const int* __restrict__ top_g, int ntop, const int* __restrict__ rhs_off, double mu, int lead) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ntop) return;
   const int v = top_var[i], r = top_r[i];
   const double h = P.hdiag[top_g[i]];
   double* d = nd_entry(P, v, v, r, r);
-  if (h == 0.0) { *d = 1.0; P.nd_rhs[rhs_off[P.nd_vnode[v]] + P.nd_voff[v] + r] = 0.0; }
-  else { const double c = covdev::clamp_diag(h); *d += mu * c * c; }
+  if (h == 0.0) { *d = lead ? 1.0 : 0.0; P.nd_rhs[rhs_off[P.nd_vnode[v]] + P.nd_voff[v] + r] = 0.0; }
+  else if (lead) { const double c = covdev::clamp_diag(h); *d += mu * c * c; }
+}
+// Distributed top (shard policy 1): one panel's column tiles and right-hand-side rows of a batch of top fronts <-> the contiguous reduce
+// buffer, dir 0 pack | 1 unpack. Entries {front, tile row | first row, tile column | rows, 0 tile | 1 right-hand side}: the first ntile are
+// 128x128 tiles (buffer [ntile][128][128], full squares at the front's own leading dimension), the rest right-hand-side segments of up to
+// 256 rows (buffer [.][256] behind the tiles). One workgroup per entry, 16-byte accesses along the rows.
+// The interior padding rows of a front carry an identity diagonal on EVERY rank's copy (k_nd_zero): only the lead rank's copy counts.
+__global__ __launch_bounds__(256) void k_nd_panel_xfer(DevProblem P, const int4* __restrict__ ent, int ntile, double* __restrict__ buf,
+                                                        const int* __restrict__ rhs_node, const int* __restrict__ own_dims, int dir, int lead) {
+  const int4 e = ent[blockIdx.x];
+  if ((int)blockIdx.x < ntile) {
+    const size_t ld = (size_t)P.nd_ntab[2 * e.x + 1];
+    double* M = P.nd_M + P.nd_ntab[2 * e.x] + (size_t)e.y * kTile * ld + (size_t)e.z * kTile;
+    double* B = buf + (size_t)blockIdx.x * kTile * kTile;
+    const int pad0 = (dir == 0 && !lead && e.y == e.z && e.y * kTile < P.nd_nI[e.x]) ? own_dims[e.x] - e.y * kTile : kTile;   // first padding row of the tile
+    for (int q = threadIdx.x; q < kTile * kTile / 2; q += 256) {
+      const int r = q / (kTile / 2), c2 = 2 * (q - r * (kTile / 2));
+      double2* m = reinterpret_cast<double2*>(M + (size_t)r * ld + c2);
+      double2* b = reinterpret_cast<double2*>(B + (size_t)r * kTile + c2);
+      if (dir == 0) *b = r < pad0 ? *m : double2{0.0, 0.0};
+      else *m = *b;
+    }
+  } else {
+    double* R = P.nd_rhs + rhs_node[e.x] + e.y;
+    double* B = buf + (size_t)ntile * kTile * kTile + (size_t)(blockIdx.x - ntile) * 256;
+    const int t = threadIdx.x;
+    if (t < e.z) { if (dir == 0) B[t] = R[t]; else R[t] = B[t]; }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
@@ -742,7 +836,7 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
   };
   // ---- the subtrees of this rank (single GPU: the whole tree), level by level
   run_levels(0, ltop, false);
-  if (ltop < nlev) {
+  if (ltop < nlev && !nd.dist) {
     // ---- agent-sharded solve: the top fronts so far hold THIS rank's residuals and subtrees only. One
     //      all-reduce over [top fronts | their right-hand sides | grad, hdiag of the top unknowns] (contiguous), then the
     //      damping of the top unknowns; from here on every rank runs the top of the tree redundantly, with no further exchange.
@@ -764,9 +858,52 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
     if (nd.ntop > 0) {
       hipLaunchKernelGGL(k_nd_gh, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 1);
       hipLaunchKernelGGL(k_nd_top_damp, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_var, (const int*)nd.top_r, (const int*)nd.top_g, nd.ntop,
-                         (const int*)nd.rhs_node, mu);
+                         (const int*)nd.rhs_node, mu, 1);
     }
     run_levels(ltop, nlev, true);
+  } else if (ltop < nlev) {
+    // ---- distributed top (shard policy 1): the top fronts stay SUMS over the ranks' copies. One all-reduce of gradient and
+    //      diag(J^T J) of the top unknowns, the damping on the lead rank's copy; then per top level the extend-add of the top children (partial
+    //      sums added to partial sums) and the panels one at a time — each panel's column block and right-hand-side rows all-reduced when it
+    //      becomes the panel (dense_cholesky_dist). Everything of the top runs on this one stream: the subtree levels above joined it, so no
+    //      gate on another stream waits for anything enqueued behind an all-reduce.
+    for (int l = ltop; l < nlev; ++l) extend(l, false, 0, st);
+    double* gh = P.nd_rhs + nd.gh_off;
+    if (nd.ntop > 0) {
+      hipLaunchKernelGGL(k_nd_gh, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 0);
+      if (ax.reduce != nullptr) ax.reduce(ax.reduce_ctx, gh, 2 * (size_t)nd.ntop, 0, st);
+      hipLaunchKernelGGL(k_nd_gh, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 1);
+      hipLaunchKernelGGL(k_nd_top_damp, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_var, (const int*)nd.top_r, (const int*)nd.top_g, nd.ntop,
+                         (const int*)nd.rhs_node, mu, nd.dist_lead ? 1 : 0);
+    }
+    struct XCtx { const DevProblem* P; NdDev* nd; const NdLevel* L; CholAux* ax; hipStream_t st; };
+    auto xchg = [](void* vc, int Pp) {
+      XCtx& x = *static_cast<XCtx*>(vc);
+      const NdLevel& L = *x.L;
+      const int nt = L.dx_nt[Pp], ne = nt + L.dx_nr[Pp];
+      if (ne == 0 || x.ax->reduce == nullptr) return;
+      const int4* ent = reinterpret_cast<const int4*>(x.nd->dist_ent) + L.dx_first[Pp];
+      const size_t n = (size_t)nt * kTile * kTile + (size_t)L.dx_nr[Pp] * 256;
+      hipLaunchKernelGGL(k_nd_panel_xfer, dim3(ne), dim3(256), 0, x.st, *x.P, ent, nt, x.nd->dist_buf, (const int*)x.nd->rhs_node, (const int*)x.nd->own_dims, 0,
+                         x.nd->dist_lead ? 1 : 0);
+      x.ax->reduce(x.ax->reduce_ctx, x.nd->dist_buf, n, 0, x.st);
+      hipLaunchKernelGGL(k_nd_panel_xfer, dim3(ne), dim3(256), 0, x.st, *x.P, ent, nt, x.nd->dist_buf, (const int*)x.nd->rhs_node, (const int*)x.nd->own_dims, 1,
+                         x.nd->dist_lead ? 1 : 0);
+    };
+    for (int l = ltop; l < nlev; ++l) {
+      extend(l, true, 0, st);
+      const NdLevel& L = nd.lev[l];
+      ax.mark(st, -3);
+      if (L.n > 0) {
+        XCtx xc{&P, &nd, &L, &ax, st};
+        DistPanels d;
+        d.np = (int)L.dx_nt.size(); d.tri = L.dt_dev.data(); d.tri_cnt = L.dt_cnt.data(); d.lead = nd.dist_lead; d.exchange = xchg; d.ctx = &xc;
+        DenseBatch bt = batch(l);
+        bt.beta0 = nullptr; bt.beta0_off = nullptr;   // (top fronts: every border tile is cleared and read)
+        dense_cholesky_dist(P.nd_M, P.nd_rhs + L.rhs_off, P.nd_Linv + L.linv_off, P.flag, L.ntot, st, ax, L.nI / kTile, bt, d);
+      }
+      ax.mark(st, -4);
+    }
   }
   auto tree_launch = [&](int l_hi, int l_lo, bool form64) {   // levels l_hi .. l_lo (downwards) in one launch
     BwdTreeLevel tl[kBwdTreeMax];

@@ -425,6 +425,16 @@ bool nd_plan_build(int K, bool vi, int nchains, const int* chain_ptr, int npairs
 
 double nd_shard_cost(const NdHostPlan& hp, int world) {
   const int nn = hp.nnodes;
+  double chain = 0.0;
+  for (int l = 0; l < hp.nlev; ++l) chain += (hp.lev_nI[l] / 256) * 140e-6 + 40e-6;
+  if (hp.shard_policy == 1) {
+    NdShardAcct a;
+    nd_shard_account(hp, world, a);
+    double busiest = 0.0;
+    for (double f : a.rank_fl) busiest = std::max(busiest, f);
+    constexpr double kCollLatency = 30e-6;   // ASSUMED per small all-reduce (not measured on xGMI)
+    return busiest / 30e12 + chain + (world > 1 ? 2.0 * (world - 1) / world * a.bytes / 150e9 + a.collectives * kCollLatency : 0.0);
+  }
   double top_fl = 0.0, exch = 0.0;
   std::vector<double> rank_fl(std::max(world, 1), 0.0);
   for (int n = 0; n < nn; ++n) {
@@ -434,23 +444,22 @@ double nd_shard_cost(const NdHostPlan& hp, int world) {
   }
   double busiest = 0.0;
   for (double f : rank_fl) busiest = std::max(busiest, f);
-  double chain = 0.0;
-  for (int l = 0; l < hp.nlev; ++l) chain += (hp.lev_nI[l] / 256) * 140e-6 + 40e-6;
   return (top_fl + busiest) / 30e12 + chain + (world > 1 ? 2.0 * (world - 1) / world * exch / 150e9 : 0.0);
 }
 
-void nd_shard_assign(NdHostPlan& hp, int world, double top_cap_bytes) {
+// The top grows from `top` (an ancestor-closed set: the roots, or policy 1's seed) downwards, heaviest subtree first, until there are at least
+// `world` subtrees and none outweighs 1.25x a rank's fair share (within the cap on the top's fronts); the subtrees are then dealt by LPT.
+static void nd_shard_grow(NdHostPlan& hp, int world, double top_cap_bytes, std::vector<char>& top, double top_bytes) {
   const int nn = hp.nnodes;
   hp.node_rank.assign(nn, -1);
   hp.nsub = 0;
+  hp.world = world;
   std::vector<double> w(nn, 0.0), sub(nn, 0.0);
   for (int n = 0; n < nn; ++n) { const double m = hp.own_dims[n], b = hp.st_dims[n]; w[n] = m * m * m / 3.0 + m * m * b + m * b * b + 1.0; }
   for (int n = nn - 1; n >= 0; --n) { sub[n] += w[n]; if (hp.parent[n] >= 0) sub[hp.parent[n]] += sub[n]; }  // children have higher indices
-  std::vector<char> top(nn, 0);
   std::vector<int> cand;
-  double top_bytes = 0.0;
   for (int n = 0; n < nn; ++n)
-    if (hp.parent[n] < 0) { top[n] = 1; top_bytes += 8.0 * (double)hp.own_dims[n] * hp.own_dims[n]; for (int c : hp.child[n]) cand.push_back(c); }
+    if (top[n]) for (int c : hp.child[n]) if (!top[c]) cand.push_back(c);
   for (int it = 0; it < 256; ++it) {
     if (cand.empty()) break;
     std::sort(cand.begin(), cand.end(), [&](int a, int b) { return sub[a] != sub[b] ? sub[a] > sub[b] : a < b; });
@@ -486,6 +495,80 @@ void nd_shard_assign(NdHostPlan& hp, int world, double top_cap_bytes) {
   for (int n = 0; n < nn; ++n) {  // parents come first: a node below a dealt subtree root inherits its rank
     if (top[n]) { hp.node_rank[n] = -1; continue; }
     hp.node_rank[n] = owner[n] >= 0 ? owner[n] : hp.node_rank[hp.parent[n]];
+  }
+}
+
+void nd_shard_assign(NdHostPlan& hp, int world, double top_cap_bytes) {
+  hp.shard_policy = 0;
+  std::vector<char> top(hp.nnodes, 0);
+  double top_bytes = 0.0;
+  for (int n = 0; n < hp.nnodes; ++n)
+    if (hp.parent[n] < 0) { top[n] = 1; top_bytes += 8.0 * (double)hp.own_dims[n] * hp.own_dims[n]; }
+  nd_shard_grow(hp, world, top_cap_bytes, top, top_bytes);
+}
+
+void nd_shard_assign_dist(NdHostPlan& hp, int world, double top_cap_bytes, int min_order) {
+  hp.shard_policy = 1;
+  const int nn = hp.nnodes;
+  std::vector<char> top(nn, 0);
+  for (int n = 0; n < nn; ++n)
+    if (hp.parent[n] < 0 || hp.own_dims[n] + hp.st_dims[n] >= min_order)
+      for (int a = n; a >= 0 && !top[a]; a = hp.parent[a]) top[a] = 1;   // with all its ancestors
+  double top_bytes = 0.0;
+  for (int n = 0; n < nn; ++n) if (top[n]) top_bytes += 8.0 * (double)(hp.own_dims[n] + hp.st_dims[n]) * (double)(hp.own_dims[n] + hp.st_dims[n]);
+  nd_shard_grow(hp, world, top_cap_bytes, top, top_bytes);
+}
+
+void nd_shard_account(const NdHostPlan& hp, int world, NdShardAcct& out) {
+  const int nn = hp.nnodes;
+  world = std::max(world, 1);
+  out = NdShardAcct();
+  out.rank_fl.assign(world, 0.0);
+  const bool sh = !hp.node_rank.empty();
+  auto is_top = [&](int n) { return !sh || hp.node_rank[n] < 0; };
+  double top_own = 0.0, rhs_top = 0.0, tiles = 0.0;
+  std::vector<int> toph(nn, 0);
+  for (int n = nn - 1; n >= 0; --n) if (is_top(n)) for (int c : hp.child[n]) if (is_top(c)) toph[n] = std::max(toph[n], toph[c] + 1);
+  std::vector<int> lev_panels;
+  for (int n = 0; n < nn; ++n) {
+    const double m = hp.own_dims[n], b = hp.st_dims[n];
+    if (!is_top(n)) { out.rank_fl[hp.node_rank[n]] += m * m * m / 3.0 + m * m * b + m * b * b; continue; }
+    top_own += m;
+    const int nIr = (hp.own_dims[n] + 127) / 128, nO = (hp.st_dims[n] + 127) / 128, np = (hp.own_dims[n] + 255) / 256;
+    rhs_top += 2.0 * (256.0 * np + 128.0 * nO);
+    if (hp.shard_policy != 1) {
+      for (double& f : out.rank_fl) f += m * m * m / 3.0 + m * m * b + m * b * b;
+      const int lo2 = 2 * np;   // live lower tiles the replicated top exchanges (nd_tables: h_top_tiles)
+      tiles += 0.5 * (double)(lo2 + nO) * (lo2 + nO + 1);
+      continue;
+    }
+    if ((int)lev_panels.size() <= toph[n]) lev_panels.resize(toph[n] + 1, 0);
+    lev_panels[toph[n]] = std::max(lev_panels[toph[n]], np);
+    // compact tile rows: the real interior tiles, then the border tiles
+    auto rows = [&](int q) { return q < nIr ? std::min(128, hp.own_dims[n] - 128 * q) : std::min(128, hp.st_dims[n] - 128 * (q - nIr)); };
+    const int Tn = nIr + nO;
+    for (int P = 0; P < np; ++P) {
+      const double k = std::min(256, hp.own_dims[n] - 256 * P), below = m - 256.0 * P - k + b;
+      const double chain = k * k * k / 3.0 + k * k * below;   // the panel's factorisation + the substitution of every row below: on every rank
+      for (double& f : out.rank_fl) f += chain;
+      for (int c = 2 * P; c < std::min(2 * P + 2, nIr); ++c) tiles += Tn - c;   // the panel's column block, from the diagonal down
+      double left = 0.0;   // rows of the trailing block above tile row q
+      for (int q = 2 * P + 2; q < Tn; ++q) {
+        const double r = rows(q);
+        if (r <= 0) continue;
+        out.rank_fl[nd_tile_owner(n, q, world)] += k * r * (2.0 * left + r);
+        left += r;
+      }
+    }
+  }
+  if (hp.shard_policy == 1) {
+    out.collectives = 1;   // gradient and diag(J^T J) of the top unknowns
+    for (int p : lev_panels) out.collectives += p;
+    out.bytes = 8.0 * (tiles * 128.0 * 128.0 + 0.0) + 8.0 * 2.0 * top_own;
+    for (int n = 0; n < nn; ++n) if (is_top(n)) out.bytes += 8.0 * 256.0 * ((hp.own_dims[n] + 255) / 256);   // right-hand-side rows of every panel
+  } else {
+    out.collectives = 1;
+    out.bytes = 8.0 * (tiles * 128.0 * 128.0 + rhs_top + 2.0 * top_own);
   }
 }
 

@@ -28,6 +28,7 @@ struct NdHostPlan {
   // every rank holds its front, the ranks' contributions are all-reduced once per linear solve). Empty: single GPU.
   std::vector<int> node_rank;
   int nsub = 0;                                      // subtrees hanging below the top nodes (the units dealt to the ranks)
+  int world = 0, shard_policy = 0;                   // ranks of the assignment | 0: replicated top | 1: distributed top (nd_shard_assign_dist)
   int top_mode = 0, leaf = 0, group_frac100 = 300;   // which candidate nd_plan_build kept: cut of a region of >= 3 agents (0 one cover | 1 two groups) | leaf size | 100 x the two groups' balance bound
   double flops = 0;                                  // partial factorisations, dense count on the real (unpadded) sizes
   size_t front_elems = 0;                            // sum over levels of batch x ntot^2
@@ -46,9 +47,22 @@ bool nd_plan_build(int K, bool vi, int nchains, const int* chain_ptr, int npairs
 // first) until there are at least `world` subtrees and none outweighs 1.25x a rank's fair share — but never beyond 48 MiB of top
 // fronts (every top front is all-reduced and factorised on every rank): rather fewer subtrees than ranks. Deterministic.
 void nd_shard_assign(NdHostPlan& hp, int world, double top_cap_bytes = 48.0 * 1048576.0);
-// what one factorisation costs a rank of a sharded solve, roughly: (replicated top + the busiest rank's subtrees) at 30 TFLOP/s, the serial panel chains of
-// every level, and the ring all-reduce of the top fronts' lower halves at 150 GB/s per link. Compares candidate shard plans (covgpu_shard_plan).
+// Policy 1, "distributed top" (DESIGN.md §7.1): the top is the ancestor-closed set of every node whose front order (own + border) is at least
+// min_order, plus the roots; it grows further, and the subtrees below it are dealt, as in nd_shard_assign. The top fronts are never exchanged
+// whole: they stay sums over the ranks' copies, every 256-column panel is all-reduced once when it becomes the panel, factorised redundantly,
+// and each rank applies the trailing update to the tile rows it owns (nd_tile_owner).
+void nd_shard_assign_dist(NdHostPlan& hp, int world, double top_cap_bytes = 48.0 * 1048576.0, int min_order = 4096);
+// policy 1: the rank that applies the trailing update to tile row q of a top front (q counts the front's real interior tiles, then its border
+// tiles: 128 rows each) — deterministic from the plan; the node id staggers the rows of small fronts over the ranks
+inline int nd_tile_owner(int node, int q, int world) { return world > 0 ? (q + node) % world : 0; }
+// what one factorisation costs a rank of a sharded solve, roughly: the busiest rank's flops (nd_shard_account) at 30 TFLOP/s, the serial panel chains
+// of every level, and the ring all-reduces at 150 GB/s per link — policy 1 adds an ASSUMED 30 us per collective (one per panel of the top; nobody has
+// measured a small all-reduce on xGMI). Compares candidate shard plans (covgpu_shard_plan).
 double nd_shard_cost(const NdHostPlan& hp, int world);
+// host accounting of a shard plan under its policy (covgpu_nd_plan_rank_flops / covgpu_nd_plan_exchange): flops of one factorisation per rank,
+// bytes all-reduced per linear solve and rank, collectives per linear solve. Sizes are the real (unpadded) front orders.
+struct NdShardAcct { std::vector<double> rank_fl; double bytes = 0.0; int collectives = 0; };
+void nd_shard_account(const NdHostPlan& hp, int world, NdShardAcct& out);
 // variable ids -> var_map[old id] (chain positions of one problem -> IR keyframes -> chain positions of a rank's sub-problem)
 void nd_plan_remap(NdHostPlan& hp, const std::vector<int>& var_map);
 

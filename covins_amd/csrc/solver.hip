@@ -403,7 +403,8 @@ extern "C" void covgpu_get_layout(covgpu_context* c, int64_t* out) {
   const DevProblem& P = c->P;
   out[0] = c->sharded ? c->world : 0; out[1] = c->sharded ? c->rank : 0; out[2] = c->nd.ntop;   // ranks | rank | scalar unknowns of the replicated top nodes
   out[3] = (int64_t)c->nd.lev.size() - c->nd.top_lev0;                                          // top levels
-  out[4] = (int64_t)(((c->nd.top_pack != nullptr ? (size_t)c->nd.n_top_tiles * kTile * kTile : c->nd.M_elems - c->nd.M_sub) + c->nd.rhs_top + 2 * (size_t)c->nd.ntop) * sizeof(double)) >> 10;  // KiB all-reduced per linear solve
+  out[4] = c->nd.dist ? (int64_t)((c->nd.dist_solve_elems * sizeof(double)) >> 10)   // distributed top: every panel's exchange + gradient, diag(J^T J) of the top unknowns
+                      : (int64_t)(((c->nd.top_pack != nullptr ? (size_t)c->nd.n_top_tiles * kTile * kTile : c->nd.M_elems - c->nd.M_sub) + c->nd.rhs_top + 2 * (size_t)c->nd.ntop) * sizeof(double)) >> 10;  // KiB all-reduced per linear solve
   out[5] = c->chol.pipe_broken ? -1 : c->chol.gates_on ? 1 : 0;   // stream ordering: 1 device flags | 0 HIP events (COVGPU_GATES=0) | -1 a gate or the backward pipeline timed out: events and the launch-per-tile substitution from then on
   out[6] = P.npad; out[7] = P.npairs; out[8] = P.nepairs; out[9] = P.nchains; out[10] = (int64_t)(c->alloc_bytes >> 20);
   if (P.nd) {  // multifrontal form: nodes, levels, serial 256-column panels (sum of the levels' interior orders / 256), root order, front bytes (MiB)
@@ -632,6 +633,22 @@ extern "C" void covgpu_nd_plan_info(const covgpu_nd_plan* pl, int64_t* out) {
   }
   out[5] = (int64_t)h.front_elems; out[6] = (int64_t)h.flops;
   out[10] = h.top_mode; out[11] = h.leaf; out[12] = h.group_frac100;   // which candidate tree (nd_plan_build): COVGPU_ND_TOP / COVGPU_ND_LEAF / COVGPU_ND_GROUP_FRAC (= out[12] / 100) reproduce it
+  out[13] = h.shard_policy;                                               // shard plans: 0 replicated top | 1 distributed top
+}
+extern "C" int32_t covgpu_nd_plan_rank_flops(const covgpu_nd_plan* pl, double* out) {
+  const NdHostPlan& h = pl->hp;
+  const int world = h.node_rank.empty() ? 1 : std::max(h.world, 1);
+  NdShardAcct a;
+  nd_shard_account(h, world, a);
+  for (int r = 0; r < world; ++r) out[r] = a.rank_fl[r];
+  return world;
+}
+extern "C" void covgpu_nd_plan_exchange(const covgpu_nd_plan* pl, int64_t* out) {
+  const NdHostPlan& h = pl->hp;
+  const int world = h.node_rank.empty() ? 1 : std::max(h.world, 1);
+  NdShardAcct a;
+  nd_shard_account(h, world, a);
+  out[0] = (int64_t)a.bytes; out[1] = a.collectives; out[2] = world; out[3] = h.shard_policy;
 }
 // per node: parent, level, own_ptr / st_ptr [nodes + 1]; variables as 2 * IR keyframe + (0 pose | 1 speed-bias)
 extern "C" void covgpu_nd_plan_arrays(const covgpu_nd_plan* pl, int32_t* parent, int32_t* level, int32_t* own_ptr, int32_t* own_var, int32_t* st_ptr,
@@ -662,6 +679,11 @@ extern "C" int32_t covgpu_shard_plan(const covgpu_options* opt, const covgpu_pro
   // (replicated top + busiest rank's subtrees) at 30 TFLOP/s + the panel chains + the ring all-reduce of the top — is kept. On the corrected 5-agent map the
   // one-separator top is 3 726 unknowns = 61 % of the flops on every rank; the two-groups tree gives two ranks a 1 968-order top (10 %) and, with its two
   // second-level separators opened, four ranks a top of 45 %. COVGPU_SHARD_TREE = 0 / 1 forces the tree, COVGPU_SHARD_CAP_MIB the cap. Deterministic.
+  // shard policy (options, COVGPU_SHARD_POLICY overrides for A/B runs): 0 the top replicated and all-reduced whole | 1 the top distributed — its fronts
+  // stay sums over the ranks, all-reduced a panel at a time (nd_shard_assign_dist)
+  int policy = opt->shard_policy;
+  if (const char* e = getenv("COVGPU_SHARD_POLICY")) policy = atoi(e);
+  if (policy != 0 && policy != 1) { g_err = "covgpu_shard_plan: shard_policy must be 0 or 1"; return 0; }
   covgpu_nd_plan* pl = nullptr;
   {
     const char* e_tree = getenv("COVGPU_SHARD_TREE");
@@ -674,7 +696,8 @@ extern "C" int32_t covgpu_shard_plan(const covgpu_options* opt, const covgpu_pro
       if (nd_plan_create_mode(opt, p, 0, &cand, mode) != COVGPU_OK) continue;
       for (double cap : caps) {
         NdHostPlan trial = cand->hp;
-        nd_shard_assign(trial, world, cap * 1048576.0);
+        if (policy == 1) nd_shard_assign_dist(trial, world, cap * 1048576.0);
+        else nd_shard_assign(trial, world, cap * 1048576.0);
         if (trial.nsub == 0) continue;
         const double cost = nd_shard_cost(trial, world);
         if (pl == nullptr || cost < best_cost) {
@@ -1023,7 +1046,14 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
         RC(dev_alloc(c, &c->d_red, (size_t)SC_COUNT + 2 * (size_t)c->world));
         static const bool pack_on = getenv("COVGPU_SHARD_PACK") == nullptr || atoi(getenv("COVGPU_SHARD_PACK")) != 0;
         nd.n_top_tiles = (int)(nd.h_top_tiles.size() / 3);
-        if (pack_on) {
+        if (nd.dist) {   // distributed top (shard policy 1): per-panel exchange entries, owned trailing-update tiles, one reduce buffer for the largest panel
+          RC(up_or_zero(&nd.dist_ent, nd.h_dist_ent, 4)); RC(up_or_zero(&nd.dist_tri, nd.h_dist_tri, 1));
+          RC(dev_alloc(c, &nd.dist_buf, std::max<size_t>(nd.dist_buf_elems, 1)));
+          for (NdLevel& L : nd.lev) {
+            L.dt_dev.assign(L.dt_cnt.size(), nullptr);
+            for (size_t q = 0; q < L.dt_cnt.size(); ++q) if (L.dt_cnt[q] > 0) L.dt_dev[q] = nd.dist_tri + L.dt_first[q];
+          }
+        } else if (pack_on) {
           RC(dev_upload(c, &nd.top_tiles, nd.h_top_tiles.data(), nd.h_top_tiles.size()));
           RC(dev_alloc(c, &nd.top_pack, (size_t)nd.n_top_tiles * kTile * kTile + nd.rhs_top + 2 * (size_t)nd.ntop));
         }
@@ -1218,6 +1248,20 @@ static void reduce_scalars(covgpu_context* c) {
   hipLaunchKernelGGL(k_shard_scal_unpack, dim3(1), dim3(64), 0, c->st, c->P, (const double*)c->d_red, c->world);
 }
 
+// Distributed top (shard policy 1): a solve issues a collective per panel of the top. A rank that repeated its solve alone after a gate or
+// pipeline time-out (what a sharded context of policy 0 does: solve_any) would pair its reductions with its peers' reductions of other panels —
+// under policy 1 any failure ends the call on EVERY rank: the collective is aborted, the peers' give-up flag raised, an error returned. A failed
+// collective is reported before a gate that timed out (the gate most likely waited behind it).
+static bool dist_sharded(const covgpu_context* c) { return c->sharded && c->shard_plan && c->shard_plan->shard_policy == 1; }
+static int dist_fail(covgpu_context* c) {
+  if (c->reducer) c->reducer->abort();
+  if (c->peer_fail) c->peer_fail->store(1);
+  const std::string why = c->coll_failed ? c->coll_err
+                                         : std::string("a device-flag gate or a hand-over of the backward substitution timed out (the distributed top does not repeat a solve on one rank)");
+  g_err = "sharded solve, rank " + std::to_string(c->rank) + ": " + why;
+  return COVGPU_ERR_NO_DEVICE;
+}
+
 // Host wait for the iteration just enqueued. One GPU: hipStreamSynchronize. Sharded: polled, so that a collective that never
 // completes (a peer died, gave up before its first collective, or never arrived) ends in an ERROR after COVGPU_COLL_TIMEOUT_S
 // (default 300 s) instead of a hang; RCCL's asynchronous communicator errors and the give-up flag of an in-process multi-GPU call
@@ -1245,6 +1289,7 @@ static int wait_iteration(covgpu_context* c) {
   }
   HIPCHK(hipStreamSynchronize(c->st));
   HIPCHK(hipGetLastError());  // a failed kernel launch anywhere in the batch just drained surfaces here
+  if (dist_sharded(c) && (c->coll_failed || c->chol.gate_failed())) return dist_fail(c);
   if (c->chol.gate_failed()) {   // a device-flag gate between two streams gave up (CholAux::wait): what this iteration computed is not ordered
     g_err = "solve: a device-flag gate between the context's streams timed out (COVGPU_GATE_TIMEOUT_S; COVGPU_GATES=0 selects HIP events)";
     return COVGPU_ERR_GATE_TIMEOUT;
@@ -1348,6 +1393,7 @@ static int solve_impl_dev(covgpu_context* c, const covgpu_options* opt, covgpu_r
       if (got) {
         for (int i = 0; i < TR_COUNT; ++i) h[i] = box[i];
         HIPCHK(hipGetLastError());
+        if (dist_sharded(c) && (c->coll_failed || c->chol.gate_failed())) { HIPCHK(hipStreamSynchronize(c->st)); return dist_fail(c); }
         if (c->chol.gate_failed()) { HIPCHK(hipStreamSynchronize(c->st)); g_err = "solve: a device-flag gate between the context's streams timed out"; return COVGPU_ERR_GATE_TIMEOUT; }
       } else {
         HIPCHK(hipMemcpyAsync(h, P.tr, TR_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->st));

@@ -12,7 +12,9 @@ replicated. Every rank
      `Group` of host threads for VIRTUAL ranks on one GPU, which is how the sharded path is verified on single-GPU boxes) and
      uploads it;
   3. runs the same device-side trust-region loop; per iteration the library enqueues four all-reduces on its own stream
-     (top fronts + right-hand sides + gradient rows once per linear solve, three small scalar exchanges);
+     (top fronts + right-hand sides + gradient rows once per linear solve, three small scalar exchanges); with
+     `opt.shard_policy = 1` (distributed top) the top fronts are instead all-reduced a 256-column panel at a time and their
+     trailing updates split over the ranks (DESIGN.md §7.1);
   4. `merge_solution` assembles the optimised map from the ranks' pieces.
 No Python code sits on the data path: the collectives are issued by libcovgpu (solver.hip: RcclReducer / GroupReducer).
 """
@@ -74,7 +76,24 @@ def shard_plan(prob: FlatProblem, opt: Options, world: int) -> Optional[ShardPla
     lib.covgpu_nd_plan_ranks(h, capi.iptr(nr))
     plan = ShardPlan(h, int(world), int(n), lr[:prob.L].copy(), ir[:prob.I].copy(), er[:prob.E].copy(), pr, sr, nr)
     plan.top_mode, plan.leaf, plan.group_frac = int(info[10]), int(info[11]), int(info[12]) / 100.0   # which candidate tree was kept (COVGPU_ND_TOP / COVGPU_ND_LEAF / COVGPU_ND_GROUP_FRAC reproduce it on one GPU)
+    plan.shard_policy = int(info[13])   # 0 replicated top | 1 distributed top (opt.shard_policy, COVGPU_SHARD_POLICY overrides)
     return plan
+
+
+def rank_flops(plan: ShardPlan) -> np.ndarray:
+    """Flops of one factorisation on every rank under the plan's policy (host accounting of the library: covgpu_nd_plan_rank_flops)."""
+    from . import backend
+    out = np.zeros(max(plan.world, 1), np.float64)
+    n = backend.lib().covgpu_nd_plan_rank_flops(plan.handle, capi.dptr(out))
+    return out[:n]
+
+
+def exchange(plan: ShardPlan) -> dict:
+    """What one linear solve all-reduces under the plan's policy (host estimate on the real front sizes: covgpu_nd_plan_exchange)."""
+    from . import backend
+    out = (C.c_int64 * 4)()
+    backend.lib().covgpu_nd_plan_exchange(plan.handle, out)
+    return {"bytes": int(out[0]), "collectives": int(out[1]), "world": int(out[2]), "policy": int(out[3])}
 
 
 def plan_digest(plan: ShardPlan) -> str:
@@ -83,6 +102,8 @@ def plan_digest(plan: ShardPlan) -> str:
     import hashlib
     h = hashlib.sha256()
     h.update(np.int64([plan.world, plan.subtrees]).tobytes())
+    if getattr(plan, "shard_policy", 0):   # (policy 0 digests stay what they were; ranks of different policies refuse each other)
+        h.update(np.int64([plan.shard_policy]).tobytes())
     for a in (plan.node_rank, plan.lm_rank, plan.imu_rank, plan.edge_rank, plan.pose_rank, plan.sb_rank):
         a = np.ascontiguousarray(a, np.int32)
         h.update(np.int64([a.size]).tobytes()); h.update(a.tobytes())

@@ -62,7 +62,7 @@ typedef struct covgpu_options {
   /* IMU noise, already discretised (orb_slam3/src/Tracking.cc:1203-1211) and gravity magnitude */
   double  sigma_a, sigma_g, sigma_aw, sigma_gw, gravity;
   int32_t verbose;
-  int32_t reserved;
+  int32_t shard_policy;        /* sharded solve: 0 replicated top (default) | 1 distributed top (COVGPU_SHARD_POLICY overrides) */
 } covgpu_options;
 
 /* Fills `o` with the reference's effective settings (dogleg, 10 iterations, Cauchy(1), Ceres 1.x
@@ -321,7 +321,8 @@ int  covgpu_nd_plan_create(const covgpu_options* opt, const covgpu_problem* p, i
 int  covgpu_nd_plan_create_pgo(const covgpu_options* opt, const covgpu_problem* p, int32_t leaf_dims, covgpu_nd_plan** out);
 void covgpu_nd_plan_destroy(covgpu_nd_plan* plan);
 /* out16 = { nodes, levels, depth, own entries, front-structure entries, front elements over all batches, flops of the partial
- *           factorisations, largest own dims, largest border dims, largest root, 0... } */
+ *           factorisations, largest own dims, largest border dims, largest root, candidate tree (top mode, leaf, 100 x group balance),
+ *           shard policy of the plan (0 replicated top | 1 distributed top), 0, 0 } */
 void covgpu_nd_plan_info(const covgpu_nd_plan* plan, int64_t* out16);
 /* parent / level [nodes]; own_ptr / st_ptr [nodes + 1]; own_var / st_var: 2 * keyframe + (0 pose | 1 speed-bias) */
 void covgpu_nd_plan_arrays(const covgpu_nd_plan* plan, int32_t* parent, int32_t* level, int32_t* own_ptr, int32_t* own_var,
@@ -340,12 +341,21 @@ void covgpu_nd_plan_arrays(const covgpu_nd_plan* plan, int32_t* parent, int32_t*
  *   3. per trust-region iteration the library issues FOUR all-reduces, all enqueued on the context's stream (no host
  *      synchronisation): inside the linear solve ONE over [top fronts | their right-hand sides | gradient and diag(J^T J) of
  *      the top unknowns] after every rank has eliminated its own subtrees, and three of 16 + 2 x world scalars;
+ *      shard_policy 1 (distributed top, opt-in): the top is every node whose front order reaches 4 096 plus its ancestors;
+ *      its fronts stay SUMS over the ranks' copies — one all-reduce of gradient and diag(J^T J) of the top unknowns, then one
+ *      per 256-column panel of the top (the panel's column block and right-hand-side rows), which every rank factorises
+ *      redundantly, while each rank applies the trailing update to the tile rows it owns only ((tile row + node) mod world);
  *   4. after the solve an unknown is valid on the rank that owns its tree node (covgpu_nd_plan_owner; top unknowns: on
  *      every rank), a landmark on its lm_rank. */
 int32_t covgpu_shard_plan(const covgpu_options* opt, const covgpu_problem* p, int32_t world, covgpu_nd_plan** plan_out,
                           int32_t* lm_rank /* [L] */, int32_t* imu_rank /* [I] */, int32_t* edge_rank /* [E] */);  /* returns the number of subtrees, 0: no split */
 void covgpu_nd_plan_owner(const covgpu_nd_plan* plan, int32_t* pose_rank /* [K] */, int32_t* sb_rank /* [K] */);   /* -1: top unknown */
 void covgpu_nd_plan_ranks(const covgpu_nd_plan* plan, int32_t* node_rank /* [nodes] */);                          /* -1: top node */
+/* host-only accounting of a shard plan under its policy: out[world] = flops of one factorisation on every rank (its subtrees + the top:
+ * whole on every rank under policy 0; the redundant panel chain + the trailing-update tiles the rank owns under policy 1). Returns world. */
+int32_t covgpu_nd_plan_rank_flops(const covgpu_nd_plan* plan, double* out);
+/* out4 = { bytes all-reduced per linear solve and rank, collectives per linear solve, world, shard policy } (host estimate on the real front sizes) */
+void covgpu_nd_plan_exchange(const covgpu_nd_plan* plan, int64_t* out4);
 typedef struct covgpu_group covgpu_group;   /* in-process group of ranks (host threads), at most 16 */
 int  covgpu_group_create(int32_t world, covgpu_group** out);
 void covgpu_group_destroy(covgpu_group* g);

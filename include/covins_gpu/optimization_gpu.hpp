@@ -60,6 +60,9 @@ struct Params {
   // over RCCL; ranks that share a device (a one-GPU box: the test form) over the library's in-process group.
   int n_gpus = 1;
   std::vector<int> devices;
+  // how the sharded solve (n_gpus > 1) treats the top of the elimination tree: 0 replicated and all-reduced whole (default) | 1 distributed —
+  // all-reduced a 256-column panel at a time, the trailing updates split over the ranks (covgpu_options::shard_policy)
+  int shard_policy = 0;
   int flatten_threads = 0;  // host threads of the Map -> IR walk over landmarks; 0 = sys.threads_server-like default (hardware, <= 16)
   // GlobalBundleAdjustment with outlier removal: derive the second round's problem on the device from the resident first round
   // (covgpu_gba_two_round: ONE Map -> IR walk and ONE upload per call); 0: the reference's literal sequence — walk, solve, erase, walk, solve
@@ -457,6 +460,7 @@ class OptimizationT {
     if (prm.n_gpus > 1) {
       std::vector<int32_t> dev(prm.n_gpus);
       for (int i = 0; i < prm.n_gpus; ++i) dev[i] = i < (int)prm.devices.size() ? prm.devices[i] : i;
+      o.shard_policy = prm.shard_policy;
       if (covgpu_gba_solve_multi(&o, &p, &r, prm.n_gpus, dev.data(), prm.th_gba_outlier_global, erase ? erase->data() : nullptr,
                                  lm_left ? lm_left->data() : nullptr, counts) != COVGPU_OK)
         detail::fatal(covgpu_last_error());
@@ -509,6 +513,7 @@ class OptimizationT {
       if (prm.n_gpus > 1) {   // (round 6) the sharded route: one upload per rank, the second round derived on every rank's device from its share
         std::vector<int32_t> dev(prm.n_gpus);
         for (int i = 0; i < prm.n_gpus; ++i) dev[i] = i < (int)prm.devices.size() ? prm.devices[i] : i;
+        o.shard_policy = prm.shard_policy;
         if (covgpu_gba_two_round_multi(&o, &p, &tr, prm.n_gpus, dev.data(), erase.data(), lm_left.data(), counts, &r1, &r2) != COVGPU_OK) detail::fatal(covgpu_last_error());
       } else if (covgpu_gba_two_round(ctx, &o, &p, &tr, erase.data(), lm_left.data(), counts, &r1, &r2) != COVGPU_OK) detail::fatal(covgpu_last_error());
       lap("upload + both rounds on the device");

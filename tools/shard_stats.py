@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Host-only: what the shard plan of a workload looks like at 2 / 4 / 8 ranks — subtrees, size of the replicated top, bytes of the one
 all-reduce per linear solve (packed live lower 128x128 tiles of the top fronts + their right-hand sides), factorisation flops of the top
-and of the busiest rank's subtrees. Usage: python tools/shard_stats.py [workload ...]   (no GPU needed: covgpu_shard_plan is host code)"""
+and of the busiest rank's subtrees; then both shard policies side by side (0 replicated top | 1 distributed top): the busiest
+rank's share of the factorisation flops, bytes all-reduced per linear solve and rank, collectives per linear solve — from the library's own
+accounting (covgpu_nd_plan_rank_flops / covgpu_nd_plan_exchange). Usage: python tools/shard_stats.py [workload ...]   (no GPU needed: covgpu_shard_plan
+is host code)"""
 import ctypes as C
 import os
 import sys
@@ -50,6 +53,22 @@ def main():
                   f"({fl[top].sum() / fl.sum():.0%}, replicated on every rank), busiest rank's subtrees {rank_fl.max():.3e} ({rank_fl.max() / fl.sum():.0%}), "
                   f"lightest {rank_fl.min():.3e}")
             plan.close()
+        print(f"{name}: policies side by side (busiest rank's share of the plan's flops | MB all-reduced per linear solve and rank | collectives per linear solve)")
+        for world in (2, 4, 8):
+            row = []
+            for policy in (0, 1):
+                o = backend.default_options(); o.shard_policy = policy
+                plan = distrib.shard_plan(p, o, world)
+                if plan is None:
+                    row.append(f"policy {policy}: does not split"); continue
+                _, own, st = plan_arrays(plan)
+                total = float((own ** 3 / 3.0 + own ** 2 * st + own * st ** 2).sum())
+                f, ex = distrib.rank_flops(plan), distrib.exchange(plan)
+                top = plan.node_rank < 0
+                row.append(f"policy {policy}: busiest {f.max() / total:.3f} ({f.max():.3e} flops), {ex['bytes'] / 1e6:8.1f} MB, {ex['collectives']:3d} collectives, "
+                           f"top {int(top.sum())} fronts / {int(own[top].sum())} unknowns")
+                plan.close()
+            print(f"  world {world}: " + " | ".join(row))
 
 
 if __name__ == "__main__":
