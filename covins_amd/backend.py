@@ -210,16 +210,22 @@ class Context:
 
     def relpose_batch(self, bt: dict, th_outlier: float = 1.3, min_inliers: int = 12):
         """Batched Optimization::OptimizeRelativePose (covgpu_relpose_batch). `bt`: dict with ptr, pA, pB, kpA, kpB, sigA, sigB,
-        camA, camB, distA, distB, T0 (see include/covgpu.h). Returns (T_ab [B,7], outlier flags [C], inliers [B])."""
+        camA, camB, distA, distB, T0 (see include/covgpu.h), optionally modelA, modelB, xiA, xiB (COVGPU_CAM_* and xi per pair and side;
+        absent = pinhole). Returns (T_ab [B,7], outlier flags [C], inliers [B])."""
         f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
         i = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         keep = dict(ptr=i(bt["ptr"]), pB=f(bt["pB"]), pA=f(bt["pA"]), kA=f(bt["kpA"]), kB=f(bt["kpB"]), sA=f(bt["sigA"]), sB=f(bt["sigB"]),
                     cA=f(bt["camA"]), cB=f(bt["camB"]), dA=i(bt["distA"]), dB=i(bt["distB"]), T=np.array(bt["T0"], dtype=np.float64, order="C"))
+        for k in ("modelA", "modelB"):
+            keep[k] = i(bt[k]) if bt.get(k) is not None else None
+        for k in ("xiA", "xiB"):
+            keep[k] = f(bt[k]) if bt.get(k) is not None else None
         B = len(keep["ptr"]) - 1
         out = np.zeros(max(int(keep["ptr"][-1]), 1), np.uint8); inl = np.zeros(max(B, 1), np.int32)
+        ip = lambda a: None if a is None else iptr(a)
         s = capi.RelposeBatch(B, iptr(keep["ptr"]), dptr(keep["pB"]), dptr(keep["pA"]), dptr(keep["kA"]), dptr(keep["kB"]), dptr(keep["sA"]),
                               dptr(keep["sB"]), dptr(keep["cA"]), dptr(keep["cB"]), iptr(keep["dA"]), iptr(keep["dB"]), dptr(keep["T"]),
-                              out.ctypes.data_as(capi._bp), iptr(inl))
+                              out.ctypes.data_as(capi._bp), iptr(inl), ip(keep["modelA"]), ip(keep["modelB"]), dptr(keep["xiA"]), dptr(keep["xiB"]))
         self._check(lib().covgpu_relpose_batch(self._h, C.byref(s), float(th_outlier), int(min_inliers)))
         return keep["T"], out[:int(keep["ptr"][-1])].astype(bool), inl[:B]
 

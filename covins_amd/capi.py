@@ -16,6 +16,7 @@ import numpy as np
 COVGPU_OK = 0
 COVGPU_DOGLEG, COVGPU_LM = 0, 1
 COVGPU_DIST_RADTAN, COVGPU_DIST_EQUIDISTANT = 0, 1
+COVGPU_CAM_PINHOLE, COVGPU_CAM_UNIFIED = 0, 1   # camera projection models (values of the reference's eCamModel)
 COVGPU_MAX_TRACE = 64
 
 _dp = C.POINTER(C.c_double)
@@ -46,10 +47,17 @@ class ProblemStruct(C.Structure):
     ]
 
 
+class ProblemStructCam(ProblemStruct):
+    """covgpu_problem as include/covgpu.h declares it: the ProblemStruct fields (the layout from before camera models, unchanged) plus the
+    two camera-model fields appended at its end. FlatProblem.as_struct always builds this one, so the library never reads past the
+    struct it is handed; it passes wherever a POINTER(ProblemStruct) is declared."""
+    _fields_ = [("cam_model", _ip), ("cam_xi", _dp)]
+
+
 class RelposeBatch(C.Structure):
     _fields_ = [("num_pairs", C.c_int32), ("corr_ptr", _ip), ("p_b", _dp), ("p_a", _dp), ("kp_a", _dp), ("kp_b", _dp), ("sigma_a", _dp),
                 ("sigma_b", _dp), ("cam_a", _dp), ("cam_b", _dp), ("dist_type_a", _ip), ("dist_type_b", _ip), ("T_ab", _dp), ("outlier", _bp),
-                ("inliers", _ip)]
+                ("inliers", _ip), ("cam_model_a", _ip), ("cam_model_b", _ip), ("xi_a", _dp), ("xi_b", _dp)]
 
 
 class Result(C.Structure):
@@ -104,6 +112,11 @@ class FlatProblem:
     edge_meas: np.ndarray = field(default_factory=lambda: np.zeros((0, 7)))
     edge_sqrt_info: np.ndarray = field(default_factory=lambda: np.zeros((0, 36)))
     edge_loss_a: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    # camera models: None (the default, and what every pinhole-only map keeps) = every camera pinhole. Otherwise [A] COVGPU_CAM_* and
+    # [A] xi of the unified rows. A None field is not an instance attribute at all (__post_init__ drops it; reads see the class default
+    # None): walks over __dict__ — the golden input digests, field-by-field comparisons, copy() — see a pinhole problem exactly as before.
+    cam_model: Optional[np.ndarray] = None
+    cam_xi: Optional[np.ndarray] = None
 
     def __post_init__(self):
         K = np.asarray(self.kf_pose).reshape(-1, 7).shape[0]
@@ -133,6 +146,11 @@ class FlatProblem:
         self.edge_meas = _f64(self.edge_meas, (-1, 7))
         self.edge_sqrt_info = _f64(self.edge_sqrt_info, (-1, 36))
         self.edge_loss_a = _f64(self.edge_loss_a, (-1,))
+        for name, conv in (("cam_model", _i32), ("cam_xi", _f64)):
+            if getattr(self, name) is None:
+                self.__dict__.pop(name, None)
+            else:
+                setattr(self, name, conv(getattr(self, name), (A,)))
         self.validate()
 
     # sizes
@@ -163,16 +181,17 @@ class FlatProblem:
         assert self.edge_j.shape[0] == E and self.edge_meas.shape[0] == E and self.edge_sqrt_info.shape[0] == E
         assert self.edge_loss_a.shape[0] == E
         if E: assert min(self.edge_i.min(), self.edge_j.min()) >= 0 and max(self.edge_i.max(), self.edge_j.max()) < K
+        # (cam_model / cam_xi are checked by the library: an invalid model or xi is COVGPU_ERR_INVALID_ARG there, and tests pass such rows on purpose)
 
     def copy(self) -> "FlatProblem":
         return FlatProblem(**{k: (None if v is None else np.array(v, copy=True)) for k, v in self.__dict__.items()})
 
-    def as_struct(self) -> ProblemStruct:
+    def as_struct(self) -> ProblemStructCam:
         """C view of the arrays (no copies; keep `self` alive while the struct is in use)."""
-        s = ProblemStruct()
+        s = ProblemStructCam()
         s.num_kf, s.num_cam, s.num_lm, s.num_obs = self.K, self.A, self.L, self.O
         s.num_imu, s.num_edge, s.num_imu_samples = self.I, self.E, self.imu_samples.shape[0]
-        for name, ctype in ProblemStruct._fields_:
+        for name, ctype in ProblemStruct._fields_ + ProblemStructCam._fields_:
             if name.startswith("num_") or name == "reserved":
                 continue
             arr = getattr(self, name)

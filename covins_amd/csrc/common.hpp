@@ -138,6 +138,12 @@ struct DevProblem {
   // one-thread kernels between the vector kernels, so an iteration needs ONE host read-back (at its end) instead of three.
   double* tr;                          // [TR_COUNT]
   double* scal_r; int* flag_r;         // the scalars / factorisation flag the step logic reads: P.scal / P.flag, or (sharded solve) their all-reduced copies
+
+  // ---- camera models (covgpu_problem::cam_model / cam_xi). uni == 0: every camera is pinhole, the arrays are not allocated, and the
+  //      reprojection kernels run their UNI = false instantiations (the pinhole code as it was); uni == 1: those with UNI = true.
+  int uni;
+  int* cam_model;                      // [A] COVGPU_CAM_*
+  double* cam_xi;                      // [A]
 };
 
 enum {
@@ -546,7 +552,8 @@ void launch_tr_accept(const DevProblem& P, hipStream_t st, double* box = nullptr
 void launch_xnorm(const DevProblem& P, hipStream_t st);         // XN2
 void launch_relpose(int num, const int* ptr, const double* pB, const double* pA, const double* kpA, const double* kpB, const double* sigA,
                     const double* sigB, const double* camA, const int* distA, const double* camB, const int* distB, double th, int min_inliers,
-                    double* T, unsigned char* outlier, int* inliers, hipStream_t st);
+                    double* T, unsigned char* outlier, int* inliers, hipStream_t st,
+                    const int* modelA = nullptr, const double* xiA = nullptr, const int* modelB = nullptr, const double* xiB = nullptr);
 void launch_reanchor(int K, const double* pose_old, const double* pose_new, double* vel, int L, const int* ref, double* lm,
                      hipStream_t st);
 

@@ -126,6 +126,38 @@ COV_DEV double wave_sum(double v) {
   return v;
 }
 
+// R5 distortion of the normalised image point m = (x, y): RadTan or Equidistant, d = d(x', y') / d(x, y). The same arithmetic as inside
+// project_point, which keeps its own copy so that the pinhole kernels compile to the code they had before the unified model existed.
+COV_DEV void distort(double x, double y, const double* dist, int dist_type, double& xd, double& yd, double& dxx, double& dxy, double& dyx,
+                     double& dyy) {
+  const double r2 = x * x + y * y;
+  if (dist_type == COVGPU_DIST_RADTAN) {
+    const double k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3];
+    const double rad = (k1 + k2 * r2) * r2, dr = k1 + 2.0 * k2 * r2;
+    xd = x + x * rad + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
+    yd = y + y * rad + 2.0 * p2 * x * y + p1 * (r2 + 2.0 * y * y);
+    const double xy2dr = 2.0 * x * y * dr;
+    dxx = 1.0 + rad + 2.0 * x * x * dr + 2.0 * p1 * y + 6.0 * p2 * x;
+    dxy = xy2dr + 2.0 * p1 * x + 2.0 * p2 * y;
+    dyx = dxy;
+    dyy = 1.0 + rad + 2.0 * y * y * dr + 2.0 * p2 * x + 6.0 * p1 * y;
+  } else {
+    const double rho = sqrt(r2);
+    if (rho < 1e-8) {
+      xd = x; yd = y; dxx = 1.0; dxy = 0.0; dyx = 0.0; dyy = 1.0;
+    } else {
+      const double th = atan(rho), t2 = th * th;
+      const double poly = 1.0 + t2 * (dist[0] + t2 * (dist[1] + t2 * (dist[2] + t2 * dist[3])));
+      const double dpoly = 1.0 + t2 * (3.0 * dist[0] + t2 * (5.0 * dist[1] + t2 * (7.0 * dist[2] + t2 * 9.0 * dist[3])));
+      const double thd = th * poly, sc = thd / rho;
+      const double dsc = (dpoly / (1.0 + r2) * rho - thd) / r2;
+      const double ir = 1.0 / rho;
+      xd = sc * x; yd = sc * y;
+      dxx = sc + x * x * dsc * ir; dxy = x * y * dsc * ir; dyx = dxy; dyy = sc + y * y * dsc * ir;
+    }
+  }
+}
+
 // R5: pinhole + radtan / equidistant. Returns false if the point is behind the camera (A.2: block zeroed).
 COV_DEV bool project_point(V3 lc, const double* intr, const double* dist, int dist_type, double& u, double& v, double* jpi /*2x3*/) {
   if (!(lc.z > 1e-10)) return false;
@@ -164,6 +196,38 @@ COV_DEV bool project_point(V3 lc, const double* intr, const double* dist, int di
     jpi[3] = intr[1] * dyx * iz; jpi[4] = intr[1] * dyy * iz; jpi[5] = -intr[1] * (dyx * x + dyy * y) * iz;
   }
   return true;
+}
+
+// R5 unified projection (aslam::UnifiedProjectionCamera, parameters [xi, fu, fv, cu, cv]): with d = |l_C| and
+// D = Z + xi d, m = (X / D, Y / D) goes through the same distortion as the pinhole model. Valid iff Z > -f(xi) d (f = xi for xi <= 1,
+// else 1 / xi) and D > 1e-10; invalid -> false (block zeroed, as for pinhole). With xi = 0 this is project_point up to rounding.
+//   dm/dl_C = (1/D) [[1 - x xi X / d, -x xi Y / d, -x (1 + xi Z / d)], [-y xi X / d, 1 - y xi Y / d, -y (1 + xi Z / d)]]
+COV_DEV bool project_point_unified(V3 lc, double xi, const double* intr, const double* dist, int dist_type, double& u, double& v,
+                                   double* jpi /*2x3*/) {
+  const double d = sqrt(lc.x * lc.x + lc.y * lc.y + lc.z * lc.z);
+  const double D = lc.z + xi * d;
+  const double fxi = xi <= 1.0 ? xi : 1.0 / xi;
+  if (!(lc.z > -fxi * d) || !(D > 1e-10)) return false;
+  const double iD = 1.0 / D, x = lc.x * iD, y = lc.y * iD;
+  double xd, yd, dxx, dxy, dyx, dyy;
+  distort(x, y, dist, dist_type, xd, yd, dxx, dxy, dyx, dyy);
+  u = intr[0] * xd + intr[2];
+  v = intr[1] * yd + intr[3];
+  if (jpi) {
+    const double a = xi / d, az = 1.0 + a * lc.z;   // d > 0 here: D > 0 and |Z| <= d
+    const double m00 = iD * (1.0 - x * a * lc.x), m01 = -iD * x * a * lc.y, m02 = -iD * x * az;
+    const double m10 = -iD * y * a * lc.x, m11 = iD * (1.0 - y * a * lc.y), m12 = -iD * y * az;
+    jpi[0] = intr[0] * (dxx * m00 + dxy * m10); jpi[1] = intr[0] * (dxx * m01 + dxy * m11); jpi[2] = intr[0] * (dxx * m02 + dxy * m12);
+    jpi[3] = intr[1] * (dyx * m00 + dyy * m10); jpi[4] = intr[1] * (dyx * m01 + dyy * m11); jpi[5] = intr[1] * (dyx * m02 + dyy * m12);
+  }
+  return true;
+}
+
+// camera of model `model` (COVGPU_CAM_*): the pinhole path unless the camera is unified
+COV_DEV bool project_camera(V3 lc, int model, double xi, const double* intr, const double* dist, int dist_type, double& u, double& v,
+                            double* jpi) {
+  if (model == COVGPU_CAM_UNIFIED) return project_point_unified(lc, xi, intr, dist, dist_type, u, v, jpi);
+  return project_point(lc, intr, dist, dist_type, u, v, jpi);
 }
 
 }  // namespace covdev

@@ -23,6 +23,8 @@ struct RelBatch {
   int* inliers;            // [num] out
   double th;
   int min_inliers;
+  const int *modelA, *modelB;       // [num] COVGPU_CAM_* per side (read when UNI)
+  const double *xiA, *xiB;          // [num]
 };
 
 COV_DEV double wsum(double v) {
@@ -31,8 +33,9 @@ COV_DEV double wsum(double v) {
   return v;
 }
 
-// residual pair of one correspondence at (q, t); JAC: 4x6 Jacobian rows rA(2), rB(2), columns [dtheta, dp]; loss-corrected
-template <bool JAC>
+// residual pair of one correspondence at (q, t); JAC: 4x6 Jacobian rows rA(2), rB(2), columns [dtheta, dp]; loss-corrected.
+// UNI: some camera of the batch is unified and the projection is chosen per side (UNI == false: the pinhole-only code).
+template <bool JAC, bool UNI>
 COV_DEV double rel_eval(const RelBatch& B, int b, int i, Q4 q, V3 t, double* r4, double* J) {
   const M3 R = qrot(q);
   const V3 PB = ld3(B.pB + 3 * (size_t)i), PA = ld3(B.pA + 3 * (size_t)i);
@@ -41,7 +44,8 @@ COV_DEV double rel_eval(const RelBatch& B, int b, int i, Q4 q, V3 t, double* r4,
   {
     const V3 X = mul(R, PB) + t;
     double u, v, jpi[6];
-    if (project_point(X, B.camA + 8 * b, B.camA + 8 * b + 4, B.distA[b], u, v, JAC ? jpi : nullptr)) {
+    if (UNI ? project_camera(X, B.modelA[b], B.xiA[b], B.camA + 8 * b, B.camA + 8 * b + 4, B.distA[b], u, v, JAC ? jpi : nullptr)
+            : project_point(X, B.camA + 8 * b, B.camA + 8 * b + 4, B.distA[b], u, v, JAC ? jpi : nullptr)) {
       const double is = 1.0 / B.sigA[i];
       const double r0 = (u - B.kpA[2 * (size_t)i]) * is, r1 = (v - B.kpA[2 * (size_t)i + 1]) * is;
       double c; const double sq = cauchy_scale(1.0, r0 * r0 + r1 * r1, &c);
@@ -62,7 +66,8 @@ COV_DEV double rel_eval(const RelBatch& B, int b, int i, Q4 q, V3 t, double* r4,
   {
     const V3 Y = mulT(R, PA - t);
     double u, v, jpi[6];
-    if (project_point(Y, B.camB + 8 * b, B.camB + 8 * b + 4, B.distB[b], u, v, JAC ? jpi : nullptr)) {
+    if (UNI ? project_camera(Y, B.modelB[b], B.xiB[b], B.camB + 8 * b, B.camB + 8 * b + 4, B.distB[b], u, v, JAC ? jpi : nullptr)
+            : project_point(Y, B.camB + 8 * b, B.camB + 8 * b + 4, B.distB[b], u, v, JAC ? jpi : nullptr)) {
       const double is = 1.0 / B.sigB[i];
       const double r0 = (u - B.kpB[2 * (size_t)i]) * is, r1 = (v - B.kpB[2 * (size_t)i + 1]) * is;
       double c; const double sq = cauchy_scale(1.0, r0 * r0 + r1 * r1, &c);
@@ -119,6 +124,7 @@ COV_DEV bool chol6_solve(const double* A /*6x6 full*/, const double* b, double* 
 
 // every lane holds identical copies of the 6-dof state and of the reduced 6x6 system: the trust-region decisions are taken
 // redundantly (bit-identical: the shuffle reductions deliver the same sums to all lanes), no LDS, no barrier
+template <bool UNI>
 COV_DEV void rel_dogleg(const RelBatch& B, int b, int o0, int n, int lane, Q4& q, V3& t, int iters) {
   double radius = 1e4, mu = 1e-8, alpha = 0.0, cost = 0.0;
   double H[36], g[6], D[6], gh[6], gn[6];
@@ -130,7 +136,7 @@ COV_DEV void rel_dogleg(const RelBatch& B, int b, int o0, int n, int lane, Q4& q
     for (int a = lane; a < n; a += 64) {
       if (B.outlier[o0 + a]) continue;
       double r[4], J[24];
-      c += rel_eval<true>(B, b, o0 + a, q, t, r, J);
+      c += rel_eval<true, UNI>(B, b, o0 + a, q, t, r, J);
       int e = 0;
 #pragma unroll
       for (int x = 0; x < 6; ++x) {
@@ -147,7 +153,7 @@ COV_DEV void rel_dogleg(const RelBatch& B, int b, int o0, int n, int lane, Q4& q
   };
   auto total_cost = [&](Q4 qq, V3 tt) {
     double c = 0.0;
-    for (int a = lane; a < n; a += 64) { if (B.outlier[o0 + a]) continue; double r[4]; c += rel_eval<false>(B, b, o0 + a, qq, tt, r, nullptr); }
+    for (int a = lane; a < n; a += 64) { if (B.outlier[o0 + a]) continue; double r[4]; c += rel_eval<false, UNI>(B, b, o0 + a, qq, tt, r, nullptr); }
     return wsum(c);
   };
   linearise();
@@ -208,24 +214,25 @@ COV_DEV void rel_dogleg(const RelBatch& B, int b, int o0, int n, int lane, Q4& q
   }
 }
 
+template <bool UNI>
 __global__ __launch_bounds__(64) void k_relpose(RelBatch B) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int o0 = B.ptr[b], n = B.ptr[b + 1] - o0;
   Q4 q = qnormalize(ldq(B.T + 7 * (size_t)b));
   V3 t = ld3(B.T + 7 * (size_t)b + 4);
   for (int a = lane; a < n; a += 64) B.outlier[o0 + a] = 0;
-  rel_dogleg(B, b, o0, n, lane, q, t, 5);                       // max_num_iterations = 5 (optimization_be.cpp:787)
+  rel_dogleg<UNI>(B, b, o0, n, lane, q, t, 5);                       // max_num_iterations = 5 (optimization_be.cpp:787)
   double bad = 0.0;
   for (int a = lane; a < n; a += 64) {                          // problem.Evaluate + threshold (:791-811)
     double r[4];
-    rel_eval<false>(B, b, o0 + a, q, t, r, nullptr);
+    rel_eval<false, UNI>(B, b, o0 + a, q, t, r, nullptr);
     const bool out = sqrt(r[0] * r[0] + r[1] * r[1]) > B.th || sqrt(r[2] * r[2] + r[3] * r[3]) > B.th;
     B.outlier[o0 + a] = out ? 1 : 0;
     bad += out ? 1.0 : 0.0;
   }
   const int nbad = (int)wsum(bad);
   if (n - nbad < B.min_inliers) { if (lane == 0) B.inliers[b] = 0; return; }   // :813-815, T12 untouched
-  rel_dogleg(B, b, o0, n, lane, q, t, 5);                       // :817-818
+  rel_dogleg<UNI>(B, b, o0, n, lane, q, t, 5);                       // :817-818
   if (lane == 0) {
     double* T = B.T + 7 * (size_t)b;
     T[0] = q.x; T[1] = q.y; T[2] = q.z; T[3] = q.w; T[4] = t.x; T[5] = t.y; T[6] = t.z;
@@ -235,10 +242,13 @@ __global__ __launch_bounds__(64) void k_relpose(RelBatch B) {
 
 void launch_relpose(int num, const int* ptr, const double* pB, const double* pA, const double* kpA, const double* kpB, const double* sigA,
                     const double* sigB, const double* camA, const int* distA, const double* camB, const int* distB, double th, int min_inliers,
-                    double* T, unsigned char* outlier, int* inliers, hipStream_t st) {
+                    double* T, unsigned char* outlier, int* inliers, hipStream_t st, const int* modelA, const double* xiA, const int* modelB,
+                    const double* xiB) {
   if (num <= 0) return;
-  RelBatch B{num, ptr, pB, pA, kpA, kpB, sigA, sigB, camA, camB, distA, distB, T, outlier, inliers, th, min_inliers};
-  hipLaunchKernelGGL(k_relpose, dim3(num), dim3(64), 0, st, B);
+  RelBatch B{num, ptr, pB, pA, kpA, kpB, sigA, sigB, camA, camB, distA, distB, T, outlier, inliers, th, min_inliers, modelA, modelB, xiA, xiB};
+  // model arrays only when some camera of the batch is unified (the host passes both sides then); else the pinhole-only kernel
+  if (modelA != nullptr && modelB != nullptr) hipLaunchKernelGGL(k_relpose<true>, dim3(num), dim3(64), 0, st, B);
+  else hipLaunchKernelGGL(k_relpose<false>, dim3(num), dim3(64), 0, st, B);
 }
 
 }  // namespace covgpu

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void k_tail_stats(DevProblem P) {
 //          Segments by blockIdx: [0, nb_obs) reprojection (grid-stride over the SoA stream) | [nb_obs, nb_obs + nb_imu) one wave per
 //          IMU factor | the rest: one thread per between factor.
 static_assert(kImuWaves == 4, "k_tail_jvp / k_tail_cost index their IMU and edge segments as 4 waves / 256 threads per workgroup");
-template <bool TWO>
+template <bool TWO, bool UNI>
 __global__ __launch_bounds__(64 * kImuWaves) void k_tail_jvp(DevProblem P, const double* __restrict__ va, const double* __restrict__ vb, int nb_obs, int nb_imu) {
   __shared__ double sm[kImuWaves][kImuLds];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(64 * kImuWaves) void k_tail_jvp(DevProblem P, const
     for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < P.O; o += nb_obs * blockDim.x) {
       ObsLin e;
       const int kf = P.obs_kf[o], l = P.obs_lm[o];
-      eval_obs<true>(P, P.pose, P.lm, o, kf, l, e);
+      eval_obs<true, UNI>(P, P.pose, P.lm, o, kf, l, e);
       {
         const double* vp = vb + (size_t)P.D * kf;
         const double* vl = vb + P.n + 3 * (size_t)l;
@@ -141,6 +141,7 @@ __global__ __launch_bounds__(64 * kImuWaves) void k_tail_jvp(DevProblem P, const
 }
 
 // ---- T5: cost of the candidate estimate, the same three segments
+template <bool UNI>
 __global__ __launch_bounds__(64 * kImuWaves) void k_tail_cost(DevProblem P, int nb_obs, int nb_imu) {
   __shared__ double sm[kImuWaves][kImuLds];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(64 * kImuWaves) void k_tail_cost(DevProblem P, int 
   if ((int)blockIdx.x < nb_obs) {
     for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < P.O; o += nb_obs * blockDim.x) {
       ObsLin e;
-      eval_obs<false>(P, P.pose_c, P.lm_c, o, P.obs_kf[o], P.obs_lm[o], e);
+      eval_obs<false, UNI>(P, P.pose_c, P.lm_c, o, P.obs_kf[o], P.obs_lm[o], e);
       acc += e.cost;
     }
     idx = blockIdx.x * 4 + wave;
@@ -332,14 +333,21 @@ void launch_tail_jvp(const DevProblem& P, bool two, hipStream_t st) {
   int a, b, c;
   tail_segments(P, a, b, c);
   if (a + b + c == 0) return;
-  if (two) hipLaunchKernelGGL(k_tail_jvp<true>, dim3(a + b + c), dim3(64 * kImuWaves), 0, st, P, (const double*)P.vtmp, (const double*)P.gn, a, b);
-  else hipLaunchKernelGGL(k_tail_jvp<false>, dim3(a + b + c), dim3(64 * kImuWaves), 0, st, P, (const double*)nullptr, (const double*)P.gn, a, b);
+  // (UNI: the problem holds unified cameras — DevProblem::uni; the pinhole-only instantiations otherwise)
+  if (P.uni) {
+    if (two) hipLaunchKernelGGL((k_tail_jvp<true, true>), dim3(a + b + c), dim3(64 * kImuWaves), 0, st, P, (const double*)P.vtmp, (const double*)P.gn, a, b);
+    else hipLaunchKernelGGL((k_tail_jvp<false, true>), dim3(a + b + c), dim3(64 * kImuWaves), 0, st, P, (const double*)nullptr, (const double*)P.gn, a, b);
+    return;
+  }
+  if (two) hipLaunchKernelGGL((k_tail_jvp<true, false>), dim3(a + b + c), dim3(64 * kImuWaves), 0, st, P, (const double*)P.vtmp, (const double*)P.gn, a, b);
+  else hipLaunchKernelGGL((k_tail_jvp<false, false>), dim3(a + b + c), dim3(64 * kImuWaves), 0, st, P, (const double*)nullptr, (const double*)P.gn, a, b);
 }
 void launch_tail_cost(const DevProblem& P, hipStream_t st) {
   int a, b, c;
   tail_segments(P, a, b, c);
   if (a + b + c == 0) return;
-  hipLaunchKernelGGL(k_tail_cost, dim3(a + b + c), dim3(64 * kImuWaves), 0, st, P, a, b);
+  if (P.uni) hipLaunchKernelGGL(k_tail_cost<true>, dim3(a + b + c), dim3(64 * kImuWaves), 0, st, P, a, b);
+  else hipLaunchKernelGGL(k_tail_cost<false>, dim3(a + b + c), dim3(64 * kImuWaves), 0, st, P, a, b);
 }
 // stage 1: the sums of T1 / T2 (+ step logic A if `with_logic`); stage 2: the candidate cost (+ step logic B)
 void launch_tail_finish(const DevProblem& P, TrConsts tc, int stage, bool two, bool with_logic, int fresh, hipStream_t st) {

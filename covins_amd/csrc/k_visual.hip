@@ -109,7 +109,7 @@ COV_DEV void z_of(const ObsLin& e, const double* R, double* Z) {
 #else
 #define PAIR_ATTR
 #endif
-template <int G>
+template <int G, bool UNI>
 __global__ __launch_bounds__(kBuildThreads) LMLIN_ATTR void k_lm_lin(DevProblem P, double mu, DevSignal sig) {
   constexpr int GROUPS = kBuildThreads / G;
   // "everything before this kernel on its stream is complete" (the previous iteration's state update, the preintegration): the side stream's
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(kBuildThreads) LMLIN_ATTR void k_lm_lin(DevProblem 
     const int a = c * G + lane;
     if (a < nobs) {
       kf = P.obs_kf[o0 + a];
-      eval_obs<true>(P, P.pose, P.lm, o0 + a, kf, l, e);
+      eval_obs<true, UNI>(P, P.pose, P.lm, o0 + a, kf, l, e);
       h[0] += e.jl[0] * e.jl[0] + e.jl[3] * e.jl[3];
       h[1] += e.jl[0] * e.jl[1] + e.jl[3] * e.jl[4];
       h[2] += e.jl[0] * e.jl[2] + e.jl[3] * e.jl[5];
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(kBuildThreads) LMLIN_ATTR void k_lm_lin(DevProblem 
     if (a >= nobs) continue;
     if (nchunk > 1) {  // multi-chunk landmark: this chunk's Jacobians were overwritten above
       kf = P.obs_kf[o0 + a];
-      eval_obs<true>(P, P.pose, P.lm, o0 + a, kf, l, e);
+      eval_obs<true, UNI>(P, P.pose, P.lm, o0 + a, kf, l, e);
     }
     double Z[18];
     z_of(e, R, Z);
@@ -214,6 +214,7 @@ __global__ __launch_bounds__(256) void k_cost_finish(DevProblem P, int nparts) {
 // One wave (= one workgroup) per keyframe: fixed-order sum over its observations. Lanes run over the OBSERVATIONS (lane l takes
 // observations l, l+64, ...), each re-linearised from the cache-resident pose / landmark rows plus the landmark's factor R and
 // t = R^T g_l (72 B); the 39 partial sums of every lane go through LDS and lane k adds column k in lane order.
+template <bool UNI>
 __global__ __launch_bounds__(64) void k_kf_reduce(DevProblem P) {
   __shared__ double sp[kRec][65];
   const int kf = blockIdx.x, lane = threadIdx.x;
@@ -226,7 +227,7 @@ __global__ __launch_bounds__(64) void k_kf_reduce(DevProblem P) {
     const int l = P.kobs_lm[t];
     const double* uvs = P.kobs + 3 * (size_t)t;
     ObsLin e;
-    eval_obs_uvs<true>(P, P.pose, P.lm, uvs[0], uvs[1], uvs[2], kf, l, e);
+    eval_obs_uvs<true, UNI>(P, P.pose, P.lm, uvs[0], uvs[1], uvs[2], kf, l, e);
     const double* rt = P.lmRT + 9 * (size_t)l;
     double R[6], Z[18];
 #pragma unroll
@@ -343,7 +344,7 @@ __global__ __launch_bounds__(kPairLanes * kPairsPerWg) PAIR_ATTR void k_pair_blo
 //  records travel per common landmark — bit-identical, half the scattered reads, and SLOWER: 0.52 instead of 0.27 ms. One or two
 //  workgroups per CU (77 KB of LDS each) cannot keep enough partner reads in flight; eight waves per CU with every read in flight can.)
 // back-substitution: dl = Hinv (-g_l - sum_a W_a^T dp[kf_a]); written to out_all[n + 3l ..]
-template <int G>
+template <int G, bool UNI>
 __global__ __launch_bounds__(kBuildThreads) void k_lm_backsub(DevProblem P, const double* __restrict__ dp, double* __restrict__ out_all) {
   constexpr int GROUPS = kBuildThreads / G;
   const int lane = threadIdx.x % G, grp = threadIdx.x / G;
@@ -355,7 +356,7 @@ __global__ __launch_bounds__(kBuildThreads) void k_lm_backsub(DevProblem P, cons
   for (int a = lane; a < nobs; a += G) {
     ObsLin e;
     const int kf = P.obs_kf[o0 + a];
-    eval_obs<true>(P, P.pose, P.lm, o0 + a, kf, l, e);
+    eval_obs<true, UNI>(P, P.pose, P.lm, o0 + a, kf, l, e);
     const double* d = dp + (size_t)P.D * kf;
     // (W^T d)_c = sum_r (Jp^T Jl)[r][c] d[r] = sum_k Jl[k][c] (Jp[k] . d)
     const double s0 = e.jp[0] * d[0] + e.jp[1] * d[1] + e.jp[2] * d[2] + e.jp[3] * d[3] + e.jp[4] * d[4] + e.jp[5] * d[5];
@@ -378,12 +379,13 @@ __global__ __launch_bounds__(kBuildThreads) void k_lm_backsub(DevProblem P, cons
 }
 
 // sum over observations of |Jp v_p[kf] + Jl v_l[lm]|^2
+template <bool UNI>
 __global__ __launch_bounds__(256) void k_obs_jvp(DevProblem P, const double* __restrict__ v_all) {
   double acc = 0.0;
   for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < P.O; o += gridDim.x * blockDim.x) {
     ObsLin e;
     const int kf = P.obs_kf[o], l = P.obs_lm[o];
-    eval_obs<true>(P, P.pose, P.lm, o, kf, l, e);
+    eval_obs<true, UNI>(P, P.pose, P.lm, o, kf, l, e);
     const double* vp = v_all + (size_t)P.D * kf;
     const double* vl = v_all + P.n + 3 * (size_t)l;
     double s0 = e.jl[0] * vl[0] + e.jl[1] * vl[1] + e.jl[2] * vl[2];
@@ -396,32 +398,35 @@ __global__ __launch_bounds__(256) void k_obs_jvp(DevProblem P, const double* __r
   part_put(P, SC_JV2, blockIdx.x * 4 + (threadIdx.x >> 6), acc);
 }
 
+template <bool UNI>
 __global__ __launch_bounds__(256) void k_obs_cost(DevProblem P, const double* __restrict__ pose, const double* __restrict__ lm) {
   double acc = 0.0;
   for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < P.O; o += gridDim.x * blockDim.x) {
     ObsLin e;
-    eval_obs<false>(P, pose, lm, o, P.obs_kf[o], P.obs_lm[o], e);
+    eval_obs<false, UNI>(P, pose, lm, o, P.obs_kf[o], P.obs_lm[o], e);
     acc += e.cost;
   }
   acc = wave_sum(acc);
   part_put(P, SC_COST, blockIdx.x * 4 + (threadIdx.x >> 6), acc);
 }
 
+template <bool UNI>
 __global__ __launch_bounds__(256) void k_obs_linearize(DevProblem P, double* r, double* Jp, double* Jl, double* cost) {
   const int o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= P.O) return;
   ObsLin e;
-  eval_obs<true>(P, P.pose, P.lm, o, P.obs_kf[o], P.obs_lm[o], e);
+  eval_obs<true, UNI>(P, P.pose, P.lm, o, P.obs_kf[o], P.obs_lm[o], e);
   r[2 * o] = e.r0; r[2 * o + 1] = e.r1; cost[o] = e.cost;
   for (int k = 0; k < 12; ++k) Jp[12 * (size_t)o + k] = e.jp[k];
   for (int k = 0; k < 6; ++k) Jl[6 * (size_t)o + k] = e.jl[k];
 }
 
+template <bool UNI>
 __global__ __launch_bounds__(256) void k_obs_norms(DevProblem P, double* norms) {
   const int o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= P.O) return;
   ObsLin e;
-  eval_obs<false>(P, P.pose, P.lm, o, P.obs_kf[o], P.obs_lm[o], e);
+  eval_obs<false, UNI>(P, P.pose, P.lm, o, P.obs_kf[o], P.obs_lm[o], e);
   norms[o] = sqrt(e.r0 * e.r0 + e.r1 * e.r1);
 }
 
@@ -435,6 +440,10 @@ static inline int stream_grid(int n) {
 template <typename F> static void with_group(int g, F&& f) {
   if (g == 4) f(std::integral_constant<int, 4>()); else if (g == 8) f(std::integral_constant<int, 8>()); else f(std::integral_constant<int, 16>());
 }
+// unified cameras in the problem (DevProblem::uni): the UNI = true instantiations, else the pinhole-only ones
+template <typename F> static void with_uni(const DevProblem& P, F&& f) {
+  if (P.uni) f(std::true_type()); else f(std::false_type());
+}
 static int lm_blocks(const DevProblem& P) { const int g = P.lm_group == 4 || P.lm_group == 8 ? P.lm_group : 16; const int groups = kBuildThreads / g; return (P.L + groups - 1) / groups; }
 
 // side != nullptr: the per-keyframe reduction (diagonal blocks, gradient, right-hand side: compute-heavy re-linearisation) runs on the
@@ -445,7 +454,8 @@ static int lm_blocks(const DevProblem& P) { const int g = P.lm_group == 4 || P.l
 void launch_lm_lin(const DevProblem& P, double mu, hipStream_t st, DevSignal sig) {
   if (P.L == 0) return;
   const int nblk = lm_blocks(P);
-  with_group(P.lm_group, [&](auto G) { hipLaunchKernelGGL(k_lm_lin<decltype(G)::value>, dim3(nblk), dim3(kBuildThreads), 0, st, P, mu, sig); });
+  with_uni(P, [&](auto U) { with_group(P.lm_group, [&](auto G) {
+    hipLaunchKernelGGL((k_lm_lin<decltype(G)::value, decltype(U)::value>), dim3(nblk), dim3(kBuildThreads), 0, st, P, mu, sig); }); });
 }
 // the two passes that write the pose system, behind launch_lm_lin on `st`
 void launch_lm_build(const DevProblem& P, double mu, hipStream_t st, hipEvent_t pose_system_cleared, hipStream_t side, hipEvent_t ev_lin, hipEvent_t ev_kf, CholAux* ax) {
@@ -461,7 +471,7 @@ void launch_lm_build(const DevProblem& P, double mu, hipStream_t st, hipEvent_t 
   if (fork) { record(ev_lin, st); wait(s2, ev_lin, pose_system_cleared); if (pose_system_cleared) wait(st, pose_system_cleared); }
   else if (pose_system_cleared) wait(s2, pose_system_cleared);
   hipLaunchKernelGGL(k_cost_finish, dim3(1), dim3(256), 0, s2, P, nblk);
-  hipLaunchKernelGGL(k_kf_reduce, dim3(P.K), dim3(64), 0, s2, P);
+  with_uni(P, [&](auto U) { hipLaunchKernelGGL(k_kf_reduce<decltype(U)::value>, dim3(P.K), dim3(64), 0, s2, P); });
   if (P.npairs) {
     static const int xcd_order = getenv("COVGPU_PAIR_XCD") == nullptr || atoi(getenv("COVGPU_PAIR_XCD")) != 0;
     const int nblk = (P.npairs + kPairsPerWg - 1) / kPairsPerWg;
@@ -491,26 +501,27 @@ void launch_kobs_build(const DevProblem& P, int* pair_oa, int* pair_ob, size_t n
 }
 void launch_lm_backsub(const DevProblem& P, const double* dp, double* out_all, hipStream_t st) {
   if (P.L == 0) return;
-  with_group(P.lm_group, [&](auto G) { hipLaunchKernelGGL(k_lm_backsub<decltype(G)::value>, dim3(lm_blocks(P)), dim3(kBuildThreads), 0, st, P, dp, out_all); });
+  with_uni(P, [&](auto U) { with_group(P.lm_group, [&](auto G) {
+    hipLaunchKernelGGL((k_lm_backsub<decltype(G)::value, decltype(U)::value>), dim3(lm_blocks(P)), dim3(kBuildThreads), 0, st, P, dp, out_all); }); });
 }
 void launch_obs_jvp(const DevProblem& P, const double* v_all, hipStream_t st) {
   if (P.O == 0) return;
-  hipLaunchKernelGGL(k_obs_jvp, dim3(stream_grid(P.O)), dim3(256), 0, st, P, v_all);
+  with_uni(P, [&](auto U) { hipLaunchKernelGGL(k_obs_jvp<decltype(U)::value>, dim3(stream_grid(P.O)), dim3(256), 0, st, P, v_all); });
 }
 void launch_obs_cost(const DevProblem& P, const double* pose, const double* lm, hipStream_t st) {
   if (P.O == 0) return;
-  hipLaunchKernelGGL(k_obs_cost, dim3(stream_grid(P.O)), dim3(256), 0, st, P, pose, lm);
+  with_uni(P, [&](auto U) { hipLaunchKernelGGL(k_obs_cost<decltype(U)::value>, dim3(stream_grid(P.O)), dim3(256), 0, st, P, pose, lm); });
 }
 void launch_obs_linearize(const DevProblem& P, double* r, double* Jp, double* Jl, double* cost, hipStream_t st) {
   if (P.O == 0) return;
-  hipLaunchKernelGGL(k_obs_linearize, dim3((P.O + 255) / 256), dim3(256), 0, st, P, r, Jp, Jl, cost);
+  with_uni(P, [&](auto U) { hipLaunchKernelGGL(k_obs_linearize<decltype(U)::value>, dim3((P.O + 255) / 256), dim3(256), 0, st, P, r, Jp, Jl, cost); });
 }
 // Map maintenance after the outlier round, on the device (optimization_be.cpp:270-290 + Map::Clean / RemoveLandmarkOutliers,
 // map_be.cpp:448-454, 698-743): per observation "loss-corrected whitened residual norm > threshold -> erase", per landmark
 // the number of observations it keeps; a landmark left with fewer than two is what RemoveLandmarkOutliers drops. One
 // sub-wave group per landmark like the linearisation, the residual evaluated in place: only O bytes + L ints go back to
 // the host instead of O doubles. counts[0] += erased observations, counts[1] += landmarks left with < 2.
-template <int G>
+template <int G, bool UNI>
 __global__ __launch_bounds__(kBuildThreads) void k_lm_outliers(DevProblem P, double th, unsigned char* __restrict__ erase, int* __restrict__ left,
                                                                unsigned long long* __restrict__ counts) {
   constexpr int GROUPS = kBuildThreads / G;
@@ -522,7 +533,7 @@ __global__ __launch_bounds__(kBuildThreads) void k_lm_outliers(DevProblem P, dou
   double kept = 0.0, bad = 0.0;
   for (int a = lane; a < nobs; a += G) {
     ObsLin e;
-    eval_obs<false>(P, P.pose, P.lm, o0 + a, P.obs_kf[o0 + a], l, e);
+    eval_obs<false, UNI>(P, P.pose, P.lm, o0 + a, P.obs_kf[o0 + a], l, e);
     const bool out = sqrt(e.r0 * e.r0 + e.r1 * e.r1) > th;
     erase[o0 + a] = out ? 1 : 0;
     kept += out ? 0.0 : 1.0; bad += out ? 1.0 : 0.0;
@@ -536,12 +547,13 @@ __global__ __launch_bounds__(kBuildThreads) void k_lm_outliers(DevProblem P, dou
 }
 void launch_lm_outliers(const DevProblem& P, double th, unsigned char* erase, int* left, unsigned long long* counts, hipStream_t st) {
   if (P.L == 0) return;
-  with_group(P.lm_group, [&](auto G) { hipLaunchKernelGGL(k_lm_outliers<decltype(G)::value>, dim3(lm_blocks(P)), dim3(kBuildThreads), 0, st, P, th, erase, left, counts); });
+  with_uni(P, [&](auto U) { with_group(P.lm_group, [&](auto G) {
+    hipLaunchKernelGGL((k_lm_outliers<decltype(G)::value, decltype(U)::value>), dim3(lm_blocks(P)), dim3(kBuildThreads), 0, st, P, th, erase, left, counts); }); });
 }
 
 void launch_obs_norms(const DevProblem& P, double* norms, hipStream_t st) {
   if (P.O == 0) return;
-  hipLaunchKernelGGL(k_obs_norms, dim3((P.O + 255) / 256), dim3(256), 0, st, P, norms);
+  with_uni(P, [&](auto U) { hipLaunchKernelGGL(k_obs_norms<decltype(U)::value>, dim3((P.O + 255) / 256), dim3(256), 0, st, P, norms); });
 }
 
 }  // namespace covgpu

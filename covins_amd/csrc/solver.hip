@@ -460,6 +460,12 @@ static int validate(const covgpu_problem* p, bool pgo, bool vi) {
     if (p->num_cam <= 0 || !p->cam_extr || !p->cam_intr || !p->cam_dist || !p->cam_dist_type) return bad("NULL camera array");
     for (int k = 0; k < K; ++k) if (p->kf_cam[k] < 0 || p->kf_cam[k] >= p->num_cam) return bad("kf_cam out of range");
     for (int a = 0; a < p->num_cam; ++a) if (p->cam_dist_type[a] != COVGPU_DIST_RADTAN && p->cam_dist_type[a] != COVGPU_DIST_EQUIDISTANT) return bad("unknown distortion type");
+    if (p->cam_model) for (int a = 0; a < p->num_cam; ++a) {
+      if (p->cam_model[a] != COVGPU_CAM_PINHOLE && p->cam_model[a] != COVGPU_CAM_UNIFIED) return bad("unknown camera model");
+      if (p->cam_model[a] != COVGPU_CAM_UNIFIED) continue;
+      if (!p->cam_xi) return bad("unified camera without cam_xi");
+      if (!std::isfinite(p->cam_xi[a]) || p->cam_xi[a] < 0.0) return bad("xi of a unified camera is negative or not finite");
+    }
     if (vi && p->num_imu > 0 && (!p->imu_kf_i || !p->imu_kf_j || !p->imu_sample_ptr || !p->imu_first)) return bad("NULL IMU array");
     if (vi && p->num_imu > 0 && p->imu_sample_ptr[p->num_imu] > 0 && !p->imu_samples) return bad("NULL IMU sample array");
     if (vi && p->num_imu > 0 && (p->imu_sample_ptr[0] != 0 || p->imu_sample_ptr[p->num_imu] != p->num_imu_samples)) return bad("imu_sample_ptr does not span the IMU samples");
@@ -817,6 +823,19 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
   RC(dev_upload(c, &P.cam_intr, p->cam_intr, (size_t)4 * P.A));
   RC(dev_upload(c, &P.cam_dist, p->cam_dist, (size_t)4 * P.A));
   RC(dev_upload(c, &P.cam_dist_type, (const int*)p->cam_dist_type, (size_t)P.A));
+  if (!pgo && p->cam_model) {   // unified cameras: their model and xi go up and the reprojection kernels run their UNI forms (DevProblem::uni)
+    std::vector<int> model(P.A);
+    std::vector<double> xi(P.A, 0.0);
+    for (int a = 0; a < P.A; ++a) {
+      model[a] = p->cam_model[a];
+      if (model[a] == COVGPU_CAM_UNIFIED) { xi[a] = p->cam_xi[a]; P.uni = 1; }
+    }
+    if (P.uni) {
+      RC(dev_upload(c, &P.cam_model, (const int*)model.data(), (size_t)P.A));
+      RC(dev_upload(c, &P.cam_xi, (const double*)xi.data(), (size_t)P.A));
+      HIPCHK(hipStreamSynchronize(c->st));   // (the host vectors die here)
+    }
+  }
   // observation stream: SoA. The interleaved keypoints are split, the landmark index of every observation is filled and the
   // keyframe-major lists are built ON THE DEVICE (k_pairs.hip) — three host loops over O and two more uploads before (12 of the 18 ms of an
   // upload of the 5-agent map)
@@ -2009,6 +2028,26 @@ extern "C" int covgpu_relpose_batch(covgpu_context* c, const covgpu_relpose_batc
   const int B = bt->num_pairs;
   if (B == 0) return COVGPU_OK;
   for (int b = 0; b < B; ++b) if (bt->corr_ptr[b + 1] < bt->corr_ptr[b]) { g_err = "covgpu_relpose_batch: corr_ptr not monotone"; return COVGPU_ERR_INVALID_ARG; }
+  for (const int32_t* m : {bt->cam_model_a, bt->cam_model_b}) if (m) for (int b = 0; b < B; ++b) {
+    if (m[b] != COVGPU_CAM_PINHOLE && m[b] != COVGPU_CAM_UNIFIED) { g_err = "covgpu_relpose_batch: unknown camera model"; return COVGPU_ERR_INVALID_ARG; }
+  }
+  // per side: model and xi of every pair (xi 0 for pinhole rows); uploaded only if some camera of the batch is unified
+  std::vector<int32_t> hmA(B, COVGPU_CAM_PINHOLE), hmB(B, COVGPU_CAM_PINHOLE);
+  std::vector<double> hxA(B, 0.0), hxB(B, 0.0);
+  bool uni = false;
+  for (int side = 0; side < 2; ++side) {
+    const int32_t* m = side ? bt->cam_model_b : bt->cam_model_a;
+    const double* x = side ? bt->xi_b : bt->xi_a;
+    std::vector<int32_t>& hm = side ? hmB : hmA;
+    std::vector<double>& hx = side ? hxB : hxA;
+    if (!m) continue;
+    for (int b = 0; b < B; ++b) {
+      if (m[b] != COVGPU_CAM_UNIFIED) continue;
+      if (!x) { g_err = "covgpu_relpose_batch: unified camera without xi"; return COVGPU_ERR_INVALID_ARG; }
+      if (!std::isfinite(x[b]) || x[b] < 0.0) { g_err = "covgpu_relpose_batch: xi of a unified camera is negative or not finite"; return COVGPU_ERR_INVALID_ARG; }
+      hm[b] = COVGPU_CAM_UNIFIED; hx[b] = x[b]; uni = true;
+    }
+  }
   const size_t C = (size_t)bt->corr_ptr[B];
   if (C > 0 && (!bt->p_a || !bt->p_b || !bt->kp_a || !bt->kp_b || !bt->sigma_a || !bt->sigma_b || !bt->outlier)) { g_err = "covgpu_relpose_batch: NULL correspondence array"; return COVGPU_ERR_INVALID_ARG; }
   std::vector<void*> tmp;
@@ -2028,9 +2067,15 @@ extern "C" int covgpu_relpose_batch(covgpu_context* c, const covgpu_relpose_batc
   HIPCHK(up(bt->cam_a, 64 * (size_t)B, (void**)&dcA)); HIPCHK(up(bt->cam_b, 64 * (size_t)B, (void**)&dcB));
   HIPCHK(up(bt->dist_type_a, 4 * (size_t)B, (void**)&dda)); HIPCHK(up(bt->dist_type_b, 4 * (size_t)B, (void**)&ddb));
   HIPCHK(up(bt->T_ab, 56 * (size_t)B, (void**)&dT));
+  int *dmA = nullptr, *dmB = nullptr;
+  double *dxA = nullptr, *dxB = nullptr;
+  if (uni) {
+    HIPCHK(up(hmA.data(), 4 * (size_t)B, (void**)&dmA)); HIPCHK(up(hmB.data(), 4 * (size_t)B, (void**)&dmB));
+    HIPCHK(up(hxA.data(), 8 * (size_t)B, (void**)&dxA)); HIPCHK(up(hxB.data(), 8 * (size_t)B, (void**)&dxB));
+  }
   HIPCHK(hipMalloc((void**)&din, 4 * (size_t)B)); tmp.push_back(din);
   HIPCHK(hipMalloc((void**)&dout, C ? C : 8)); tmp.push_back(dout);
-  launch_relpose(B, dptr_, dpB, dpA, dkA, dkB, dsA, dsB, dcA, dda, dcB, ddb, th_outlier, min_inliers, dT, dout, din, c->st);
+  launch_relpose(B, dptr_, dpB, dpA, dkA, dkB, dsA, dsB, dcA, dda, dcB, ddb, th_outlier, min_inliers, dT, dout, din, c->st, dmA, dxA, dmB, dxB);
   HIPCHK(hipMemcpyAsync(bt->T_ab, dT, 56 * (size_t)B, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipMemcpyAsync(bt->inliers, din, 4 * (size_t)B, hipMemcpyDeviceToHost, c->st));
   if (C) HIPCHK(hipMemcpyAsync(bt->outlier, dout, C, hipMemcpyDeviceToHost, c->st));

@@ -18,7 +18,8 @@ struct ObsLin {
 
 
 // R4 + R6 for one observation. `fixed` zeroes the pose Jacobian (constant parameter block, opt_be.cpp:329-341).
-template <bool JAC>
+// UNI: the problem holds unified cameras (DevProblem::uni) and the projection is chosen per camera; UNI == false is the pinhole-only code.
+template <bool JAC, bool UNI = false>
 COV_DEV void eval_obs_uvs(const DevProblem& P, const double* __restrict__ pose, const double* __restrict__ lm, double mu_, double mv_, double sigma, int kf, int l,
                           ObsLin& out) {
   const int cam = P.kf_cam[kf];
@@ -30,7 +31,9 @@ COV_DEV void eval_obs_uvs(const DevProblem& P, const double* __restrict__ pose, 
   const V3 ls = mulT(Rws, lw - ld3(ps + 4));
   const V3 lc = mulT(Rsc, ls - ld3(ex + 4));
   double u, v, jpi[6];
-  const bool ok = project_point(lc, P.cam_intr + 4 * cam, P.cam_dist + 4 * cam, P.cam_dist_type[cam], u, v, JAC ? jpi : nullptr);
+  const bool ok = UNI ? project_camera(lc, P.cam_model[cam], P.cam_xi[cam], P.cam_intr + 4 * cam, P.cam_dist + 4 * cam, P.cam_dist_type[cam], u, v,
+                                       JAC ? jpi : nullptr)
+                      : project_point(lc, P.cam_intr + 4 * cam, P.cam_dist + 4 * cam, P.cam_dist_type[cam], u, v, JAC ? jpi : nullptr);
   if (!ok) {
     out.r0 = out.r1 = 0.0; out.cost = 0.0;
     if (JAC) {
@@ -63,9 +66,9 @@ COV_DEV void eval_obs_uvs(const DevProblem& P, const double* __restrict__ pose, 
 }
 
 // the same from the landmark-major observation stream
-template <bool JAC>
+template <bool JAC, bool UNI = false>
 COV_DEV void eval_obs(const DevProblem& P, const double* __restrict__ pose, const double* __restrict__ lm, int o, int kf, int l, ObsLin& out) {
-  eval_obs_uvs<JAC>(P, pose, lm, P.obs_u[o], P.obs_v[o], P.obs_sigma[o], kf, l, out);
+  eval_obs_uvs<JAC, UNI>(P, pose, lm, P.obs_u[o], P.obs_v[o], P.obs_sigma[o], kf, l, out);
 }
 
 }  // namespace covgpu

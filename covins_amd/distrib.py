@@ -138,8 +138,8 @@ def check_plan_digest(store, rank: int, world: int, mine: str) -> None:
 
 
 def shard_problem(prob: FlatProblem, plan: ShardPlan, rank: int) -> FlatProblem:
-    """Rank `rank`'s share: every keyframe (states are replicated, 128 B each), its landmarks with their observations,
-    its IMU factors, its between factors."""
+    """Rank `rank`'s share: every keyframe (states are replicated, 128 B each), every camera (with its model), its landmarks with their
+    observations, its IMU factors, its between factors."""
     lm = plan.lm_rank == rank
     n_obs = np.diff(prob.lm_obs_ptr)
     obs = np.repeat(lm, n_obs)
@@ -156,7 +156,7 @@ def shard_problem(prob: FlatProblem, plan: ShardPlan, rank: int) -> FlatProblem:
         imu_sample_ptr=np.concatenate([[0], np.cumsum(n_smp[imu])]).astype(np.int32), imu_samples=prob.imu_samples[smp],
         imu_first=prob.imu_first[imu], imu_noise=None if prob.imu_noise is None else prob.imu_noise[imu],
         edge_i=prob.edge_i[ed], edge_j=prob.edge_j[ed], edge_meas=prob.edge_meas[ed], edge_sqrt_info=prob.edge_sqrt_info[ed],
-        edge_loss_a=prob.edge_loss_a[ed])
+        edge_loss_a=prob.edge_loss_a[ed], cam_model=prob.cam_model, cam_xi=prob.cam_xi)   # (every rank projects with the full camera table)
 
 
 def merge_solution(prob: FlatProblem, plan: ShardPlan, parts: Sequence[FlatProblem]) -> FlatProblem:

@@ -66,6 +66,16 @@ class SlamMap:
     loops: List[LoopConstraint] = field(default_factory=list)
     # ground truth (synthetic maps only; used for ATE, never by the optimiser)
     truth: Dict[str, np.ndarray] = field(default_factory=dict)
+    # camera models (keyframe_base.cpp:58-82): None = every camera pinhole (PinholeCamera). Otherwise [A] capi.COVGPU_CAM_* and [A] xi
+    # of the unified rows (UnifiedProjectionCamera: intrinsics [xi, fu, fv, cu, cv], fu fv cu cv in cam_intr). Pinhole maps keep None.
+    cam_model: Optional[np.ndarray] = None
+    cam_xi: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        # (as capi.FlatProblem: a None camera-model field is no instance attribute — walks over __dict__ see a pinhole map as before)
+        for name in ("cam_model", "cam_xi"):
+            if getattr(self, name) is None:
+                self.__dict__.pop(name, None)
 
     @property
     def K(self): return self.kf_pose.shape[0]
@@ -202,6 +212,7 @@ def flatten_gba(m: SlamMap, visual_only: bool, loop_loss: bool, use_loops: bool 
         edge_meas=np.array(meas).reshape(-1, 7) if E else np.zeros((0, 7)),
         edge_sqrt_info=np.tile(GBA_LOOP_SQRT_INFO.reshape(1, 36), (E, 1)),
         edge_loss_a=np.full(E, 1.0 if loop_loss else 0.0),
+        cam_model=None if m.cam_model is None else m.cam_model.copy(), cam_xi=None if m.cam_xi is None else m.cam_xi.copy(),
     )
     return prob, FlatIndex(kf_rows, lm_rows, obs_rows)
 

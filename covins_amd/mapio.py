@@ -169,19 +169,24 @@ def load_map(path: str) -> SlamMap:
     kf_cam = np.zeros(K, np.int32)
     for i, k in enumerate(kfs):
         c = k["calibration"]
-        # KeyframeBase's constructor exits on anything but pinhole / omni x radtan / equidistant (keyframe_base.cpp:58-82); omni
-        # needs a 5-parameter unified-projection camera this back-end does not implement: refuse, do not
-        # silently flatten such a map as pinhole + radtan
-        if c["cam_model"] != 0:
-            raise ValueError(f"keyframe {k['id']}: camera model {c['cam_model']} is not PINHOLE(0): unsupported")
+        # KeyframeBase's constructor exits on anything but pinhole / omni x radtan / equidistant (keyframe_base.cpp:58-82). Omni is
+        # aslam's UnifiedProjectionCamera, whose constructor takes exactly 5 parameters [xi, fu, fv, cu, cv]: any other omni keyframe
+        # is refused, not flattened as something it is not
+        if c["cam_model"] not in (0, 1):
+            raise ValueError(f"keyframe {k['id']}: camera model {c['cam_model']} is neither PINHOLE(0) nor OMNI(1): unsupported")
+        if c["cam_model"] == 1 and len(c["intrinsics"]) != 5:
+            raise ValueError(f"keyframe {k['id']}: OMNI(1) camera with {len(c['intrinsics'])} intrinsics, the unified projection "
+                             "needs 5 (xi fu fv cu cv): unsupported")
         if c["dist_model"] not in (0, 1):
             raise ValueError(f"keyframe {k['id']}: distortion model {c['dist_model']} is neither RADTAN(0) nor EQUI(1): unsupported")
-        key = (k["id"][1], c["dist_model"], tuple(c["intrinsics"]), tuple(c["dist_coeffs"][:4]), tuple(k["T_s_c"].reshape(-1)),
+        key = (k["id"][1], c["cam_model"], c["dist_model"], tuple(c["intrinsics"]), tuple(c["dist_coeffs"][:4]), tuple(k["T_s_c"].reshape(-1)),
                c["sigma_a_c"], c["sigma_g_c"], c["sigma_aw_c"], c["sigma_gw_c"], c["g"])
         if key not in cam_rows:
             cam_rows[key] = len(cams); cams.append((k, c))
         kf_cam[i] = cam_rows[key]
     A = len(cams)
+    omni = any(c["cam_model"] == 1 for _, c in cams)   # pinhole-only maps keep SlamMap.cam_model = None
+    intr4 = lambda c: c["intrinsics"][1:5] if c["cam_model"] == 1 else c["intrinsics"][:4]
     imu_ptr = np.zeros(K + 1, np.int64)
     chunks = []
     for i, k in enumerate(kfs):
@@ -211,7 +216,7 @@ def load_map(path: str) -> SlamMap:
         kf_bias_g=np.array([k["bias_gyro"] for k in kfs]).reshape(K, 3),
         kf_pred=link([k["id_predecessor"] for k in kfs]), kf_succ=link([k["id_successor"] for k in kfs]), kf_cam=kf_cam,
         cam_extr=np.array([_pose_row(k["T_s_c"]) for k, _ in cams]).reshape(A, 7),
-        cam_intr=np.array([c["intrinsics"][:4] for _, c in cams]).reshape(A, 4),
+        cam_intr=np.array([intr4(c) for _, c in cams]).reshape(A, 4),
         cam_dist=np.array([np.pad(c["dist_coeffs"], (0, 4))[:4] for _, c in cams]).reshape(A, 4),
         cam_dist_type=np.array([c["dist_model"] for _, c in cams], np.int32),
         cam_imu_calib=np.array([[c["sigma_a_c"], c["sigma_g_c"], c["sigma_aw_c"], c["sigma_gw_c"], c["g"]] for _, c in cams]).reshape(A, 5),
@@ -220,7 +225,9 @@ def load_map(path: str) -> SlamMap:
         lm_pos=np.array([l["pos_w"] for l in lms]).reshape(len(lms), 3), lm_invalid=np.zeros(len(lms), bool),
         lm_ref_kf=np.array([row.get(l["id_reference"], -1) for l in lms], np.int32), lm_gba_optimized=np.zeros(len(lms), bool),
         lm_obs_ptr=np.array(ptr, np.int32), obs_kf=np.array(obs_kf, np.int32), obs_uv=np.array(obs_uv, np.float32).reshape(-1, 2),
-        obs_octave=np.array(obs_oct, np.int32), loops=loops)
+        obs_octave=np.array(obs_oct, np.int32), loops=loops,
+        cam_model=np.array([c["cam_model"] for _, c in cams], np.int32) if omni else None,
+        cam_xi=np.array([c["intrinsics"][0] if c["cam_model"] == 1 else 0.0 for _, c in cams], np.float64) if omni else None)
 
 
 # ------------------------------------------------------------------------------------------------ writer (fixtures / tests)
@@ -266,7 +273,9 @@ def save_map(path: str, m: SlamMap) -> None:
         w.f64(float(m.kf_time[i])); w.idpair(ids[i])
         cam = int(m.kf_cam[i]); ic = m.cam_imu_calib[cam]
         Tsc = _pose_mat(m.cam_extr[cam])
-        w.eigen(Tsc); w.i32(0); w.i32(int(m.cam_dist_type[cam])); w.colvec([752.0, 480.0]); w.colvec(m.cam_dist[cam]); w.colvec(m.cam_intr[cam])
+        omni = m.cam_model is not None and int(m.cam_model[cam]) == 1   # OMNI(1): intrinsics [xi, fu, fv, cu, cv]
+        intr = np.concatenate([[m.cam_xi[cam]], m.cam_intr[cam]]) if omni else m.cam_intr[cam]
+        w.eigen(Tsc); w.i32(1 if omni else 0); w.i32(int(m.cam_dist_type[cam])); w.colvec([752.0, 480.0]); w.colvec(m.cam_dist[cam]); w.colvec(intr)
         fx, fy, cx, cy = m.cam_intr[cam]
         w.eigen(np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]]))
         for v in (176.0, 7.8, ic[0], ic[1], 0.0, 0.0, ic[2], ic[3], 3600.0, ic[4]):

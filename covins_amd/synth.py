@@ -17,7 +17,7 @@ random-walk drift, and loop constraints are noisy ground-truth relative poses.
 from __future__ import annotations
 
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass, replace, field
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -75,6 +75,46 @@ class SynthConfig:
     imu_noise: bool = True
     recorded_imu: bool = True             # MH03-05 at their own keyframe times: the recorded 200 Hz samples (needs imu_noise: a noise-free map is all-synthetic)
     seed: int = 0
+    # opt-in camera per agent (one SynthCamera per entry of `agents`). None: every agent the EuRoC pinhole + RadTan camera, and the map is
+    # exactly what it was before camera models existed (SlamMap.cam_model stays None)
+    cameras: Optional[Sequence["SynthCamera"]] = None
+
+
+# equidistant (Kannala-Brandt) coefficients of the synthetic equidistant cameras: a mild lens, monotone over the image
+EQUI_DIST = np.array([-0.0113, 0.0412, -0.0489, 0.0187])
+
+
+@dataclass
+class SynthCamera:
+    """Camera of one synthetic agent: model capi.COVGPU_CAM_PINHOLE | COVGPU_CAM_UNIFIED, distortion COVGPU_DIST_RADTAN | _EQUIDISTANT,
+    xi of the unified model. Intrinsics are EuRoC's; the distortion coefficients DIST (RadTan) or EQUI_DIST (Equidistant)."""
+    model: int = 0
+    dist_type: int = 0
+    xi: float = 0.0
+
+    @property
+    def dist(self) -> np.ndarray:
+        return DIST if self.dist_type == 0 else EQUI_DIST
+
+
+def project_camera(pc: np.ndarray, cam: SynthCamera) -> np.ndarray:
+    """Pixels [N,2] of camera-frame points [N,3] under `cam` (the arithmetic of DESIGN.md 2, R5 row; points must be valid)."""
+    X, Y, Z = pc[:, 0], pc[:, 1], pc[:, 2]
+    D = Z + (cam.xi * np.sqrt(X * X + Y * Y + Z * Z) if cam.model == 1 else 0.0)
+    x, y = X / D, Y / D
+    d = cam.dist
+    if cam.dist_type == 0:
+        r2 = x * x + y * y
+        rad = (d[0] + d[1] * r2) * r2
+        xd = x + x * rad + 2 * d[2] * x * y + d[3] * (r2 + 2 * x * x)
+        yd = y + y * rad + 2 * d[3] * x * y + d[2] * (r2 + 2 * y * y)
+    else:
+        rho = np.sqrt(x * x + y * y)
+        th = np.arctan(rho); t2 = th * th
+        thd = th * (1 + t2 * (d[0] + t2 * (d[1] + t2 * (d[2] + t2 * d[3]))))
+        sc = np.where(rho < 1e-8, 1.0, thd / np.where(rho < 1e-8, 1.0, rho))
+        xd, yd = sc * x, sc * y
+    return np.stack([INTR[0] * xd + INTR[2], INTR[1] * yd + INTR[3]], 1)
 
 
 def _project(pc: np.ndarray):
@@ -389,6 +429,13 @@ def make_map(cfg: SynthConfig) -> SlamMap:
     lm_true = lm_all[good]
     lm_ref = lm_birth[good].astype(np.int32)
     lm_obs_ptr = np.concatenate([[0], np.cumsum(np.bincount(obs_l, minlength=L))]).astype(np.int32)
+    if cfg.cameras is not None:   # the same observations (visibility is decided with the pinhole camera), measured by each agent's own camera
+        assert len(cfg.cameras) == A, "one SynthCamera per agent"
+        pcam = Rc_true[obs_k].inv().apply(lm_true[obs_l] - pc_true[obs_k])
+        obs_uv = obs_uv.copy()
+        for a, cam in enumerate(cfg.cameras):
+            sel_a = kf_client[obs_k] == a
+            obs_uv[sel_a] = project_camera(pcam[sel_a], cam)
     # measurement noise, gross outliers, float32 storage
     uv_meas = obs_uv + rng.normal(0, cfg.px_noise, obs_uv.shape)
     if cfg.outlier_frac > 0:
@@ -448,6 +495,11 @@ def make_map(cfg: SynthConfig) -> SlamMap:
         loops=loops,
         truth=dict(kf_pose=pose_rows(q_true, p_true), kf_velocity=v_true, kf_bias_a=ba_true, kf_bias_g=bg_true, lm_pos=lm_true),
     )
+    if cfg.cameras is not None:
+        m.cam_model = np.array([c.model for c in cfg.cameras], np.int32)
+        m.cam_xi = np.array([c.xi if c.model == 1 else 0.0 for c in cfg.cameras], np.float64)
+        m.cam_dist_type = np.array([c.dist_type for c in cfg.cameras], np.int32)
+        m.cam_dist = np.stack([c.dist for c in cfg.cameras]).astype(np.float64)
     return m
 
 
@@ -485,6 +537,11 @@ def config_named(name: str, seed: int = 0) -> SynthConfig:
                            loops_per_pair=1, seed=seed)
     if name == "micro":           # tests/golden/refmap: the saved map written by the reference's own cereal code (tools/make_ref_cereal_fixture.py)
         return SynthConfig(agents=(1, 3), max_kf_per_agent=6, new_lm_per_kf=10, track_window=3, fuse_window=2, loops_per_pair=1, seed=7)
+    if name == "micro_omni":      # tests/golden/refmap_omni.npz: `micro` seen by two unified-projection cameras (tools/make_ref_cereal_fixture_omni.py)
+        return replace(config_named("micro"), cameras=(SynthCamera(1, 0, 0.9), SynthCamera(1, 1, 1.3)))
+    if name == "mixed":           # the camera models side by side: pinhole + RadTan, unified + RadTan (xi 0.9), unified + Equidistant (xi 1.3)
+        return SynthConfig(agents=(1, 2, 3), max_kf_per_agent=40, new_lm_per_kf=25, track_window=6, seed=seed,
+                           cameras=(SynthCamera(0, 0), SynthCamera(1, 0, 0.9), SynthCamera(1, 1, 1.3)))
     if name == "small":           # GPU parity tests / smoke
         return SynthConfig(agents=(1, 2, 3), max_kf_per_agent=60, new_lm_per_kf=30, track_window=8, seed=seed)
     raise KeyError(name)

@@ -46,6 +46,11 @@ enum { COVGPU_DOGLEG = 0, COVGPU_LM = 1 };
  * only construct RadTan / Equidistant, keyframe_base.cpp:58-82) */
 enum { COVGPU_DIST_RADTAN = 0, COVGPU_DIST_EQUIDISTANT = 1 };
 
+/* projection model of a camera; the values are those of the reference's eCamModel (keyframe_base.cpp:58-82).
+ * COVGPU_CAM_UNIFIED is aslam::UnifiedProjectionCamera: parameters [xi, fu, fv, cu, cv], with xi in cam_xi and fu fv cu cv in
+ * cam_intr; d = |l_C|, m = (X, Y) / (Z + xi d) goes through the camera's distortion. */
+enum { COVGPU_CAM_PINHOLE = 0, COVGPU_CAM_UNIFIED = 1 };
+
 /* ---------------------------------------------------------------- options */
 typedef struct covgpu_options {
   int32_t strategy;            /* COVGPU_DOGLEG | COVGPU_LM                                         */
@@ -126,6 +131,11 @@ typedef struct covgpu_problem {
   const double*  edge_meas;      /* [E][7] */
   const double*  edge_sqrt_info; /* [E][36] */
   const double*  edge_loss_a;    /* [E] */
+
+  /* camera models (appended: the offsets above are unchanged). cam_model NULL = every camera pinhole and cam_xi is not read.
+   * An unknown model, a unified row with cam_xi NULL, or a non-finite or negative xi is COVGPU_ERR_INVALID_ARG. */
+  const int32_t* cam_model;      /* [A] COVGPU_CAM_* or NULL                        */
+  const double*  cam_xi;         /* [A] xi of the unified rows (others not read)   */
 } covgpu_problem;
 
 /* per-iteration trace, for parity tests against the oracle */
@@ -228,7 +238,8 @@ int covgpu_covisibility(covgpu_context* ctx, int32_t threshold, int64_t capacity
  * norm exceeds th_outlier in either image are dropped, fewer than min_inliers (reference: 12) left -> inliers = 0 and T_ab
  * untouched, else 5 more iterations. NB with Cauchy(1) the corrected norm is < 1, so the reference's configured
  * opt.th_outlier_align = 1.3 never removes anything; that behaviour is reproduced as is.
- * Pairs b = 0..num-1 own correspondences [corr_ptr[b], corr_ptr[b+1]). cam_* rows: fx fy cx cy d0 d1 d2 d3. All HOST pointers. */
+ * Pairs b = 0..num-1 own correspondences [corr_ptr[b], corr_ptr[b+1]). cam_* rows: fx fy cx cy d0 d1 d2 d3. All HOST pointers.
+ * cam_model_a / _b (appended fields, NULL = pinhole) and xi_a / _b select the projection per side as covgpu_problem's cam_model / cam_xi. */
 typedef struct covgpu_relpose_batch_t {
   int32_t num_pairs;
   const int32_t* corr_ptr;      /* [num_pairs + 1] */
@@ -245,6 +256,10 @@ typedef struct covgpu_relpose_batch_t {
   double*        T_ab;          /* [num_pairs][7] in/out */
   uint8_t*       outlier;       /* [C] out: 1 = correspondence removed (matches1[i] = NULL, :807) */
   int32_t*       inliers;       /* [num_pairs] out: the function's return value per pair */
+  const int32_t* cam_model_a;   /* [num_pairs] COVGPU_CAM_* or NULL (pinhole) */
+  const int32_t* cam_model_b;   /* [num_pairs] or NULL */
+  const double*  xi_a;          /* [num_pairs] read for unified rows */
+  const double*  xi_b;          /* [num_pairs] */
 } covgpu_relpose_batch_t;
 int covgpu_relpose_batch(covgpu_context* ctx, const covgpu_relpose_batch_t* batch, double th_outlier, int32_t min_inliers);
 

@@ -88,6 +88,15 @@ inline auto visit_observations(const L& lm, F&& f, int) -> decltype(Types::visit
 template <class Types, class L, class F>
 inline void visit_observations(const L& lm, F&& f, long) { const auto obs = lm.GetObservations(); for (auto& m : obs) f(m.first, m.second); }
 
+// projection model of a keyframe's camera through the optional trait Types::camera_model(keyframe, &model, &xi) (COVGPU_CAM_*; false =
+// unknown model); a binding without it has pinhole cameras only
+template <class Types, class K>
+inline auto camera_model(const K& kf, int* model, double* xi, int) -> decltype(Types::camera_model(kf, model, xi), bool()) {
+  return Types::camera_model(kf, model, xi);
+}
+template <class Types, class K>
+inline bool camera_model(const K&, int* model, double* xi, long) { *model = COVGPU_CAM_PINHOLE; *xi = 0.0; return true; }
+
 inline void fatal(const char* msg) {  // the reference prints COUTFATAL and exit(-1) (e.g. optimization_be.cpp:113-114)
   std::fprintf(stderr, "[covins_gpu] FATAL: %s\n", msg);
   std::exit(-1);
@@ -187,6 +196,8 @@ struct Flat {  // owning storage behind one covgpu_problem
   std::vector<double> pose, sb, cam_extr, cam_intr, cam_dist, lm, uv, sigma, samples, first, noise, meas, info, loss;
   std::vector<uint8_t> fixed;
   std::vector<int32_t> kf_cam, cam_type, obs_ptr, obs_kf, imu_i, imu_j, imu_ptr, ei, ej;
+  std::vector<int32_t> cam_model;   // [A] COVGPU_CAM_*
+  std::vector<double> cam_xi;       // [A]
   covgpu_problem view() {
     covgpu_problem p{};
     p.num_kf = (int32_t)fixed.size(); p.num_cam = (int32_t)cam_type.size(); p.num_lm = (int32_t)(lm.size() / 3);
@@ -200,6 +211,9 @@ struct Flat {  // owning storage behind one covgpu_problem
     p.imu_kf_i = imu_i.data(); p.imu_kf_j = imu_j.data(); p.imu_sample_ptr = imu_ptr.data(); p.imu_samples = samples.data();
     p.imu_first = first.data(); p.imu_noise = noise.data();
     p.edge_i = ei.data(); p.edge_j = ej.data(); p.edge_meas = meas.data(); p.edge_sqrt_info = info.data(); p.edge_loss_a = loss.data();
+    bool uni = false;   // camera models only when some camera is unified (a pinhole-only map runs the pinhole kernels, NULL)
+    for (int32_t m : cam_model) uni = uni || m == COVGPU_CAM_UNIFIED;
+    if (uni && cam_model.size() == cam_type.size()) { p.cam_model = cam_model.data(); p.cam_xi = cam_xi.data(); }
     return p;
   }
 };
@@ -209,6 +223,8 @@ struct Flat {  // owning storage behind one covgpu_problem
 // `Types` must provide (see tests/cpp/standin_map.hpp and INTEGRATION.md):
 //   typedefs  Map, Keyframe, Landmark, TransformType, Vector3Type
 //   static bool camera(const Keyframe&, double intr[4], double dist[4], int* dist_type);   false = unknown model
+//   optional: static bool camera_model(const Keyframe&, int* model, double* xi);   COVGPU_CAM_PINHOLE | COVGPU_CAM_UNIFIED and the
+//             unified model's xi (intr[4] then holds fu fv cu cv); false = unknown model. Absent: every camera is pinhole.
 //   static int  imu_count(const Keyframe&);
 //   static void imu_sample(const Keyframe&, int i, double* dt, double acc[3], double gyr[3]);
 //   static void imu_first(const Keyframe&, double acc0[3], double gyr0[3]);
@@ -278,13 +294,14 @@ class OptimizationT {
       // Extrinsics, intrinsics and distortion are constant parameter blocks OF THIS KEYFRAME (:336,349,352:
       // kf->ceres_extrinsics_ / camera_ of every keyframe). Identical rows are shared: normally one per agent, but a
       // keyframe whose calibration differs from its agent's earlier ones gets its own camera row.
-      double intr[4], dist[4], e7[7]; int dt = 0;
-      if (!Types::camera(*kf, intr, dist, &dt)) detail::fatal("Unknown projection / distortion type.");  // :112-115, 201-204
+      double intr[4], dist[4], e7[7], xi = 0.0; int dt = 0, model = COVGPU_CAM_PINHOLE;
+      if (!Types::camera(*kf, intr, dist, &dt) || !detail::camera_model<Types>(*kf, &model, &xi, 0))
+        detail::fatal("Unknown projection / distortion type.");  // :104-115, 187-221
       detail::transform_to_pose(kf->GetStateExtrinsics(), e7);
       std::vector<int32_t>& cands = cams_of_client[kf->id_.second];
       int32_t cam = -1;
       for (int32_t c : cands) {
-        bool same = f.cam_type[c] == dt;
+        bool same = f.cam_type[c] == dt && f.cam_model[c] == model && f.cam_xi[c] == xi;
         for (int i = 0; same && i < 7; ++i) same = f.cam_extr[7 * c + i] == e7[i];
         for (int i = 0; same && i < 4; ++i) same = f.cam_intr[4 * c + i] == intr[i] && f.cam_dist[4 * c + i] == dist[i];
         if (same) { cam = c; break; }
@@ -293,6 +310,7 @@ class OptimizationT {
         cam = (int32_t)f.cam_type.size(); cands.push_back(cam);
         f.cam_extr.insert(f.cam_extr.end(), e7, e7 + 7); f.cam_intr.insert(f.cam_intr.end(), intr, intr + 4);
         f.cam_dist.insert(f.cam_dist.end(), dist, dist + 4); f.cam_type.push_back(dt);
+        f.cam_model.push_back(model); f.cam_xi.push_back(xi);
       }
       f.kf_cam.push_back(cam);
     }
@@ -784,15 +802,18 @@ class OptimizationT {
   static void OptimizeRelativePoseBatch(std::vector<RelPoseJob>& jobs) {
     const size_t B = jobs.size();
     if (B == 0) return;
-    std::vector<int32_t> ptr(1, 0), dA(B), dB(B), inl(B);
-    std::vector<double> pB, pA, kA, kB, sA, sB, camA(8 * B), camB(8 * B), T(7 * B);
+    std::vector<int32_t> ptr(1, 0), dA(B), dB(B), inl(B), mA(B), mB(B);
+    std::vector<double> pB, pA, kA, kB, sA, sB, camA(8 * B), camB(8 * B), T(7 * B), xA(B), xB(B);
+    bool uni = false;
     std::vector<std::vector<int>> index(B);   // correspondence -> position in matches1
     for (size_t b = 0; b < B; ++b) {
       RelPoseJob& j = jobs[b];
       int da = 0, db = 0;
-      if (!Types::camera(*j.kf1, &camA[8 * b], &camA[8 * b + 4], &da) || !Types::camera(*j.kf2, &camB[8 * b], &camB[8 * b + 4], &db))
-        detail::fatal("Unknown projection / distortion type.");  // :668-671, 695-697
+      if (!Types::camera(*j.kf1, &camA[8 * b], &camA[8 * b + 4], &da) || !Types::camera(*j.kf2, &camB[8 * b], &camB[8 * b + 4], &db) ||
+          !detail::camera_model<Types>(*j.kf1, &mA[b], &xA[b], 0) || !detail::camera_model<Types>(*j.kf2, &mB[b], &xB[b], 0))
+        detail::fatal("Unknown projection / distortion type.");  // :668-671, 676-752
       dA[b] = da; dB[b] = db;
+      uni = uni || mA[b] == COVGPU_CAM_UNIFIED || mB[b] == COVGPU_CAM_UNIFIED;
       detail::transform_to_pose(*j.T12, &T[7 * b]);
       // TcwA = (Tws1 Tsc1)^-1, TcwB = (Tws2 Tsc1)^-1 — the reference uses kf1's extrinsics for both (:640-641)
       TransformType TwcA, TwcB;
@@ -821,6 +842,7 @@ class OptimizationT {
     bt.num_pairs = (int32_t)B; bt.corr_ptr = ptr.data(); bt.p_b = pB.data(); bt.p_a = pA.data(); bt.kp_a = kA.data(); bt.kp_b = kB.data();
     bt.sigma_a = sA.data(); bt.sigma_b = sB.data(); bt.cam_a = camA.data(); bt.cam_b = camB.data(); bt.dist_type_a = dA.data(); bt.dist_type_b = dB.data();
     bt.T_ab = T.data(); bt.outlier = out.data(); bt.inliers = inl.data();
+    if (uni) { bt.cam_model_a = mA.data(); bt.cam_model_b = mB.data(); bt.xi_a = xA.data(); bt.xi_b = xB.data(); }
     covgpu_context* ctx = Context();
     if (covgpu_relpose_batch(ctx, &bt, params().th_outlier_align, 12) != COVGPU_OK) detail::fatal(covgpu_last_error());
     for (size_t b = 0; b < B; ++b) {
