@@ -229,6 +229,41 @@ class Context:
         self._check(lib().covgpu_relpose_batch(self._h, C.byref(s), float(th_outlier), int(min_inliers)))
         return keep["T"], out[:int(keep["ptr"][-1])].astype(bool), inl[:B]
 
+    def abspose_ransac_batch(self, bt: dict, **opts):
+        """Batched Se3Solver::projectiveAlignment (covgpu_abspose_ransac_batch, DESIGN.md §4.10). `bt`: dict with ptr [num+1], bearing [C,3],
+        point_w [C,3], sigma_angle [C], optionally seed [num] (uint64; absent = opts seed + b) and T0 [num,7] (what untouched rows hold).
+        `opts`: min_inliers, max_iterations, probability, threshold, seed (defaults: covgpu_default_ransac_opts). Returns dict(T_wc [num,7],
+        inlier [C] bool, inliers [num], iterations [num], best_draw [num])."""
+        o = capi.RansacOpts()
+        lib().covgpu_default_ransac_opts(C.byref(o))
+        for k, v in opts.items():
+            if not hasattr(o, k):
+                raise TypeError(f"unknown RANSAC option {k}")
+            setattr(o, k, v)
+        ptr = np.ascontiguousarray(bt["ptr"], dtype=np.int32)
+        B = len(ptr) - 1
+        Cn = int(ptr[-1]) if B >= 0 and len(ptr) else 0
+        f = np.ascontiguousarray(bt["bearing"], dtype=np.float64).reshape(-1, 3)
+        P = np.ascontiguousarray(bt["point_w"], dtype=np.float64).reshape(-1, 3)
+        sg = np.ascontiguousarray(bt["sigma_angle"], dtype=np.float64)
+        seed = None if bt.get("seed") is None else np.ascontiguousarray(bt["seed"], dtype=np.uint64)
+        T = np.array(bt["T0"], dtype=np.float64, order="C").reshape(-1, 7) if bt.get("T0") is not None else np.zeros((max(B, 1), 7))
+        mask = np.zeros(max(Cn, 1), np.uint8)
+        inl, its, bd = (np.zeros(max(B, 1), np.int32) for _ in range(3))
+        s = capi.AbsposeBatch(B, iptr(ptr), dptr(f), dptr(P), dptr(sg), None if seed is None else seed.ctypes.data_as(C.POINTER(C.c_uint64)),
+                              dptr(T), mask.ctypes.data_as(capi._bp), iptr(inl), iptr(its), iptr(bd))
+        self._check(lib().covgpu_abspose_ransac_batch(self._h, C.byref(s), C.byref(o)))
+        return dict(T_wc=T[:max(B, 0)], inlier=mask[:Cn].astype(bool), inliers=inl[:max(B, 0)], iterations=its[:max(B, 0)], best_draw=bd[:max(B, 0)])
+
+    def p3p_batch(self, f, P):
+        """covgpu_p3p_batch: f, P [n,4,3] -> (T [n,4,7] every solution, qx qy qz qw x y z, ascending v = s3/s1; nsol [n]; chosen [n], -1: none)."""
+        f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 4, 3)
+        P = np.ascontiguousarray(P, dtype=np.float64).reshape(-1, 4, 3)
+        n = f.shape[0]
+        T = np.zeros((max(n, 1), 4, 7)); ns = np.zeros(max(n, 1), np.int32); ch = np.zeros(max(n, 1), np.int32)
+        self._check(lib().covgpu_p3p_batch(self._h, n, dptr(f), dptr(P), dptr(T), iptr(ns), iptr(ch)))
+        return T[:n], ns[:n], ch[:n]
+
     def set_profiling(self, on: bool):
         lib().covgpu_set_profiling(self._h, int(on))
 

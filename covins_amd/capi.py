@@ -199,6 +199,16 @@ class FlatProblem:
         return s
 
 
+class AbsposeBatch(C.Structure):
+    _fields_ = [("num", C.c_int32), ("corr_ptr", _ip), ("bearing", _dp), ("point_w", _dp), ("sigma_angle", _dp), ("seed", C.POINTER(C.c_uint64)),
+                ("T_wc", _dp), ("inlier", _bp), ("inliers", _ip), ("iterations", _ip), ("best_draw", _ip)]
+
+
+class RansacOpts(C.Structure):
+    _fields_ = [("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("probability", C.c_double), ("threshold", C.c_double),
+                ("seed", C.c_uint64)]
+
+
 def declare(lib: C.CDLL, prefix: str) -> None:
     """Attach argtypes/restype for the entry points shared by libcovgpu (prefix 'covgpu_', with a context
     argument) and — test side only — the oracle (prefix 'covo_', no context)."""
@@ -231,6 +241,9 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("pgo_partition", [C.c_int32, C.c_int32, _ip, _ip, _ip], C.c_int32)
         d("gn_step", [C.c_void_p, OP, PP, C.c_double, _dp, _dp, _dp])
         d("relpose_batch", [C.c_void_p, C.POINTER(RelposeBatch), C.c_double, C.c_int32])
+        d("default_ransac_opts", [C.POINTER(RansacOpts)], None)
+        d("abspose_ransac_batch", [C.c_void_p, C.POINTER(AbsposeBatch), C.POINTER(RansacOpts)])
+        d("p3p_batch", [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _ip])
         d("outlier_pass", [C.c_void_p, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])
         d("covisibility", [C.c_void_p, C.c_int32, C.c_int64, _ip, _ip, _ip, C.POINTER(C.c_int64)])
         d("gba_solve_multi", [OP, PP, RP, C.c_int32, _ip, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])

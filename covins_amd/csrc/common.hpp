@@ -554,6 +554,11 @@ void launch_relpose(int num, const int* ptr, const double* pB, const double* pA,
                     const double* sigB, const double* camA, const int* distA, const double* camB, const int* distB, double th, int min_inliers,
                     double* T, unsigned char* outlier, int* inliers, hipStream_t st,
                     const int* modelA = nullptr, const double* xiA = nullptr, const int* modelB = nullptr, const double* xiB = nullptr);
+// k_abspose.hip: batched Se3Solver::projectiveAlignment (one 256-thread workgroup per candidate; LDS sized by the largest candidate)
+void launch_abspose(int num, const int* ptr, const double* f, const double* P, const double* sig, const unsigned long long* seed, double* T,
+                    unsigned char* inlier, int* inliers, int* iterations, int* best_draw, int min_inliers, int max_iterations, double probability,
+                    double threshold, int max_n, hipStream_t st);
+void launch_p3p(int num, const double* F, const double* P, double* T, int* nsol, int* chosen, hipStream_t st);
 void launch_reanchor(int K, const double* pose_old, const double* pose_new, double* vel, int L, const int* ref, double* lm,
                      hipStream_t st);
 

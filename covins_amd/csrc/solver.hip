@@ -2084,6 +2084,92 @@ extern "C" int covgpu_relpose_batch(covgpu_context* c, const covgpu_relpose_batc
   return COVGPU_OK;
 }
 
+extern "C" void covgpu_default_ransac_opts(covgpu_ransac_opts* o) {
+  if (!o) return;
+  o->min_inliers = 6; o->max_iterations = 300; o->probability = 0.99; o->threshold = 25.0; o->seed = 0;   // config_backend.yaml:85-88
+}
+
+extern "C" int covgpu_abspose_ransac_batch(covgpu_context* c, const covgpu_abspose_batch_t* bt, const covgpu_ransac_opts* opts) {
+  HIPCHK(hipSetDevice(c->device));
+  auto bad = [](const char* m) { g_err = std::string("covgpu_abspose_ransac_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
+  if (!bt || !opts) return bad("NULL batch or options");
+  if (bt->num < 0) return bad("num < 0");
+  if (opts->max_iterations <= 0) return bad("max_iterations <= 0");
+  if (opts->max_iterations > 100000) return bad("max_iterations > 100000 (a candidate makes up to 11 max_iterations draws in one launch)");
+  if (!(opts->probability > 0.0 && opts->probability < 1.0)) return bad("probability outside (0, 1)");
+  if (!std::isfinite(opts->threshold) || !(opts->threshold > 0.0)) return bad("threshold not finite or not positive");
+  const int B = bt->num;
+  if (B == 0) return COVGPU_OK;
+  if (!bt->corr_ptr || !bt->T_wc || !bt->inliers) return bad("NULL array");
+  if (bt->corr_ptr[0] != 0) return bad("corr_ptr[0] != 0");
+  int max_n = 0;
+  for (int b = 0; b < B; ++b) {
+    if (bt->corr_ptr[b + 1] < bt->corr_ptr[b]) return bad("corr_ptr not monotone");
+    max_n = std::max(max_n, bt->corr_ptr[b + 1] - bt->corr_ptr[b]);
+  }
+  const size_t C = (size_t)bt->corr_ptr[B];
+  if (C > 0 && (!bt->bearing || !bt->point_w || !bt->sigma_angle || !bt->inlier)) return bad("NULL correspondence array");
+  for (size_t i = 0; i < 3 * C; ++i)
+    if (!std::isfinite(bt->bearing[i]) || !std::isfinite(bt->point_w[i])) return bad("non-finite bearing or point");
+  std::vector<uint64_t> seeds(B);
+  for (int b = 0; b < B; ++b) seeds[b] = bt->seed ? bt->seed[b] : opts->seed + (uint64_t)b;
+  std::vector<void*> tmp;
+  auto up = [&](const void* h, size_t bytes, void** d) -> hipError_t {
+    hipError_t e = hipMalloc(d, bytes ? bytes : 8);
+    if (e != hipSuccess) return e;
+    tmp.push_back(*d);
+    return bytes ? hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, c->st) : hipSuccess;
+  };
+  struct Free { std::vector<void*>& v; ~Free() { for (void* p : v) (void)hipFree(p); } } free_tmp{tmp};
+  int *dptr_ = nullptr, *din = nullptr, *dit = nullptr, *dbd = nullptr;
+  double *df = nullptr, *dP = nullptr, *ds = nullptr, *dT = nullptr;
+  unsigned long long* dseed = nullptr;
+  unsigned char* dmask = nullptr;
+  HIPCHK(up(bt->corr_ptr, sizeof(int) * (B + 1), (void**)&dptr_));
+  HIPCHK(up(bt->bearing, 24 * C, (void**)&df)); HIPCHK(up(bt->point_w, 24 * C, (void**)&dP)); HIPCHK(up(bt->sigma_angle, 8 * C, (void**)&ds));
+  HIPCHK(up(seeds.data(), 8 * (size_t)B, (void**)&dseed));
+  HIPCHK(up(bt->T_wc, 56 * (size_t)B, (void**)&dT));   // untouched rows come back as they went
+  HIPCHK(hipMalloc((void**)&dmask, C ? C : 8)); tmp.push_back(dmask);
+  HIPCHK(hipMalloc((void**)&din, 4 * (size_t)B)); tmp.push_back(din);
+  HIPCHK(hipMalloc((void**)&dit, 4 * (size_t)B)); tmp.push_back(dit);
+  HIPCHK(hipMalloc((void**)&dbd, 4 * (size_t)B)); tmp.push_back(dbd);
+  launch_abspose(B, dptr_, df, dP, ds, dseed, dT, dmask, din, dit, dbd, opts->min_inliers, opts->max_iterations, opts->probability, opts->threshold,
+                 max_n, c->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(bt->T_wc, dT, 56 * (size_t)B, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(bt->inliers, din, 4 * (size_t)B, hipMemcpyDeviceToHost, c->st));
+  if (bt->iterations) HIPCHK(hipMemcpyAsync(bt->iterations, dit, 4 * (size_t)B, hipMemcpyDeviceToHost, c->st));
+  if (bt->best_draw) HIPCHK(hipMemcpyAsync(bt->best_draw, dbd, 4 * (size_t)B, hipMemcpyDeviceToHost, c->st));
+  if (C) HIPCHK(hipMemcpyAsync(bt->inlier, dmask, C, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return COVGPU_OK;
+}
+
+extern "C" int covgpu_p3p_batch(covgpu_context* c, int32_t n, const double* f, const double* P, double* T, int32_t* nsol, int32_t* chosen) {
+  HIPCHK(hipSetDevice(c->device));
+  if (n < 0) { g_err = "covgpu_p3p_batch: n < 0"; return COVGPU_ERR_INVALID_ARG; }
+  if (n == 0) return COVGPU_OK;
+  if (!f || !P || !T || !nsol || !chosen) { g_err = "covgpu_p3p_batch: NULL array"; return COVGPU_ERR_INVALID_ARG; }
+  for (size_t i = 0; i < (size_t)12 * n; ++i)
+    if (!std::isfinite(f[i]) || !std::isfinite(P[i])) { g_err = "covgpu_p3p_batch: non-finite bearing or point"; return COVGPU_ERR_INVALID_ARG; }
+  std::vector<void*> tmp;
+  struct Free { std::vector<void*>& v; ~Free() { for (void* p : v) (void)hipFree(p); } } free_tmp{tmp};
+  auto A = [&](void** p, size_t bytes) { hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) tmp.push_back(*p); return e; };
+  double *df, *dP, *dT; int *dn, *dc;
+  HIPCHK(A((void**)&df, 96 * (size_t)n)); HIPCHK(A((void**)&dP, 96 * (size_t)n)); HIPCHK(A((void**)&dT, 224 * (size_t)n));
+  HIPCHK(A((void**)&dn, 4 * (size_t)n)); HIPCHK(A((void**)&dc, 4 * (size_t)n));
+  HIPCHK(hipMemcpyAsync(df, f, 96 * (size_t)n, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipMemcpyAsync(dP, P, 96 * (size_t)n, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipMemsetAsync(dT, 0, 224 * (size_t)n, c->st));
+  launch_p3p(n, df, dP, dT, dn, dc, c->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(T, dT, 224 * (size_t)n, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(nsol, dn, 4 * (size_t)n, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(chosen, dc, 4 * (size_t)n, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return COVGPU_OK;
+}
+
 extern "C" int covgpu_pgo_reanchor(covgpu_context* c, int32_t K, const double* pose_old, const double* pose_new, double* velocity, int32_t L,
                                    const int32_t* ref_kf, double* lm_pos) {
   HIPCHK(hipSetDevice(c->device));

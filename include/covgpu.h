@@ -414,6 +414,32 @@ void covgpu_get_profile(covgpu_context* ctx, double* out8);
  * [11] flops of one multifrontal factorisation of the resident problem (dense count on the fronts' real sizes), [12..15] 0 */
 void covgpu_get_profile2(covgpu_context* ctx, double* out16);
 
+
+/* ---------------------------------------------------------------- loop-candidate geometric verification
+ * Batched Se3Solver::projectiveAlignment (Se3Solver.cpp:59-110): per candidate b an opengv-style RANSAC (GP3P with one camera at zero
+ * offset = central P3P, 4th correspondence picks the solution) over the correspondences [corr_ptr[b], corr_ptr[b+1]):
+ * unit bearing f_i in the query camera, world point P_i, sigma_angle_i = sqrt(2) s^2 / fu^2 with s = 0.8 (octave + 1), fu = (fx + fy) / 2.
+ * Score ||normalize(R^T (P_i - t)) - f_i||^2 / sigma_angle_i, inlier iff score < threshold. Draw d, slot k uses
+ * splitmix64(seed_b + 4 d + k) in a partial Fisher-Yates over [0, n). One workgroup per candidate, one launch per call.
+ * max_iterations must lie in 1..100000 (a candidate makes at most 11 max_iterations + 1 draws). */
+typedef struct covgpu_abspose_batch_t {
+  int32_t num;              const int32_t* corr_ptr;     /* [num+1] */
+  const double* bearing;    /* [C][3] */   const double* point_w; /* [C][3] */   const double* sigma_angle; /* [C] */
+  const uint64_t* seed;     /* [num] or NULL = opts seed + b */
+  double*  T_wc;            /* [num][7] out, qx qy qz qw x y z; untouched when inliers[b] == 0 */
+  uint8_t* inlier;          /* [C] out */
+  int32_t* inliers;         /* [num] out: inlier count, 0 = no transform found */
+  int32_t* iterations;      /* [num] out or NULL */
+  int32_t* best_draw;       /* [num] out or NULL: draw index of the model (for parity tests) */
+} covgpu_abspose_batch_t;
+typedef struct { int32_t min_inliers; int32_t max_iterations; double probability; double threshold; uint64_t seed; } covgpu_ransac_opts;
+void covgpu_default_ransac_opts(covgpu_ransac_opts*);   /* 6, 300, 0.99, 25.0, 0 (config_backend.yaml:85-88) */
+int  covgpu_abspose_ransac_batch(covgpu_context*, const covgpu_abspose_batch_t*, const covgpu_ransac_opts*);
+/* test entry point: the P3P of every quadruple on its first three correspondences, all solutions (ascending v = s3/s1), and the one the
+ * 4th correspondence picks (-1: none) */
+int  covgpu_p3p_batch(covgpu_context*, int32_t n, const double* f /*[n][4][3]*/, const double* P /*[n][4][3]*/,
+                      double* T /*[n][4][7]*/, int32_t* nsol /*[n]*/, int32_t* chosen /*[n]*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,13 @@ struct Params {
   // map). NOT reproduced: Clean's second loop over every keyframe's landmark vector (:719-729), which only finds landmarks that a keyframe
   // references but the map does not list — none in a consistent map. tests/test_facade.py compares the two ends.
   int device_clean = 0;
+  // loop-candidate geometric verification, Se3Solver (config_backend.yaml:85-88: placerec.ransac.*). ransac_probability: the reference's
+  // Se3Solver stores its ransacProb but never hands it to opengv, which runs with its own default 0.99 — the facade's Se3Solver uses this
+  // value, not the constructor's, so the default reproduces the reference
+  int ransac_min_inliers = 6;
+  double ransac_probability = 0.99;
+  int ransac_max_iterations = 300;
+  double ransac_class_threshold = 25;
   // (IMU noise and gravity are NOT parameters: every IMU factor carries its keyframe's own VICalibration values,
   //  Types::imu_calib, as the reference's per-keyframe preintegrators do — keyframe_be.cpp:187-195.)
 };
@@ -96,6 +103,30 @@ inline auto camera_model(const K& kf, int* model, double* xi, int) -> decltype(T
 }
 template <class Types, class K>
 inline bool camera_model(const K&, int* model, double* xi, long) { *model = COVGPU_CAM_PINHOLE; *xi = 0.0; return true; }
+
+// unit bearing of feature i of a keyframe through the optional trait Types::bearing(keyframe, i, out3) (false: i is past the keyframe's
+// bearings_); without it keyframe_be.cpp:209-218 on keypoints_undistorted_ and the pinhole intrinsics of Types::camera
+template <class Types, class K>
+inline auto bearing(const K& kf, size_t i, double* out, int) -> decltype(Types::bearing(kf, i, out), bool()) {
+  return Types::bearing(kf, i, out);
+}
+template <class Types, class K>
+inline bool bearing(const K& kf, size_t i, double* out, long) {
+  if (i >= kf.keypoints_undistorted_.size()) return false;
+  double intr[4], dist[4]; int dt = 0;
+  if (!Types::camera(kf, intr, dist, &dt)) return false;
+  const double x = (kf.keypoints_undistorted_[i][0] - intr[2]) * (1.0 / intr[0]), y = (kf.keypoints_undistorted_[i][1] - intr[3]) * (1.0 / intr[1]);
+  const double n = std::sqrt(x * x + y * y + 1.0);
+  out[0] = x / n; out[1] = y / n; out[2] = 1.0 / n;
+  return true;
+}
+
+// RANSAC seed of a (query, candidate) keyframe pair from their ids: a candidate's draws do not depend on the batch it is verified in
+template <class K>
+inline uint64_t abspose_seed(const K* query, const K* cand) {
+  auto id = [](const K* k) -> uint64_t { return k ? ((uint64_t)k->id_.first << 20) ^ (uint64_t)k->id_.second : 0; };
+  return id(query) * 0x9E3779B97F4A7C15ull + id(cand);
+}
 
 inline void fatal(const char* msg) {  // the reference prints COUTFATAL and exit(-1) (e.g. optimization_be.cpp:113-114)
   std::fprintf(stderr, "[covins_gpu] FATAL: %s\n", msg);
@@ -860,6 +891,107 @@ class OptimizationT {
     jobs[0].kf1 = kf1; jobs[0].kf2 = kf2; jobs[0].matches1 = &matches1; jobs[0].T12 = &T12;
     OptimizeRelativePoseBatch(jobs);
     return jobs[0].result;
+  }
+};
+
+// ---- Se3Solver (Se3Solver.h / Se3Solver.cpp:59-110): the 3D-2D RANSAC of a loop candidate, batched (covgpu_abspose_ransac_batch,
+//      DESIGN.md §4.10). Drop-in for covins::Se3Solver: same constructor, setRansacParams and projectiveAlignment; Tws is the query
+//      camera in the world (opengv's transformation_t, what placerec_be.cpp:132 uses as Twc1). ProjectiveAlignmentBatch verifies many
+//      candidates with ONE library call per distinct threshold (placerec_be.cpp:116-139 runs them one by one).
+template <class Types>
+class Se3SolverT {
+ public:
+  using Keyframe = typename Types::Keyframe;
+  using Landmark = typename Types::Landmark;
+  using KeyframePtr = std::shared_ptr<Keyframe>;
+  using LandmarkPtr = std::shared_ptr<Landmark>;
+  using LandmarkVector = std::vector<LandmarkPtr>;
+  using TransformType = typename Types::TransformType;
+
+  // the reference's defaults (Se3Solver.h); callers pass covins_params::placerec::ransac::* (Params::ransac_*)
+  Se3SolverT(const size_t minInliers = 30, const double ransacProb = 0.999, const size_t maxIter = 300)
+      : mMinInliers(minInliers), mRansacProb(ransacProb), mMaxIter(maxIter) {}
+  void setRansacParams(const int minInliers, const double ransacProb, const int maxIter) {
+    mMinInliers = (size_t)minInliers; mRansacProb = ransacProb; mMaxIter = (size_t)maxIter;
+  }
+
+  // one loop candidate: matches[i] = the landmark matched to feature i of kf (NULL: none). kf_candidate only seeds the draws.
+  struct AbsPoseJob {
+    KeyframePtr kf, kf_candidate;
+    LandmarkVector* matches = nullptr;
+    double threshold = 25.0;
+    TransformType* Tws = nullptr;
+    bool found = false;   // out: projectiveAlignment's return value
+    int inliers = 0;      // out
+  };
+
+  void ProjectiveAlignmentBatch(std::vector<AbsPoseJob>& jobs) const {
+    std::vector<double> ths;
+    for (const AbsPoseJob& j : jobs) if (std::find(ths.begin(), ths.end(), j.threshold) == ths.end()) ths.push_back(j.threshold);
+    for (double th : ths) run(jobs, th);
+  }
+
+  bool projectiveAlignment(const KeyframePtr keyframePtr, LandmarkVector& mapPointMatches, const double threshold, TransformType& Tws) const {
+    std::vector<AbsPoseJob> jobs(1);
+    jobs[0].kf = keyframePtr; jobs[0].matches = &mapPointMatches; jobs[0].threshold = threshold; jobs[0].Tws = &Tws;
+    ProjectiveAlignmentBatch(jobs);
+    return jobs[0].found;
+  }
+
+ private:
+  size_t mMinInliers;
+  double mRansacProb;   // stored, not used: see Params::ransac_probability
+  size_t mMaxIter;
+
+  void run(std::vector<AbsPoseJob>& jobs, double th) const {
+    std::vector<size_t> sel;
+    for (size_t b = 0; b < jobs.size(); ++b) if (jobs[b].threshold == th) sel.push_back(b);
+    const size_t B = sel.size();
+    std::vector<int32_t> ptr(1, 0);
+    std::vector<double> f, P, sg, T(7 * B, 0.0);
+    std::vector<uint64_t> seed(B);
+    std::vector<std::vector<size_t>> indMap(B);
+    for (size_t s = 0; s < B; ++s) {
+      AbsPoseJob& j = jobs[sel[s]];
+      const LandmarkVector& m = *j.matches;
+      for (size_t i = 0; i < m.size(); ++i) if (m[i] && !m[i]->IsInvalid()) indMap[s].push_back(i);   // Se3Solver.cpp:66-75
+      double intr[4], dist[4]; int dt = 0;
+      if (!Types::camera(*j.kf, intr, dist, &dt)) detail::fatal("Unknown projection / distortion type.");
+      const double fu = (intr[0] + intr[1]) / 2.0;
+      // FrameNoncentralAbsoluteAdapter: i < min(bearings_.size(), matches.size()), null / invalid matches skipped
+      for (size_t i = 0; i < m.size(); ++i) {
+        double b3[3];
+        if (!detail::bearing<Types>(*j.kf, i, b3, 0)) break;
+        if (!m[i] || m[i]->IsInvalid()) continue;
+        const auto pw = m[i]->GetWorldPos();
+        const double sd = 0.8 * ((double)j.kf->keypoints_aors_[i][1] + 1);
+        f.insert(f.end(), b3, b3 + 3);
+        for (int k = 0; k < 3; ++k) P.push_back(pw[k]);
+        sg.push_back(std::sqrt(2) * sd * sd / (fu * fu));
+      }
+      ptr.push_back((int32_t)sg.size());
+      seed[s] = detail::abspose_seed(j.kf.get(), j.kf_candidate.get());
+    }
+    std::vector<uint8_t> mask(sg.size() + 1);
+    std::vector<int32_t> inl(B);
+    covgpu_abspose_batch_t bt{};
+    bt.num = (int32_t)B; bt.corr_ptr = ptr.data(); bt.bearing = f.data(); bt.point_w = P.data(); bt.sigma_angle = sg.data(); bt.seed = seed.data();
+    bt.T_wc = T.data(); bt.inlier = mask.data(); bt.inliers = inl.data();
+    covgpu_ransac_opts o;
+    covgpu_default_ransac_opts(&o);
+    o.min_inliers = (int32_t)mMinInliers; o.max_iterations = (int32_t)mMaxIter; o.threshold = th;
+    o.probability = OptimizationT<Types>::params().ransac_probability;
+    if (covgpu_abspose_ransac_batch(OptimizationT<Types>::Context(), &bt, &o) != COVGPU_OK) detail::fatal(covgpu_last_error());
+    for (size_t s = 0; s < B; ++s) {
+      AbsPoseJob& j = jobs[sel[s]];
+      j.inliers = inl[s]; j.found = inl[s] > 0;
+      if (!j.found) continue;                                        // :81-83: matches and Tws untouched
+      LandmarkVector& m = *j.matches;
+      std::vector<bool> keep(m.size(), false);
+      for (int32_t c = ptr[s]; c < ptr[s + 1]; ++c) if (mask[c]) keep[indMap[s][c - ptr[s]]] = true;   // :85-93
+      for (size_t i = 0; i < m.size(); ++i) if (!keep[i]) m[i].reset();                               // :94-98
+      detail::pose_to_transform(&T[7 * s], *j.Tws);                                                   // :100-102
+    }
   }
 };
 
