@@ -10,11 +10,16 @@ Inputs are uploaded to HBM before the timed region; every step restarts from the
 --gpus N (one process per GPU) the ONE map is sharded by subtree of the elimination tree and every rank runs the same
 iterations (strong scaling); the collectives are issued by libcovgpu over RCCL.
 
-The timed region runs WITHOUT profiling events; one extra, un-timed step with profiling on supplies the phase times
-and the per-launch kernel durations of the `roofline` object. `cpu_baseline` runs the oracle (CPU port of the same
-algorithm on all host threads; reduced system by the threaded multifrontal port) on THE SAME workload in the same run, three
-repetitions, median, and
-`delta_ate_gpu_cpu_m` compares the two final trajectories (north star: within 1e-3 m).
+A plain run does only what the headline figure needs: it builds and uploads the map, runs the warm-up and the timed steps,
+writes --dump-outputs if asked, and prints the metric line (value, ms_per_step, the map's sizes and layout, the last step's
+costs). The timed region runs WITHOUT profiling events.
+
+--full adds, after the timed region, everything else the benchmark measures: the sustained leg, one extra, un-timed step
+with profiling on (phase times, the per-launch kernel durations of the `roofline` objects), the trajectory errors, the
+whole-call and pose-graph side figures, the C++ facade call, the configs[4] leg, and `cpu_baseline`: the oracle (CPU port
+of the same algorithm on all host threads; reduced system by the threaded multifrontal port) on THE SAME workload in the
+same run, three repetitions, median, with `delta_ate_gpu_cpu_m` comparing the two final trajectories (north star: within
+1e-3 m). The options that shape those legs (--no-cpu-baseline, --no-e2e, --sustain-s, --a12-leg, ...) act under --full only.
 
 Prints ONE JSON line on rank 0.
 """
@@ -211,6 +216,15 @@ def run_a12_leg(args, rank, local_rank, world, strategy, store):
         ctx.close()
 
 
+def emit(out):
+    """Prints the result line. RCCL prints its version banner through C stdio, which would otherwise be flushed AFTER this line
+    at exit: flush it first so that the JSON line is the last thing on stdout."""
+    import ctypes
+    ctypes.CDLL(None).fflush(None)
+    sys.stdout.flush()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -219,16 +233,19 @@ def main():
     ap.add_argument("--workload", default="mh12345", help="mh12345 (BASELINE metric) | mh123 | mh01 | small | a12 (configs[4] at its stated 12 x 1667 keyframes / 2M landmarks) | a12x1000 | a12x500")
     ap.add_argument("--strategy", default="dogleg", choices=["dogleg", "lm"])
     ap.add_argument("--iterations", type=int, default=10, help="trust-region iteration cap per step (reference: 10)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every other leg of the benchmark (profiled step and "
+                    "rooflines, trajectory errors, sustained leg, whole-call / pose-graph / C++ facade figures, configs[4] leg, CPU baselines); "
+                    "off: the headline line only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baselines (--full)")
     ap.add_argument("--force-shard", action="store_true", help="run the agent-sharded path (plan, sub-problem, RCCL collectives) even on ONE GPU")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the whole-call timing after the timed region (profiling runs)")
-    ap.add_argument("--a12-steps", type=int, default=5, help="timed steps of the a12 leg (after one warm-up)")
-    ap.add_argument("--no-a12-cpu", action="store_true", help="skip the a12 leg's one-iteration CPU baseline (about a minute of host time)")
+    ap.add_argument("--no-e2e", action="store_true", help="skip the whole-call timing after the timed region (--full; profiling runs)")
+    ap.add_argument("--a12-steps", type=int, default=5, help="timed steps of the a12 leg (after one warm-up; --full)")
+    ap.add_argument("--no-a12-cpu", action="store_true", help="skip the a12 leg's one-iteration CPU baseline (--full; about a minute of host time)")
     ap.add_argument("--a12-leg", type=int, default=-1, help="after the metric's workload, also time BASELINE configs[4] at its stated size (12 x 1667 keyframes, 2M landmarks) "
-                    "on the same ranks and report it as `a12_leg` with rooflines of its own (1 / 0; default: on for the metric's workload at any --gpus — the "
+                    "on the same ranks and report it as `a12_leg` with rooflines of its own (1 / 0; default: on under --full for the metric's workload at any --gpus — the "
                     "configuration the north star names for the scaling curve; ~70 s of map generation + upload, 3 + 1 steps)")
     ap.add_argument("--sustain-s", type=float, default=8.0, help="after the timed region, repeat the same steps back to back for about this many seconds, "
-                    "un-timed in `value` and reported as `sustained`: long enough for an external GPU-utilisation sampler to see the device busy (0: off)")
+                    "un-timed in `value` and reported as `sustained` (--full): long enough for an external GPU-utilisation sampler to see the device busy (0: off)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (optimised poses, "
                     "speed-bias, landmarks, cost trace, result) as float64 DIR/<name>.npy, at most 64 MB in all; the inputs are the same on every run")
     args = ap.parse_args()
@@ -254,7 +271,7 @@ def main():
     m = synth.make_map(cfg)
     full, _ = mapdata.flatten_gba(m, visual_only=False, loop_loss=True)
     pgo_prm = mapdata.PgoParams()
-    pgo_prob, _ = mapdata.flatten_pgo(m, {}, pgo_prm)  # the pose graph of the same (still drifted) map, for the side figure below
+    pgo_prob = mapdata.flatten_pgo(m, {}, pgo_prm)[0] if args.full else None  # the pose graph of the same (still drifted) map, for the side figure below
     opt = backend.default_options(strategy=strategy, max_iterations=args.iterations, device=local_rank)
     ctx = backend.Context(local_rank)
     plan, keep = None, None
@@ -304,6 +321,46 @@ def main():
         sol_timed = assemble(ctx.download(), PrefixStore("timed/", keep[0]) if world > 1 else None)
         if rank == 0:
             dump_outputs(args.dump_outputs, sol_timed, res)
+    # ---- the headline line: the timed steps and the map they ran on (nothing here runs on the GPU)
+    lay = ctx.layout()
+    out = None
+    if rank == 0:
+        k_free = int(full.K - full.kf_fixed.sum())
+        out = {
+            "metric": "GBA iterations/sec, 5-agent EuRoC merged map" if args.workload == "mh12345" else f"GBA iterations/sec, {args.workload}",
+            "value": iters_all / dt, "unit": "iterations/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+            "data": ("synthetic map on the EuRoC ground-truth trajectories MH01-05 (orb_slam3/evaluation/Ground_truth/EuRoC_left_cam), EuRoC calibration; "
+                     "IMU of agents 3-5: the RECORDED 200 Hz samples (EuRoC_IMU/MH03-05.txt), agents 1-2: synthesised from the trajectory (no recording in the "
+                     "tree); landmarks, pixel measurements (1 px noise), drift of the initial estimate and loop constraints synthetic") if args.workload == "mh12345"
+                    else "synthetic (covins_amd/synth.py; recorded EuRoC IMU where an agent runs MH03-05 at its own keyframe times)",
+            "config": {"workload": f"{args.workload}: {len(cfg.agents)}-agent EuRoC MH-shaped merged map, visual-inertial GBA "
+                                   f"(K={full.K} keyframes, L={full.L} landmarks, O={full.O} observations, I={full.I} IMU factors, "
+                                   f"E={full.E} loop edges; reduced camera system 15K={15 * full.K}: "
+                                   + (f"multifrontal MFMA Cholesky over a nested-dissection tree of {lay['nd_fronts']} fronts in {lay['nd_levels']} levels, "
+                                      f"{lay['nd_serial_panels']} serial 256-column panels, root front of order {lay['nd_root_order']})" if lay["nd_fronts"] else
+                                      (f"speed-bias chains eliminated block-tridiagonally, pose system 6K={6 * full.K} as {lay['blocks']} agent blocks + "
+                                       f"{lay['border_kf']} shared keyframes)" if lay["arrow"] else f"dense MFMA Cholesky on the 6K={6 * full.K} pose system)")),
+                       "layout": lay,
+                       "strategy": args.strategy, "iterations_per_step": args.iterations,
+                       "sharding": ("none (1 GPU)" if not sharded else
+                                    f"ONE map sharded over {world} ranks: {plan.subtrees} subtrees of the elimination tree dealt to the ranks, "
+                                    f"{lay['top_unknowns']} scalar unknowns in the replicated top ({int((plan.pose_rank < 0).sum())} shared keyframe poses); "
+                                    f"{'RCCL' if world > 1 or keep == ('rccl',) else 'in-process one-rank group'} all-reduce (issued by libcovgpu on its own stream) of the top fronts + right-hand sides + gradient rows ({lay['allreduce_kib'] / 1024:.1f} MiB per linear solve) "
+                                    f"and 3 scalar exchanges per iteration: {shard_stats['collectives']} collectives, {shard_stats['bytes'] / 1e6:.1f} MB on rank 0 "
+                                    f"in the timed steps + warm-up")},
+            "kf_per_s": k_free * iters_all / dt,
+            "iterations_executed": iters_all,
+            "final_cost": res.final_cost, "initial_cost": res.initial_cost,
+            "upload_s_not_in_value": t_up,  # host layout build (chains, covisible-pair lists) + H2D; PCIe-inclusive cost of one call
+        }
+    if not args.full:
+        distrib.barrier(ctx, sharded)
+        ctx.close()
+        if rank == 0:
+            emit(out)
+        return
     # sustained leg (not `value`): the same step repeated for --sustain-s seconds, so that a sampler outside this process (rocm-smi every
     # few seconds) sees the GPU busy — the timed region above is 20 steps x ~35 ms and falls between two samples
     sustained = None
@@ -322,7 +379,6 @@ def main():
     ctx.solve_resident(opt)
     prof = ctx.profile()
     ctx.set_profiling(False)
-    lay = ctx.layout()
     # sharded: assemble the optimised map from the ranks' pieces (small: poses, speed-bias, landmark positions)
     sol = assemble(ctx.download(), keep[0] if world > 1 else None)
     prob = full
@@ -343,8 +399,6 @@ def main():
         except Exception:
             pass
         truth = m.truth["kf_pose"][:, 4:]
-        n = 15 * prob.K
-        k_free = int(prob.K - prob.kf_fixed.sum())
         syrk_tflops = prof["syrk_flops"] / (prof["syrk_ms"] * 1e-3) / 1e12 if prof["syrk_ms"] > 0 else 0.0
         # algorithmic HBM bytes of one linearise+Schur pass (first, second and third terms)
         nnzS = prof["offdiag_blocks"] + prob.K  # covisible keyframe pairs incl. the diagonal
@@ -357,36 +411,9 @@ def main():
         potrf_tflops = prof["potrf_flops"] / (prof["potrf_ms"] * 1e-3) / 1e12 if prof["potrf_ms"] > 0 else 0.0
         n_lin = max(prof["n_factor"], 1)
         t_ideal_ms = (b_iter / (HBM_PEAK_GBS * 1e9) + prof["plan_flops"] / (FP64_MATRIX_PEAK_TFLOPS * 1e12)) * 1e3
-        out = {
-            "metric": "GBA iterations/sec, 5-agent EuRoC merged map" if args.workload == "mh12345" else f"GBA iterations/sec, {args.workload}",
-            "value": iters_all / dt, "unit": "iterations/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "data": ("synthetic map on the EuRoC ground-truth trajectories MH01-05 (orb_slam3/evaluation/Ground_truth/EuRoC_left_cam), EuRoC calibration; "
-                     "IMU of agents 3-5: the RECORDED 200 Hz samples (EuRoC_IMU/MH03-05.txt), agents 1-2: synthesised from the trajectory (no recording in the "
-                     "tree); landmarks, pixel measurements (1 px noise), drift of the initial estimate and loop constraints synthetic") if args.workload == "mh12345"
-                    else "synthetic (covins_amd/synth.py; recorded EuRoC IMU where an agent runs MH03-05 at its own keyframe times)",
-            "timed_region": "profiling events off; phase / kernel figures below come from one extra un-timed step",
-            "config": {"workload": f"{args.workload}: {len(cfg.agents)}-agent EuRoC MH-shaped merged map, visual-inertial GBA "
-                                   f"(K={prob.K} keyframes, L={prob.L} landmarks, O={prob.O} observations, I={prob.I} IMU factors, "
-                                   f"E={prob.E} loop edges; reduced camera system 15K={n}: "
-                                   + (f"multifrontal MFMA Cholesky over a nested-dissection tree of {lay['nd_fronts']} fronts in {lay['nd_levels']} levels, "
-                                      f"{lay['nd_serial_panels']} serial 256-column panels, root front of order {lay['nd_root_order']})" if lay["nd_fronts"] else
-                                      (f"speed-bias chains eliminated block-tridiagonally, pose system 6K={6 * prob.K} as {lay['blocks']} agent blocks + "
-                                       f"{lay['border_kf']} shared keyframes)" if lay["arrow"] else f"dense MFMA Cholesky on the 6K={6 * prob.K} pose system)")),
-                       "layout": lay,
-                       "nnzS_fill": (2 * prof["offdiag_blocks"] + prob.K) / float(prob.K) ** 2,
-                       "strategy": args.strategy, "iterations_per_step": args.iterations,
-                       "sharding": ("none (1 GPU)" if not sharded else
-                                    f"ONE map sharded over {world} ranks: {plan.subtrees} subtrees of the elimination tree dealt to the ranks, "
-                                    f"{lay['top_unknowns']} scalar unknowns in the replicated top ({int((plan.pose_rank < 0).sum())} shared keyframe poses); "
-                                    f"{'RCCL' if world > 1 or keep == ('rccl',) else 'in-process one-rank group'} all-reduce (issued by libcovgpu on its own stream) of the top fronts + right-hand sides + gradient rows ({lay['allreduce_kib'] / 1024:.1f} MiB per linear solve) "
-                                    f"and 3 scalar exchanges per iteration: {shard_stats['collectives']} collectives, {shard_stats['bytes'] / 1e6:.1f} MB on rank 0 "
-                                    f"in the timed steps + warm-up")},
-            "kf_per_s": k_free * iters_all / dt,
-            "iterations_executed": iters_all,
-            "final_cost": res.final_cost, "initial_cost": res.initial_cost,
-            "upload_s_not_in_value": t_up,  # host layout build (chains, covisible-pair lists) + H2D; PCIe-inclusive cost of one call
+        out["timed_region"] = "profiling events off; phase / kernel figures below come from one extra un-timed step"
+        out["config"]["nnzS_fill"] = (2 * prof["offdiag_blocks"] + prob.K) / float(prob.K) ** 2
+        out.update({
             "ate_rmse_m": {"initial": synth.ate_rmse(prob.kf_pose[:, 4:], truth), "final": synth.ate_rmse(sol.kf_pose[:, 4:], truth),
                            "initial_sim3": synth.ate_rmse(prob.kf_pose[:, 4:], truth, with_scale=True),
                            "final_sim3": synth.ate_rmse(sol.kf_pose[:, 4:], truth, with_scale=True)},  # evo_ape -va / -vas
@@ -433,7 +460,7 @@ def main():
                                        "underneath) against SURVEY.md 8(d)'s algorithmic bytes (inputs once, H/g blocks, S blocks once). The pass "
                                        "really moves more: the fill and the per-observation records of the atomic-free, bit-reproducible build "
                                        "(DESIGN.md 4.1, 6)"},
-        }
+        })
         out["roofline_build"]["frac"] = out["roofline_build"]["achieved"] / HBM_PEAK_GBS
         if sustained is not None:
             out["sustained"] = sustained
@@ -535,12 +562,7 @@ def main():
         if rank == 0:
             out["a12_leg"] = a12_leg
     if rank == 0:
-        # RCCL prints its version banner through C stdio, which would otherwise be flushed AFTER this line at exit: flush it
-        # first so that the JSON line is the last thing on stdout
-        import ctypes
-        ctypes.CDLL(None).fflush(None)
-        sys.stdout.flush()
-        print(json.dumps(out), flush=True)
+        emit(out)
 
 
 if __name__ == "__main__":
