@@ -255,6 +255,38 @@ class Context:
         self._check(lib().covgpu_abspose_ransac_batch(self._h, C.byref(s), C.byref(o)))
         return dict(T_wc=T[:max(B, 0)], inlier=mask[:Cn].astype(bool), inliers=inl[:max(B, 0)], iterations=its[:max(B, 0)], best_draw=bd[:max(B, 0)])
 
+    def match_batch(self, sets: dict, set_a, set_b, mode: str = "dense", **opts):
+        """Batched ORB descriptor matching of loop candidates (covgpu_match_batch). `sets`: dict with row_ptr
+        [num_sets+1], desc [rows,32] uint8 and optionally skip [rows] (DENSE only). Job j matches set set_a[j] (query) against set
+        set_b[j]. mode "dense" (LandmarkMatchingAlgorithm + DenseMatcher) or "knn2" (BFMatcher knnMatch k=2 + distance and ratio tests).
+        `opts`: dist_threshold, ratio (defaults: covgpu_default_match_opts). Returns dict(match [sumA] local B row or -1, dist [sumA],
+        nmatches [num_jobs], offset [num_jobs+1] the output rows of job j are offset[j]:offset[j+1])."""
+        m = {"dense": capi.MATCH_DENSE, "knn2": capi.MATCH_KNN2}.get(mode, mode)
+        o = capi.MatchOpts()
+        lib().covgpu_default_match_opts(C.byref(o), int(m) if isinstance(m, int) else -1)
+        for k, v in opts.items():
+            if k not in ("dist_threshold", "ratio"):
+                raise TypeError(f"unknown match option {k}")
+            setattr(o, k, v)
+        ptr = np.ascontiguousarray(sets["row_ptr"], dtype=np.int32)
+        S = len(ptr) - 1
+        desc = np.ascontiguousarray(sets["desc"], dtype=np.uint8).reshape(-1, 32)
+        skip = None if sets.get("skip") is None else np.ascontiguousarray(sets["skip"], dtype=np.uint8)
+        sa = np.ascontiguousarray(set_a, dtype=np.int32).ravel()
+        sb = np.ascontiguousarray(set_b, dtype=np.int32).ravel()
+        J = len(sa)
+        if len(sb) != J:
+            raise ValueError("set_a and set_b differ in length")
+        ok = S >= 0 and np.all((sa >= 0) & (sa < S))
+        nA = (ptr[sa + 1] - ptr[sa]) if ok and J else np.zeros(J, np.int32)
+        off = np.zeros(J + 1, np.int64); off[1:] = np.cumsum(np.maximum(nA, 0))
+        tot = int(off[-1])
+        match = np.full(max(tot, 1), -1, np.int32); dist = np.full(max(tot, 1), -1, np.int32); nm = np.zeros(max(J, 1), np.int32)
+        s = capi.MatchBatch(S, iptr(ptr), desc.ctypes.data_as(capi._bp), None if skip is None else skip.ctypes.data_as(capi._bp), J,
+                            iptr(sa), iptr(sb), iptr(match), iptr(dist), iptr(nm))
+        self._check(lib().covgpu_match_batch(self._h, C.byref(s), C.byref(o)))
+        return dict(match=match[:tot], dist=dist[:tot], nmatches=nm[:J], offset=off)
+
     def p3p_batch(self, f, P):
         """covgpu_p3p_batch: f, P [n,4,3] -> (T [n,4,7] every solution, qx qy qz qw x y z, ascending v = s3/s1; nsol [n]; chosen [n], -1: none)."""
         f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 4, 3)

@@ -209,6 +209,18 @@ class RansacOpts(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+MATCH_DENSE, MATCH_KNN2, MATCH_MAX_ROWS = 0, 1, 4096   # include/covgpu.h
+
+
+class MatchBatch(C.Structure):
+    _fields_ = [("num_sets", C.c_int32), ("row_ptr", _ip), ("desc", _bp), ("skip", _bp), ("num_jobs", C.c_int32), ("set_a", _ip), ("set_b", _ip),
+                ("match", _ip), ("dist", _ip), ("nmatches", _ip)]
+
+
+class MatchOpts(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("dist_threshold", C.c_float), ("ratio", C.c_float)]
+
+
 def declare(lib: C.CDLL, prefix: str) -> None:
     """Attach argtypes/restype for the entry points shared by libcovgpu (prefix 'covgpu_', with a context
     argument) and — test side only — the oracle (prefix 'covo_', no context)."""
@@ -244,6 +256,8 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("default_ransac_opts", [C.POINTER(RansacOpts)], None)
         d("abspose_ransac_batch", [C.c_void_p, C.POINTER(AbsposeBatch), C.POINTER(RansacOpts)])
         d("p3p_batch", [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _ip])
+        d("default_match_opts", [C.POINTER(MatchOpts), C.c_int32], None)
+        d("match_batch", [C.c_void_p, C.POINTER(MatchBatch), C.POINTER(MatchOpts)])
         d("outlier_pass", [C.c_void_p, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])
         d("covisibility", [C.c_void_p, C.c_int32, C.c_int64, _ip, _ip, _ip, C.POINTER(C.c_int64)])
         d("gba_solve_multi", [OP, PP, RP, C.c_int32, _ip, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])

@@ -559,6 +559,12 @@ void launch_abspose(int num, const int* ptr, const double* f, const double* P, c
                     unsigned char* inlier, int* inliers, int* iterations, int* best_draw, int min_inliers, int max_iterations, double probability,
                     double threshold, int max_n, hipStream_t st);
 void launch_p3p(int num, const double* F, const double* P, double* T, int* nsol, int* chosen, hipStream_t st);
+// k_match.hip: batched ORB descriptor matching of loop candidates (DENSE: scan + assignbest replay; KNN2: scan only)
+constexpr int kMatchScanRows = 256;   // query rows per scan workgroup (grid = num_jobs * ceil(max query rows / 256))
+size_t match_assign_lds_bytes(int maxA, int maxB);
+void launch_match(int mode, int num_jobs, int maxA, int maxB, const unsigned char* desc, const unsigned char* skip, const int* row_ptr,
+                  const int* set_a, const int* set_b, const int* out_off, int* lists, int* match, int* dist, int* nmatches, int dcut,
+                  float thr, float ratio, hipStream_t st);
 void launch_reanchor(int K, const double* pose_old, const double* pose_new, double* vel, int L, const int* ref, double* lm,
                      hipStream_t st);
 

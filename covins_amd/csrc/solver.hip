@@ -2170,6 +2170,84 @@ extern "C" int covgpu_p3p_batch(covgpu_context* c, int32_t n, const double* f, c
   return COVGPU_OK;
 }
 
+extern "C" void covgpu_default_match_opts(covgpu_match_opts* o, int32_t mode) {
+  if (!o) return;
+  o->mode = mode;
+  o->dist_threshold = mode == COVGPU_MATCH_KNN2 ? 40.0f : 50.0f;   // img_match_thres (config_backend.yaml:38); LandmarkMatchingAlgorithm(50.0)
+  o->ratio = 0.8f;                                                 // ratio_thres (config_backend.yaml:39), KNN2 only
+}
+
+extern "C" int covgpu_match_batch(covgpu_context* c, const covgpu_match_batch_t* bt, const covgpu_match_opts* opts) {
+  auto bad = [](const char* m) { g_err = std::string("covgpu_match_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
+  if (!c) return bad("NULL context");
+  if (!bt || !opts) return bad("NULL batch or options");
+  if (opts->mode != COVGPU_MATCH_DENSE && opts->mode != COVGPU_MATCH_KNN2) return bad("unknown mode");
+  if (!std::isfinite(opts->dist_threshold) || !(opts->dist_threshold > 0.0f)) return bad("dist_threshold not finite or not positive");
+  if (!std::isfinite(opts->ratio) || !(opts->ratio > 0.0f)) return bad("ratio not finite or not positive");
+  const bool dense = opts->mode == COVGPU_MATCH_DENSE;
+  if (bt->num_sets < 0 || bt->num_jobs < 0) return bad("num_sets or num_jobs < 0");
+  if (!dense && bt->skip) return bad("skip must be NULL in KNN2");
+  if (bt->num_sets > 0 && !bt->row_ptr) return bad("NULL row_ptr");
+  if (bt->num_sets > 0 && bt->row_ptr[0] != 0) return bad("row_ptr[0] != 0");
+  for (int s = 0; s < bt->num_sets; ++s) {
+    if (bt->row_ptr[s + 1] < bt->row_ptr[s]) return bad("row_ptr not monotone");
+    if (bt->row_ptr[s + 1] - bt->row_ptr[s] > COVGPU_MATCH_MAX_ROWS) return bad("a set holds more than COVGPU_MATCH_MAX_ROWS rows");
+  }
+  const size_t R = bt->num_sets > 0 ? (size_t)bt->row_ptr[bt->num_sets] : 0;
+  if (R > 0 && !bt->desc) return bad("NULL desc");
+  const int J = bt->num_jobs;
+  if (J > 0 && (!bt->set_a || !bt->set_b || !bt->nmatches)) return bad("NULL job array");
+  std::vector<int32_t> off(J > 0 ? J : 1, 0);
+  size_t totalA = 0;
+  int maxA = 0, maxB = 0;
+  for (int j = 0; j < J; ++j) {
+    if (bt->set_a[j] < 0 || bt->set_a[j] >= bt->num_sets || bt->set_b[j] < 0 || bt->set_b[j] >= bt->num_sets) return bad("set index out of range");
+    const int nA = bt->row_ptr[bt->set_a[j] + 1] - bt->row_ptr[bt->set_a[j]];
+    off[j] = (int32_t)totalA;
+    totalA += (size_t)nA;
+    if (totalA > (size_t)INT32_MAX) return bad("more than 2^31 - 1 output rows");
+    maxA = std::max(maxA, nA);
+    maxB = std::max(maxB, bt->row_ptr[bt->set_b[j] + 1] - bt->row_ptr[bt->set_b[j]]);
+  }
+  if (totalA > 0 && !bt->match) return bad("NULL match");
+  if (J == 0) return COVGPU_OK;
+  const int tiles = (maxA + kMatchScanRows - 1) / kMatchScanRows;  // scan workgroups per job (launch_match): one 1-D grid of J * tiles
+  if ((int64_t)J * tiles > (int64_t)INT32_MAX) return bad("num_jobs * ceil(max query rows / 256) exceeds 2^31 - 1 workgroups");
+  HIPCHK(hipSetDevice(c->device));                                   // the first device call: every argument is checked above
+  int dcut = 0;                                                    // (float)d < dist_threshold  <=>  d < dcut, for d in 0..256
+  while (dcut <= 256 && (float)dcut < opts->dist_threshold) ++dcut;
+  std::vector<void*> tmp;
+  struct Free { std::vector<void*>& v; ~Free() { for (void* p : v) (void)hipFree(p); } } free_tmp{tmp};
+  auto A = [&](void** p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 16); if (e == hipSuccess) tmp.push_back(*p); return e; };
+  unsigned char *ddesc = nullptr, *dskip = nullptr;
+  int *dptr_ = nullptr, *dsa = nullptr, *dsb = nullptr, *doff = nullptr, *dlist = nullptr, *dmatch = nullptr, *ddist = nullptr, *dn = nullptr;
+  HIPCHK(A((void**)&ddesc, 32 * R));
+  if (R) HIPCHK(hipMemcpyAsync(ddesc, bt->desc, 32 * R, hipMemcpyHostToDevice, c->st));
+  if (dense && bt->skip) {
+    HIPCHK(A((void**)&dskip, R));
+    if (R) HIPCHK(hipMemcpyAsync(dskip, bt->skip, R, hipMemcpyHostToDevice, c->st));
+  }
+  HIPCHK(A((void**)&dptr_, 4 * ((size_t)bt->num_sets + 1)));
+  HIPCHK(hipMemcpyAsync(dptr_, bt->row_ptr, 4 * ((size_t)bt->num_sets + 1), hipMemcpyHostToDevice, c->st));
+  HIPCHK(A((void**)&dsa, 4 * (size_t)J)); HIPCHK(A((void**)&dsb, 4 * (size_t)J)); HIPCHK(A((void**)&doff, 4 * (size_t)J));
+  HIPCHK(hipMemcpyAsync(dsa, bt->set_a, 4 * (size_t)J, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipMemcpyAsync(dsb, bt->set_b, 4 * (size_t)J, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipMemcpyAsync(doff, off.data(), 4 * (size_t)J, hipMemcpyHostToDevice, c->st));
+  if (dense) HIPCHK(A((void**)&dlist, 16 * totalA));
+  HIPCHK(A((void**)&dmatch, 4 * totalA)); HIPCHK(A((void**)&ddist, 4 * totalA)); HIPCHK(A((void**)&dn, 4 * (size_t)J));
+  HIPCHK(hipMemsetAsync(dn, 0, 4 * (size_t)J, c->st));
+  launch_match(opts->mode, J, maxA, maxB, ddesc, dskip, dptr_, dsa, dsb, doff, dlist, dmatch, ddist, dn, dcut, opts->dist_threshold, opts->ratio,
+               c->st);
+  HIPCHK(hipGetLastError());
+  if (totalA) {
+    HIPCHK(hipMemcpyAsync(bt->match, dmatch, 4 * totalA, hipMemcpyDeviceToHost, c->st));
+    if (bt->dist) HIPCHK(hipMemcpyAsync(bt->dist, ddist, 4 * totalA, hipMemcpyDeviceToHost, c->st));
+  }
+  HIPCHK(hipMemcpyAsync(bt->nmatches, dn, 4 * (size_t)J, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return COVGPU_OK;
+}
+
 extern "C" int covgpu_pgo_reanchor(covgpu_context* c, int32_t K, const double* pose_old, const double* pose_new, double* velocity, int32_t L,
                                    const int32_t* ref_kf, double* lm_pos) {
   HIPCHK(hipSetDevice(c->device));

@@ -440,6 +440,40 @@ int  covgpu_abspose_ransac_batch(covgpu_context*, const covgpu_abspose_batch_t*,
 int  covgpu_p3p_batch(covgpu_context*, int32_t n, const double* f /*[n][4][3]*/, const double* P /*[n][4][3]*/,
                       double* T /*[n][4][7]*/, int32_t* nsol /*[n]*/, int32_t* chosen /*[n]*/);
 
+
+/* ---------------------------------------------------------------- loop-candidate descriptor matching
+ * Brute-force Hamming matching of 32-byte ORB descriptors (distance = popcount of eight 32-bit XORs, feature_matcher_be.cpp:49-64),
+ * job j matching the rows of set set_a[j] (query, "A") against those of set set_b[j] (candidate, "B"). Two modes:
+ *  COVGPU_MATCH_DENSE  LandmarkMatchingAlgorithm(dist_threshold) + estd2::DenseMatcher(numBest = 4, no ratio test), placerec_be.cpp:84-90.
+ *    Rows with skip[r] != 0 (keypoint without a valid landmark, LandmarkMatchingAlgorithm::doSetup) take no part. Every A row keeps
+ *    the 4 best (b, d) with d < dist_threshold, B rows scanned in ascending order, a row inserted iff d < list[3].d, at
+ *    std::lower_bound (before equal distances; the last entry drops out). Then DenseMatcher::assignbest is replayed in the
+ *    single-thread order (A rows ascending): a free B row is taken, a held one is stolen on a strictly smaller distance and the loser
+ *    re-assigned from its entry 1. Every held B row is a match (a, b, d); the reference emits them in ascending b.
+ *  COVGPU_MATCH_KNN2   cv::BFMatcher(NORM_HAMMING).knnMatch(k = 2) + distance test + ratio test, placerec_gen_be.cpp:82-114: the two
+ *    nearest train rows by (d, index); A row a matches iff B has >= 2 rows, (float)d1 <= dist_threshold and
+ *    (float)d1 < ratio * (float)d2 in float32. skip must be NULL. Matches are emitted in ascending a.
+ * Outputs of job j start at row offset sum_{j' < j} rows(set_a[j']): match[] = local B row or -1, dist[] = its distance or -1;
+ * nmatches[j] = the number of matches (what ComputeSE3 tests against matches_thres). Every set holds at most COVGPU_MATCH_MAX_ROWS
+ * rows, and num_jobs * ceil(max rows(set_a[j]) / 256) may not exceed 2^31 - 1. All arguments (the context included) are checked
+ * before any device work; zero jobs and empty sets are valid. */
+#define COVGPU_MATCH_DENSE 0
+#define COVGPU_MATCH_KNN2 1
+#define COVGPU_MATCH_MAX_ROWS 4096
+typedef struct covgpu_match_batch_t {
+  int32_t num_sets;         const int32_t* row_ptr;      /* [num_sets+1], monotone, row_ptr[0] == 0 */
+  const uint8_t* desc;      /* [rows][32] */
+  const uint8_t* skip;      /* [rows] or NULL = none; DENSE only (must be NULL in KNN2) */
+  int32_t num_jobs;         const int32_t* set_a;        /* [num_jobs] query set */   const int32_t* set_b; /* [num_jobs] candidate set */
+  int32_t* match;           /* [sum of rows(set_a[j])] out */
+  int32_t* dist;            /* [sum of rows(set_a[j])] out or NULL */
+  int32_t* nmatches;        /* [num_jobs] out */
+} covgpu_match_batch_t;
+typedef struct { int32_t mode; float dist_threshold; float ratio; } covgpu_match_opts;
+/* DENSE: 50 (placerec_be.cpp:85); KNN2: 40, 0.8 (config_backend.yaml:38-39). ratio is read in KNN2 only but must be finite and positive. */
+void covgpu_default_match_opts(covgpu_match_opts*, int32_t mode);
+int  covgpu_match_batch(covgpu_context*, const covgpu_match_batch_t*, const covgpu_match_opts*);
+
 #ifdef __cplusplus
 }
 #endif

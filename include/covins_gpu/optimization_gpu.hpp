@@ -121,6 +121,28 @@ inline bool bearing(const K& kf, size_t i, double* out, long) {
   return true;
 }
 
+// descriptor matrix of a keyframe (which = 0: descriptors_, the ORB rows of its keypoints; 1: descriptors_add_, COVINS-G's) through the
+// optional trait Types::descriptors(keyframe, which, &rows, &data) (false: none); without it the cv::Mat fields rows / data, which hold
+// 32-byte CV_8U rows back to back as ORB extraction leaves them. The keyframe is taken non-const: KeyframeBase's accessors are.
+template <class Types, class K>
+inline auto descriptors(K& kf, int which, int* rows, const uint8_t** data, int)
+    -> decltype(Types::descriptors(kf, which, rows, data), bool()) {
+  return Types::descriptors(kf, which, rows, data);
+}
+template <class Types, class K>
+inline bool descriptors(K& kf, int which, int* rows, const uint8_t** data, long) {
+  const auto& M = which == 0 ? kf.descriptors_ : kf.descriptors_add_;
+  *rows = M.rows; *data = reinterpret_cast<const uint8_t*>(M.data);
+  return true;
+}
+
+// landmark of feature k through the optional trait Types::landmark(keyframe, k); without it KeyframeBase::GetLandmark(k), which COVINS
+// declares non-const (keyframe_base.hpp:124)
+template <class Types, class K>
+inline auto landmark(K& kf, size_t k, int) -> decltype(Types::landmark(kf, k)) { return Types::landmark(kf, k); }
+template <class Types, class K>
+inline auto landmark(K& kf, size_t k, long) -> decltype(kf.GetLandmark((int)k)) { return kf.GetLandmark((int)k); }
+
 // RANSAC seed of a (query, candidate) keyframe pair from their ids: a candidate's draws do not depend on the batch it is verified in
 template <class K>
 inline uint64_t abspose_seed(const K* query, const K* cand) {
@@ -992,6 +1014,76 @@ class Se3SolverT {
       for (size_t i = 0; i < m.size(); ++i) if (!keep[i]) m[i].reset();                               // :94-98
       detail::pose_to_transform(&T[7 * s], *j.Tws);                                                   // :100-102
     }
+  }
+};
+
+
+// ---- descriptor matching of the loop candidates (covgpu_match_batch): ComputeSE3's first step for all candidates of a
+//      query keyframe in ONE library call. MatchLandmarksBatch is COVINS's LandmarkMatchingAlgorithm(50) + estd2::DenseMatcher(8)
+//      over descriptors_ (placerec_be.cpp:84-90; rows without a valid landmark skipped, as LandmarkMatchingAlgorithm::doSetup does);
+//      MatchImagesBatch is COVINS-G's BFMatcher(NORM_HAMMING).knnMatch(k = 2) + distance and ratio tests over descriptors_add_
+//      (placerec_gen_be.cpp:82-114). Each returns, per candidate, the match list in the reference's order (ascending idxB for the
+//      former, ascending idxA for the latter); its size is ComputeSE3's nmatches. Invalid candidates are the caller's to drop first.
+template <class Types>
+class LoopMatcherT {
+ public:
+  using Keyframe = typename Types::Keyframe;
+  using KeyframePtr = std::shared_ptr<Keyframe>;
+  struct Match {   // covins::Match (matcher/MatchingAlgorithm.h): idxA in the query, idxB in the candidate
+    size_t idxA, idxB;
+    double distance;
+  };
+  using Matches = std::vector<Match>;
+
+  static std::vector<Matches> MatchLandmarksBatch(const KeyframePtr& query, const std::vector<KeyframePtr>& candidates, float thr = 50.0f) {
+    covgpu_match_opts o;
+    covgpu_default_match_opts(&o, COVGPU_MATCH_DENSE);
+    o.dist_threshold = thr;
+    return run(query, candidates, o, 0);
+  }
+  static std::vector<Matches> MatchImagesBatch(const KeyframePtr& query, const std::vector<KeyframePtr>& candidates, float img_match_thres = 40.0f,
+                                               float ratio_thres = 0.8f) {
+    covgpu_match_opts o;
+    covgpu_default_match_opts(&o, COVGPU_MATCH_KNN2);
+    o.dist_threshold = img_match_thres; o.ratio = ratio_thres;
+    return run(query, candidates, o, 1);
+  }
+
+ private:
+  static std::vector<Matches> run(const KeyframePtr& query, const std::vector<KeyframePtr>& candidates, const covgpu_match_opts& o, int which) {
+    const bool dense = o.mode == COVGPU_MATCH_DENSE;
+    const size_t J = candidates.size();
+    std::vector<int32_t> ptr(1, 0), sa(J, 0), sb(J);
+    std::vector<uint8_t> desc, skip;
+    auto add = [&](Keyframe& kf) {
+      int rows = 0; const uint8_t* data = nullptr;
+      if (!detail::descriptors<Types>(kf, which, &rows, &data, 0)) rows = 0;
+      desc.insert(desc.end(), data, data + 32 * (size_t)rows);
+      if (dense)
+        for (int k = 0; k < rows; ++k) {
+          const auto lm = detail::landmark<Types>(kf, (size_t)k, 0);
+          skip.push_back(!lm || lm->IsInvalid() ? 1 : 0);
+        }
+      ptr.push_back(ptr.back() + rows);
+    };
+    add(*query);
+    for (size_t j = 0; j < J; ++j) { add(*candidates[j]); sb[j] = (int32_t)(j + 1); }
+    const size_t nA = (size_t)ptr[1];
+    std::vector<int32_t> match(nA * J + 1), dist(nA * J + 1), nm(J + 1);
+    covgpu_match_batch_t bt{};
+    bt.num_sets = (int32_t)J + 1; bt.row_ptr = ptr.data(); bt.desc = desc.data(); bt.skip = dense ? skip.data() : nullptr;
+    bt.num_jobs = (int32_t)J; bt.set_a = sa.data(); bt.set_b = sb.data(); bt.match = match.data(); bt.dist = dist.data(); bt.nmatches = nm.data();
+    if (covgpu_match_batch(OptimizationT<Types>::Context(), &bt, &o) != COVGPU_OK) detail::fatal(covgpu_last_error());
+    std::vector<Matches> out(J);
+    for (size_t j = 0; j < J; ++j) {
+      const int32_t* m = &match[j * nA];
+      const int32_t* d = &dist[j * nA];
+      Matches& r = out[j];
+      r.reserve((size_t)nm[j]);
+      for (size_t a = 0; a < nA; ++a) if (m[a] >= 0) r.push_back(Match{a, (size_t)m[a], (double)d[a]});
+      if (dense) std::sort(r.begin(), r.end(), [](const Match& x, const Match& y) { return x.idxB < y.idxB; });   // matchBody:98 emits by B row
+    }
+    return out;
   }
 };
 
