@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <cstdlib>
 #include <stdint.h>
 
 #include <map>
@@ -201,6 +202,11 @@ inline bool first_use_on_device(std::atomic<unsigned long long>& seen) {
   return (seen.fetch_or(bit, std::memory_order_acq_rel) & bit) == 0;
 }
 struct DevSignal { long long* flag = nullptr; long long seq = 0; };
+// the integer value of environment variable `name` (INTEGRATION.md §4 lists every one the library reads); `fallback` when it is not set
+inline int env_int(const char* name, int fallback) {
+  const char* e = getenv(name);
+  return e != nullptr ? atoi(e) : fallback;
+}
 // ---- launchers (each enqueues on `st`, no synchronisation)
 void launch_kobs_build(const DevProblem& P, int* pair_oa, int* pair_ob, size_t nent, hipStream_t st);  // upload: keyframe-major copies, Z slots, pair lists -> Z slots
 void launch_lm_lin(const DevProblem& P, double mu, hipStream_t st, DevSignal sig = DevSignal());   // landmark-major linearisation: records, H_ll, g_l, cost partials
@@ -349,7 +355,7 @@ struct DenseBatch {
   hipEvent_t pre_trsm = nullptr;
   int* bwd_cnt = nullptr;          // [n] zeroed ticket counters: whole-front backward substitution in one launch (k_panel.hip: k_bwd_front)
   double* bwd_scr = nullptr;       // its scratch: [n][interior tiles <= 4][row chunks][128]
-  double* bwd_pipe = nullptr;      // k_bwd_pipe's sentinel-filled scratch (fronts of bwd_pipe_min_tiles() interior tiles and more); nullptr: launch per tile
+  double* bwd_pipe = nullptr;      // k_bwd_pipe's sentinel-filled scratch (fronts of kBwdPipeMinTiles interior tiles and more); nullptr: launch per tile
   int *pipe_dead = nullptr, *pipe_dead_h = nullptr; double pipe_timeout_s = 3.0;   // CholAux::gate_dead / gate_dead_h / gate_timeout_s
   const int* own_dims_h = nullptr; // host copy of own_dims (flop accounting of the profiled run)
   const int* own_dims = nullptr;   // device, [n]: real interior order of every matrix of the batch — substitutions and rank updates stop at a
@@ -380,14 +386,20 @@ struct DistPanels {
 };
 void dense_cholesky_dist(double* S, double* b, double* Linv, int* flag, int npad, hipStream_t st, CholAux& ax, int tstop, DenseBatch bt,
                          const DistPanels& d);
-int bwd_pipe_min_tiles();    // fronts of at least this many interior tiles: backward substitution as one pipelined launch (k_chol.hip)
-int bwd_front_max_tiles();   // fronts of at most this many interior tiles: backward substitution in one launch (k_chol.hip)
+// Fronts of at most this many interior tiles run their whole backward substitution in ONE launch (k_bwd_front: the last workgroup solves the
+// interior tiles one after the other). Measured in round 5 on the corrected 5-agent map, whose upper levels hold fronts of 5-6 tiles: the
+// serial part costs ~15 us per tile (dependent loads of one workgroup), a launch per tile 8.6 — 4: 212.8 it/s, 8: 211.8, 16: 200.0.
+constexpr int kBwdFrontMaxTiles = 4;
+// Fronts of at least this many interior tiles: one launch, one workgroup per tile, hand-overs inside the launch (k_panel.hip: k_bwd_pipe) —
+// unless COVGPU_BWD_PIPE=0 turns that form off (bwd_pipe_on, k_chol.hip).
+constexpr int kBwdPipeMinTiles = 2;
+bool bwd_pipe_on();
 void dense_backward_solve(double* S, double* b, double* Linv, int npad, hipStream_t st, int tfact, int tend, DenseBatch bt = DenseBatch());
 // 256-column panel chain (k_panel.hip): with it the Linv buffer holds, per tile, the eight 16x16 diagonal-block inverses
 // instead of the 128x128 inverse. COVGPU_PANEL=0 selects the round-2a chain (two 128-column potrf + inverse per panel).
-bool launch_potrf_panel(double* S, size_t ld, int t0, int w, double* Linv, int* flag, double* b, int npad, int nbt, size_t sM, size_t sL, size_t sR,
+void launch_potrf_panel(double* S, size_t ld, int t0, int w, double* Linv, int* flag, double* b, int npad, int nbt, size_t sM, size_t sL, size_t sR,
                         hipStream_t st, const long long* btab = nullptr, int nb = -1, const int* own = nullptr, const int* list = nullptr, int n_big = 0,
-                        int n_small = 0, DevSignal sa = DevSignal(), DevSignal sb = DevSignal());   // returns false if nothing was launched   // nb: 16-column blocks to factor (-1: the whole panel); own / list / n_big / n_small: k_panel.hip (round 6)
+                        int n_small = 0);   // nb: 16-column blocks to factor (-1: the whole panel); own / list / n_big / n_small: k_panel.hip (round 6)
 void launch_bwd_given(const double* S, size_t ld, int r0, int r1, double* y, double* x, int ncol, int nbt, size_t sM, size_t sR, hipStream_t st,
                       const long long* btab, const int* live, int tI, BwdXfer xf = BwdXfer());
 void launch_bwd_front(const double* S, int tI, int ntiles, int nchunk, double* y, const double* Linv, int nbt, size_t sL, size_t sR, hipStream_t st,

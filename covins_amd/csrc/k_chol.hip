@@ -58,17 +58,11 @@ constexpr int kLdsPad = 2;   // LDS pitch = K chunk + 2 doubles: the fragment re
                             // Rounds 1-4 used + 1 ("odd pitch" — odd in DOUBLES, i.e. 34 / 66 dwords): two-way conflicts, SQ_LDS_BANK_CONFLICT = 25 % of
                             // the LDS cycles of the quarter-tile kernel (profiles/r05*_pmc_gemm_*.csv)
 constexpr int LDT = KC + kLdsPad;   // LDS pitch (doubles) of the full-tile kernels
-#ifndef COVGPU_PFF
-#define COVGPU_PFF 1
-#endif
-#ifndef COVGPU_PFQ
-#define COVGPU_PFQ 2   // round 4: 4 (+2 % on a map whose trailing updates were ~300 workgroups: one per CU). Round 5, corrected map (~1 000 workgroups per
-                       // launch): two chunks in flight are 138 VGPRs instead of 210 — three workgroups per CU instead of two: 233.9 / 233.5 against 231.8 / 231.2 it/s
-#endif
-#ifndef COVGPU_PFR
-#define COVGPU_PFR 2   // the 64x64 RECT form (a dozen workgroups on the serial chain: the next panel's diagonal block): chunks in flight
-#endif
-constexpr int PFF = COVGPU_PFF, PFQ = COVGPU_PFQ, PFR = COVGPU_PFR;   // chunks in flight in registers: full tiles, quarter forms
+constexpr int PFF = 1;   // chunks in flight in registers: full tiles
+constexpr int PFQ = 2;   // quarter forms. Round 4: 4 (+2 % on a map whose trailing updates were ~300 workgroups: one per CU). Round 5, corrected map
+                         // (~1 000 workgroups per launch): two chunks in flight are 138 VGPRs instead of 210 — three workgroups per CU instead of two:
+                         // 233.9 / 233.5 against 231.8 / 231.2 it/s
+constexpr int PFR = 2;   // the 64x64 RECT form (a dozen workgroups on the serial chain: the next panel's diagonal block)
 
 enum { MODE_SYRK_TRI = 0, MODE_SYRK_RECT = 1, MODE_TRSM = 2 };
 
@@ -303,17 +297,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_abt_q(GemmArgs g) { gemm_abt_bo
 // map) the period is one bulk launch and the chain hides inside it — there the mask only costs (bulk 8 % slower,
 // 37.5 vs 40.7 TFLOP/s); once the bulk is shorter than the ~400 us chain the period is the chain — there the mask
 // helps (no starvation). The two effects cancel: factor+solve 34.3-34.4 ms with N = 1, 2, 4 against 34.1-34.8 ms
-// without. The mask is therefore OPT-IN (COVGPU_CU_MASK=N).
+// without. The side streams therefore take no mask (the CU-mask form is retired).
 static hipStream_t make_side_stream(int priority) {
   hipStream_t s2 = nullptr;
-  const char* on = getenv("COVGPU_CU_MASK");  // N = CUs per XCD kept free for the main stream (bits 0 .. 8N-1)
-  const int nres = on ? atoi(on) : 0;
-  if (nres > 0 && nres <= 8) {
-    uint32_t mask[8];
-    for (int w = 0; w < 8; ++w) mask[w] = 0xFFFFFFFFu;
-    for (int b = 0; b < 8 * nres; ++b) mask[b >> 5] &= ~(1u << (b & 31));
-    if (hipExtStreamCreateWithCUMask(&s2, 8, mask) == hipSuccess) return s2;
-  }
   (void)hipStreamCreateWithPriority(&s2, hipStreamNonBlocking, priority);
   return s2;
 }
@@ -336,7 +322,7 @@ void CholAux::init() {
   if (!gate_dead_h && hipHostMalloc((void**)&gate_dead_h, 4 * sizeof(int), hipHostMallocDefault) == hipSuccess) gate_dead_h[0] = gate_dead_h[1] = gate_dead_h[2] = gate_dead_h[3] = 0;
   if (const char* e = getenv("COVGPU_GATE_TIMEOUT_S")) gate_timeout_s = std::max(getenv("COVGPU_GATE_TIMEOUT_MIN") ? atof(getenv("COVGPU_GATE_TIMEOUT_MIN")) : 0.01, atof(e));   // (the tests of the fallback set it below a kernel's duration)
   if (!gate_flags && !gates_broken) {
-    static const bool want = getenv("COVGPU_GATES") == nullptr || atoi(getenv("COVGPU_GATES")) != 0;
+    static const bool want = env_int("COVGPU_GATES", 1) != 0;
     if (want && gate_dead != nullptr && gate_dead_h != nullptr && hipMalloc((void**)&gate_flags, kGateSlots * sizeof(long long)) == hipSuccess) {
       (void)hipMemset(gate_flags, 0, kGateSlots * sizeof(long long));
       (void)hipDeviceSynchronize();   // (once per context: the fills are complete before the first gate polls)
@@ -346,15 +332,11 @@ void CholAux::init() {
   }
 }
 // ---- device-flag ordering between the streams of a context (common.hpp: CholAux::record / wait)
-#ifndef COVGPU_SIGNAL_RMW
-#define COVGPU_SIGNAL_RMW 0
-#endif
 __global__ void k_signal(long long* flag, long long seq, long long* log) {
   // (a plain agent-scope store: an event is recorded on ONE stream, so the numbers of a slot arrive in order; a returning read-modify-write here
   //  made the boundary behind the signal 4-5 us instead of ~1: covgpu gate log, round 6)
   if (threadIdx.x == 0) {
-    if (COVGPU_SIGNAL_RMW) __hip_atomic_fetch_max(flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else __hip_atomic_store(flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (log) log[0] = wall_clock64();
   }
 }
@@ -430,12 +412,11 @@ void CholAux::record_handle(DevSignal d, hipStream_t s) { if (d.flag != nullptr)
 void CholAux::wait(hipStream_t s, hipEvent_t e0, hipEvent_t e1, hipEvent_t e2, hipEvent_t e3) { sync(s, nullptr, 0, nullptr, 0, e0, e1, e2, e3); }
 void CholAux::sync(hipStream_t s, hipEvent_t r0, int tag0, hipEvent_t r1, int tag1, hipEvent_t e0, hipEvent_t e1, hipEvent_t e2, hipEvent_t e3) {
   hipEvent_t es[4] = {e0, e1, e2, e3};
-  static const bool merged = getenv("COVGPU_GATE_MERGE") == nullptr || atoi(getenv("COVGPU_GATE_MERGE")) != 0;
-  if (!gates_on || !merged) {
+  if (!gates_on) {
     if (r0 != nullptr) record(r0, s, tag0);
     if (r1 != nullptr) record(r1, s, tag1);
-    if (!gates_on) { for (hipEvent_t e : es) if (e != nullptr) (void)hipStreamWaitEvent(s, e, 0); return; }
-    r0 = r1 = nullptr;
+    for (hipEvent_t e : es) if (e != nullptr) (void)hipStreamWaitEvent(s, e, 0);
+    return;
   }
   GateArgs g; g.n = 0; g.dead = gate_dead; g.dead_h = gate_dead_h; g.limit = (long long)(gate_timeout_s * 1e8); g.log = nullptr; g.np = 0; g.base = gate_flags;
   g.pf[0] = g.pf[1] = nullptr; g.ps[0] = g.ps[1] = 0;
@@ -562,9 +543,9 @@ void CholAux::collect() {
 }
 
 // trailing updates given as explicit tile lists of at most this many entries (incl. the XCD padding) run as 64x64 quadrants
-static const int kQuarterMax = getenv("COVGPU_QUARTER_MAX") ? atoi(getenv("COVGPU_QUARTER_MAX")) : 1024;
+static const int kQuarterMax = env_int("COVGPU_QUARTER_MAX", 1024);
 // look-ahead update of the rows below the next panel (stream R): tiles up to which it runs as quarter tiles
-static const int kRectQuarterMax = getenv("COVGPU_RECTR_QUARTER_MAX") ? atoi(getenv("COVGPU_RECTR_QUARTER_MAX")) : 512;
+constexpr int kRectQuarterMax = 512;
 
 void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int npad, hipStream_t st, CholAux& ax, int tstop, bool solve,
                               DenseBatch bt) {
@@ -668,8 +649,7 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
   // chain that follows a bulk update — the next diagonal look-ahead, the look-ahead of the next panel's rows — writes those two tile columns only and
   // waits for the FIRST launch (eA). With one launch the chain of a big front waited for the whole previous bulk update every panel: on the 5-agent
   // map's root (3 726 unknowns, 15 panels, bulk 100 us) the period was bulk -> diagonal look-ahead -> bulk = 165 us instead of the chain's 128.
-  static const bool col_split = getenv("COVGPU_BULK_SPLIT") == nullptr || atoi(getenv("COVGPU_BULK_SPLIT")) != 0;
-  const int key = ((T * 4096 + nbt) * 8 + bt.split_ta) * 2 + (col_split ? 1 : 0);
+  const int key = (T * 4096 + nbt) * 8 + bt.split_ta;
   if (bt.live_h != nullptr && tc.key != key) {  // live-tile lists of every panel's bulk update (static per problem)
     tc.clear();
     tc.key = key;
@@ -681,31 +661,21 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
       if (tb >= T) break;
       bool ok = true;
       if (last && bt.split_ta > 0) ok = build_list(t0, tb, 1, tc.listA, tc.countA) && build_list(t0, tb, 2, tc.listB, tc.countB);
-      else if (col_split && !last) ok = build_list(t0, tb, 3, tc.listC[P], tc.countC[P]) && build_list(t0, tb, 4, tc.list[P], tc.count[P]);   // (the last panel's update is ONE launch on the chain's stream)
+      else if (!last) ok = build_list(t0, tb, 3, tc.listC[P], tc.countC[P]) && build_list(t0, tb, 4, tc.list[P], tc.count[P]);   // (the last panel's update is ONE launch on the chain's stream)
       else ok = build_list(t0, tb, 0, tc.list[P], tc.count[P]);
       if (!ok) { tc.clear(); break; }
     }
   }
   // k_potrf_panel of big panel P, all fronts of the batch; profiling: an event pair around the launch and its algorithmic flops
   // (per front n^3 / 3 for the factorisation + n^2 for the forward substitution riding along, n = the front's REAL columns in the panel)
-  // records of the chain's stream waiting to be published by the next panel factorisation's first thread (CholAux::publish_handle)
-  DevSignal pend[2]; hipEvent_t pend_ev[2] = {nullptr, nullptr}; int pend_tag[2] = {0, 0}; int npend = 0;
-  auto flush_pending = [&]() {   // no factorisation follows (or none was launched): an ordinary launch publishes them
-    if (npend == 0) return;
-    hipLaunchKernelGGL(k_signal2, dim3(1), dim3(64), 0, M, pend[0], npend > 1 ? pend[1] : DevSignal());
-    npend = 0;
-  };
   auto potrf = [&](int t0, int w, int nbp) {
     const bool prof = ax.profile && nbp != 0;
     if (prof) {
       while (ax.prof_ev2.size() < 2 * (ax.prof_flops2.size() + 1)) { hipEvent_t e; (void)hipEventCreate(&e); ax.prof_ev2.push_back(e); }
       (void)hipEventRecord(ax.prof_ev2[2 * ax.prof_flops2.size()], M);
     }
-    const DevSignal sa = npend > 0 ? pend[0] : DevSignal(), sb = npend > 1 ? pend[1] : DevSignal();
-    bool launched;
-    if (bt.plist != nullptr) launched = launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, M, bt.tab, nbp, bt.own_dims, bt.plist, bt.pbig_h[t0 / 2], bt.psmall_h[t0 / 2], sa, sb);
-    else launched = launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, M, bt.tab, nbp, nullptr, nullptr, 0, 0, sa, sb);
-    if (launched) npend = 0; else flush_pending();
+    if (bt.plist != nullptr) launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, M, bt.tab, nbp, bt.own_dims, bt.plist, bt.pbig_h[t0 / 2], bt.psmall_h[t0 / 2]);
+    else launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, M, bt.tab, nbp);
     if (prof) {
       double fl = 0.0;
       for (int a = 0; a < nbt; ++a) {
@@ -720,8 +690,7 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
   bool split_last = false;  // the last panel's bulk update was left running on B for the caller (DenseBatch::split_ta)
   bool tail_on_chain = false;  // the last panel ran whole on the chain's own stream: nothing of it to join (every event packet on
                                // the chain's stream is a few microseconds between two dependent kernels)
-  static const bool early_wait2_env = getenv("COVGPU_EARLY_WAIT") == nullptr || atoi(getenv("COVGPU_EARLY_WAIT")) != 0;
-  static const bool trace2 = getenv("COVGPU_TRACE_PANELS") != nullptr && atoi(getenv("COVGPU_TRACE_PANELS")) >= 2;   // dev aid: per-kernel marks, tag 100 (P + 1) + k
+  static const bool trace2 = env_int("COVGPU_TRACE_PANELS", 0) >= 2;   // dev aid: per-kernel marks, tag 100 (P + 1) + k
   for (int P = 0; P < NP; ++P) {
     const int t0 = 2 * P, w = (T - t0 >= 2) ? 2 : 1;
     const int h0 = (t0 + 2 < T) ? t0 + 2 : T, h1 = (t0 + 4 < T) ? t0 + 4 : T;  // rows h = [h0, h1), rows r = [h1, T)
@@ -746,7 +715,6 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
       }
     }
     if (P == Pstop) {  // only the look-ahead updates of the last eliminated panel; nothing of this panel is factored
-      flush_pending();
       record(eH[P], H, 100 * (P + 1) + 10);
       record(eC[P], R, 100 * (P + 1) + 12);
       record(eB[P], B, 100 * (P + 1) + 11);
@@ -767,9 +735,8 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
       if (P == 0 && bt.pre_trsm != nullptr) wait(M, bt.pre_trsm);   // rows below the first panel: second half of the caller's extend-add
       bool split_done = false;
       if (T > h0) {
-        const bool early_wait2 = early_wait2_env;
         const bool split = bt.split_ta > 0 && bt.live_h != nullptr && kd(P) > 0 && (tc.listA != nullptr || tc.listB != nullptr);
-        const bool waitedA = early_wait2 && split && P >= 1;
+        const bool waitedA = split && P >= 1;
         // rows h / rest rows carry panel P-1 | (beside them instead of between the substitution and the update: see the multi-panel branch) bulk(P-1)'s first launch
         if (P > 0) wait(M, h1 > h0 ? eHp[P] : nullptr, T > h1 ? e2[P] : nullptr, waitedA ? eA[P - 1] : nullptr);
         // (measured and dropped: solving only the rows the parents' first panel receives here and the others on the bulk stream —
@@ -780,7 +747,7 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
         // bulk(P-1) was the previous writer of the trailing tiles. The part of this update that stays on the chain's stream (rows < split_ta: what
         // build_list puts into the first launch beside tile columns 0, 1) only meets the FIRST launch of that bulk update — on the 5-agent map's upper levels (borders of
         // 2 000 unknowns) the whole of it is 160 us, and the next level's first panel waited for it; the rest follows it on the bulk stream anyway
-        if (P >= 1 && !waitedA) wait(M, split ? eA[P - 1] : eB[P - 1]);
+        if (P >= 1 && !waitedA) wait(M, eB[P - 1]);
         const int tb = h0, nt = T - tb;
         auto syrk = [&](hipStream_t s2, const int* list, int count, double flops) {
           GemmArgs g{S, ld, t0 * kTile, kd(P), tb * kTile, tb * kTile, tb * kTile, nt, nullptr, nullptr, nullptr, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, nullptr, bt.tab, bt.own_dims};
@@ -840,8 +807,6 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
       //  all of it behind the ONE event of the chain-bound form: 140-160 us per panel. Events after every kernel: 284 -> 298 it/s, and
       //  no loss on the one-panel fronts. COVGPU_CHAIN_PAIRS restores a threshold.)
       static const double chain_pairs = getenv("COVGPU_CHAIN_PAIRS") ? atof(getenv("COVGPU_CHAIN_PAIRS")) : 0.0;
-      static const bool early_wait = getenv("COVGPU_EARLY_WAIT") == nullptr || atoi(getenv("COVGPU_EARLY_WAIT")) != 0;
-      static const bool merge_trsm = getenv("COVGPU_TRSM_MERGE") != nullptr && atoi(getenv("COVGPU_TRSM_MERGE")) != 0;
       const bool chain_bound = bulk_pairs <= chain_pairs;
       potrf(t0, w, nbp);
       // rows below the first panel: second half of the caller's extend-add. IN FRONT of the record below — the rest rows' substitution on stream R
@@ -852,31 +817,25 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
       // panel, eH, recorded after the look-ahead update of the next diagonal block — the rest rows (which only need the factored
       // panel), the next panel's rows on stream H and the bulk update all start from it, two small kernels later than they could.
       // While the bulk update is long (the period is the bulk) they start as early as possible: an event after each kernel.
-      // merge_trsm (round 5, opt-in: COVGPU_TRSM_MERGE=1): rows h AND the rest rows in ONE substitution launch on the chain's stream — every 16-row
-      // slab is a workgroup of its own, so the launch is as long as one slab while workgroup slots are free — instead of the rest rows on stream R
-      // behind an event: a record whose waiter is blocked on it at that moment costs the RECORDING stream ~13 us as well
-      // (profiles/r05z_iteration_timeline.csv: both substitutions start 14 us after the factorisation ends), a record nobody is waiting for yet ~6.
-      // Measured: 233.5 / 233.1 against 232.6 / 232.0 it/s, configs[4] 20.0 against 20.3 — within noise, so the default stays the round-4 form.
-      const bool merge = merge_trsm && !chain_bound && h1 > h0 && T > h1;
+      // (Merging rows h and the rest rows into one substitution launch on this stream was measured within noise in round 5: DESIGN.md.)
       bool waitedA = false;
-      hipEvent_t rec1 = (!chain_bound && !merge) ? e1[P] : nullptr;   // "panel P factored": the rest rows' substitution (stream R) starts from it
+      hipEvent_t rec1 = !chain_bound ? e1[P] : nullptr;   // "panel P factored": the rest rows' substitution (stream R) starts from it
       if (h1 > h0) {
-        // rows h carry the look-ahead update of panel P-1 (stream H, above) | ... and, merged, the rest rows theirs (stream R) | bulk(P-1)'s first launch.
+        // rows h carry the look-ahead update of panel P-1 (stream H, above) | bulk(P-1)'s first launch.
         // (round 6: the record behind the factorisation and these waits are ONE launch — CholAux::sync)
-        waitedA = early_wait && P >= 1 && P + 1 < NP;
-        ax.sync(M, rec1, 100 * (P + 1) + 13, nullptr, 0, P > 0 ? eHp[P] : nullptr, merge && P > 0 ? e2[P] : nullptr, waitedA ? eA[P - 1] : nullptr);
+        waitedA = P >= 1 && P + 1 < NP;
+        ax.sync(M, rec1, 100 * (P + 1) + 13, nullptr, 0, P > 0 ? eHp[P] : nullptr, waitedA ? eA[P - 1] : nullptr);
         rec1 = nullptr;
         // (round 5: the wait of the next-diagonal update below for bulk(P-1)'s first launch — 30-40 us of slack — rides along with the one above.
         //  Measured: no difference (231.1 / 230.5 against 231.4 / 231.2 it/s) — a wait whose event completed long ago costs nothing; the 13-14 us
         //  between two kernels of this stream come from the RECORD behind the first when its waiter is blocked on it at that moment: DESIGN.md 4.6)
-        launch_trsm_sub(S, ld, t0, w, h0, merge ? T : h1, Linv, b, npad, nbt, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, M, true, bt.tab, nbp, bt.own_dims);
+        launch_trsm_sub(S, ld, t0, w, h0, h1, Linv, b, npad, nbt, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, M, true, bt.tab, nbp, bt.own_dims);
         if (trace2) ax.mark(M, 100 * (P + 1) + 2);   // rows h solved
       }
       if (rec1 != nullptr) record(rec1, M, 100 * (P + 1) + 13);
       // (round 6: "rows h solved" is published together with "next diagonal block updated", one launch behind that small update instead of one
       //  launch in front of it and one behind: its waiters — the next panel's look-ahead on stream H — have ~50 us of slack)
-      static const bool late_eh = getenv("COVGPU_LATE_EH") == nullptr || atoi(getenv("COVGPU_LATE_EH")) != 0;
-      const bool eh_now = !chain_bound && !(late_eh && P + 1 < NP);
+      const bool eh_now = !chain_bound && P + 1 == NP;
       if (eh_now) record(eH[P], M, 100 * (P + 1) + 10);
       // ---- M: look-ahead part of SYRK(P) on the next panel's 2x2 diagonal tiles
       if (P + 1 < NP) {
@@ -887,27 +846,15 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
       }
       // (A bulk launched at the same instant as the next diagonal update takes every workgroup slot first and the chain waits
       //  ~75 us for the first round of tiles to retire: the bulk starts after that small kernel in either regime.)
+      // (Both records are published by a launch of their own enqueued before any of their waiters: letting the next panel's factorisation publish
+      //  them deadlocks once two streams share a hardware queue — round 6, DESIGN.md.)
       if (chain_bound || eh_now) record(chain_bound ? eH[P] : eRc[P], M, 100 * (P + 1) + (chain_bound ? 10 : 16));
-      else {
-        // (round 6, OPT-IN: COVGPU_RECORD_RIDE=1) both records ride with the NEXT panel's factorisation, whose first thread publishes them — one launch
-        // less per panel (-1 % of the factorisation). Their waiters (stream H's look-ahead of the next panel, the bulk update) are then enqueued BEFORE
-        // the launch that publishes: harmless while every stream has a hardware queue of its own, a deadlock (until the gate's timeout) as soon as
-        // two streams of the process share one — a gate in front of the publishing launch in the same queue holds it back. Several contexts in one
-        // process (virtual ranks, the facade's context beside another) do share queues: tests/test_gpu_shard.py hung on it. Default: off —
-        // every gate is enqueued after the launch that publishes its record, and the ordering cannot deadlock whatever the queue mapping.
-        static const bool ride = getenv("COVGPU_RECORD_RIDE") != nullptr && atoi(getenv("COVGPU_RECORD_RIDE")) != 0;
-        if (ride && ax.gates_on && npend == 0) {
-          pend[0] = ax.publish_handle(eH[P], M, 100 * (P + 1) + 10); pend[1] = ax.publish_handle(eRc[P], M, 100 * (P + 1) + 16);
-          npend = (pend[0].flag != nullptr && pend[1].flag != nullptr) ? 2 : 0;
-          if (npend == 0) { record(eH[P], M, 100 * (P + 1) + 10); record(eRc[P], M, 100 * (P + 1) + 16); }   // (out of slots: HIP events took over inside publish_handle's fallback)
-        } else ax.sync(M, eH[P], 100 * (P + 1) + 10, eRc[P], 100 * (P + 1) + 16);
-      }
-      if (T > h1 && !merge) {
+      else ax.sync(M, eH[P], 100 * (P + 1) + 10, eRc[P], 100 * (P + 1) + 16);
+      if (T > h1) {
         wait(R, chain_bound ? eH[P] : e1[P]);   // (measured, round 4: waiting for rows h instead — so that the chain's substitution runs alone — 299.9 -> 297.5 it/s)
         launch_trsm_sub(S, ld, t0, w, h1, T, Linv, b, npad, nbt, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, R, false, bt.tab, nbp, bt.own_dims);
         if (trace2) ax.mark(R, 100 * (P + 1) + 4);   // rest rows solved
       }
-      if (merge) wait(R, eH[P]);   // (eC then stands for "every row below panel P is solved" as before: its waiters — the bulk update, stream H — need not change)
       record(eC[P], R, 100 * (P + 1) + 12);
       bulk_wait_rc = !chain_bound;   // (measured again in round 4 with the 60 us panel: without this wait 298.6 -> 292.7 it/s)
     }
@@ -936,17 +883,10 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
       const int cntC = (listed && P < (int)tc.listC.size() && tc.listC[P] != nullptr) ? tc.countC[P] : 0;
       if (!listed || tc.count[P] > 0 || cntC > 0) {
         if (ax.profile) (void)hipEventRecord(ax.prof_ev[2 * ax.prof_flops.size()], B);
-        // A long bulk update keeps every CU full for hundreds of microseconds, and the next panel's factorisation — one 16-wave workgroup that needs an
-        // EMPTY CU — waits for its tail (12-agent map, root: period = bulk + the whole exposed chain). In pieces of kBulkChunk tiles the chip drains
-        // between two launches and the waiting workgroup (higher stream priority) gets its CU. (0: one launch.)
-        static const int kBulkChunk = getenv("COVGPU_BULK_CHUNK") ? atoi(getenv("COVGPU_BULK_CHUNK")) : 0;
         auto tri = [&](const int* list, int count) {
-          if (count <= kQuarterMax) { g.tri = list; hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_TRI, 64, 64>), dim3(count, 1, 4), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), B, g); return; }
-          const int step = kBulkChunk > 0 ? std::max(512, (kBulkChunk / 8) * 8) : count;
-          for (int o = 0; o < count; o += step) {
-            g.tri = list + o;
-            hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(std::min(step, count - o), 1), dim3(256), lds_gemm, B, g);
-          }
+          g.tri = list;
+          if (count <= kQuarterMax) hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_TRI, 64, 64>), dim3(count, 1, 4), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), B, g);
+          else hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(count, 1), dim3(256), lds_gemm, B, g);
         };
         if (cntC > 0) {   // the next-but-one panel's two tile columns first: what the chain waits for
           tri(tc.listC[P], cntC);
@@ -965,7 +905,6 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
     record(eB[P], B, 100 * (P + 1) + 11);
     if (!recA) record(eA[P], B, 100 * (P + 1) + 18);
   }
-  flush_pending();
   wait(M, !split_last && !tail_on_chain ? eB[Plast] : nullptr, Plast >= 1 ? eB[Plast - 1] : nullptr, !tail_on_chain ? eC[Plast] : nullptr, !tail_on_chain ? eH[Plast] : nullptr);
   if (!solve) return;
   // y = L^-1 b was formed along the way (potrf: y_p = L_pp^-1 b_p; every TRSM: b[rows] -= L[rows, p] y_p) and lives
@@ -1010,17 +949,9 @@ void dense_cholesky_dist(double* S, double* b, double* Linv, int* flag, int npad
   }
 }
 
-// Fronts of at most this many interior tiles run their whole backward substitution in ONE launch (k_bwd_front: the last workgroup solves the
-// interior tiles one after the other). Measured in round 5 on the corrected 5-agent map, whose upper levels hold fronts of 5-6 tiles: the
-// serial part costs ~15 us per tile (dependent loads of one workgroup), a launch per tile 8.6 — 4: 212.8 it/s, 8: 211.8, 16: 200.0.
-int bwd_front_max_tiles() {
-  static const int v = getenv("COVGPU_BWD_FRONT_TILES") ? std::max(1, atoi(getenv("COVGPU_BWD_FRONT_TILES"))) : 4;
-  return v;
-}
-// Fronts of at least this many interior tiles: one launch, one workgroup per tile, hand-overs inside the launch (k_panel.hip: k_bwd_pipe).
-// COVGPU_BWD_PIPE=0 disables it.
-int bwd_pipe_min_tiles() {
-  static const int v = (getenv("COVGPU_BWD_PIPE") && atoi(getenv("COVGPU_BWD_PIPE")) == 0) ? (1 << 30) : getenv("COVGPU_BWD_PIPE_MIN") ? std::max(1, atoi(getenv("COVGPU_BWD_PIPE_MIN"))) : 2;
+// the pipelined backward substitution (k_panel.hip: k_bwd_pipe, k_bwd_tree); COVGPU_BWD_PIPE=0 disables it
+bool bwd_pipe_on() {
+  static const bool v = env_int("COVGPU_BWD_PIPE", 1) != 0;
   return v;
 }
 // L^T x = y for the factored tile columns [0, tfact) of an npad-order matrix; for tile rows p in [tfact, tend) x_p is
@@ -1031,12 +962,12 @@ void dense_backward_solve(double* S, double* b, double* Linv, int npad, hipStrea
   {
     // multifrontal front of few interior tiles: given rows and every interior tile in ONE launch (k_panel.hip: k_bwd_front)
     const int nt_real = bt.own_max > 0 ? std::min(tfact, (bt.own_max + kTile - 1) / kTile) : tfact;
-    if (bt.bwd_pipe != nullptr && bt.pipe_dead != nullptr && bt.xfer.gidx != nullptr && bt.tab != nullptr && bt.live != nullptr && nt_real >= bwd_pipe_min_tiles() && nbt <= 65535) {
+    if (bt.bwd_pipe != nullptr && bt.pipe_dead != nullptr && bt.xfer.gidx != nullptr && bt.tab != nullptr && bt.live != nullptr && bwd_pipe_on() && nt_real >= kBwdPipeMinTiles && nbt <= 65535) {
       launch_bwd_pipe(S, tfact, nt_real, ((tend - tfact) * kTile + kPipeChunk - 1) / kPipeChunk, b + npad, Linv, nbt, bt.sL, bt.sR, st, bt.tab, bt.live, bt.xfer, bt.bwd_pipe, bt.pipe_dead,
                       bt.pipe_dead_h, bt.pipe_timeout_s);
       return;
     }
-    if (bt.bwd_cnt != nullptr && bt.bwd_scr != nullptr && bt.xfer.gidx != nullptr && bt.tab != nullptr && bt.live != nullptr && nt_real >= 1 && nt_real <= bwd_front_max_tiles() &&
+    if (bt.bwd_cnt != nullptr && bt.bwd_scr != nullptr && bt.xfer.gidx != nullptr && bt.tab != nullptr && bt.live != nullptr && nt_real >= 1 && nt_real <= kBwdFrontMaxTiles &&
         nbt <= 65536) {
       const int nchunk = std::max(1, ((tend - tfact) * kTile + 255) / 256);
       launch_bwd_front(S, tfact, nt_real, nchunk, b + npad, Linv, nbt, bt.sL, bt.sR, st, bt.tab, bt.live, bt.xfer, bt.bwd_cnt, bt.bwd_scr);

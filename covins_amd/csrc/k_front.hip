@@ -396,9 +396,10 @@ struct NdLevArgs {
 // (ONE launch over the tiles of all levels — a level per launch was seven dependent host enqueues at the head of every linearisation,
 //  with the chip idle behind them: blocks [blk0[l], blk0[l + 1]) belong to level l, tile (tr, tc) of its front number `fz`)
 struct NdZeroArgs { int nlev; int first[24], n[24], nI[24], T[24]; long long blk0[25]; const int *own_dims, *st_dims, *bb_off, *bb; int first_top; };
-// the extend-add stores the border x border tiles whole instead of k_nd_zero clearing them (COVGPU_STORE_BORDER=0: round 5's clearing; needs COVGPU_BETA0 on)
-static bool nd_store_border() {
-  static const bool v = (getenv("COVGPU_STORE_BORDER") == nullptr || atoi(getenv("COVGPU_STORE_BORDER")) != 0) && (getenv("COVGPU_BETA0") == nullptr || atoi(getenv("COVGPU_BETA0")) != 0);
+// COVGPU_BETA0 (on unless 0): the first rank update of a border x border tile no child adds into starts it from zero (GemmArgs::beta0), and the
+// extend-add stores the tiles a child does add into whole — k_nd_zero clears neither. Off: k_nd_zero clears every border tile (round 5's form).
+static bool nd_beta0() {
+  static const bool v = env_int("COVGPU_BETA0", 1) != 0;
   return v;
 }
 __global__ __launch_bounds__(256) void k_nd_zero(DevProblem P, NdZeroArgs z) {
@@ -694,10 +695,9 @@ void launch_nd_init(const DevProblem& P, const NdDev& nd, hipStream_t st) {
 
 void launch_nd_zero(const DevProblem& P, const NdDev& nd, hipStream_t st) {
   NdZeroArgs z;
-  static const bool beta0 = getenv("COVGPU_BETA0") == nullptr || atoi(getenv("COVGPU_BETA0")) != 0;   // (A/B switch; k_front.hip's batch() reads the same)
-  z.nlev = 0; z.blk0[0] = 0; z.own_dims = nd.own_dims; z.st_dims = nd.st_dims; z.bb_off = nd.bb_off; z.bb = beta0 ? nd.bb : nullptr;
+  z.nlev = 0; z.blk0[0] = 0; z.own_dims = nd.own_dims; z.st_dims = nd.st_dims; z.bb_off = nd.bb_off; z.bb = nd_beta0() ? nd.bb : nullptr;
   // nodes are numbered in level order: the first node of the first top level (sharded solve) — below it the extend-add stores the border tiles
-  z.first_top = !nd_store_border() ? 0 : (nd.top_lev0 < (int)nd.lev.size() ? nd.lev[nd.top_lev0].first : nd.nnodes);
+  z.first_top = !nd_beta0() ? 0 : (nd.top_lev0 < (int)nd.lev.size() ? nd.lev[nd.top_lev0].first : nd.nnodes);
   auto flush = [&] {
     if (z.nlev > 0 && z.blk0[z.nlev] > 0) hipLaunchKernelGGL(k_nd_zero, dim3((unsigned)z.blk0[z.nlev]), dim3(256), 0, st, P, z);
     z.nlev = 0; z.blk0[0] = 0;
@@ -717,12 +717,12 @@ void launch_nd_zero(const DevProblem& P, const NdDev& nd, hipStream_t st) {
 
 bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hipStream_t st, CholAux& ax) {
   const int nlev = (int)nd.lev.size(), ltop = nd.top_lev0;
-  static const bool lookahead = getenv("COVGPU_ND_LOOKAHEAD") == nullptr || atoi(getenv("COVGPU_ND_LOOKAHEAD")) != 0;
+  static const bool lookahead = env_int("COVGPU_ND_LOOKAHEAD", 1) != 0;
   ax.init();
   {  // scratch of the one-launch backward substitution (k_bwd_front): [fronts][interior tiles <= 4][256-row chunks of the border][128]
     size_t need = 0;
     for (const NdLevel& L : nd.lev)
-      need = std::max(need, (size_t)L.n * std::min(bwd_front_max_tiles(), (L.own_max + kTile - 1) / kTile) * std::max(1, (L.ntot - L.nI + 255) / 256) * kTile);
+      need = std::max(need, (size_t)L.n * std::min(kBwdFrontMaxTiles, (L.own_max + kTile - 1) / kTile) * std::max(1, (L.ntot - L.nI + 255) / 256) * kTile);
     if (need > ax.bwd_scr_elems) {
       if (ax.bwd_scr) (void)hipFree(ax.bwd_scr);
       ax.bwd_scr = nullptr; ax.bwd_scr_elems = 0;
@@ -734,7 +734,7 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
     size_t need = 0;
     for (const NdLevel& L : nd.lev) {
       const int T = std::min(L.nI / kTile, (L.own_max + kTile - 1) / kTile);
-      if (L.n > 0 && T >= bwd_pipe_min_tiles()) need = std::max(need, (size_t)L.n * T * ((L.ntot - L.nI + kPipeChunk - 1) / kPipeChunk + 1) * kTile);
+      if (L.n > 0 && bwd_pipe_on() && T >= kBwdPipeMinTiles) need = std::max(need, (size_t)L.n * T * ((L.ntot - L.nI + kPipeChunk - 1) / kPipeChunk + 1) * kTile);
     }
     {
       size_t tree = 0, tree2 = 0;
@@ -755,13 +755,12 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
       } else ax.bwd_pipe = nullptr;                // (launch per tile)
     }
   }
-  static const bool fused_bwd = getenv("COVGPU_ND_BWD_FUSED") == nullptr || atoi(getenv("COVGPU_ND_BWD_FUSED")) != 0;
-  static const bool tree_env = getenv("COVGPU_BWD_TREE") == nullptr || atoi(getenv("COVGPU_BWD_TREE")) != 0;
-  // the bottom levels' backward substitution as one launch (k_bwd_tree): needs the pipeline's scratch and the give-up word
-  const bool tree_ok = tree_env && fused_bwd && nd.tree_fill != nullptr && !ax.pipe_broken && ax.bwd_pipe != nullptr && ax.gate_dead != nullptr && bwd_pipe_min_tiles() <= 2;
-  static const bool tree_top_env = getenv("COVGPU_BWD_TREE_TOP") == nullptr || atoi(getenv("COVGPU_BWD_TREE_TOP")) != 0;
+  static const bool fused_bwd = env_int("COVGPU_ND_BWD_FUSED", 1) != 0;
+  static const bool tree_env = env_int("COVGPU_BWD_TREE", 1) != 0;
+  // the bottom levels' backward substitution as one launch (k_bwd_tree): needs the pipeline (not COVGPU_BWD_PIPE=0), its scratch and the give-up word
+  const bool tree_ok = tree_env && fused_bwd && nd.tree_fill != nullptr && !ax.pipe_broken && ax.bwd_pipe != nullptr && ax.gate_dead != nullptr && bwd_pipe_on();
   const bool tree_on = tree_ok && nd.tree_levels >= 2;
-  const bool tree_top_on = tree_ok && tree_top_env && nd.tree_top0 < (int)nd.lev.size();
+  const bool tree_top_on = tree_ok && nd.tree_top0 < (int)nd.lev.size();
   ax.mark(st, -1);
   // (the right-hand sides were cleared on the head stream of the build, beside the fronts: solver.hip enqueue_build)
   {
@@ -775,10 +774,8 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
     DenseBatch bt;
     bt.n = L.n; bt.sM = 0; bt.sL = (size_t)L.nI * kTile; bt.sR = (size_t)2 * L.ntot;
     bt.live = L.live; bt.tI = L.nI / kTile; bt.live_h = L.live_h.data();
-    static const bool beta0 = getenv("COVGPU_BETA0") == nullptr || atoi(getenv("COVGPU_BETA0")) != 0;
-    if (beta0 && nd.bb != nullptr) { bt.beta0_off = nd.bb_off + L.first; bt.beta0 = nd.bb; }
-    static const bool plists = getenv("COVGPU_POTRF_LISTS") == nullptr || atoi(getenv("COVGPU_POTRF_LISTS")) != 0;
-    if (plists && L.plist != nullptr) { bt.plist = L.plist; bt.pbig_h = L.pbig.data(); bt.psmall_h = L.psmall.data(); }
+    if (nd_beta0() && nd.bb != nullptr) { bt.beta0_off = nd.bb_off + L.first; bt.beta0 = nd.bb; }
+    if (L.plist != nullptr) { bt.plist = L.plist; bt.pbig_h = L.pbig.data(); bt.psmall_h = L.psmall.data(); }
     bt.tab = P.nd_ntab + 2 * (size_t)L.first; bt.tri_slot = l; bt.own_max = L.own_max; bt.own_dims = nd.own_dims + L.first; bt.own_dims_h = nd.h_own_dims.data() + L.first;
     return bt;
   };
@@ -789,13 +786,13 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
     const int countA = top_children ? L.ext2_countA : L.ext_countA;
     if (part == 1) count = countA;
     if (part == 2) { first += countA; count -= countA; }
-    static const bool records = getenv("COVGPU_EXT_RECORDS") == nullptr || atoi(getenv("COVGPU_EXT_RECORDS")) != 0;
+    static const bool records = env_int("COVGPU_EXT_RECORDS", 1) != 0;
     if (count > 0 && records && nd.extr != nullptr)
       hipLaunchKernelGGL(k_nd_extend_rec, dim3(count), dim3(256), 0, s2, P, lev_args(P, nd, l), (const int*)(nd.extr + (size_t)kExtRec * first),
-                         (const int*)(nd.extr + (size_t)kExtRec * nd.ext_over), top_children ? 1 : 0, (!top_children && l < ltop && nd_store_border()) ? 1 : 0, sig);
+                         (const int*)(nd.extr + (size_t)kExtRec * nd.ext_over), top_children ? 1 : 0, (!top_children && l < ltop && nd_beta0()) ? 1 : 0, sig);
     else if (count > 0)
       hipLaunchKernelGGL(k_nd_extend, dim3(count), dim3(256), 0, s2, P, lev_args(P, nd, l), (const int*)(nd.extw + 8 * (size_t)first),
-                         (const int*)(top_children ? nd.extc2 : nd.extc), top_children ? 1 : 0, (!top_children && l < ltop && nd_store_border()) ? 1 : 0, sig);
+                         (const int*)(top_children ? nd.extc2 : nd.extc), top_children ? 1 : 0, (!top_children && l < ltop && nd_beta0()) ? 1 : 0, sig);
     return count > 0;
   };
   // split: the trailing update of this level's last panel is split for the look-ahead into the next level (DenseBatch::split_ta)
@@ -847,13 +844,11 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
       // ONE all-reduce of [live lower tiles of the top fronts, packed | top right-hand sides | grad, hdiag of the top unknowns]: the
       // fronts are stored as full squares, of which the exchange needs half (33.6 -> 17.9 MB for the 5-agent map's root)
       const size_t ntile = (size_t)nd.n_top_tiles * kTile * kTile, nvec = nd.rhs_top + 2 * (size_t)nd.ntop;
-      if (nd.top_pack != nullptr) {
-        if (nd.n_top_tiles > 0) hipLaunchKernelGGL(k_nd_top_pack, dim3(nd.n_top_tiles), dim3(256), 0, st, P, (const int*)nd.top_tiles, nd.top_pack, 0);
-        if (nvec > 0) (void)hipMemcpyAsync(nd.top_pack + ntile, P.nd_rhs, nvec * sizeof(double), hipMemcpyDeviceToDevice, st);
-        ax.reduce(ax.reduce_ctx, nd.top_pack, ntile + nvec, 0, st);
-        if (nd.n_top_tiles > 0) hipLaunchKernelGGL(k_nd_top_pack, dim3(nd.n_top_tiles), dim3(256), 0, st, P, (const int*)nd.top_tiles, nd.top_pack, 1);
-        if (nvec > 0) (void)hipMemcpyAsync(P.nd_rhs, nd.top_pack + ntile, nvec * sizeof(double), hipMemcpyDeviceToDevice, st);
-      } else ax.reduce(ax.reduce_ctx, P.nd_M + nd.M_sub, (nd.M_elems - nd.M_sub) + nd.rhs_top + 2 * (size_t)nd.ntop, 0, st);   // (whole squares: COVGPU_SHARD_PACK=0)
+      if (nd.n_top_tiles > 0) hipLaunchKernelGGL(k_nd_top_pack, dim3(nd.n_top_tiles), dim3(256), 0, st, P, (const int*)nd.top_tiles, nd.top_pack, 0);
+      if (nvec > 0) (void)hipMemcpyAsync(nd.top_pack + ntile, P.nd_rhs, nvec * sizeof(double), hipMemcpyDeviceToDevice, st);
+      ax.reduce(ax.reduce_ctx, nd.top_pack, ntile + nvec, 0, st);
+      if (nd.n_top_tiles > 0) hipLaunchKernelGGL(k_nd_top_pack, dim3(nd.n_top_tiles), dim3(256), 0, st, P, (const int*)nd.top_tiles, nd.top_pack, 1);
+      if (nvec > 0) (void)hipMemcpyAsync(P.nd_rhs, nd.top_pack + ntile, nvec * sizeof(double), hipMemcpyDeviceToDevice, st);
     }
     if (nd.ntop > 0) {
       hipLaunchKernelGGL(k_nd_gh, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 1);

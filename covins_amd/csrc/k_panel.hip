@@ -18,8 +18,8 @@
 //                   substitution on Z = X^T kept in accumulator layout — a finished 16x16 block Z_j IS the B operand of the
 //                   trailing updates acc_i -= L_ij Z_j (the C/D layout of v_mfma_f64_16x16x4 equals its B layout), and
 //                   Z_j = Dinv_j acc_j needs only the small block inverses. Exact substitution between blocks: better
-//                   conditioned than the product with a 128x128 explicit inverse it replaces. (k_trsm_sub: the same with one
-//                   wave per slab, bound by one SIMD's matrix pipe; COVGPU_TRSM4=0.)
+//                   conditioned than the product with a 128x128 explicit inverse it replaces. (Round 4's one wave per slab,
+//                   bound by one SIMD's matrix pipe, is retired.)
 //   k_bwd_step_sub  backward substitution per 128-tile with the same block inverses.
 // A logical row permutation makes every MFMA operand a contiguous 32-byte load: hardware k-slot (lane>>4, step s) carries
 // logical index 4*(lane>>4)+s instead of (lane>>4)+4*s — consistently for A and B, so products are unchanged.
@@ -216,14 +216,8 @@ COV_DEV void panel_out(const double* pan, double* sRhs, const double* rs, double
 template <int NWV>
 COV_DEV void potrf_panel_body(double* __restrict__ M, size_t ld, int k0, int nb, double* __restrict__ Dinv_out, int* flag,
                               const double* __restrict__ rhs, double* __restrict__ yout, size_t bsM, size_t bsL, size_t bsR,
-                              const long long* __restrict__ btab, const int* __restrict__ own, const int* __restrict__ list, DevSignal sa, DevSignal sb) {
+                              const long long* __restrict__ btab, const int* __restrict__ own, const int* __restrict__ list) {
   constexpr int PROWS = (NWV == 16) ? 256 : PROWS4;   // (shadows the 16-wave constant)
-  // records of the chain's stream that stand right in front of this launch are published by its first thread (CholAux::publish_handle): at this
-  // point everything enqueued before the launch is complete — one launch less per panel on the serial chain
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (sa.flag != nullptr) __hip_atomic_store(sa.flag, sa.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (sb.flag != nullptr) __hip_atomic_store(sb.flag, sb.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
   constexpr int NTW = (NWV == 16) ? 12 : 3;           // tile waves
   const int front = list != nullptr ? list[blockIdx.x] : (int)blockIdx.x;
   if (own != nullptr) {
@@ -497,14 +491,14 @@ COV_DEV void potrf_panel_body(double* __restrict__ M, size_t ld, int k0, int nb,
 
 __global__ __launch_bounds__(64 * NW) void k_potrf_panel(double* __restrict__ M, size_t ld, int k0, int nb, double* __restrict__ Dinv_out, int* flag,
                                                          const double* __restrict__ rhs, double* __restrict__ yout, size_t bsM, size_t bsL, size_t bsR,
-                                                         const long long* __restrict__ btab, const int* __restrict__ own, const int* __restrict__ list, DevSignal sa, DevSignal sb) {
-  potrf_panel_body<16>(M, ld, k0, nb, Dinv_out, flag, rhs, yout, bsM, bsL, bsR, btab, own, list, sa, sb);
+                                                         const long long* __restrict__ btab, const int* __restrict__ own, const int* __restrict__ list) {
+  potrf_panel_body<16>(M, ld, k0, nb, Dinv_out, flag, rhs, yout, bsM, bsL, bsR, btab, own, list);
 }
 // (three workgroups per CU: 42 KB of LDS each; at most 168 registers per wave)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_potrf_panel4(double* __restrict__ M, size_t ld, int k0, int nb, double* __restrict__ Dinv_out, int* flag,
                                                          const double* __restrict__ rhs, double* __restrict__ yout, size_t bsM, size_t bsL, size_t bsR,
-                                                         const long long* __restrict__ btab, const int* __restrict__ own, const int* __restrict__ list, DevSignal sa, DevSignal sb) {
-  potrf_panel_body<4>(M, ld, k0, nb, Dinv_out, flag, rhs, yout, bsM, bsL, bsR, btab, own, list, sa, sb);
+                                                         const long long* __restrict__ btab, const int* __restrict__ own, const int* __restrict__ list) {
+  potrf_panel_body<4>(M, ld, k0, nb, Dinv_out, flag, rhs, yout, bsM, bsL, bsR, btab, own, list);
 }
 
 struct TrsmSubArgs {
@@ -520,97 +514,9 @@ struct TrsmSubArgs {
   const int* own;                    // [batch] real interior order of every front (nullptr: the launch-wide NB applies to all)
 };
 
-// X = A L^-T on a 16-row slab, L = the (16 NB)-order factor at (k0, k0). One wave, everything in registers.
-// (Measured and dropped: FOUR waves per slab for the 16 slabs of the next panel's rows on the serial chain — block columns dealt
-//  to the waves, Z_j handed on through LDS with one LDS-only barrier per step. Correct, but 260 VGPRs once unrolled — the
-//  workgroup then only starts on an empty CU — and 3.01 vs 2.95 ms for the whole solve.)
-// acc[i][reg] at lane (n = lane & 15, fk = lane >> 4) holds Z[16 i + 4 fk + reg][n] = X[row0 + n][k0 + 16 i + 4 fk + reg].
-template <int NB>
-COV_DEV void trsm_sub_body(const TrsmSubArgs& g) {
-  const int batch = blockIdx.y, lane = threadIdx.x, n = lane & 15, fk = lane >> 4;
-  const int row0 = g.r0 + PB * (int)blockIdx.x;
-  if (g.chain) __builtin_amdgcn_s_setprio(3);  // resident beside bulk-update waves that keep the matrix pipe busy: without it the slab runs 2.5x longer
-  if (g.live != nullptr) {
-    const int nI = g.live[2 * batch], nO = g.live[2 * batch + 1];
-    const int tp = g.k0 / kTile, tr = row0 / kTile;
-    if (!(tp < nI || (tp >= g.tI && tp - g.tI < nO))) return;
-    if (!(tr < nI || (tr >= g.tI && tr - g.tI < nO))) return;
-  }
-  double* Mb = g.M + (g.btab != nullptr ? (size_t)g.btab[2 * batch] : (size_t)batch * g.bsM);
-  const size_t ld = g.btab != nullptr ? (size_t)g.btab[2 * batch + 1] : g.ld;
-  const double* Db = g.Dinv + (size_t)batch * g.bsL;
-  const int pr = 4 * (n & 3) + (n >> 2);  // logical row carried by A-operand lane n
-  double* Arow = Mb + (size_t)(row0 + n) * ld + g.k0 + 4 * fk;
-  const double* Lrow = Mb + (size_t)(g.k0 + pr) * ld + g.k0 + 4 * fk;
-  const double* Drow = Db + pr * PB + 4 * fk;
-  auto Ltile = [&](int i, int j) { return *reinterpret_cast<const v4f64*>(Lrow + (size_t)(PB * i) * ld + PB * j); };
-  auto Dblk = [&](int j) { return *reinterpret_cast<const v4f64*>(Drow + (size_t)(j >> 3) * kTile * kTile + (j & 7) * 256); };
-  v4f64 acc[NB];
-#pragma unroll
-  for (int i = 0; i < NB; ++i) acc[i] = *reinterpret_cast<const v4f64*>(Arow + PB * i);
-  // The L tiles stream through a small ring of registers, fetched RING-1 tiles ahead of their use across block-column
-  // boundaries (every index below is a compile-time constant once the loops are unrolled). With a whole block column
-  // double-buffered the kernel needed 416 VGPRs: a wave then only starts on a SIMD that is EMPTY, and on the serial
-  // chain it queued behind the bulk update's workgroups (18 us alone, 52 us average in the run). ~200 fit beside one.
-  constexpr int RING = 5;
-  v4f64 ring[RING], dcur = Dblk(0), dnxt = dcur;
-  int pi = 1, pj = 0, pt = 0;  // prefetch cursor: next tile (pi, pj) to fetch goes to ring[pt % RING]
-#pragma unroll
-  for (int k = 0; k < RING - 1; ++k)
-    if (pj < NB - 1) { ring[pt % RING] = Ltile(pi, pj); ++pt; if (++pi >= NB) { ++pj; pi = pj + 1; } }
-  int t = 0;
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    if (j + 1 < NB) dnxt = Dblk(j + 1);
-    v4f64 Z = v4f64{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < 4; ++s) Z = __builtin_amdgcn_mfma_f64_16x16x4f64(dcur[s], acc[j][s], Z, 0, 0, 0);
-    acc[j] = Z;
-    const v4f64 Zn = -Z;
-#pragma unroll
-    for (int i = j + 1; i < NB; ++i) {
-      if (pj < NB - 1) { ring[pt % RING] = Ltile(pi, pj); ++pt; if (++pi >= NB) { ++pj; pi = pj + 1; } }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(ring[t % RING][s], Zn[s], acc[i], 0, 0, 0);
-      ++t;
-    }
-    dcur = dnxt;
-  }
-#pragma unroll
-  for (int i = 0; i < NB; ++i) *reinterpret_cast<v4f64*>(Arow + PB * i) = acc[i];
-  if (g.rhs != nullptr) {  // rhs[row0 + n] -= sum_k X[n][k] y[k]: lane partial, fixed butterfly over the four lanes sharing n
-    const double* yv = g.yvec + (size_t)batch * g.bsR + g.k0 + 4 * fk;
-    double part = 0.0;
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const v4f64 y4 = *reinterpret_cast<const v4f64*>(yv + PB * i);
-#pragma unroll
-      for (int s = 0; s < 4; ++s) part += acc[i][s] * y4[s];
-    }
-    part += __shfl_xor(part, 16, 64);
-    part += __shfl_xor(part, 32, 64);
-    if (fk == 0) g.rhs[(size_t)batch * g.bsR + row0 + n] -= part;
-  }
-}
-
-// The launch is sized for the widest front of the batch; a front with fewer real columns in this panel runs the shorter body
-// (its further columns are identity padding: X = A = 0 there), one without any returns at once.
-template <int NB>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_trsm_sub(TrsmSubArgs g) {
-  if (g.own != nullptr) {
-    const int real = g.own[blockIdx.y] - g.k0;
-    if (real <= 0) return;
-    const int nbf = (real + PB - 1) / PB;
-    if (NB > 4 && nbf <= 4) { trsm_sub_body<4>(g); return; }
-    if (NB > 8 && nbf <= 8) { trsm_sub_body<8>(g); return; }
-    if (NB > 12 && nbf <= 12) { trsm_sub_body<12>(g); return; }
-  }
-  trsm_sub_body<NB>(g);
-}
-
-// The same substitution with FOUR waves per slab, one per SIMD: the single wave above is bound by ITS matrix pipe (544 v_mfma_f64_16x16x4 of
-// 64 cycles, dependent or not: 14.5 us before any load latency), and on the serial chain sixteen slabs are all there is to run. Wave w owns
-// the blocks i = w, w + 4, ... of Z. Nobody waits at a barrier: block j of Z goes through LDS (all sixteen kept) behind a counter the
+// X = A L^-T on a 16-row slab, L = the (16 NB)-order factor at (k0, k0), with FOUR waves per slab, one per SIMD: a single wave (round 4's form,
+// retired) is bound by ITS matrix pipe (544 v_mfma_f64_16x16x4 of 64 cycles, dependent or not: 14.5 us before any load latency), and on the serial
+// chain sixteen slabs are all there is to run. Wave w owns the blocks i = w, w + 4, ... of Z. Nobody waits at a barrier: block j of Z goes through LDS (all sixteen kept) behind a counter the
 // other waves poll, and the wave that owns block j + 1 applies L(j+1, j) to it FIRST, publishes Z_{j+1} = Dinv_{j+1} acc_{j+1} and only
 // then catches up on its other blocks — the chain is (read Z_j, 4 MFMAs, 4 MFMAs, write Z_{j+1}) per step, everything else fills in behind.
 // The L tiles of a wave stream through a ring of registers in a FIXED order (step-major; its slot of the next owner's block row is fetched
@@ -1460,8 +1366,8 @@ void launch_pipe_fill(double* buf, size_t n, hipStream_t st) {
 void launch_bwd_tree(const double* M, const BwdTreeLevel* lev, int nlev, BwdXfer xf, double* pipe, int* dead, int* dead_h, double timeout_s, hipStream_t st, bool form64) {
   BwdTreeArgs a;
   a.base = BwdPipeArgs{M, 0, 0, 0, nullptr, nullptr, 0, 0, nullptr, nullptr, xf, pipe, pipe, dead, dead_h, (long long)(timeout_s * 1e8), 2047, 0, 1};
-  static const int check = getenv("COVGPU_PIPE_SPIN_CHECK") ? std::max(1, atoi(getenv("COVGPU_PIPE_SPIN_CHECK"))) : 2048;
-  static const int fault = getenv("COVGPU_PIPE_FAULT") ? atoi(getenv("COVGPU_PIPE_FAULT")) : 0;
+  static const int check = std::max(1, env_int("COVGPU_PIPE_SPIN_CHECK", 2048));
+  static const int fault = env_int("COVGPU_PIPE_FAULT", 0);
   a.base.check = check - 1; a.base.fault = fault;
   a.nlev = nlev; a.wg0[0] = 0;
   size_t off = 0;
@@ -1483,16 +1389,16 @@ void launch_bwd_tree(const double* M, const BwdTreeLevel* lev, int nlev, BwdXfer
 void launch_bwd_pipe(const double* S, int tI, int ntiles, int nchunk, double* y, const double* Linv, int nbt, size_t sL, size_t sR, hipStream_t st,
                      const long long* btab, const int* live, BwdXfer xf, double* pipe, int* dead, int* dead_h, double timeout_s) {
   BwdPipeArgs g{S, tI, ntiles, nchunk, y, Linv, sL, sR, btab, live, xf, pipe, pipe + (size_t)nbt * ntiles * nchunk * kTile, dead, dead_h, (long long)(timeout_s * 1e8), 2047, 0, 0};
-  static const int fault = getenv("COVGPU_PIPE_FAULT") ? atoi(getenv("COVGPU_PIPE_FAULT")) : 0;
+  static const int fault = env_int("COVGPU_PIPE_FAULT", 0);
   g.fault = fault;
-  static const int check = getenv("COVGPU_PIPE_SPIN_CHECK") ? std::max(1, atoi(getenv("COVGPU_PIPE_SPIN_CHECK"))) : 2048;   // (the test of the fallback: 1)
+  static const int check = std::max(1, env_int("COVGPU_PIPE_SPIN_CHECK", 2048));   // (the test of the fallback: 1)
   g.check = check - 1;
   constexpr size_t lds = (size_t)128 * 7 * 8 * sizeof(double);   // the packed blocks of the diagonal tile
   static std::atomic<unsigned long long> seen{0}, seen64{0};
   if (first_use_on_device(seen)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   // few tiles in the launch: the form with the 64x64 inverses (a whole CU per tile workgroup)
-  static const int max64 = getenv("COVGPU_BWD_PIPE64") ? atoi(getenv("COVGPU_BWD_PIPE64")) : 128;
-  if (nbt * ntiles <= max64) {
+  constexpr int kPipe64Max = 128;
+  if (nbt * ntiles <= kPipe64Max) {
     constexpr size_t lds64 = (size_t)kP64Doubles * sizeof(double);
     if (first_use_on_device(seen64)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd_pipe64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64);
     hipLaunchKernelGGL(k_bwd_pipe64, dim3(ntiles * nchunk + ntiles, nbt), dim3(256), lds64, st, g);
@@ -1509,10 +1415,10 @@ void launch_bwd_given(const double* S, size_t ld, int r0, int r1, double* y, dou
                      sR, btab, live, tI, xf);
 }
 
-bool launch_potrf_panel(double* S, size_t ld, int t0, int w, double* Linv, int* flag, double* b, int npad, int nbt, size_t sM, size_t sL, size_t sR,
-                        hipStream_t st, const long long* btab, int nb, const int* own, const int* list, int n_big, int n_small, DevSignal sa, DevSignal sb) {
+void launch_potrf_panel(double* S, size_t ld, int t0, int w, double* Linv, int* flag, double* b, int npad, int nbt, size_t sM, size_t sL, size_t sR,
+                        hipStream_t st, const long long* btab, int nb, const int* own, const int* list, int n_big, int n_small) {
   if (nb < 0) nb = 8 * w;
-  if (nb == 0) return false;  // an all-padding panel of every front of the batch: L = I, Dinv = I, y = 0 are in place
+  if (nb == 0) return;  // an all-padding panel of every front of the batch: L = I, Dinv = I, y = 0 are in place
   static std::atomic<unsigned long long> seen{0};
   if (first_use_on_device(seen)) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_potrf_panel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelLds);
@@ -1521,20 +1427,18 @@ bool launch_potrf_panel(double* S, size_t ld, int t0, int w, double* Linv, int* 
   double* Lp = Linv + (size_t)t0 * kTile * kTile;
   const double* yb = b ? b + npad : nullptr;
   if (list == nullptr) {   // every front of the batch in the sixteen-wave form (arrow blocks of the pose graph, the dense solve)
-    hipLaunchKernelGGL(k_potrf_panel, dim3(nbt), dim3(64 * NW), kPanelLds, st, S, ld, t0 * kTile, nb, Lp, flag, (const double*)b, (double*)yb, sM, sL, sR, btab, own, list, sa, sb);
-    return true;
+    hipLaunchKernelGGL(k_potrf_panel, dim3(nbt), dim3(64 * NW), kPanelLds, st, S, ld, t0 * kTile, nb, Lp, flag, (const double*)b, (double*)yb, sM, sL, sR, btab, own, list);
+    return;
   }
   // list[0 .. n_big): fronts with more than 128 real columns in this panel | list[n_big .. n_big + n_small): the others that have any (four waves)
   // The four-wave form runs three fronts per CU on the same three matrix pipes: per front it is slower (one tile wave per SIMD instead of four), so it
   // only pays when the small fronts outnumber the CUs — 5-agent map, 182 speed-bias segments: 245 it/s with it against 250 without.
-  static const int small_min = getenv("COVGPU_POTRF4_MIN") ? atoi(getenv("COVGPU_POTRF4_MIN")) : 384;
-  if (n_small <= small_min) { n_big += n_small; n_small = 0; }
-  // (the pending records go out with the first launch that happens; false: nothing was launched — the caller publishes them itself)
-  if (n_big > 0) hipLaunchKernelGGL(k_potrf_panel, dim3(n_big), dim3(64 * NW), kPanelLds, st, S, ld, t0 * kTile, nb, Lp, flag, (const double*)b, (double*)yb, sM, sL, sR, btab, own, list, sa, sb);
+  constexpr int kSmallMin = 384;
+  if (n_small <= kSmallMin) { n_big += n_small; n_small = 0; }
+  if (n_big > 0) hipLaunchKernelGGL(k_potrf_panel, dim3(n_big), dim3(64 * NW), kPanelLds, st, S, ld, t0 * kTile, nb, Lp, flag, (const double*)b, (double*)yb, sM, sL, sR, btab, own, list);
   if (n_small > 0)
     hipLaunchKernelGGL(k_potrf_panel4, dim3(n_small), dim3(256), kPanelLds4, st, S, ld, t0 * kTile, std::min(nb, 8), Lp, flag, (const double*)b, (double*)yb, sM, sL, sR, btab, own,
-                       list + n_big, n_big > 0 ? DevSignal() : sa, n_big > 0 ? DevSignal() : sb);
-  return n_big > 0 || n_small > 0;
+                       list + n_big);
 }
 
 void launch_trsm_sub(double* S, size_t ld, int t0, int w, int r0, int r1, const double* Linv, double* b, int npad, int nbt, size_t sM, size_t sL,
@@ -1544,18 +1448,10 @@ void launch_trsm_sub(double* S, size_t ld, int t0, int w, int r0, int r1, const 
   const dim3 grid((r1 - r0) * (kTile / PB), nbt);
   // nb: 16-column blocks of the panel that hold real columns (the rest is identity padding with zeros below: X = A there)
   const int need = nb > 0 ? std::min(nb, 8 * w) : 8 * w;
-  static const int four = getenv("COVGPU_TRSM4") == nullptr ? 1 : atoi(getenv("COVGPU_TRSM4"));   // 0: one wave per slab everywhere; 2: four waves on the serial chain only
-  if (four == 1 || (four == 2 && chain)) {
-    if (need <= 4) hipLaunchKernelGGL(k_trsm_sub4<4>, grid, dim3(256), 0, st, g);
-    else if (need <= 8) hipLaunchKernelGGL(k_trsm_sub4<8>, grid, dim3(256), 0, st, g);
-    else if (need <= 12) hipLaunchKernelGGL(k_trsm_sub4<12>, grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(k_trsm_sub4<16>, grid, dim3(256), 0, st, g);
-    return;
-  }
-  if (need <= 4) hipLaunchKernelGGL(k_trsm_sub<4>, grid, dim3(64), 0, st, g);
-  else if (need <= 8) hipLaunchKernelGGL(k_trsm_sub<8>, grid, dim3(64), 0, st, g);
-  else if (need <= 12) hipLaunchKernelGGL(k_trsm_sub<12>, grid, dim3(64), 0, st, g);
-  else hipLaunchKernelGGL(k_trsm_sub<16>, grid, dim3(64), 0, st, g);
+  if (need <= 4) hipLaunchKernelGGL(k_trsm_sub4<4>, grid, dim3(256), 0, st, g);
+  else if (need <= 8) hipLaunchKernelGGL(k_trsm_sub4<8>, grid, dim3(256), 0, st, g);
+  else if (need <= 12) hipLaunchKernelGGL(k_trsm_sub4<12>, grid, dim3(256), 0, st, g);
+  else hipLaunchKernelGGL(k_trsm_sub4<16>, grid, dim3(256), 0, st, g);
 }
 
 void launch_bwd_front(const double* S, int tI, int ntiles, int nchunk, double* y, const double* Linv, int nbt, size_t sL, size_t sR, hipStream_t st,

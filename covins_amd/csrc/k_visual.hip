@@ -92,25 +92,8 @@ COV_DEV void z_of(const ObsLin& e, const double* R, double* Z) {
   }
 }
 
-// (compile-time A/B: -DCOVGPU_LMLIN_WAVES=n / -DCOVGPU_PAIR_WAVES=n cap the registers for n waves per SIMD; tools/gpu_ab.sh with COVGPU_LIBRARY)
-#ifndef COVGPU_LMLIN_WAVES
-#define COVGPU_LMLIN_WAVES 0
-#endif
-#ifndef COVGPU_PAIR_WAVES
-#define COVGPU_PAIR_WAVES 0
-#endif
-#if COVGPU_LMLIN_WAVES > 0
-#define LMLIN_ATTR __attribute__((amdgpu_waves_per_eu(COVGPU_LMLIN_WAVES, COVGPU_LMLIN_WAVES)))
-#else
-#define LMLIN_ATTR
-#endif
-#if COVGPU_PAIR_WAVES > 0
-#define PAIR_ATTR __attribute__((amdgpu_waves_per_eu(COVGPU_PAIR_WAVES, COVGPU_PAIR_WAVES)))
-#else
-#define PAIR_ATTR
-#endif
 template <int G, bool UNI>
-__global__ __launch_bounds__(kBuildThreads) LMLIN_ATTR void k_lm_lin(DevProblem P, double mu, DevSignal sig) {
+__global__ __launch_bounds__(kBuildThreads) void k_lm_lin(DevProblem P, double mu, DevSignal sig) {
   constexpr int GROUPS = kBuildThreads / G;
   // "everything before this kernel on its stream is complete" (the previous iteration's state update, the preintegration): the side stream's
   // kernels of this pass start from it — published here instead of by a launch in front of the pass's critical path
@@ -281,7 +264,7 @@ __global__ __launch_bounds__(64) void k_kf_reduce(DevProblem P) {
 // 0.78 ms on the 5-agent map, the longest kernel of the linearisation.)
 constexpr int kPairLanes = 16, kPairsPerWg = 8;
 constexpr int kPairChunk = 64;   // consecutive workgroups (of kPairsPerWg pairs) that one XCD takes together
-__global__ __launch_bounds__(kPairLanes * kPairsPerWg) PAIR_ATTR void k_pair_blocks(DevProblem P, int pair_xcd_order) {
+__global__ __launch_bounds__(kPairLanes * kPairsPerWg) void k_pair_blocks(DevProblem P) {
   __shared__ double sp[kPairsPerWg][36][kPairLanes + 1];
   const int grp = threadIdx.x / kPairLanes, g = threadIdx.x % kPairLanes;
   // XCD-aware order (round 5): workgroup b runs on XCD b % 8 (observed dispatch order; placement affects speed only). The pair list is sorted by
@@ -293,7 +276,7 @@ __global__ __launch_bounds__(kPairLanes * kPairsPerWg) PAIR_ATTR void k_pair_blo
   //  a chunk spans ~10 row keyframes, an XCD gets every eighth chunk.)
   const int nblk = (P.npairs + kPairsPerWg - 1) / kPairsPerWg;
   const int kx = (int)blockIdx.x >> 3, xcd = (int)blockIdx.x & 7;
-  const int lb = pair_xcd_order ? ((kx / kPairChunk) * 8 + xcd) * kPairChunk + kx % kPairChunk : (int)blockIdx.x;
+  const int lb = ((kx / kPairChunk) * 8 + xcd) * kPairChunk + kx % kPairChunk;
   const int p = lb * kPairsPerWg + grp;
   const bool ok = lb < nblk && p < P.npairs;
   const int e0 = ok ? P.pair_ptr[p] : 0, e1 = ok ? P.pair_ptr[p + 1] : 0;
@@ -473,10 +456,9 @@ void launch_lm_build(const DevProblem& P, double mu, hipStream_t st, hipEvent_t 
   hipLaunchKernelGGL(k_cost_finish, dim3(1), dim3(256), 0, s2, P, nblk);
   with_uni(P, [&](auto U) { hipLaunchKernelGGL(k_kf_reduce<decltype(U)::value>, dim3(P.K), dim3(64), 0, s2, P); });
   if (P.npairs) {
-    static const int xcd_order = getenv("COVGPU_PAIR_XCD") == nullptr || atoi(getenv("COVGPU_PAIR_XCD")) != 0;
     const int nblk = (P.npairs + kPairsPerWg - 1) / kPairsPerWg;
     const int nchunk8 = (nblk + 8 * kPairChunk - 1) / (8 * kPairChunk);   // rounds of eight chunks
-    hipLaunchKernelGGL(k_pair_blocks, dim3(xcd_order ? nchunk8 * 8 * kPairChunk : nblk), dim3(kPairLanes * kPairsPerWg), 0, st, P, xcd_order);
+    hipLaunchKernelGGL(k_pair_blocks, dim3(nchunk8 * 8 * kPairChunk), dim3(kPairLanes * kPairsPerWg), 0, st, P);
   }
   // (fork: the caller joins the side stream back — it has more on it)
 }

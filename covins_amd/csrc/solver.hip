@@ -337,8 +337,7 @@ extern "C" int covgpu_create(const covgpu_options* opt, covgpu_context** out) {
   HIPCHK(hipHostMalloc((void**)&c->h_scal, (SC_COUNT + 4) * sizeof(double), hipHostMallocDefault));
   HIPCHK(hipHostMalloc((void**)&c->h_tr, TR_COUNT * sizeof(double), hipHostMallocDefault));
   {
-    static const bool box_on = getenv("COVGPU_MAILBOX") == nullptr || atoi(getenv("COVGPU_MAILBOX")) != 0;
-    if (box_on && hipHostMalloc((void**)&c->h_box, (TR_COUNT + 1) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
+    if (hipHostMalloc((void**)&c->h_box, (TR_COUNT + 1) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
       std::memset(c->h_box, 0, (TR_COUNT + 1) * sizeof(double));
       if (hipHostGetDevicePointer((void**)&c->d_box, c->h_box, 0) != hipSuccess) c->d_box = nullptr;
     } else { (void)hipGetLastError(); c->h_box = nullptr; }
@@ -404,7 +403,7 @@ extern "C" void covgpu_get_layout(covgpu_context* c, int64_t* out) {
   out[0] = c->sharded ? c->world : 0; out[1] = c->sharded ? c->rank : 0; out[2] = c->nd.ntop;   // ranks | rank | scalar unknowns of the replicated top nodes
   out[3] = (int64_t)c->nd.lev.size() - c->nd.top_lev0;                                          // top levels
   out[4] = c->nd.dist ? (int64_t)((c->nd.dist_solve_elems * sizeof(double)) >> 10)   // distributed top: every panel's exchange + gradient, diag(J^T J) of the top unknowns
-                      : (int64_t)(((c->nd.top_pack != nullptr ? (size_t)c->nd.n_top_tiles * kTile * kTile : c->nd.M_elems - c->nd.M_sub) + c->nd.rhs_top + 2 * (size_t)c->nd.ntop) * sizeof(double)) >> 10;  // KiB all-reduced per linear solve
+                      : (int64_t)(((size_t)c->nd.n_top_tiles * kTile * kTile + c->nd.rhs_top + 2 * (size_t)c->nd.ntop) * sizeof(double)) >> 10;  // KiB all-reduced per linear solve
   out[5] = c->chol.pipe_broken ? -1 : c->chol.gates_on ? 1 : 0;   // stream ordering: 1 device flags | 0 HIP events (COVGPU_GATES=0) | -1 a gate or the backward pipeline timed out: events and the launch-per-tile substitution from then on
   out[6] = P.npad; out[7] = P.npairs; out[8] = P.nepairs; out[9] = P.nchains; out[10] = (int64_t)(c->alloc_bytes >> 20);
   if (P.nd) {  // multifrontal form: nodes, levels, serial 256-column panels (sum of the levels' interior orders / 256), root order, front bytes (MiB)
@@ -783,17 +782,16 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
   P.I = vi ? p->num_imu : 0; P.E = p->num_edge;
   P.S = P.I ? p->imu_sample_ptr[P.I] : 0;
   P.vi = vi; P.D = vi ? 15 : 6; P.n = P.D * P.K;
-  {  // lanes per landmark of the landmark-major kernels, from the mean track length (COVGPU_LM_GROUP forces 4 / 8 / 16)
+  {  // lanes per landmark of the landmark-major kernels, from the mean track length
     const double mean_track = P.L > 0 ? (double)P.O / P.L : 0.0;
     P.lm_group = mean_track <= 5.0 ? 4 : (mean_track <= 8.0 ? 8 : 16);   // configs[4] (4.1): linearise+Schur 4.65 ms at 16 lanes, 4.24 at 8, 4.11 at 4; 5-agent map (10.0): 16 and 8 alike
-    if (const char* e = getenv("COVGPU_LM_GROUP")) { const int g = atoi(e); if (g == 4 || g == 8 || g == 16) P.lm_group = g; }
   }
   P.npad = ((6 * P.K + kTile - 1) / kTile) * kTile;  // dense stage = pose-pose system only (k_struct.hip)
   P.N = P.n + 3 * P.L;
   // IMU chains -> chain-major keyframe order
   std::vector<int> perm, pos_kf, chain_ptr;
   // pose graph on the elimination tree (round 6; COVGPU_PGO_ND=0: round 2's block-arrow scheme of k_pgo.hip on a dense matrix)
-  const bool pgo_nd_on = getenv("COVGPU_PGO_ND") == nullptr || atoi(getenv("COVGPU_PGO_ND")) != 0;   // (read per upload: the parity test switches it)
+  const bool pgo_nd_on = env_int("COVGPU_PGO_ND", 1) != 0;   // (read per upload: the parity test switches it)
   const char* e_pgo_dense = getenv("COVGPU_PGO_DENSE");
   const bool pgo_nd = pgo && pgo_nd_on && allow_arrow && p->num_edge > 0 && !(e_pgo_dense && e_pgo_dense[0] == '1') && !c->sharded;
   if (pgo_nd) build_chains_pgo(p, perm, pos_kf, chain_ptr);
@@ -1063,7 +1061,6 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
         }
         RC(dev_upload(c, &P.vw, vw.data(), vw.size()));
         RC(dev_alloc(c, &c->d_red, (size_t)SC_COUNT + 2 * (size_t)c->world));
-        static const bool pack_on = getenv("COVGPU_SHARD_PACK") == nullptr || atoi(getenv("COVGPU_SHARD_PACK")) != 0;
         nd.n_top_tiles = (int)(nd.h_top_tiles.size() / 3);
         if (nd.dist) {   // distributed top (shard policy 1): per-panel exchange entries, owned trailing-update tiles, one reduce buffer for the largest panel
           RC(up_or_zero(&nd.dist_ent, nd.h_dist_ent, 4)); RC(up_or_zero(&nd.dist_tri, nd.h_dist_tri, 1));
@@ -1072,7 +1069,7 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
             L.dt_dev.assign(L.dt_cnt.size(), nullptr);
             for (size_t q = 0; q < L.dt_cnt.size(); ++q) if (L.dt_cnt[q] > 0) L.dt_dev[q] = nd.dist_tri + L.dt_first[q];
           }
-        } else if (pack_on) {
+        } else {
           RC(dev_upload(c, &nd.top_tiles, nd.h_top_tiles.data(), nd.h_top_tiles.size()));
           RC(dev_alloc(c, &nd.top_pack, (size_t)nd.n_top_tiles * kTile * kTile + nd.rhs_top + 2 * (size_t)nd.ntop));
         }
@@ -1350,14 +1347,12 @@ static int solve_impl_dev(covgpu_context* c, const covgpu_options* opt, covgpu_r
   int it = 0, accepted = 0, term = 0;
   // COVGPU_TAIL=0: the round-3 tail (two J*v passes of three kernels, seven partial-sum finishers, four one-thread logic kernels:
   // ~25 dependent launches); default: the fused tail of k_tail.hip (8 launches, one J*v pass for both dogleg directions)
-  static const bool fused_tail = getenv("COVGPU_TAIL") == nullptr || atoi(getenv("COVGPU_TAIL")) != 0;
+  static const bool fused_tail = env_int("COVGPU_TAIL", 1) != 0;
   const bool two = o.strategy == COVGPU_DOGLEG;
   const bool coll = c->sharded && c->reducer != nullptr;   // scalar all-reduce between a finish and the step logic that reads it
-  static const bool host_timing = getenv("COVGPU_HOST_TIMING") != nullptr;   // dev aid: host enqueue time | host wait per iteration
   bool use_box = false;
   while (it < o.max_iterations) {
     use_box = false;
-    const auto t_enq0 = std::chrono::steady_clock::now();
     if (fused_tail) {
       if (!reuse) {
         const double damp = (o.strategy == COVGPU_LM) ? 1.0 / h[TR_RADIUS] : h[TR_MU];
@@ -1374,7 +1369,7 @@ static int solve_impl_dev(covgpu_context* c, const covgpu_options* opt, covgpu_r
       if (coll) { reduce_scalars(c); launch_tail_logic(P, tc, 2, 0, c->st); }
       // (one GPU, no profiling events to collect: the state the host needs travels through the pinned mailbox, no D2H copy, no sleeping wait)
       static const bool dev_aids = getenv("COVGPU_TRACE_PANELS") != nullptr || getenv("COVGPU_GATE_LOG") != nullptr;   // (their print-outs read events / device logs behind a synchronisation)
-      use_box = c->d_box != nullptr && !coll && !c->profiling && !host_timing && !dev_aids;
+      use_box = c->d_box != nullptr && !coll && !c->profiling && !dev_aids;
       if (use_box) c->box_seq += 1.0;
       launch_tr_accept(P, c->st, use_box ? c->d_box : nullptr, c->box_seq);
     } else {
@@ -1398,7 +1393,6 @@ static int solve_impl_dev(covgpu_context* c, const covgpu_options* opt, covgpu_r
     reduce_scalars(c);
     launch_tr_decide(P, tc, c->st);
     }
-    const auto t_enq1 = std::chrono::steady_clock::now();
     if (use_box) {
       // poll the sequence word (the kernel stores it with release semantics behind the state); every 4096 polls look at the stream: an error, or a stream
       // that drained without the word arriving (never observed), ends in the ordinary path
@@ -1422,9 +1416,6 @@ static int solve_impl_dev(covgpu_context* c, const covgpu_options* opt, covgpu_r
       HIPCHK(hipMemcpyAsync(h, P.tr, TR_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->st));
       RC(wait_iteration(c));
     }
-    if (host_timing)
-      std::fprintf(stderr, "[covgpu] iteration %d: host enqueue %.0f us, host wait %.0f us\n", it, std::chrono::duration<double>(t_enq1 - t_enq0).count() * 1e6,
-                   std::chrono::duration<double>(std::chrono::steady_clock::now() - t_enq1).count() * 1e6);
     collect_profile(c, !reuse, !reuse);
     if (!got_initial) { res->initial_cost = h[TR_INITCOST]; got_initial = true; }
     if (h[TR_RETRY] != 0.0) { reuse = false; continue; }  // factorisation failed: same iteration again with the raised damping

@@ -1,6 +1,6 @@
 // panel_probe.hip — correctness + phase timing of the 256-column panel chain kernels (k_panel.hip) on an idle GPU (dev tool):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DCOVGPU_PROBE tools/panel_probe.hip -o /tmp/panel_probe && /tmp/panel_probe
-// Checks k_potrf_panel (nb = 16 and 8, batched, with the right-hand side riding along), k_trsm_sub<16|8> and
+// Checks k_potrf_panel (nb = 16 and 8, batched, with the right-hand side riding along), k_trsm_sub4<16|8> and
 // k_bwd_step_sub against a host Cholesky in double precision.
 #include <algorithm>
 #include <cmath>
@@ -178,7 +178,7 @@ int main() {
       }
     }
     printf("  max|L - L_host| %.3e (max|L| %.2e)  max|y - y_host| %.3e  max|Dinv L - I| %.3e  upper triangle touched %.1e  flag %d\n", eL, lmax, eY, eD, eU, fl);
-    printf("k_trsm_sub<%d> on %d slabs x%d: best %.1f us   max|X - X_host| %.3e  max|rhs - rhs_host| %.3e\n", nb, (N - k0 - n) / 16, NBT, bestT * 1e3, eX, eR);
+    printf("k_trsm_sub4<%d> on %d slabs x%d: best %.1f us   max|X - X_host| %.3e  max|rhs - rhs_host| %.3e\n", nb, (N - k0 - n) / 16, NBT, bestT * 1e3, eX, eR);
     if (nb == 8) {
       // backward step on tile t0: x_p = L_pp^-T y_p, y[cols < k0] -= L[tile rows, cols]^T x_p (the columns left of the tile
       // hold arbitrary numbers here: fill them)
