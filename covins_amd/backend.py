@@ -55,6 +55,10 @@ def lib() -> C.CDLL:
         _LIB.covgpu_get_profile2.restype = None
         _LIB.covgpu_get_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         _LIB.covgpu_get_layout.restype = None
+        _LIB.covgpu_get_kernel_forms.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
+        _LIB.covgpu_get_kernel_forms.restype = C.c_int
+        _LIB.covgpu_kernel_form_name.argtypes = [C.c_int32]
+        _LIB.covgpu_kernel_form_name.restype = C.c_char_p
     return _LIB
 
 
@@ -66,6 +70,12 @@ def pgo_partition(num_kf: int, edge_i, edge_j):
     out = np.empty(num_kf, np.int32)
     n = lib().covgpu_pgo_partition(num_kf, len(ei), ei.ctypes.data_as(capi._ip), ej.ctypes.data_as(capi._ip), out.ctypes.data_as(capi._ip))
     return out, int(n)
+
+
+def kernel_form_names():
+    """Names of the kernel forms Context.kernel_forms() counts, in the library's order."""
+    n = lib().covgpu_get_kernel_forms(None, None, 0)
+    return [lib().covgpu_kernel_form_name(i).decode() for i in range(n)]
 
 
 def default_options(**kw) -> Options:
@@ -312,6 +322,13 @@ class Context:
         keys = ("shard_world", "shard_rank", "top_unknowns", "top_levels", "allreduce_kib", "stream_ordering", "dense_order", "covisible_pairs",
                 "edge_pairs", "chains", "device_mib", "nd_fronts", "nd_levels", "nd_serial_panels", "nd_root_order", "nd_front_mib")
         return {k: int(out[i]) for i, k in enumerate(keys)}
+
+    def kernel_forms(self) -> dict:
+        """Launches per kernel form of the linear solves on this context since its last upload (include/covgpu.h lists the forms)."""
+        names = kernel_form_names()
+        out = (C.c_int64 * len(names))()
+        lib().covgpu_get_kernel_forms(self._h, out, len(names))
+        return {k: int(out[i]) for i, k in enumerate(names)}
 
     # ---- per-kernel entry points (tests)
     def residual_norms(self, prob, opt):

@@ -242,6 +242,31 @@ struct PgoPlan;
 // pose graph: the system assembled in P.Sred / P.bred -> dst (IR layout); block-arrow elimination (k_pgo.hip) or plain dense Cholesky
 void launch_pose_graph_solve(const DevProblem& P, double* dst, hipStream_t st, CholAux& ax, PgoPlan* pgo);
 void launch_zero_system(const DevProblem& P, hipStream_t st);       // every small per-iteration buffer, one launch
+// ---- census of kernel forms (covgpu_get_kernel_forms, include/covgpu.h): which of the shape-dependent launch forms of the linear solve a context
+// has issued since its last upload. Host-side integers bumped at the launch sites; nothing of it reaches the device. The names (kFormNames,
+// k_chol.hip) are listed in include/covgpu.h in this order.
+enum KernelForm {
+  KF_POTRF_PANEL = 0, KF_POTRF_PANEL_FRONTS, KF_POTRF_PANEL4, KF_POTRF_PANEL4_FRONTS, KF_POTRF_SKIPPED,
+  KF_TRSM_SUB4_4, KF_TRSM_SUB4_8, KF_TRSM_SUB4_12, KF_TRSM_SUB4_16,
+  KF_GEMM_TRI_FULL, KF_GEMM_TRI_QUAD, KF_GEMM_TRI_GRID, KF_GEMM_RECT_FULL, KF_GEMM_RECT_QUAD,
+  KF_BULK_ONE_LAUNCH, KF_BULK_TWO_LAUNCHES, KF_LAST_UPDATE_WHOLE, KF_LAST_UPDATE_SPLIT, KF_PANEL_ONE_TILE, KF_KD_CUT, KF_KD_ZERO, KF_GEMM_BETA0,
+  KF_BWD_FRONT, KF_BWD_PIPE, KF_BWD_PIPE64, KF_BWD_TREE, KF_BWD_TREE64, KF_BWD_GIVEN, KF_BWD_STEP_SUB,
+  KF_ND_EXTEND_REC, KF_ND_EXTEND, KF_ND_EXTEND_SPLIT,
+  KF_ND_TOP_PACK, KF_ND_GH, KF_ND_TOP_DAMP, KF_ND_PANEL_XFER, KF_DIST_PANEL,
+  KF_PGO_ARROW, KF_PGO_DENSE,
+  KF_COUNT
+};
+extern const char* const kFormNames[KF_COUNT];
+struct FormCensus { long long n[KF_COUNT] = {}; };
+// the census the launchers of this host thread count into (nullptr: none); set for the length of one solve by solver.hip (FormScope)
+extern thread_local FormCensus* t_forms;
+inline void form_hit(int f, long long k = 1) { if (t_forms != nullptr) t_forms->n[f] += k; }
+struct FormScope {
+  FormCensus* prev;
+  explicit FormScope(FormCensus* c) : prev(t_forms) { t_forms = c; }
+  ~FormScope() { t_forms = prev; }
+  FormScope(const FormScope&) = delete; FormScope& operator=(const FormScope&) = delete;
+};
 // per-context resources of the dense factorisation: auxiliary stream for the look-ahead, ordering events, and
 // (profiling only) one timed event pair around every bulk trailing-update launch
 struct CholAux {
@@ -270,6 +295,7 @@ struct CholAux {
     int *listA = nullptr, *listB = nullptr; int countA = 0, countB = 0;   // last panel's update split at DenseBatch::split_ta
     void clear();
   };
+  FormCensus forms;               // launches per kernel form since the last upload (covgpu_get_kernel_forms)
   TriCache tri0;                  // block-arrow batches of the pose-graph solve (k_pgo.hip)
   std::vector<TriCache> tri_lev;  // one per level of the multifrontal solve (k_front.hip), selected by DenseBatch::tri_slot
   void tri_clear();

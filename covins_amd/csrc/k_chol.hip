@@ -542,6 +542,20 @@ void CholAux::collect() {
   prof_flops2.clear();
 }
 
+// census of kernel forms (common.hpp: KernelForm; the same names, in the same order, in include/covgpu.h)
+thread_local FormCensus* t_forms = nullptr;
+const char* const kFormNames[KF_COUNT] = {
+  "k_potrf_panel", "k_potrf_panel.fronts", "k_potrf_panel4", "k_potrf_panel4.fronts", "potrf_skipped",
+  "k_trsm_sub4<4>", "k_trsm_sub4<8>", "k_trsm_sub4<12>", "k_trsm_sub4<16>",
+  "k_gemm_abt.tri", "k_gemm_abt_q.tri", "k_gemm_abt.tri_grid", "k_gemm_abt.rect", "k_gemm_abt_q.rect",
+  "bulk_one_launch", "bulk_two_launches", "last_update_whole", "last_update_split", "panel_one_tile", "kd_cut", "kd_zero", "gemm_beta0",
+  "k_bwd_front", "k_bwd_pipe", "k_bwd_pipe64", "k_bwd_tree", "k_bwd_tree64", "k_bwd_given", "k_bwd_step_sub",
+  "k_nd_extend_rec", "k_nd_extend", "nd_extend_split",
+  "k_nd_top_pack", "k_nd_gh", "k_nd_top_damp", "k_nd_panel_xfer", "dist_panel",
+  "pgo_arrow", "pgo_dense",
+};
+static_assert(sizeof(kFormNames) / sizeof(kFormNames[0]) == KF_COUNT, "one name per kernel form");
+
 // trailing updates given as explicit tile lists of at most this many entries (incl. the XCD padding) run as 64x64 quadrants
 static const int kQuarterMax = env_int("COVGPU_QUARTER_MAX", 1024);
 // look-ahead update of the rows below the next panel (stream R): tiles up to which it runs as quarter tiles
@@ -578,6 +592,7 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
   auto rect = [&](int r0, int r1, int tc0, int ntc, int kt0, int KD, hipStream_t s2, bool quad) {
     if (r1 <= r0 || ntc <= 0 || KD <= 0) return;
     GemmArgs g{S, ld, kt0 * kTile, KD, r0 * kTile, tc0 * kTile, tc0 * kTile, r1 - r0, nullptr, nullptr, nullptr, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, nullptr, bt.tab, bt.own_dims};
+    form_hit(quad ? KF_GEMM_RECT_QUAD : KF_GEMM_RECT_FULL);
     if (quad) hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_RECT, 64, 64>), dim3(ntc, r1 - r0, 4 * nbt), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), s2, g);
     else hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_RECT>, dim3(ntc, r1 - r0, nbt), dim3(256), lds_gemm, s2, g);
   };
@@ -670,6 +685,11 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
   // (per front n^3 / 3 for the factorisation + n^2 for the forward substitution riding along, n = the front's REAL columns in the panel)
   auto potrf = [&](int t0, int w, int nbp) {
     const bool prof = ax.profile && nbp != 0;
+    if (w == 1) form_hit(KF_PANEL_ONE_TILE);
+    if (T > t0 + w) {   // K range of this panel's rank update (kd)
+      if (kd(t0 / 2) == 0) form_hit(KF_KD_ZERO);
+      else if (kd(t0 / 2) < w * kTile) form_hit(KF_KD_CUT);
+    }
     if (prof) {
       while (ax.prof_ev2.size() < 2 * (ax.prof_flops2.size() + 1)) { hipEvent_t e; (void)hipEventCreate(&e); ax.prof_ev2.push_back(e); }
       (void)hipEventRecord(ax.prof_ev2[2 * ax.prof_flops2.size()], M);
@@ -755,6 +775,8 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
           if (ax.profile) (void)hipEventRecord(ax.prof_ev[2 * ax.prof_flops.size()], s2);
           // a short list runs at the LATENCY of one workgroup's K loop (16 chunks of 64 MFMAs per wave): as 64x64 quadrants it is
           // four times as many workgroups, each four times shorter
+          form_hit(list == nullptr ? KF_GEMM_TRI_GRID : count <= kQuarterMax ? KF_GEMM_TRI_QUAD : KF_GEMM_TRI_FULL);
+          if (g.beta0 != nullptr && t0 == 0) form_hit(KF_GEMM_BETA0);
           if (list != nullptr && count <= kQuarterMax)
             hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_TRI, 64, 64>), dim3(count, 1, 4), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), s2, g);
           else if (list != nullptr) hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(count, 1), dim3(256), lds_gemm, s2, g);
@@ -781,6 +803,7 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
             const int na = std::min(nl, bt.split_ta);
             pairsA += (double)na * (na + 1) / 2 * per_k * kf;
           }
+          form_hit(split ? KF_LAST_UPDATE_SPLIT : KF_LAST_UPDATE_WHOLE);
           if (split) {
             // look-ahead across levels: the tiles the parents' first panel receives on the chain's stream, the rest on the bulk stream
             if (tc.countA > 0) syrk(M, tc.listA, tc.countA, pairsA);
@@ -885,16 +908,23 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
         if (ax.profile) (void)hipEventRecord(ax.prof_ev[2 * ax.prof_flops.size()], B);
         auto tri = [&](const int* list, int count) {
           g.tri = list;
+          form_hit(count <= kQuarterMax ? KF_GEMM_TRI_QUAD : KF_GEMM_TRI_FULL);
+          if (g.beta0 != nullptr && t0 == 0) form_hit(KF_GEMM_BETA0);
           if (count <= kQuarterMax) hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_TRI, 64, 64>), dim3(count, 1, 4), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), B, g);
           else hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(count, 1), dim3(256), lds_gemm, B, g);
         };
+        form_hit(cntC > 0 && listed && tc.count[P] > 0 ? KF_BULK_TWO_LAUNCHES : KF_BULK_ONE_LAUNCH);
         if (cntC > 0) {   // the next-but-one panel's two tile columns first: what the chain waits for
           tri(tc.listC[P], cntC);
           record(eA[P], B, 100 * (P + 1) + 18); recA = true;
           if (trace2) ax.mark(B, 100 * (P + 1) + 8);   // first bulk launch done
         }
         if (listed) { if (tc.count[P] > 0) tri(tc.list[P], tc.count[P]); }
-        else hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(nblk, nbt), dim3(256), lds_gemm, B, g);
+        else {
+          form_hit(KF_GEMM_TRI_GRID);
+          if (g.beta0 != nullptr && t0 == 0) form_hit(KF_GEMM_BETA0);
+          hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(nblk, nbt), dim3(256), lds_gemm, B, g);
+        }
         if (ax.profile) {
           (void)hipEventRecord(ax.prof_ev[2 * ax.prof_flops.size() + 1], B);
           ax.prof_flops.push_back(flops);
@@ -934,6 +964,7 @@ void dense_cholesky_dist(double* S, double* b, double* Linv, int* flag, int npad
   for (int P = 0; P < Pstop; ++P) {
     const int t0 = 2 * P, w = (T - t0 >= 2) ? 2 : 1, tb = t0 + 2;
     ax.mark(st, P);
+    form_hit(KF_DIST_PANEL);
     if (d.exchange != nullptr) d.exchange(d.ctx, P);
     const int nbp = bt.own_max > 0 ? std::max(0, std::min(8 * w, (bt.own_max - t0 * kTile + 15) / 16)) : -1;
     if (bt.plist != nullptr) launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, st, bt.tab, nbp, bt.own_dims, bt.plist, bt.pbig_h[P], bt.psmall_h[P]);
@@ -943,6 +974,7 @@ void dense_cholesky_dist(double* S, double* b, double* Linv, int* flag, int npad
     if (T > tb && kd(P) > 0 && count > 0 && d.tri[P] != nullptr) {
       GemmArgs g{S, ld, t0 * kTile, kd(P), tb * kTile, tb * kTile, tb * kTile, T - tb, nullptr, nullptr, nullptr, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, nullptr, bt.tab, bt.own_dims};
       g.tri = d.tri[P];
+      form_hit(count <= kQuarterMax ? KF_GEMM_TRI_QUAD : KF_GEMM_TRI_FULL);
       if (count <= kQuarterMax) hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_TRI, 64, 64>), dim3(count, 1, 4), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), st, g);
       else hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(count, 1), dim3(256), lds_gemm, st, g);
     }

@@ -787,6 +787,7 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
     if (part == 1) count = countA;
     if (part == 2) { first += countA; count -= countA; }
     static const bool records = env_int("COVGPU_EXT_RECORDS", 1) != 0;
+    if (count > 0) { form_hit(records && nd.extr != nullptr ? KF_ND_EXTEND_REC : KF_ND_EXTEND); if (part != 0) form_hit(KF_ND_EXTEND_SPLIT); }
     if (count > 0 && records && nd.extr != nullptr)
       hipLaunchKernelGGL(k_nd_extend_rec, dim3(count), dim3(256), 0, s2, P, lev_args(P, nd, l), (const int*)(nd.extr + (size_t)kExtRec * first),
                          (const int*)(nd.extr + (size_t)kExtRec * nd.ext_over), top_children ? 1 : 0, (!top_children && l < ltop && nd_beta0()) ? 1 : 0, sig);
@@ -839,6 +840,8 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
     //      damping of the top unknowns; from here on every rank runs the top of the tree redundantly, with no further exchange.
     for (int l = ltop; l < nlev; ++l) extend(l, false, 0, st);
     double* gh = P.nd_rhs + nd.gh_off;
+    if (nd.ntop > 0) { form_hit(KF_ND_GH, 2); form_hit(KF_ND_TOP_DAMP); }
+    if (ax.reduce != nullptr && nd.n_top_tiles > 0) form_hit(KF_ND_TOP_PACK, 2);
     if (nd.ntop > 0) hipLaunchKernelGGL(k_nd_gh, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 0);
     if (ax.reduce != nullptr) {
       // ONE all-reduce of [live lower tiles of the top fronts, packed | top right-hand sides | grad, hdiag of the top unknowns]: the
@@ -865,6 +868,7 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
     for (int l = ltop; l < nlev; ++l) extend(l, false, 0, st);
     double* gh = P.nd_rhs + nd.gh_off;
     if (nd.ntop > 0) {
+      form_hit(KF_ND_GH, 2); form_hit(KF_ND_TOP_DAMP);
       hipLaunchKernelGGL(k_nd_gh, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 0);
       if (ax.reduce != nullptr) ax.reduce(ax.reduce_ctx, gh, 2 * (size_t)nd.ntop, 0, st);
       hipLaunchKernelGGL(k_nd_gh, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 1);
@@ -879,6 +883,7 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
       if (ne == 0 || x.ax->reduce == nullptr) return;
       const int4* ent = reinterpret_cast<const int4*>(x.nd->dist_ent) + L.dx_first[Pp];
       const size_t n = (size_t)nt * kTile * kTile + (size_t)L.dx_nr[Pp] * 256;
+      form_hit(KF_ND_PANEL_XFER, 2);
       hipLaunchKernelGGL(k_nd_panel_xfer, dim3(ne), dim3(256), 0, x.st, *x.P, ent, nt, x.nd->dist_buf, (const int*)x.nd->rhs_node, (const int*)x.nd->own_dims, 0,
                          x.nd->dist_lead ? 1 : 0);
       x.ax->reduce(x.ax->reduce_ctx, x.nd->dist_buf, n, 0, x.st);

@@ -1383,6 +1383,7 @@ void launch_bwd_tree(const double* M, const BwdTreeLevel* lev, int nlev, BwdXfer
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd_tree), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd_tree64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64);
   }
+  form_hit(form64 ? KF_BWD_TREE64 : KF_BWD_TREE);
   if (form64) hipLaunchKernelGGL(k_bwd_tree64, dim3(a.wg0[nlev]), dim3(256), lds64, st, a);
   else hipLaunchKernelGGL(k_bwd_tree, dim3(a.wg0[nlev]), dim3(256), lds, st, a);
 }
@@ -1401,9 +1402,11 @@ void launch_bwd_pipe(const double* S, int tI, int ntiles, int nchunk, double* y,
   if (nbt * ntiles <= kPipe64Max) {
     constexpr size_t lds64 = (size_t)kP64Doubles * sizeof(double);
     if (first_use_on_device(seen64)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd_pipe64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64);
+    form_hit(KF_BWD_PIPE64);
     hipLaunchKernelGGL(k_bwd_pipe64, dim3(ntiles * nchunk + ntiles, nbt), dim3(256), lds64, st, g);
     return;
   }
+  form_hit(KF_BWD_PIPE);
   hipLaunchKernelGGL(k_bwd_pipe, dim3(ntiles * nchunk + ntiles, nbt), dim3(256), lds, st, g);
 }
 
@@ -1411,6 +1414,7 @@ void launch_bwd_pipe(const double* S, int tI, int ntiles, int nchunk, double* y,
 void launch_bwd_given(const double* S, size_t ld, int r0, int r1, double* y, double* x, int ncol, int nbt, size_t sM, size_t sR, hipStream_t st,
                       const long long* btab, const int* live, int tI, BwdXfer xf) {
   if (r1 <= r0 || ncol <= 0) return;
+  form_hit(KF_BWD_GIVEN);
   hipLaunchKernelGGL(k_bwd_given, dim3((ncol + 127) / 128, nbt), dim3(256), (size_t)(r1 - r0) * sizeof(double), st, S, ld, r0, r1, y, (const double*)x, ncol, sM,
                      sR, btab, live, tI, xf);
 }
@@ -1418,7 +1422,7 @@ void launch_bwd_given(const double* S, size_t ld, int r0, int r1, double* y, dou
 void launch_potrf_panel(double* S, size_t ld, int t0, int w, double* Linv, int* flag, double* b, int npad, int nbt, size_t sM, size_t sL, size_t sR,
                         hipStream_t st, const long long* btab, int nb, const int* own, const int* list, int n_big, int n_small) {
   if (nb < 0) nb = 8 * w;
-  if (nb == 0) return;  // an all-padding panel of every front of the batch: L = I, Dinv = I, y = 0 are in place
+  if (nb == 0) { form_hit(KF_POTRF_SKIPPED); return; }  // an all-padding panel of every front of the batch: L = I, Dinv = I, y = 0 are in place
   static std::atomic<unsigned long long> seen{0};
   if (first_use_on_device(seen)) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_potrf_panel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelLds);
@@ -1427,6 +1431,7 @@ void launch_potrf_panel(double* S, size_t ld, int t0, int w, double* Linv, int* 
   double* Lp = Linv + (size_t)t0 * kTile * kTile;
   const double* yb = b ? b + npad : nullptr;
   if (list == nullptr) {   // every front of the batch in the sixteen-wave form (arrow blocks of the pose graph, the dense solve)
+    form_hit(KF_POTRF_PANEL); form_hit(KF_POTRF_PANEL_FRONTS, nbt);
     hipLaunchKernelGGL(k_potrf_panel, dim3(nbt), dim3(64 * NW), kPanelLds, st, S, ld, t0 * kTile, nb, Lp, flag, (const double*)b, (double*)yb, sM, sL, sR, btab, own, list);
     return;
   }
@@ -1435,6 +1440,8 @@ void launch_potrf_panel(double* S, size_t ld, int t0, int w, double* Linv, int* 
   // only pays when the small fronts outnumber the CUs — 5-agent map, 182 speed-bias segments: 245 it/s with it against 250 without.
   constexpr int kSmallMin = 384;
   if (n_small <= kSmallMin) { n_big += n_small; n_small = 0; }
+  if (n_big > 0) { form_hit(KF_POTRF_PANEL); form_hit(KF_POTRF_PANEL_FRONTS, n_big); }
+  if (n_small > 0) { form_hit(KF_POTRF_PANEL4); form_hit(KF_POTRF_PANEL4_FRONTS, n_small); }
   if (n_big > 0) hipLaunchKernelGGL(k_potrf_panel, dim3(n_big), dim3(64 * NW), kPanelLds, st, S, ld, t0 * kTile, nb, Lp, flag, (const double*)b, (double*)yb, sM, sL, sR, btab, own, list);
   if (n_small > 0)
     hipLaunchKernelGGL(k_potrf_panel4, dim3(n_small), dim3(256), kPanelLds4, st, S, ld, t0 * kTile, std::min(nb, 8), Lp, flag, (const double*)b, (double*)yb, sM, sL, sR, btab, own,
@@ -1448,6 +1455,7 @@ void launch_trsm_sub(double* S, size_t ld, int t0, int w, int r0, int r1, const 
   const dim3 grid((r1 - r0) * (kTile / PB), nbt);
   // nb: 16-column blocks of the panel that hold real columns (the rest is identity padding with zeros below: X = A there)
   const int need = nb > 0 ? std::min(nb, 8 * w) : 8 * w;
+  form_hit(need <= 4 ? KF_TRSM_SUB4_4 : need <= 8 ? KF_TRSM_SUB4_8 : need <= 12 ? KF_TRSM_SUB4_12 : KF_TRSM_SUB4_16);
   if (need <= 4) hipLaunchKernelGGL(k_trsm_sub4<4>, grid, dim3(256), 0, st, g);
   else if (need <= 8) hipLaunchKernelGGL(k_trsm_sub4<8>, grid, dim3(256), 0, st, g);
   else if (need <= 12) hipLaunchKernelGGL(k_trsm_sub4<12>, grid, dim3(256), 0, st, g);
@@ -1456,11 +1464,13 @@ void launch_trsm_sub(double* S, size_t ld, int t0, int w, int r0, int r1, const 
 
 void launch_bwd_front(const double* S, int tI, int ntiles, int nchunk, double* y, const double* Linv, int nbt, size_t sL, size_t sR, hipStream_t st,
                       const long long* btab, const int* live, BwdXfer xf, int* cnt, double* scr) {
+  form_hit(KF_BWD_FRONT);
   hipLaunchKernelGGL(k_bwd_front, dim3(ntiles * nchunk, nbt), dim3(256), 0, st, S, tI, nchunk, y, Linv, sL, sR, btab, live, xf, cnt, scr);
 }
 
 void launch_bwd_step_sub(const double* S, size_t ld, int p, const double* Linv_p, double* y, double* x, int ncol, int nblocks, int nbt, size_t sM,
                          size_t sL, size_t sR, hipStream_t st, const long long* btab, const int* live, int tI, BwdXfer xf) {
+  form_hit(KF_BWD_STEP_SUB);
   hipLaunchKernelGGL(k_bwd_step_sub, dim3(nblocks, nbt), dim3(256), 0, st, S, ld, p, Linv_p, y, x, ncol, sM, sL, sR, btab, live, tI, xf);
 }
 

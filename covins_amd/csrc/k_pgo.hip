@@ -238,6 +238,7 @@ __global__ __launch_bounds__(256) void k_pg_scatter_solution(DevProblem P, doubl
 // degenerates to a sparse Cholesky on the poses): block-arrow elimination when a plan exists, else the plain dense Cholesky
 void launch_pose_graph_solve(const DevProblem& P, double* dst, hipStream_t st, CholAux& ax, PgoPlan* pgo) {
   hipLaunchKernelGGL(k_pg_gather_rhs, dim3((P.npad + 255) / 256), dim3(256), 0, st, P);
+  form_hit(pgo != nullptr ? KF_PGO_ARROW : KF_PGO_DENSE);
   if (pgo != nullptr) launch_pgo_block_solve(P, *pgo, st, ax);
   else dense_cholesky_solve_raw(P.Sred, P.bp, P.Linv, P.flag, P.npad, st, ax);
   hipLaunchKernelGGL(k_pg_scatter_solution, dim3((P.n + 255) / 256), dim3(256), 0, st, P, dst);

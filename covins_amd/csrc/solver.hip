@@ -47,6 +47,7 @@ struct covgpu_profile_t {
 // elimination tree of the last single-GPU GBA upload and what it was built for (upload_impl)
 struct PlanCache {
   bool valid = false; int K = 0; bool vi = false; int leaf = 0;
+  int top_env = -1; double frac_env = 0.0;   // COVGPU_ND_TOP / COVGPU_ND_GROUP_FRAC as nd_plan_build read them (-1 / 0: not set)
   std::vector<int> chain_ptr, pos_kf;
   std::vector<uint64_t> keys;   // sorted (position i << 32 | position j) of every covisible / loop-edge pair
   NdHostPlan hp;
@@ -396,6 +397,13 @@ extern "C" void covgpu_get_profile2(covgpu_context* c, double* out) {
 // out[16] = { shard world, shard rank, scalar unknowns of the replicated top, top levels, KiB all-reduced per linear solve, stream ordering (1 flags | 0 events | -1 fell back: events and no in-launch hand-overs),
 //             dense order npad, covisible pairs, edge pairs, IMU chains, device MiB allocated for the problem,
 //             fronts, levels, serial 256-column panels, order of the root level, MiB of fronts } (include/covgpu.h)
+// launches per kernel form of the linear solves since the last upload (include/covgpu.h lists the forms)
+extern "C" int covgpu_get_kernel_forms(covgpu_context* c, int64_t* out, int32_t n) {
+  for (int i = 0; i < n && i < KF_COUNT; ++i) out[i] = c != nullptr ? (int64_t)c->chol.forms.n[i] : 0;
+  return KF_COUNT;
+}
+extern "C" const char* covgpu_kernel_form_name(int32_t i) { return i >= 0 && i < KF_COUNT ? kFormNames[i] : nullptr; }
+
 extern "C" void covgpu_get_layout(covgpu_context* c, int64_t* out) {
   for (int i = 0; i < 16; ++i) out[i] = 0;
   if (!c->have) return;
@@ -775,6 +783,7 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
   const bool vi = !pgo && !opt->visual_only;
   RC(validate(p, pgo, vi));
   free_problem(c);
+  c->chol.forms = FormCensus();   // the census counts from the last upload
   DevProblem& P = c->P;
   std::memset(&P, 0, sizeof(P));
   P.K = p->num_kf; P.A = p->num_cam;
@@ -999,14 +1008,18 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
           keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
         }
         PlanCache& pc = c->plan_cache;
-        const bool hit = pc.valid && pc.K == P.K && pc.vi == vi && pc.leaf == leaf && pc.chain_ptr == chain_ptr && pc.pos_kf == pos_kf &&
+        // (nd_plan_build reads both on every call: a tree built under another value is another tree)
+        const char *e_top = getenv("COVGPU_ND_TOP"), *e_frac = getenv("COVGPU_ND_GROUP_FRAC");
+        const int top_env = e_top ? (atoi(e_top) != 0 ? 1 : 0) : -1;
+        const double frac_env = e_frac ? std::max(2.0, atof(e_frac)) : 0.0;
+        const bool hit = pc.valid && pc.K == P.K && pc.vi == vi && pc.leaf == leaf && pc.top_env == top_env && pc.frac_env == frac_env && pc.chain_ptr == chain_ptr && pc.pos_kf == pos_kf &&
                          std::includes(pc.keys.begin(), pc.keys.end(), keys.begin(), keys.end());
         if (hit) nhp = pc.hp;
         else {
           if (!nd_plan_build(P.K, vi, P.nchains, chain_ptr.data(), (int)h_pair_i.size(), h_pair_i.data(), h_pair_j.data(), P.nepairs, ei.data(), ej.data(), leaf, nhp)) {
             g_err = "nested-dissection plan: a coupling joins two branches"; return COVGPU_ERR_INVALID_ARG;
           }
-          pc.valid = true; pc.K = P.K; pc.vi = vi; pc.leaf = leaf; pc.chain_ptr = chain_ptr; pc.pos_kf = pos_kf; pc.keys.swap(keys); pc.hp = nhp;
+          pc.valid = true; pc.K = P.K; pc.vi = vi; pc.leaf = leaf; pc.top_env = top_env; pc.frac_env = frac_env; pc.chain_ptr = chain_ptr; pc.pos_kf = pos_kf; pc.keys.swap(keys); pc.hp = nhp;
         }
       }
       if (nhp.maxdepth > 64) { g_err = "nested-dissection plan: tree deeper than 64 levels"; return COVGPU_ERR_INVALID_ARG; }
@@ -1203,6 +1216,7 @@ static void enqueue_solve(covgpu_context* c, double* dst_all) {
   // with profiling on, every bulk trailing-update (SYRK) launch gets its own event pair on its stream so that
   // bench.py can quote the dominant kernel's duration
   if (c->profiling) (void)hipEventRecord(c->ev[2], c->st);
+  FormScope census(&c->chol.forms);   // the launchers below count their forms into this context (covgpu_get_kernel_forms)
   if (P.nd) {   // GBA: multifrontal solve of the whole system (k_front.hip)
     if (!launch_nd_solve(P, c->nd, dst_all, c->cur_damp, c->st, c->chol) && !c->coll_failed) { c->coll_failed = true; c->coll_err = "scratch allocation of the backward substitution failed"; }
   }
@@ -2001,7 +2015,10 @@ extern "C" int covgpu_solve_reduced(covgpu_context* c, int32_t n, const double* 
   HIPCHK(hipMemcpyAsync(dS, Sp.data(), Sp.size() * sizeof(double), hipMemcpyHostToDevice, c->st));
   HIPCHK(hipMemcpyAsync(db, bp.data(), bp.size() * sizeof(double), hipMemcpyHostToDevice, c->st));
   HIPCHK(hipMemsetAsync(df, 0, 4 * sizeof(int), c->st));
-  dense_cholesky_solve_raw(dS, db, dL, df, npad, c->st, c->chol);
+  {
+    FormScope census(&c->chol.forms);
+    dense_cholesky_solve_raw(dS, db, dL, df, npad, c->st, c->chol);
+  }
   int flag = 0;
   HIPCHK(hipMemcpyAsync(x, db, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipMemcpyAsync(&flag, df, sizeof(int), hipMemcpyDeviceToHost, c->st));

@@ -413,6 +413,54 @@ void covgpu_get_profile(covgpu_context* ctx, double* out8);
  * its launches, [9] its launches, [10] its algorithmic flops (per front n^3/3 + n^2 on the front's real columns in the panel),
  * [11] flops of one multifrontal factorisation of the resident problem (dense count on the fronts' real sizes), [12..15] 0 */
 void covgpu_get_profile2(covgpu_context* ctx, double* out16);
+/* Census of kernel forms: which of the shape-dependent launch forms of the linear solve (multifrontal GBA solve, pose-graph solve,
+ * covgpu_solve_reduced) this context has issued since its last upload. Host-side integers counted where the launches are issued: nothing is
+ * added to the device work. out[i], i < min(n, return value), = count of form i; the return value is the number of forms; the name of form i
+ * is covgpu_kernel_form_name(i) (NULL outside the range). A count is a number of LAUNCHES unless its line says otherwise. The forms, in order:
+ *
+ *   FORMS-BEGIN
+ *   k_potrf_panel          panel factorisation, sixteen waves per front
+ *   k_potrf_panel.fronts   ... fronts (workgroups) over those launches
+ *   k_potrf_panel4         panel factorisation, four waves per front (more than 384 fronts of a level with 1..128 real columns in the panel)
+ *   k_potrf_panel4.fronts  ... fronts over those launches
+ *   potrf_skipped          panels not launched at all: identity padding in every front of the batch
+ *   k_trsm_sub4<4>         substitution below a panel of <= 4 real 16-column blocks
+ *   k_trsm_sub4<8>         ... 5..8
+ *   k_trsm_sub4<12>        ... 9..12
+ *   k_trsm_sub4<16>        ... 13..16
+ *   k_gemm_abt.tri         trailing update of a tile list as full 128x128 tiles
+ *   k_gemm_abt_q.tri       trailing update of a tile list as 64x64 quadrants (lists up to 1024 entries)
+ *   k_gemm_abt.tri_grid    trailing update as the implicit triangle grid (batches without live-tile lists: dense solve)
+ *   k_gemm_abt.rect        look-ahead update of the next panel's rows as full tiles
+ *   k_gemm_abt_q.rect      ... as quadrants (diagonal blocks, rows h; rest rows up to 512 tiles)
+ *   bulk_one_launch        bulk updates (not a front's last) issued as one launch
+ *   bulk_two_launches      ... as two: the next-but-one panel's two tile columns first
+ *   last_update_whole      a batch's last trailing update issued whole on the chain's stream
+ *   last_update_split      ... split for the look-ahead into the next level (split_ta)
+ *   panel_one_tile         panels one tile wide (odd tile count)
+ *   kd_cut                 panels whose rank update runs a K range cut below the panel's width (the level's largest real interior order)
+ *   kd_zero                panels whose rank update is skipped: no real column in the panel
+ *   gemm_beta0             first-panel trailing updates given a map of border tiles that start from zero
+ *   k_bwd_front            backward substitution of a level, fronts of 1..4 interior tiles, one launch
+ *   k_bwd_pipe             backward substitution of a level as a pipeline of tile workgroups
+ *   k_bwd_pipe64           ... its form with 64x64 inverses (at most 128 tile workgroups)
+ *   k_bwd_tree             bottom levels' backward substitution in one launch
+ *   k_bwd_tree64           top levels' backward substitution in one launch
+ *   k_bwd_given            backward substitution per tile: the given rows
+ *   k_bwd_step_sub         backward substitution per tile: one interior tile
+ *   k_nd_extend_rec        extend-add from packed records
+ *   k_nd_extend            extend-add from index tables (COVGPU_EXT_RECORDS=0)
+ *   nd_extend_split        extend-add launches that carry one half of a level split for the look-ahead
+ *   k_nd_top_pack          sharded solve: top fronts packed / unpacked around the all-reduce
+ *   k_nd_gh                sharded solve: gradient and diagonal of the top unknowns gathered / scattered
+ *   k_nd_top_damp          sharded solve: damping of the top unknowns
+ *   k_nd_panel_xfer        sharded solve, distributed top: a panel's exchange packed / unpacked
+ *   dist_panel             sharded solve, distributed top: panels factored by dense_cholesky_dist
+ *   pgo_arrow              pose-graph solves by the block-arrow elimination
+ *   pgo_dense              pose-graph solves by one dense factorisation
+ *   FORMS-END */
+int  covgpu_get_kernel_forms(covgpu_context* ctx, int64_t* out, int32_t n);
+const char* covgpu_kernel_form_name(int32_t i);
 
 
 /* ---------------------------------------------------------------- loop-candidate geometric verification

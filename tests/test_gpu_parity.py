@@ -163,7 +163,8 @@ def test_schur_pgo(ctx, small_map):
     assert rel_err(S, S0) < 1e-10 and rel_err(b, b0) < 1e-10 and abs(c - c0) < 1e-12 * c0
 
 
-@pytest.mark.parametrize("n", [1, 100, 128, 129, 300, 700, 1100, 2600])
+# both sides of the 128 / 256 boundaries (tile, panel) and the smallest odd / even tile counts beyond one panel: 127 .. 1025 = 1, 2, 2, 3, 3, 4, 4, 5, 9 tiles
+@pytest.mark.parametrize("n", [1, 100, 128, 129, 300, 700, 1100, 2600, 127, 255, 256, 257, 383, 385, 512, 513, 1025])
 def test_mfma_cholesky_solve(ctx, n):
     rng = np.random.default_rng(n)
     A = rng.normal(0, 1, (n, n + 5))
@@ -176,6 +177,26 @@ def test_mfma_cholesky_solve(ctx, n):
     assert rel_err(x, x0) < 1e-10
     rc0, xo = covo.solve_reduced(S, b)
     assert rc0 == 0 and rel_err(x, xo) < 1e-10
+
+
+def test_mfma_cholesky_solve_forms(ctx, tiny_vi):
+    """Which kernel forms the dense solve ran (Context.kernel_forms(), counted from the last upload): the forms no multifrontal front reaches — the
+    panel one tile wide of an odd tile count, the trailing update as an implicit triangle grid, the substitution launched per tile — run here,
+    the first only at odd tile counts."""
+    g, _ = opts()
+    for n, tiles in ((256, 2), (257, 3), (512, 4), (1025, 9)):
+        ctx.upload(tiny_vi, g)               # the census counts from the last upload
+        rng = np.random.default_rng(n)
+        A = rng.normal(0, 1, (n, n + 5))
+        S = A @ A.T + 0.5 * n * np.eye(n)
+        rc, x = ctx.solve_reduced(S, rng.normal(0, 1, n))
+        f = ctx.kernel_forms()
+        assert rc == 0
+        assert f["panel_one_tile"] == tiles % 2, f
+        assert f["k_potrf_panel"] == (tiles + 1) // 2 and f["k_potrf_panel.fronts"] == f["k_potrf_panel"] and f["k_potrf_panel4"] == 0, f
+        assert f["k_bwd_step_sub"] == tiles and f["k_bwd_front"] == f["k_bwd_pipe"] == f["k_bwd_tree"] == 0, f
+        assert (f["k_gemm_abt.tri_grid"] > 0) == (tiles > 4) and f["k_gemm_abt.tri"] == f["k_gemm_abt_q.tri"] == 0, f
+        assert (f["k_trsm_sub4<16>"] > 0) == (tiles > 2) and (f["k_gemm_abt_q.rect"] > 0) == (tiles > 2), f   # (one panel: nothing below it)
 
 
 def test_mfma_cholesky_detects_indefinite(ctx):

@@ -154,3 +154,15 @@ def test_tum_writer(tmp_path, tiny_map):
     mapdata.write_tum(str(f), tiny_map, client=0)
     rows = np.loadtxt(f)
     assert rows.shape == ((tiny_map.kf_client == 0).sum(), 8) and np.all(np.diff(rows[:, 0]) > 0)
+
+
+def test_kernel_form_names_match_header():
+    """The census of kernel forms (covgpu_get_kernel_forms): the names are the contract; the header lists them in the library's order."""
+    hdr = open(os.path.join(ROOT, "include", "covgpu.h")).read()
+    block = hdr[hdr.index("FORMS-BEGIN"):hdr.index("FORMS-END")].splitlines()[1:]
+    listed = [ln.replace("*", " ", 1).split()[0] for ln in block if ln.replace("*", " ", 1).split()]
+    names = backend.kernel_form_names()
+    assert listed == names and len(set(names)) == len(names) >= 30
+    out = (C.c_int64 * len(names))()
+    assert backend.lib().covgpu_get_kernel_forms(None, out, len(names)) == len(names) and not any(out)   # (no context: zeros)
+    assert backend.lib().covgpu_kernel_form_name(len(names)) is None and backend.lib().covgpu_kernel_form_name(-1) is None

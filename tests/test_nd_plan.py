@@ -274,3 +274,45 @@ def test_pose_graph_plan_replays_to_the_dense_solve(name, kf, leaf):
     if info[0] > 3:
         # the root separates agents (a cover of the few loop edges) or halves of a time axis (~5 keyframes): far below the system's order
         assert od[np.asarray(parent) < 0].max() <= max(90, 6 * p.K // 8)
+
+
+def test_sweep_of_plan_shapes_reaches_what_the_device_test_relies_on():
+    """tests/forms_util.SWEEP is what tests/test_gpu_forms.py runs on the device to reach every kernel form of the multifrontal solve. Which form a
+    launch takes is decided by the shape of the fronts; the shapes are checked here, from the host plan's arrays alone, so that a change of the
+    plan heuristics that loses one fails on the CPU and says which:
+      - more than 384 fronts with 1 .. 128 own columns in one level and panel at the four-wave point (kSmallMin of launch_potrf_panel), and at most
+        384 at every other point (all below the 12-agent size);
+      - a front with more than 4 interior tiles (beyond k_bwd_front) and one with exactly 1;
+      - a level whose padded order is an odd number of tiles;
+      - a front that is not a root and has an EMPTY border (the constant pose of the visual-only map);
+      - own orders on both sides of 128 and of 256, within 16 of them (k_potrf_panel's 128-column halves, the panel boundary);
+      - the two ways of cutting three agents give different trees (COVGPU_ND_TOP);
+      - what only size selects, at the 12-agent point alone: a look-ahead update of more than 512 tiles (k_gemm_abt.rect as full tiles) and a level of
+        two-tile fronts with more than 128 tile workgroups (k_bwd_pipe instead of k_bwd_pipe64)."""
+    from tests import forms_util as fu
+    shapes = {pt.id: fu.plan_shape(pt) for pt in fu.SWEEP}
+    for pt in fu.SWEEP:
+        s = shapes[pt.id]
+        n = (6 if pt.visual_only else 15) * fu.point_problem(pt).K
+        assert s["own"].sum() == n, pt.id
+        if pt is fu.FOUR_WAVE:
+            assert s["max_small"] > fu.K_SMALL_MIN, (pt.id, s["max_small"])
+        else:
+            assert s["max_small"] <= fu.K_SMALL_MIN, (pt.id, s["max_small"])
+    own = np.concatenate([s["own"] for s in shapes.values()])
+    tiles = np.concatenate([s["tiles"] for s in shapes.values()])
+    assert (tiles > 4).any() and (tiles == 1).any()
+    assert any(t % 2 == 1 for s in shapes.values() for t in s["lev_tiles"])
+    vo = [shapes[pt.id] for pt in fu.SWEEP if pt.visual_only]
+    assert any(((s["border"] == 0) & (s["parent"] >= 0) & (s["own"] == 6)).any() for s in vo), "the constant pose's front: own 6, no border, a parent"
+    for edge in (128, 256):
+        assert ((own >= edge - 16) & (own <= edge)).any() and ((own > edge) & (own <= edge + 16)).any(), edge
+    top = {pt.env["COVGPU_ND_TOP"]: shapes[pt.id] for pt in fu.SWEEP if "COVGPU_ND_TOP" in pt.env}
+    assert set(top) == {"0", "1"}
+    assert (top["0"]["fronts"], top["0"]["levels"], top["0"]["root_order"]) != (top["1"]["fronts"], top["1"]["levels"], top["1"]["root_order"])
+    big = [pt for pt in fu.SWEEP if pt.map.startswith("a12")]
+    assert len(big) == 1 and shapes[big[0].id]["rect_max"] > 512 and shapes[big[0].id]["pipe_max"] > 128, (shapes[big[0].id]["rect_max"], shapes[big[0].id]["pipe_max"])
+    assert all(shapes[pt.id]["rect_max"] <= 512 for pt in fu.SWEEP if pt is not big[0])
+    # the default-plan point of the four-wave map stays below the threshold: the four-wave form is the leaf size's doing
+    dflt = [pt for pt in fu.SWEEP if pt.map == fu.FOUR_WAVE.map and pt.kf == fu.FOUR_WAVE.kf and pt.leaf == 0 and not pt.env]
+    assert len(dflt) == 1 and shapes[dflt[0].id]["max_small"] <= fu.K_SMALL_MIN
