@@ -297,6 +297,104 @@ class Context:
         self._check(lib().covgpu_match_batch(self._h, C.byref(s), C.byref(o)))
         return dict(match=match[:tot], dist=dist[:tot], nmatches=nm[:J], offset=off)
 
+    @staticmethod
+    def _guided_opts(mode, opts):
+        o = capi.GuidedOpts()
+        lib().covgpu_default_guided_opts(C.byref(o), mode)
+        for k, v in opts.items():
+            if k not in ("th_low", "radius", "scale_factor", "num_octaves", "agreement"):
+                raise TypeError(f"unknown guided-matching option {k}")
+            setattr(o, k, v)
+        return o
+
+    @staticmethod
+    def _keypoint_sets(sets: dict, keep: list):
+        """covgpu_keypoint_sets_t of `sets` (row_ptr, kp [rows,2], level, desc [rows,32], bounds [S,4], optional grid_inv [S,2]); the
+        arrays it points into are appended to `keep`."""
+        ptr = np.ascontiguousarray(sets["row_ptr"], dtype=np.int32).ravel()
+        S = len(ptr) - 1
+        kp = np.ascontiguousarray(sets["kp"], dtype=np.float32).reshape(-1, 2)
+        level = np.ascontiguousarray(sets["level"], dtype=np.int32).ravel()
+        desc = np.ascontiguousarray(sets["desc"], dtype=np.uint8).reshape(-1, 32)
+        bounds = np.ascontiguousarray(sets["bounds"], dtype=np.float64).reshape(-1, 4)
+        grid = None if sets.get("grid_inv") is None else np.ascontiguousarray(sets["grid_inv"], dtype=np.float64).reshape(-1, 2)
+        rows = int(ptr[-1]) if S > 0 else 0
+        if len(kp) != rows or len(level) != rows or len(desc) != rows or len(bounds) != S or (grid is not None and len(grid) != S):
+            raise ValueError("keypoint set arrays do not fit row_ptr")
+        keep += [ptr, kp, level, desc, bounds, grid]
+        return capi.KeypointSets(S, iptr(ptr), kp.ctypes.data_as(capi._fp), iptr(level), desc.ctypes.data_as(capi._bp), dptr(bounds),
+                                 dptr(grid)), ptr, S, rows
+
+    def search_se3_batch(self, sets: dict, set_1, set_2, T12, **opts):
+        """Batched FeatureMatcher::SearchBySE3 (covgpu_search_se3_batch, DESIGN.md §4.12). `sets`: the keypoint sets (row_ptr, kp, level,
+        desc, bounds, optional grid_inv) plus K [S,4] and per row lm_pos [rows,3], lm_max_distance, lm_desc [rows,32], lm_free. Job j
+        searches set set_1[j] (query) and set set_2[j] (candidate) under T12[j] = [qx qy qz qw x y z]. `opts`: th_low, radius,
+        scale_factor, num_octaves, agreement (defaults: covgpu_default_guided_opts). Returns dict(match [sum n1] candidate row or -1,
+        match1 [sum n1], match2 [sum n2] the two directions, nfound [num_jobs], offset / offset2 [num_jobs+1] the rows of job j)."""
+        o = self._guided_opts(capi.GUIDED_SE3, opts)
+        keep = []
+        ks, ptr, S, rows = self._keypoint_sets(sets, keep)
+        f64 = lambda k, w: np.ascontiguousarray(sets[k], dtype=np.float64).reshape((-1,) + w)
+        K, pos, maxd = f64("K", (4,)), f64("lm_pos", (3,)), f64("lm_max_distance", ())
+        ldesc = np.ascontiguousarray(sets["lm_desc"], dtype=np.uint8).reshape(-1, 32)
+        free = np.ascontiguousarray(sets["lm_free"], dtype=np.uint8).ravel()
+        if len(K) != S or len(pos) != rows or len(maxd) != rows or len(ldesc) != rows or len(free) != rows:
+            raise ValueError("landmark arrays do not fit row_ptr")
+        s1 = np.ascontiguousarray(set_1, dtype=np.int32).ravel()
+        s2 = np.ascontiguousarray(set_2, dtype=np.int32).ravel()
+        T = np.ascontiguousarray(T12, dtype=np.float64).reshape(-1, 7)
+        J = len(s1)
+        if len(s2) != J or len(T) != J:
+            raise ValueError("set_1, set_2 and T12 differ in length")
+        ok = J > 0 and np.all((s1 >= 0) & (s1 < S) & (s2 >= 0) & (s2 < S))
+        off1 = np.zeros(J + 1, np.int64); off2 = np.zeros(J + 1, np.int64)
+        if ok:
+            off1[1:] = np.cumsum(np.maximum(ptr[s1 + 1] - ptr[s1], 0)); off2[1:] = np.cumsum(np.maximum(ptr[s2 + 1] - ptr[s2], 0))
+        t1, t2 = int(off1[-1]), int(off2[-1])
+        match = np.full(max(t1, 1), -1, np.int32); m1 = np.full(max(t1, 1), -1, np.int32); m2 = np.full(max(t2, 1), -1, np.int32)
+        nf = np.zeros(max(J, 1), np.int32)
+        bp = lambda a: a.ctypes.data_as(capi._bp)
+        s = capi.SearchSe3Batch(ks, dptr(K), dptr(pos), dptr(maxd), bp(ldesc), bp(free), J, iptr(s1), iptr(s2), dptr(T), iptr(match),
+                                iptr(m1), iptr(m2), iptr(nf))
+        self._check(lib().covgpu_search_se3_batch(self._h, C.byref(s), C.byref(o)))
+        return dict(match=match[:t1], match1=m1[:t1], match2=m2[:t2], nfound=nf[:J], offset=off1, offset2=off2)
+
+    def search_projection_batch(self, sets: dict, jobs: dict, **opts):
+        """Batched FeatureMatcher::SearchByProjection (covgpu_search_projection_batch, DESIGN.md §4.12). `sets`: the keypoint sets plus
+        cam [S,8] (fx fy cx cy d0..d3), dist_type [S], optional cam_model / xi [S] and taken [rows]. `jobs`: set [J], T_cw [J,7],
+        point_ptr [J+1] and per point p_w [P,3], normal [P,3], min_distance, max_distance, desc [P,32], optional skip and existing_idx.
+        `opts` as search_se3_batch. Returns dict(claimed [P] keypoint row or -1, remap_to [P], best_dist [P], nmatches [J])."""
+        o = self._guided_opts(capi.GUIDED_PROJECTION, opts)
+        keep = []
+        ks, ptr, S, rows = self._keypoint_sets(sets, keep)
+        bp = lambda a: None if a is None else a.ctypes.data_as(capi._bp)
+        u8 = lambda d, k: None if d.get(k) is None else np.ascontiguousarray(d[k], dtype=np.uint8).ravel()
+        i32 = lambda d, k: None if d.get(k) is None else np.ascontiguousarray(d[k], dtype=np.int32).ravel()
+        cam = np.ascontiguousarray(sets["cam"], dtype=np.float64).reshape(-1, 8)
+        dt, cm, taken = i32(sets, "dist_type"), i32(sets, "cam_model"), u8(sets, "taken")
+        xi = None if sets.get("xi") is None else np.ascontiguousarray(sets["xi"], dtype=np.float64).ravel()
+        if len(cam) != S or len(dt) != S or (cm is not None and len(cm) != S) or (xi is not None and len(xi) != S) \
+                or (taken is not None and len(taken) != rows):
+            raise ValueError("camera or taken arrays do not fit row_ptr")
+        st = i32(jobs, "set")
+        J = len(st)
+        T = np.ascontiguousarray(jobs["T_cw"], dtype=np.float64).reshape(-1, 7)
+        pp = i32(jobs, "point_ptr")
+        f64 = lambda k, w: np.ascontiguousarray(jobs[k], dtype=np.float64).reshape((-1,) + w)
+        pw, nrm, mind, maxd = f64("p_w", (3,)), f64("normal", (3,)), f64("min_distance", ()), f64("max_distance", ())
+        pdesc = np.ascontiguousarray(jobs["desc"], dtype=np.uint8).reshape(-1, 32)
+        skip, ex = u8(jobs, "skip"), i32(jobs, "existing_idx")
+        P = len(pw)
+        if len(T) != J or len(pp) != J + 1 or int(pp[-1]) != P or any(a is not None and len(a) != P for a in (nrm, mind, maxd, pdesc, skip, ex)):
+            raise ValueError("job or point arrays differ in length")
+        claimed = np.full(max(P, 1), -1, np.int32); remap = np.full(max(P, 1), -1, np.int32); bd = np.full(max(P, 1), -1, np.int32)
+        nm = np.zeros(max(J, 1), np.int32)
+        s = capi.SearchProjectionBatch(ks, bp(taken), dptr(cam), iptr(dt), None if cm is None else iptr(cm), dptr(xi), J, iptr(st), dptr(T),
+                                       iptr(pp), dptr(pw), dptr(nrm), dptr(mind), dptr(maxd), bp(pdesc), bp(skip),
+                                       None if ex is None else iptr(ex), iptr(claimed), iptr(remap), iptr(bd), iptr(nm))
+        self._check(lib().covgpu_search_projection_batch(self._h, C.byref(s), C.byref(o)))
+        return dict(claimed=claimed[:P], remap_to=remap[:P], best_dist=bd[:P], nmatches=nm[:J])
+
     def p3p_batch(self, f, P):
         """covgpu_p3p_batch: f, P [n,4,3] -> (T [n,4,7] every solution, qx qy qz qw x y z, ascending v = s3/s1; nsol [n]; chosen [n], -1: none)."""
         f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 4, 3)

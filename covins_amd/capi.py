@@ -221,6 +221,32 @@ class MatchOpts(C.Structure):
     _fields_ = [("mode", C.c_int32), ("dist_threshold", C.c_float), ("ratio", C.c_float)]
 
 
+GUIDED_SE3, GUIDED_PROJECTION = 0, 1   # include/covgpu.h
+_fp = C.POINTER(C.c_float)
+
+
+class GuidedOpts(C.Structure):
+    _fields_ = [("th_low", C.c_int32), ("radius", C.c_double), ("scale_factor", C.c_double), ("num_octaves", C.c_int32),
+                ("agreement", C.c_int32)]
+
+
+class KeypointSets(C.Structure):
+    _fields_ = [("num_sets", C.c_int32), ("row_ptr", _ip), ("kp", _fp), ("level", _ip), ("desc", _bp), ("bounds", _dp), ("grid_inv", _dp)]
+
+
+class SearchSe3Batch(C.Structure):
+    _fields_ = [("sets", KeypointSets), ("K", _dp), ("lm_pos", _dp), ("lm_max_distance", _dp), ("lm_desc", _bp), ("lm_free", _bp),
+                ("num_jobs", C.c_int32), ("set_1", _ip), ("set_2", _ip), ("T12", _dp), ("match", _ip), ("match1", _ip), ("match2", _ip),
+                ("nfound", _ip)]
+
+
+class SearchProjectionBatch(C.Structure):
+    _fields_ = [("sets", KeypointSets), ("taken", _bp), ("cam", _dp), ("dist_type", _ip), ("cam_model", _ip), ("xi", _dp),
+                ("num_jobs", C.c_int32), ("set", _ip), ("T_cw", _dp), ("point_ptr", _ip), ("p_w", _dp), ("normal", _dp),
+                ("min_distance", _dp), ("max_distance", _dp), ("p_desc", _bp), ("skip", _bp), ("existing_idx", _ip),
+                ("claimed", _ip), ("remap_to", _ip), ("best_dist", _ip), ("nmatches", _ip)]
+
+
 def declare(lib: C.CDLL, prefix: str) -> None:
     """Attach argtypes/restype for the entry points shared by libcovgpu (prefix 'covgpu_', with a context
     argument) and — test side only — the oracle (prefix 'covo_', no context)."""
@@ -258,6 +284,9 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("p3p_batch", [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _ip])
         d("default_match_opts", [C.POINTER(MatchOpts), C.c_int32], None)
         d("match_batch", [C.c_void_p, C.POINTER(MatchBatch), C.POINTER(MatchOpts)])
+        d("default_guided_opts", [C.POINTER(GuidedOpts), C.c_int32], None)
+        d("search_se3_batch", [C.c_void_p, C.POINTER(SearchSe3Batch), C.POINTER(GuidedOpts)])
+        d("search_projection_batch", [C.c_void_p, C.POINTER(SearchProjectionBatch), C.POINTER(GuidedOpts)])
         d("outlier_pass", [C.c_void_p, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])
         d("covisibility", [C.c_void_p, C.c_int32, C.c_int64, _ip, _ip, _ip, C.POINTER(C.c_int64)])
         d("gba_solve_multi", [OP, PP, RP, C.c_int32, _ip, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])

@@ -603,6 +603,35 @@ size_t match_assign_lds_bytes(int maxA, int maxB);
 void launch_match(int mode, int num_jobs, int maxA, int maxB, const unsigned char* desc, const unsigned char* skip, const int* row_ptr,
                   const int* set_a, const int* set_b, const int* out_off, int* lists, int* match, int* dist, int* nmatches, int dcut,
                   float thr, float ratio, hipStream_t st);
+// k_guided.hip: batched guided matching of loop candidates (SearchBySE3: two-direction scan + agreement; SearchByProjection: scan with
+// per-point lists + the sequential claim replay). Device arrays; a tile is {job, direction, first point, points} of at most 256 points.
+constexpr int kGuidedScanPoints = 256;
+constexpr int kGuidedListCap = 8;      // PROJECTION: entries a point keeps for the replay (more: the replay rescans)
+struct GuidedSets {
+  const int4* kpr;                     // [rows] {bits of float x, bits of float y, level (INT_MIN: taken), visiting rank within the set}
+  const uint4* kdesc;                  // [rows][2]
+  const int* row_ptr;
+  const int* perm;                     // [rows] visiting rank -> local row
+  const double* bounds;                // [sets][4]
+};
+struct GuidedOptsDev { int th_low; double radius, scale_factor, log_sf; int num_octaves, agreement; };
+struct GuidedSe3Args {
+  GuidedSets S;
+  const double* K; const double* lm_pos; const double* lm_maxd; const uint4* lm_desc; const unsigned char* lm_free;
+  const int* set_1; const int* set_2; const double* T12; const int* off1; const int* off2;
+  int* m1; int* m2; int* match; int* nfound;
+};
+struct GuidedProjArgs {
+  GuidedSets S;
+  const double* cam; const int* dist_type; const int* cam_model; const double* xi;
+  const int* set; const double* T_cw; const int* point_ptr;
+  const double* p_w; const double* normal; const double* min_d; const double* max_d; const uint4* p_desc; const unsigned char* skip;
+  const int* existing;
+  int* lists; int* cnt; float* target; double* rad; int* lvl; int* dold;     // scan -> replay: [P][8], [P], [P][2], [P], [P], [P]
+  int* claimed; int* remap_to; int* best_dist; int* nmatches;
+};
+void launch_guided_se3(const GuidedSe3Args& A, const GuidedOptsDev& O, int num_jobs, const int4* tiles, int num_tiles, hipStream_t st);
+void launch_guided_projection(const GuidedProjArgs& A, const GuidedOptsDev& O, int num_jobs, const int4* tiles, int num_tiles, hipStream_t st);
 void launch_reanchor(int K, const double* pose_old, const double* pose_new, double* vel, int L, const int* ref, double* lm,
                      hipStream_t st);
 

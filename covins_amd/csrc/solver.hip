@@ -2256,6 +2256,214 @@ extern "C" int covgpu_match_batch(covgpu_context* c, const covgpu_match_batch_t*
   return COVGPU_OK;
 }
 
+extern "C" void covgpu_default_guided_opts(covgpu_guided_opts* o, int32_t mode) {
+  if (!o) return;
+  o->th_low = 50;                                                  // desc_matching_th_low_ (feature_matcher_be.hpp)
+  o->radius = mode == COVGPU_GUIDED_PROJECTION ? 10.0 : 9.5;       // config_backend.yaml:45-50
+  o->scale_factor = 2.0; o->num_octaves = 1;                       // features::scale_factor, features::num_octaves
+  o->agreement = 0;
+}
+
+namespace {
+
+// Checks shared by the two guided entry points; the message of the first violation, or nullptr.
+const char* guided_check(const covgpu_keypoint_sets_t& s, const covgpu_guided_opts* o) {
+  if (!o) return "NULL options";
+  if (o->th_low < 0 || o->th_low > 255) return "th_low outside [0, 255]";
+  if (!std::isfinite(o->radius) || !(o->radius > 0.0)) return "radius not finite or not positive";
+  if (o->num_octaves < 1) return "num_octaves < 1";
+  if (o->num_octaves > 1 && (!std::isfinite(o->scale_factor) || !(o->scale_factor > 1.0))) return "scale_factor not finite or not above 1";
+  if (o->agreement != 0 && o->agreement != 1) return "agreement is neither 0 nor 1";
+  if (s.num_sets < 0) return "num_sets < 0";
+  if (s.num_sets > 0 && !s.row_ptr) return "NULL row_ptr";
+  if (s.num_sets > 0 && s.row_ptr[0] != 0) return "row_ptr[0] != 0";
+  for (int i = 0; i < s.num_sets; ++i) {
+    if (s.row_ptr[i + 1] < s.row_ptr[i]) return "row_ptr not monotone";
+    if (s.row_ptr[i + 1] - s.row_ptr[i] > COVGPU_MATCH_MAX_ROWS) return "a set holds more than COVGPU_MATCH_MAX_ROWS rows";
+  }
+  if (s.num_sets > 0 && !s.bounds) return "NULL bounds";
+  if (s.num_sets > 0 && s.row_ptr[s.num_sets] > 0 && (!s.kp || !s.level || !s.desc)) return "NULL keypoint array";
+  return nullptr;
+}
+
+// Device records of the keypoints: {x, y, level, visiting rank}. Grid order is ascending (cell_x, cell_y, index) with the cell of
+// AssignFeaturesToGrid (keyframe_base.cpp:134-139) clamped to the 64 x 48 grid; index order when the set has no grid. A taken keypoint
+// (SearchByProjection's vpMatched[idx] != NULL) gets level INT_MIN and so fails every level window.
+std::vector<int4> guided_records(const covgpu_keypoint_sets_t& s, const uint8_t* taken) {
+  const size_t R = s.num_sets > 0 ? (size_t)s.row_ptr[s.num_sets] : 0;
+  std::vector<int4> rec(R);
+  std::vector<int> cell, order;
+  for (int i = 0; i < s.num_sets; ++i) {
+    const int r0 = s.row_ptr[i], n = s.row_ptr[i + 1] - r0;
+    order.resize(n);
+    for (int k = 0; k < n; ++k) order[k] = k;
+    if (s.grid_inv && s.grid_inv[2 * i] > 0.0) {
+      cell.resize(n);
+      for (int k = 0; k < n; ++k) {
+        const double cx = std::round((double)s.kp[2 * (size_t)(r0 + k)] * s.grid_inv[2 * i]);
+        const double cy = std::round((double)s.kp[2 * (size_t)(r0 + k) + 1] * s.grid_inv[2 * i + 1]);
+        const int ix = cx >= 0.0 ? (cx <= 63.0 ? (int)cx : 63) : 0, iy = cy >= 0.0 ? (cy <= 47.0 ? (int)cy : 47) : 0;   // (a NaN goes to cell 0)
+        cell[k] = ix * 48 + iy;
+      }
+      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cell[a] < cell[b]; });
+    }
+    for (int rank = 0; rank < n; ++rank) {
+      const size_t r = (size_t)r0 + order[rank];
+      int4 e;
+      std::memcpy(&e.x, &s.kp[2 * r], 4); std::memcpy(&e.y, &s.kp[2 * r + 1], 4);
+      e.z = (taken && taken[r]) ? INT32_MIN : s.level[r];
+      e.w = rank;
+      rec[r] = e;
+    }
+  }
+  return rec;
+}
+
+struct GuidedUpload {
+  covgpu_context* c;
+  std::vector<void*> tmp;
+  ~GuidedUpload() { for (void* p : tmp) (void)hipFree(p); }
+  hipError_t alloc(void** p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 16); if (e == hipSuccess) tmp.push_back(*p); return e; }
+  hipError_t up(const void* h, size_t bytes, void** d) {
+    hipError_t e = alloc(d, bytes);
+    if (e != hipSuccess || !bytes) return e;
+    return hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, c->st);
+  }
+};
+
+}  // namespace
+
+extern "C" int covgpu_search_se3_batch(covgpu_context* c, const covgpu_search_se3_batch_t* bt, const covgpu_guided_opts* opts) {
+  auto bad = [](const char* m) { g_err = std::string("covgpu_search_se3_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
+  if (!c) return bad("NULL context");
+  if (!bt) return bad("NULL batch");
+  if (const char* m = guided_check(bt->sets, opts)) return bad(m);
+  const covgpu_keypoint_sets_t& s = bt->sets;
+  const int S = s.num_sets, J = bt->num_jobs;
+  const size_t R = S > 0 ? (size_t)s.row_ptr[S] : 0;
+  if (J < 0) return bad("num_jobs < 0");
+  if (S > 0 && !bt->K) return bad("NULL K");
+  if (R > 0 && (!bt->lm_pos || !bt->lm_max_distance || !bt->lm_desc || !bt->lm_free)) return bad("NULL landmark array");
+  if (J > 0 && (!bt->set_1 || !bt->set_2 || !bt->T12 || !bt->nfound)) return bad("NULL job array");
+  std::vector<int32_t> off1(J > 0 ? J : 1, 0), off2(J > 0 ? J : 1, 0);
+  std::vector<int4> tiles;
+  size_t tot1 = 0, tot2 = 0;
+  for (int j = 0; j < J; ++j) {
+    if (bt->set_1[j] < 0 || bt->set_1[j] >= S || bt->set_2[j] < 0 || bt->set_2[j] >= S) return bad("set index out of range");
+    for (int k = 0; k < 7; ++k) if (!std::isfinite(bt->T12[7 * (size_t)j + k])) return bad("non-finite T12");
+    const int n1 = s.row_ptr[bt->set_1[j] + 1] - s.row_ptr[bt->set_1[j]], n2 = s.row_ptr[bt->set_2[j] + 1] - s.row_ptr[bt->set_2[j]];
+    off1[j] = (int32_t)tot1; off2[j] = (int32_t)tot2;
+    tot1 += (size_t)n1; tot2 += (size_t)n2;
+    if (tot1 > (size_t)INT32_MAX || tot2 > (size_t)INT32_MAX) return bad("more than 2^31 - 1 output rows");
+    for (int dir = 0; dir < 2; ++dir)
+      for (int f = 0, n = dir ? n2 : n1; f < n; f += kGuidedScanPoints) tiles.push_back(make_int4(j, dir, f, std::min(kGuidedScanPoints, n - f)));
+    if (tiles.size() > (size_t)INT32_MAX) return bad("more than 2^31 - 1 scan workgroups");
+  }
+  if (tot1 > 0 && !bt->match) return bad("NULL match");
+  if (J == 0) return COVGPU_OK;
+  HIPCHK(hipSetDevice(c->device));                                   // the first device call: every argument is checked above
+  const std::vector<int4> rec = guided_records(s, nullptr);
+  GuidedUpload U{c};
+  GuidedSe3Args A{};
+  HIPCHK(U.up(rec.data(), 16 * R, (void**)&A.S.kpr)); HIPCHK(U.up(s.desc, 32 * R, (void**)&A.S.kdesc));
+  HIPCHK(U.up(s.row_ptr, 4 * ((size_t)S + 1), (void**)&A.S.row_ptr)); HIPCHK(U.up(s.bounds, 32 * (size_t)S, (void**)&A.S.bounds));
+  HIPCHK(U.up(bt->K, 32 * (size_t)S, (void**)&A.K)); HIPCHK(U.up(bt->lm_pos, 24 * R, (void**)&A.lm_pos));
+  HIPCHK(U.up(bt->lm_max_distance, 8 * R, (void**)&A.lm_maxd)); HIPCHK(U.up(bt->lm_desc, 32 * R, (void**)&A.lm_desc));
+  HIPCHK(U.up(bt->lm_free, R, (void**)&A.lm_free));
+  HIPCHK(U.up(bt->set_1, 4 * (size_t)J, (void**)&A.set_1)); HIPCHK(U.up(bt->set_2, 4 * (size_t)J, (void**)&A.set_2));
+  HIPCHK(U.up(bt->T12, 56 * (size_t)J, (void**)&A.T12));
+  HIPCHK(U.up(off1.data(), 4 * (size_t)J, (void**)&A.off1)); HIPCHK(U.up(off2.data(), 4 * (size_t)J, (void**)&A.off2));
+  int4* dtiles = nullptr;
+  HIPCHK(U.up(tiles.data(), 16 * tiles.size(), (void**)&dtiles));
+  HIPCHK(U.alloc((void**)&A.m1, 4 * tot1)); HIPCHK(U.alloc((void**)&A.m2, 4 * tot2)); HIPCHK(U.alloc((void**)&A.match, 4 * tot1));
+  HIPCHK(U.alloc((void**)&A.nfound, 4 * (size_t)J));
+  HIPCHK(hipMemsetAsync(A.nfound, 0, 4 * (size_t)J, c->st));
+  const GuidedOptsDev O{opts->th_low, opts->radius, opts->scale_factor, std::log(opts->scale_factor), opts->num_octaves, opts->agreement};
+  launch_guided_se3(A, O, J, dtiles, (int)tiles.size(), c->st);
+  HIPCHK(hipGetLastError());
+  if (tot1) HIPCHK(hipMemcpyAsync(bt->match, A.match, 4 * tot1, hipMemcpyDeviceToHost, c->st));
+  if (tot1 && bt->match1) HIPCHK(hipMemcpyAsync(bt->match1, A.m1, 4 * tot1, hipMemcpyDeviceToHost, c->st));
+  if (tot2 && bt->match2) HIPCHK(hipMemcpyAsync(bt->match2, A.m2, 4 * tot2, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(bt->nfound, A.nfound, 4 * (size_t)J, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return COVGPU_OK;
+}
+
+extern "C" int covgpu_search_projection_batch(covgpu_context* c, const covgpu_search_projection_batch_t* bt, const covgpu_guided_opts* opts) {
+  auto bad = [](const char* m) { g_err = std::string("covgpu_search_projection_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
+  if (!c) return bad("NULL context");
+  if (!bt) return bad("NULL batch");
+  if (const char* m = guided_check(bt->sets, opts)) return bad(m);
+  const covgpu_keypoint_sets_t& s = bt->sets;
+  const int S = s.num_sets, J = bt->num_jobs;
+  const size_t R = S > 0 ? (size_t)s.row_ptr[S] : 0;
+  if (J < 0) return bad("num_jobs < 0");
+  if (S > 0 && (!bt->cam || !bt->dist_type)) return bad("NULL camera array");
+  for (int i = 0; i < S; ++i) {
+    if (bt->dist_type[i] != COVGPU_DIST_RADTAN && bt->dist_type[i] != COVGPU_DIST_EQUIDISTANT) return bad("unknown distortion type");
+    if (!bt->cam_model || bt->cam_model[i] == COVGPU_CAM_PINHOLE) continue;
+    if (bt->cam_model[i] != COVGPU_CAM_UNIFIED) return bad("unknown camera model");
+    if (!bt->xi) return bad("unified camera without xi");
+    if (!std::isfinite(bt->xi[i]) || bt->xi[i] < 0.0) return bad("xi of a unified camera is negative or not finite");
+  }
+  if (J > 0 && (!bt->set || !bt->T_cw || !bt->point_ptr || !bt->nmatches)) return bad("NULL job array");
+  if (J > 0 && bt->point_ptr[0] != 0) return bad("point_ptr[0] != 0");
+  std::vector<int4> tiles;
+  for (int j = 0; j < J; ++j) {
+    if (bt->set[j] < 0 || bt->set[j] >= S) return bad("set index out of range");
+    if (bt->point_ptr[j + 1] < bt->point_ptr[j]) return bad("point_ptr not monotone");
+    for (int k = 0; k < 7; ++k) if (!std::isfinite(bt->T_cw[7 * (size_t)j + k])) return bad("non-finite T_cw");
+    for (int f = 0, n = bt->point_ptr[j + 1] - bt->point_ptr[j]; f < n; f += kGuidedScanPoints)
+      tiles.push_back(make_int4(j, 0, f, std::min(kGuidedScanPoints, n - f)));
+  }
+  const size_t P = J > 0 ? (size_t)bt->point_ptr[J] : 0;
+  if (P > 0 && (!bt->p_w || !bt->normal || !bt->min_distance || !bt->max_distance || !bt->p_desc || !bt->claimed || !bt->remap_to))
+    return bad("NULL point array");
+  if (bt->existing_idx)
+    for (int j = 0; j < J; ++j) {
+      const int n = s.row_ptr[bt->set[j] + 1] - s.row_ptr[bt->set[j]];
+      for (int p = bt->point_ptr[j]; p < bt->point_ptr[j + 1]; ++p)
+        if (bt->existing_idx[p] < -1 || bt->existing_idx[p] >= n) return bad("existing_idx out of range");
+    }
+  if (J == 0) return COVGPU_OK;
+  HIPCHK(hipSetDevice(c->device));                                   // the first device call: every argument is checked above
+  const std::vector<int4> rec = guided_records(s, bt->taken);
+  GuidedUpload U{c};
+  GuidedProjArgs A{};
+  HIPCHK(U.up(rec.data(), 16 * R, (void**)&A.S.kpr)); HIPCHK(U.up(s.desc, 32 * R, (void**)&A.S.kdesc));
+  HIPCHK(U.up(s.row_ptr, 4 * ((size_t)S + 1), (void**)&A.S.row_ptr)); HIPCHK(U.up(s.bounds, 32 * (size_t)S, (void**)&A.S.bounds));
+  HIPCHK(U.up(bt->cam, 64 * (size_t)S, (void**)&A.cam)); HIPCHK(U.up(bt->dist_type, 4 * (size_t)S, (void**)&A.dist_type));
+  std::vector<double> xi(S, 0.0);                                    // 0 for the pinhole rows, whose xi is not read
+  if (bt->cam_model) {
+    for (int i = 0; i < S; ++i) if (bt->cam_model[i] == COVGPU_CAM_UNIFIED) xi[i] = bt->xi[i];
+    HIPCHK(U.up(bt->cam_model, 4 * (size_t)S, (void**)&A.cam_model)); HIPCHK(U.up(xi.data(), 8 * (size_t)S, (void**)&A.xi));
+  }
+  HIPCHK(U.up(bt->set, 4 * (size_t)J, (void**)&A.set)); HIPCHK(U.up(bt->T_cw, 56 * (size_t)J, (void**)&A.T_cw));
+  HIPCHK(U.up(bt->point_ptr, 4 * ((size_t)J + 1), (void**)&A.point_ptr));
+  HIPCHK(U.up(bt->p_w, 24 * P, (void**)&A.p_w)); HIPCHK(U.up(bt->normal, 24 * P, (void**)&A.normal));
+  HIPCHK(U.up(bt->min_distance, 8 * P, (void**)&A.min_d)); HIPCHK(U.up(bt->max_distance, 8 * P, (void**)&A.max_d));
+  HIPCHK(U.up(bt->p_desc, 32 * P, (void**)&A.p_desc));
+  if (bt->skip) HIPCHK(U.up(bt->skip, P, (void**)&A.skip));
+  if (bt->existing_idx) HIPCHK(U.up(bt->existing_idx, 4 * P, (void**)&A.existing));
+  int4* dtiles = nullptr;
+  HIPCHK(U.up(tiles.data(), 16 * tiles.size(), (void**)&dtiles));
+  HIPCHK(U.alloc((void**)&A.lists, 4 * kGuidedListCap * P)); HIPCHK(U.alloc((void**)&A.cnt, 4 * P)); HIPCHK(U.alloc((void**)&A.target, 8 * P));
+  HIPCHK(U.alloc((void**)&A.rad, 8 * P)); HIPCHK(U.alloc((void**)&A.lvl, 4 * P)); HIPCHK(U.alloc((void**)&A.dold, 4 * P));
+  HIPCHK(U.alloc((void**)&A.claimed, 4 * P)); HIPCHK(U.alloc((void**)&A.remap_to, 4 * P)); HIPCHK(U.alloc((void**)&A.best_dist, 4 * P));
+  HIPCHK(U.alloc((void**)&A.nmatches, 4 * (size_t)J));
+  const GuidedOptsDev O{opts->th_low, opts->radius, opts->scale_factor, std::log(opts->scale_factor), opts->num_octaves, opts->agreement};
+  launch_guided_projection(A, O, J, dtiles, (int)tiles.size(), c->st);
+  HIPCHK(hipGetLastError());
+  if (P) {
+    HIPCHK(hipMemcpyAsync(bt->claimed, A.claimed, 4 * P, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(bt->remap_to, A.remap_to, 4 * P, hipMemcpyDeviceToHost, c->st));
+    if (bt->best_dist) HIPCHK(hipMemcpyAsync(bt->best_dist, A.best_dist, 4 * P, hipMemcpyDeviceToHost, c->st));
+  }
+  HIPCHK(hipMemcpyAsync(bt->nmatches, A.nmatches, 4 * (size_t)J, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return COVGPU_OK;
+}
+
 extern "C" int covgpu_pgo_reanchor(covgpu_context* c, int32_t K, const double* pose_old, const double* pose_new, double* velocity, int32_t L,
                                    const int32_t* ref_kf, double* lm_pos) {
   HIPCHK(hipSetDevice(c->device));

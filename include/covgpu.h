@@ -522,6 +522,103 @@ typedef struct { int32_t mode; float dist_threshold; float ratio; } covgpu_match
 void covgpu_default_match_opts(covgpu_match_opts*, int32_t mode);
 int  covgpu_match_batch(covgpu_context*, const covgpu_match_batch_t*, const covgpu_match_opts*);
 
+/* ---------------------------------------------------------------- loop-candidate guided matching
+ * FeatureMatcher::SearchBySE3 (feature_matcher_be.cpp:293-498) and FeatureMatcher::SearchByProjection (:168-291), many jobs per call.
+ * Both project landmarks into a keyframe, collect the keypoints within a radius (KeyframeBase::GetFeaturesInArea, keyframe_base.cpp:
+ * 262-318), keep those whose level lies in [predicted - 1, predicted] (LandmarkBase::PredictScale, landmark_base.cpp:120-133) and take
+ * the smallest Hamming distance (:49-64) with `<`: the first keypoint visited wins a tie.
+ *
+ * Keypoint sets (covgpu_keypoint_sets_t, CSR over row_ptr, at most COVGPU_MATCH_MAX_ROWS rows each): kp = keypoints_distorted_ (float,
+ * as KeypointType), level = (int)keypoints_aors_[i][1], desc = descriptors_ row, bounds = xmin xmax ymin ymax of IsInImage
+ * (keyframe_base.cpp:414-416: x >= xmin && x < xmax && y >= ymin && y < ymax). grid_inv selects the visiting order per set: with
+ * grid_inv[2s] > 0 the keyframe's grid order (AssignFeaturesToGrid, :122-143), ascending (cell_x, cell_y, index) with
+ * cell = (int)round((double)kp * grid_inv), grid_inv = 64 / image width and 48 / image height; a cell outside the 64 x 48 grid is
+ * clamped to it (the reference writes out of bounds there). With grid_inv NULL or grid_inv[2s] <= 0 the brute-force order, ascending
+ * index. The two branches of GetFeaturesInArea return the same keypoints, so only the order differs. The area test is the reference's:
+ * the target narrowed to float, distance = float32 sqrt(dx*dx + dy*dy) without fused multiply-add, accepted iff (double)distance <= radius.
+ * PredictScale: n = ceil(log(max_distance / (double)(float)dist) / log(scale_factor)) clamped to [0, num_octaves - 1].
+ *
+ * covgpu_search_se3_batch — job j = (query set set_1[j], candidate set set_2[j], T12[j] = [qx qy qz qw x y z], p_1 = R12 p_2 + t12).
+ *   Per keypoint row: lm_pos = the row's landmark in that keyframe's own camera frame (Tcw * p_w), lm_max_distance, lm_desc =
+ *   Landmark::GetDescriptor() (not the keypoint's row), lm_free = landmark present, valid and not alreadyMatched (:313-339, :412-418);
+ *   rows with lm_free == 0 are not searched for, and their other lm_ fields are not read. Reproduced as they are:
+ *   (1) the projection is K p / z (:351-352, :431-432), no distortion, against distorted keypoints; (2) radius * 2.0^level, never
+ *   scale_factor (:366, :443); (3) the projection into keyframe 1 is tested against keyframe 2's bounds (:433); (4) direction 1->2
+ *   accepts bestDist <= th_low (:403), direction 2->1 bestDist < th_low (:479); (5) agreement == 0: row i agrees iff match2[i] == i with
+ *   i the QUERY row (:486-495), rows i >= rows(set_2) never (the reference reads past match2); agreement == 1: match2[match1[i]] == i;
+ *   (6) z < 0 skips, z == 0 goes on as IEEE has it; (7) no min/max-distance and no viewing-angle test.
+ *   match[] (rows of set_1[j], jobs back to back) = the candidate row whose landmark becomes matches12[i], or -1; nfound[j] = the return
+ *   value. match1 / match2 (optional) = the two directions' raw matches.
+ * covgpu_search_projection_batch — job j = (set set[j], T_cw[j] = [q, t] with p_c = R p_w + t, points point_ptr[j]..point_ptr[j+1]).
+ *   Per point: world position, normal, min_distance, max_distance, descriptor, skip (invalid or in spAlreadyFound, :184), existing_idx =
+ *   GetFeatureIndex(kf) or -1. Per keypoint row: taken = vpMatched[idx] != NULL on entry. The keyframe's camera (cam = fx fy cx cy
+ *   d0..d3, dist_type, cam_model, xi as covgpu_relpose_batch_t) projects; a failed projection skips the point. Filters: z < 0, IsInImage,
+ *   0.8 min_distance <= |p_w - O_w| <= 1.2 max_distance (:208-215, landmark_base.cpp:68-76), PO . n >= 0.5 dist (:220). Radius =
+ *   radius * scale_factor^level (:227). The points run in order (:240, :284): a point sees the keypoints that are not taken and that no
+ *   earlier point has claimed; with bestDist <= th_low it claims its best keypoint when existing_idx == -1, else it claims nothing and
+ *   remap_to[p] = bestIdx unless hamming(desc_p, desc[existing_idx]) < bestDist (:260-281; the dist_newplace test of :270-277 compares
+ *   bestDist with itself and never fires). claimed[p] / remap_to[p] = keypoint row or -1, best_dist[p] = bestDist when it is <= th_low,
+ *   else -1; nmatches[j] = the return value.
+ * All HOST pointers. Checked before any device work: NULL pointers, row limits, set and existing_idx ranges, radius > 0 and finite (the
+ * reference CHECK_GTs it), scale_factor > 1 when num_octaves > 1, num_octaves >= 1, 0 <= th_low <= 255; a violation is
+ * COVGPU_ERR_INVALID_ARG. Zero jobs, empty sets and empty point lists are valid. */
+#define COVGPU_GUIDED_SE3 0
+#define COVGPU_GUIDED_PROJECTION 1
+typedef struct covgpu_guided_opts {
+  int32_t th_low;         /* desc_matching_th_low_, 50 */
+  double  radius;         /* th: 9.5 (SE3), 10.0 (PROJECTION), config_backend.yaml:45-50 */
+  double  scale_factor;   /* features::scale_factor, 2.0 */
+  int32_t num_octaves;    /* features::num_octaves, 1 */
+  int32_t agreement;      /* SE3: 0 = the reference's literal test, 1 = match2[match1[i]] == i */
+} covgpu_guided_opts;
+typedef struct covgpu_keypoint_sets_t {
+  int32_t num_sets;         const int32_t* row_ptr;      /* [num_sets+1], monotone, row_ptr[0] == 0 */
+  const float*   kp;        /* [rows][2] */
+  const int32_t* level;     /* [rows] */
+  const uint8_t* desc;      /* [rows][32] */
+  const double*  bounds;    /* [num_sets][4] xmin xmax ymin ymax */
+  const double*  grid_inv;  /* [num_sets][2] or NULL */
+} covgpu_keypoint_sets_t;
+typedef struct covgpu_search_se3_batch_t {
+  covgpu_keypoint_sets_t sets;
+  const double*  K;                /* [num_sets][4] fx fy cx cy of calibration_.K */
+  const double*  lm_pos;           /* [rows][3] */
+  const double*  lm_max_distance;  /* [rows] */
+  const uint8_t* lm_desc;          /* [rows][32] */
+  const uint8_t* lm_free;          /* [rows] */
+  int32_t num_jobs;         const int32_t* set_1;        /* [num_jobs] */   const int32_t* set_2; /* [num_jobs] */
+  const double*  T12;              /* [num_jobs][7] */
+  int32_t* match;                  /* [sum of rows(set_1[j])] out */
+  int32_t* match1;                 /* [sum of rows(set_1[j])] out or NULL */
+  int32_t* match2;                 /* [sum of rows(set_2[j])] out or NULL */
+  int32_t* nfound;                 /* [num_jobs] out */
+} covgpu_search_se3_batch_t;
+typedef struct covgpu_search_projection_batch_t {
+  covgpu_keypoint_sets_t sets;
+  const uint8_t* taken;            /* [rows] or NULL = none */
+  const double*  cam;              /* [num_sets][8] fx fy cx cy d0 d1 d2 d3 */
+  const int32_t* dist_type;        /* [num_sets] COVGPU_DIST_* */
+  const int32_t* cam_model;        /* [num_sets] COVGPU_CAM_* or NULL (pinhole) */
+  const double*  xi;               /* [num_sets], read for unified rows */
+  int32_t num_jobs;         const int32_t* set;          /* [num_jobs] */
+  const double*  T_cw;             /* [num_jobs][7] */
+  const int32_t* point_ptr;        /* [num_jobs+1], monotone, point_ptr[0] == 0 */
+  const double*  p_w;              /* [P][3] */
+  const double*  normal;           /* [P][3] */
+  const double*  min_distance;     /* [P] */
+  const double*  max_distance;     /* [P] */
+  const uint8_t* p_desc;           /* [P][32] */
+  const uint8_t* skip;             /* [P] or NULL = none */
+  const int32_t* existing_idx;     /* [P] or NULL = all -1 */
+  int32_t* claimed;                /* [P] out */
+  int32_t* remap_to;               /* [P] out */
+  int32_t* best_dist;              /* [P] out or NULL */
+  int32_t* nmatches;               /* [num_jobs] out */
+} covgpu_search_projection_batch_t;
+void covgpu_default_guided_opts(covgpu_guided_opts*, int32_t mode);
+int  covgpu_search_se3_batch(covgpu_context*, const covgpu_search_se3_batch_t*, const covgpu_guided_opts*);
+int  covgpu_search_projection_batch(covgpu_context*, const covgpu_search_projection_batch_t*, const covgpu_guided_opts*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <unordered_map>
@@ -142,6 +143,50 @@ template <class Types, class K>
 inline auto landmark(K& kf, size_t k, int) -> decltype(Types::landmark(kf, k)) { return Types::landmark(kf, k); }
 template <class Types, class K>
 inline auto landmark(K& kf, size_t k, long) -> decltype(kf.GetLandmark((int)k)) { return kf.GetLandmark((int)k); }
+
+// ---- what the guided matching (LoopMatcherT::SearchBySE3Batch / SearchByProjection) reads beyond the above, each through an optional
+//      trait with the COVINS member as the fallback.
+// Landmark::GetDescriptor() (landmark_base.hpp:77), 32 bytes copied out: Types::landmark_descriptor(landmark, out32); false = none
+template <class Types, class L>
+inline auto landmark_descriptor(L& lm, uint8_t* out, int) -> decltype(Types::landmark_descriptor(lm, out), bool()) {
+  return Types::landmark_descriptor(lm, out);
+}
+template <class Types, class L>
+inline bool landmark_descriptor(L& lm, uint8_t* out, long) {
+  const auto M = lm.GetDescriptor();
+  if (M.cols * M.rows < 32) return false;
+  std::memcpy(out, M.data, 32);
+  return true;
+}
+// normal_, min_distance_, max_distance_ of a landmark: Types::landmark_scale(landmark, normal3, &min, &max). LandmarkBase keeps them
+// protected; the fallback divides GetMinDistanceInvariance() / GetMaxDistanceInvariance() by their 0.8 / 1.2 (landmark_base.cpp:68-76),
+// which can differ from the member in the last bit — a binding that wants the reference's decisions to the bit supplies the trait.
+template <class Types, class L>
+inline auto landmark_scale(L& lm, double* n, double* mn, double* mx, int) -> decltype(Types::landmark_scale(lm, n, mn, mx), void()) {
+  Types::landmark_scale(lm, n, mn, mx);
+}
+template <class Types, class L>
+inline void landmark_scale(L& lm, double* n, double* mn, double* mx, long) {
+  const auto v = lm.GetNormal();
+  n[0] = v[0]; n[1] = v[1]; n[2] = v[2];
+  *mn = lm.GetMinDistanceInvariance() / 0.8; *mx = lm.GetMaxDistanceInvariance() / 1.2;
+}
+// IsInImage's bounds (xmin xmax ymin ymax, keyframe_base.cpp:414-416) and the grid state (grid_width_inv_, grid_height_inv_ when
+// assigned_to_grid_, else 0 0 = brute-force order, :273): Types::keyframe_image(keyframe, bounds4, grid_inv2)
+template <class Types, class K>
+inline auto keyframe_image(K& kf, double* b, double* g, int) -> decltype(Types::keyframe_image(kf, b, g), void()) { Types::keyframe_image(kf, b, g); }
+template <class Types, class K>
+inline void keyframe_image(K& kf, double* b, double* g, long) {
+  b[0] = kf.img_dim_x_min_; b[1] = kf.img_dim_x_max_; b[2] = kf.img_dim_y_min_; b[3] = kf.img_dim_y_max_;
+  g[0] = kf.assigned_to_grid_ ? kf.grid_width_inv_ : 0.0; g[1] = kf.assigned_to_grid_ ? kf.grid_height_inv_ : 0.0;
+}
+// Keyframe::RemapLandmark(lm, now, new) (keyframe_be.cpp:484-495): Types::remap_landmark(keyframe_ptr, landmark_ptr, now, new)
+template <class Types, class KP, class LP>
+inline auto remap_landmark(const KP& kf, const LP& lm, size_t now, size_t to, int) -> decltype(Types::remap_landmark(kf, lm, now, to), void()) {
+  Types::remap_landmark(kf, lm, now, to);
+}
+template <class Types, class KP, class LP>
+inline void remap_landmark(const KP& kf, const LP& lm, size_t now, size_t to, long) { kf->RemapLandmark(lm, now, to); }
 
 // RANSAC seed of a (query, candidate) keyframe pair from their ids: a candidate's draws do not depend on the batch it is verified in
 template <class K>
@@ -1035,6 +1080,136 @@ class LoopMatcherT {
   };
   using Matches = std::vector<Match>;
 
+  using Landmark = typename Types::Landmark;
+  using LandmarkPtr = std::shared_ptr<Landmark>;
+  using LandmarkVector = std::vector<LandmarkPtr>;
+  using TransformType = typename Types::TransformType;
+
+  // ---- guided matching (covgpu_search_se3_batch / covgpu_search_projection_batch). The reference's constants:
+  //      desc_matching_th_low_ and covins_params::features::scale_factor / num_octaves; agreement 0 = SearchBySE3's literal agreement
+  //      test (feature_matcher_be.cpp:486-495), 1 = match2[match1[i]] == i.
+  //      The three entry points are member templates only so that an explicit instantiation of LoopMatcherT on a binding without the
+  //      members they read (keypoints_aors_, GetFeatureIndex, ...) still compiles; call them without template arguments.
+  struct GuidedParams { int th_low = 50; double scale_factor = 2.0; int num_octaves = 1; int agreement = 0; };
+  static GuidedParams& guided_params() { static GuidedParams p; return p; }
+
+  // FeatureMatcher::SearchBySE3 (feature_matcher_be.cpp:293-498) for many (kf1, kf2, T12) in ONE library call: matches12[i] =
+  // kf2->GetLandmarks()[match] for every agreed row, found = the return value. matches12 holds the matches so far (alreadyMatched).
+  struct Se3SearchJob { KeyframePtr kf1, kf2; LandmarkVector* matches12 = nullptr; const TransformType* T12 = nullptr; int found = 0; };
+  template <class Binding = Types>
+  static void SearchBySE3Batch(std::vector<Se3SearchJob>& jobs, double th = 9.5) {
+    const size_t J = jobs.size();
+    if (J == 0) return;
+    KpSets S;
+    std::vector<double> K, pos, maxd, T(7 * J);
+    std::vector<uint8_t> ldesc, lfree;
+    std::vector<int32_t> s1(J), s2(J), off(J + 1, 0);
+    std::vector<LandmarkVector> lms2(J);
+    for (size_t j = 0; j < J; ++j) {
+      Se3SearchJob& job = jobs[j];
+      const LandmarkVector lms1 = job.kf1->GetLandmarks();
+      lms2[j] = job.kf2->GetLandmarks();
+      const size_t n1 = lms1.size(), n2 = lms2[j].size();
+      if (job.matches12->size() < n1) job.matches12->resize(n1);
+      std::vector<bool> already1(n1, false), already2(n2, false);                     // :313-324
+      for (size_t i = 0; i < n1; ++i) {
+        const LandmarkPtr& m = (*job.matches12)[i];
+        if (!m) continue;
+        already1[i] = true;
+        const int idx2 = m->GetFeatureIndex(job.kf2);
+        if (idx2 >= 0 && idx2 < (int)n2) already2[idx2] = true;
+      }
+      for (int side = 0; side < 2; ++side) {
+        Keyframe& kf = side ? *job.kf2 : *job.kf1;
+        const LandmarkVector& lms = side ? lms2[j] : lms1;
+        const std::vector<bool>& already = side ? already2 : already1;
+        (side ? s2 : s1)[j] = S.add(kf, lms.size());
+        double intr[4], dist[4]; int dt = 0;
+        if (!Types::camera(kf, intr, dist, &dt)) detail::fatal("Unknown projection / distortion type.");
+        K.insert(K.end(), intr, intr + 4);                                             // calibration_.K (:297-298)
+        TransformType Twc;
+        detail::mat_mul(kf.GetPoseTws(), kf.GetStateExtrinsics(), Twc);                // GetPoseTcw()^-1 (:301-302)
+        for (size_t i = 0; i < lms.size(); ++i) {
+          double p3[3] = {0, 0, 0}, mx = 1.0, mn = 0.0, nrm[3];
+          uint8_t d[32] = {};
+          const LandmarkPtr& lm = lms[i];
+          bool free = lm && !already[i] && !lm->IsInvalid();                           // :334-339, :412-418
+          if (free) {
+            detail::to_camera(Twc, lm->GetWorldPos(), p3);                             // :342-343, :421-422
+            detail::landmark_scale<Types>(*lm, nrm, &mn, &mx, 0);
+            free = detail::landmark_descriptor<Types>(*lm, d, 0);                      // (descrMP.cols == 0: every candidate is skipped, :386)
+          }
+          pos.insert(pos.end(), p3, p3 + 3); maxd.push_back(mx); ldesc.insert(ldesc.end(), d, d + 32); lfree.push_back(free ? 1 : 0);
+        }
+      }
+      detail::transform_to_pose(*job.T12, &T[7 * j]);
+      off[j + 1] = off[j] + (int32_t)n1;
+    }
+    std::vector<int32_t> match((size_t)off[J] + 1), nf(J);
+    covgpu_search_se3_batch_t bt{};
+    bt.sets = S.view();
+    bt.K = K.data(); bt.lm_pos = pos.data(); bt.lm_max_distance = maxd.data(); bt.lm_desc = ldesc.data(); bt.lm_free = lfree.data();
+    bt.num_jobs = (int32_t)J; bt.set_1 = s1.data(); bt.set_2 = s2.data(); bt.T12 = T.data(); bt.match = match.data(); bt.nfound = nf.data();
+    const covgpu_guided_opts o = guided_opts(COVGPU_GUIDED_SE3, th);
+    if (covgpu_search_se3_batch(OptimizationT<Types>::Context(), &bt, &o) != COVGPU_OK) detail::fatal(covgpu_last_error());
+    for (size_t j = 0; j < J; ++j) {
+      for (int32_t i = off[j]; i < off[j + 1]; ++i)
+        if (match[i] >= 0) (*jobs[j].matches12)[i - off[j]] = lms2[j][match[i]];      // :491
+      jobs[j].found = nf[j];
+    }
+  }
+  // same signature as the reference
+  template <class Binding = Types>
+  static auto SearchBySE3(KeyframePtr kf1, KeyframePtr kf2, LandmarkVector& matches12, const TransformType T12, const double th) -> int {
+    std::vector<Se3SearchJob> jobs(1);
+    jobs[0].kf1 = kf1; jobs[0].kf2 = kf2; jobs[0].matches12 = &matches12; jobs[0].T12 = &T12;
+    SearchBySE3Batch(jobs, th);
+    return jobs[0].found;
+  }
+
+  // FeatureMatcher::SearchByProjection (feature_matcher_be.cpp:168-291; placerec_be.cpp:194), the reference's signature and return
+  // value: claims go into vpMatched, remap proposals through Keyframe::RemapLandmark in point order.
+  template <class Binding = Types>
+  static auto SearchByProjection(KeyframePtr kf, TransformType Tcw, const LandmarkVector& points, LandmarkVector& matched, double th) -> int {
+    KpSets S;
+    S.add(*kf, matched.size());
+    const size_t n = matched.size(), P = points.size();
+    std::vector<uint8_t> taken(n), pdesc(32 * P + 32), skip(P + 1);
+    std::set<const Landmark*> found;                                                   // spAlreadyFound (:175-176)
+    for (size_t i = 0; i < n; ++i) { taken[i] = matched[i] ? 1 : 0; if (matched[i]) found.insert(matched[i].get()); }
+    double cam[8], xi = 0.0, T[7];
+    int32_t dt = 0, model = COVGPU_CAM_PINHOLE, set0 = 0, pptr[2] = {0, (int32_t)P}, nm = 0;
+    int dti = 0, mi = 0;
+    if (!Types::camera(*kf, cam, cam + 4, &dti) || !detail::camera_model<Types>(*kf, &mi, &xi, 0)) detail::fatal("Unknown projection / distortion type.");
+    dt = dti; model = mi;
+    detail::transform_to_pose(Tcw, T);
+    std::vector<double> pw(3 * P + 3), nrm(3 * P + 3), mn(P + 1), mx(P + 1);
+    std::vector<int32_t> existing(P + 1, -1), claimed(P + 1), remap(P + 1);
+    for (size_t p = 0; p < P; ++p) {
+      const LandmarkPtr& lm = points[p];
+      skip[p] = !lm || lm->IsInvalid() || found.count(lm.get()) || !detail::landmark_descriptor<Types>(*lm, &pdesc[32 * p], 0);   // :184
+      if (skip[p]) continue;
+      const auto w = lm->GetWorldPos();
+      for (int k = 0; k < 3; ++k) pw[3 * p + k] = w[k];
+      detail::landmark_scale<Types>(*lm, &nrm[3 * p], &mn[p], &mx[p], 0);
+      const int e = lm->GetFeatureIndex(kf);                                           // :260
+      existing[p] = e >= 0 && e < (int)n ? e : -1;
+    }
+    covgpu_search_projection_batch_t bt{};
+    bt.sets = S.view();
+    bt.taken = taken.data(); bt.cam = cam; bt.dist_type = &dt; bt.cam_model = &model; bt.xi = &xi;
+    bt.num_jobs = 1; bt.set = &set0; bt.T_cw = T; bt.point_ptr = pptr;
+    bt.p_w = pw.data(); bt.normal = nrm.data(); bt.min_distance = mn.data(); bt.max_distance = mx.data(); bt.p_desc = pdesc.data();
+    bt.skip = skip.data(); bt.existing_idx = existing.data(); bt.claimed = claimed.data(); bt.remap_to = remap.data(); bt.nmatches = &nm;
+    const covgpu_guided_opts o = guided_opts(COVGPU_GUIDED_PROJECTION, th);
+    if (covgpu_search_projection_batch(OptimizationT<Types>::Context(), &bt, &o) != COVGPU_OK) detail::fatal(covgpu_last_error());
+    for (size_t p = 0; p < P; ++p) {
+      if (claimed[p] >= 0) matched[claimed[p]] = points[p];                            // :284
+      if (remap[p] >= 0) detail::remap_landmark<Types>(kf, points[p], (size_t)existing[p], (size_t)remap[p], 0);   // :280
+    }
+    return nm;
+  }
+
   static std::vector<Matches> MatchLandmarksBatch(const KeyframePtr& query, const std::vector<KeyframePtr>& candidates, float thr = 50.0f) {
     covgpu_match_opts o;
     covgpu_default_match_opts(&o, COVGPU_MATCH_DENSE);
@@ -1050,6 +1225,45 @@ class LoopMatcherT {
   }
 
  private:
+  // keypoint sets of the guided matching: keypoints_distorted_, (int)keypoints_aors_[i][1], descriptors_ rows, bounds and grid state
+  struct KpSets {
+    std::vector<int32_t> ptr{0}, level;
+    std::vector<float> kp;
+    std::vector<uint8_t> desc;
+    std::vector<double> bounds, grid;
+    template <class K>   // (a template: instantiated only for bindings that call the guided matching)
+    int32_t add(K& kf, size_t n) {
+      int rows = 0; const uint8_t* data = nullptr;
+      if (!detail::descriptors<Types>(kf, 0, &rows, &data, 0)) rows = 0;
+      if ((size_t)rows < n || kf.keypoints_distorted_.size() < n || kf.keypoints_aors_.size() < n)
+        detail::fatal("guided matching: fewer keypoints or descriptors than landmark slots");
+      for (size_t i = 0; i < n; ++i) {
+        kp.push_back(kf.keypoints_distorted_[i][0]); kp.push_back(kf.keypoints_distorted_[i][1]);
+        level.push_back((int32_t)kf.keypoints_aors_[i][1]);
+      }
+      desc.insert(desc.end(), data, data + 32 * n);
+      double b[4], g[2];
+      detail::keyframe_image<Types>(kf, b, g, 0);
+      bounds.insert(bounds.end(), b, b + 4); grid.insert(grid.end(), g, g + 2);
+      ptr.push_back(ptr.back() + (int32_t)n);
+      return (int32_t)ptr.size() - 2;
+    }
+    covgpu_keypoint_sets_t view() {
+      kp.reserve(1); level.reserve(1); desc.reserve(1);                                // non-NULL data() for empty sets
+      covgpu_keypoint_sets_t s{};
+      s.num_sets = (int32_t)ptr.size() - 1; s.row_ptr = ptr.data(); s.kp = kp.data(); s.level = level.data(); s.desc = desc.data();
+      s.bounds = bounds.data(); s.grid_inv = grid.data();
+      return s;
+    }
+  };
+  static covgpu_guided_opts guided_opts(int mode, double th) {
+    covgpu_guided_opts o;
+    covgpu_default_guided_opts(&o, mode);
+    const GuidedParams& g = guided_params();
+    o.th_low = g.th_low; o.radius = th; o.scale_factor = g.scale_factor; o.num_octaves = g.num_octaves; o.agreement = g.agreement;
+    return o;
+  }
+
   static std::vector<Matches> run(const KeyframePtr& query, const std::vector<KeyframePtr>& candidates, const covgpu_match_opts& o, int which) {
     const bool dense = o.mode == COVGPU_MATCH_DENSE;
     const size_t J = candidates.size();
