@@ -107,6 +107,36 @@ def gba_two_round_multi(prob: FlatProblem, opt: Options, threshold: float, devic
     return q, r1, r2, erase[:prob.O].astype(bool), left[:prob.L], (int(cnt[0]), int(cnt[1]))
 
 
+class ConsistencyFilter:
+    """The covisibility-consistency groups of PlaceRecognition::DetectLoop (placerec_be.cpp:391-460): sequential host state of one
+    detector. feed(candidates, group_of) takes one query's loop candidates (Context.detect_candidates_batch) and returns
+    mvpEnoughConsistentCandidates; group_of(k) gives candidate k's connected keyframes. `threshold` is cov_consistency_thres."""
+
+    def __init__(self, threshold: int = 3):
+        self.threshold = int(threshold)
+        self.groups = []                       # mvConsistentGroups: (set of keyframes, consistency counter)
+
+    def feed(self, candidates, group_of):
+        if len(candidates) == 0:
+            self.groups = []
+            return []
+        enough, current, taken = [], [], set()
+        for cand in candidates:
+            group = {int(k) for k in group_of(cand)}
+            group.add(int(cand))
+            hits = [g for g, (prev, _) in enumerate(self.groups) if not group.isdisjoint(prev)]
+            for g in hits:
+                if g not in taken:
+                    taken.add(g)
+                    current.append((group, self.groups[g][1] + 1))
+            if any(self.groups[g][1] + 1 >= self.threshold for g in hits):
+                enough.append(int(cand))
+            if not hits:
+                current.append((group, 0))
+        self.groups = current
+        return enough
+
+
 class Context:
     """One solver context = one HIP stream + HBM workspace (covgpu_create / covgpu_destroy)."""
 
@@ -394,6 +424,94 @@ class Context:
                                        None if ex is None else iptr(ex), iptr(claimed), iptr(remap), iptr(bd), iptr(nm))
         self._check(lib().covgpu_search_projection_batch(self._h, C.byref(s), C.byref(o)))
         return dict(claimed=claimed[:P], remap_to=remap[:P], best_dist=bd[:P], nmatches=nm[:J])
+
+    @staticmethod
+    def _bow_vocab(voc: dict, keep: list):
+        """covgpu_bow_vocab_t over the flat form of covins_amd/vocio.py (`keep` holds the arrays alive)."""
+        i32 = lambda k: np.ascontiguousarray(voc[k], dtype=np.int32).ravel()
+        parent, cptr, child, wid = i32("parent"), i32("child_ptr"), i32("child"), i32("word_id")
+        desc = np.ascontiguousarray(voc["desc"], dtype=np.uint8).reshape(-1, 32)
+        weight = np.ascontiguousarray(voc["weight"], dtype=np.float64).ravel()
+        N = len(parent)
+        if len(cptr) != N + 1 or len(child) != max(N - 1, 0) or len(desc) != N or len(wid) != N or len(weight) != N:
+            raise ValueError("vocabulary arrays differ in length")
+        keep += [parent, cptr, child, wid, desc, weight]
+        return capi.BowVocab(N, int(voc["num_words"]), int(voc["k"]), int(voc["L"]), int(voc["scoring"]), int(voc["weighting"]),
+                             iptr(parent), iptr(cptr), iptr(child), desc.ctypes.data_as(capi._bp), iptr(wid), dptr(weight))
+
+    def bow_transform_batch(self, voc: dict, sets: dict, levelsup: int = 4, capacity: Optional[int] = None):
+        """DBoW2's transform(features, bow_vec, feat_vec, levelsup) of every descriptor set (covgpu_bow_transform_batch, DESIGN.md
+        §4.13). `voc`: a vocabulary as covins_amd/vocio.py reads it; `sets`: row_ptr [S+1] and desc [rows,32] as for match_batch.
+        Returns dict(bow_ptr [S+1], word, value: the L1-normalised bow vectors as one CSR; row_word [rows] the word of each
+        descriptor, -1 if stopped; row_node [rows] its FeatureVector key; total). `capacity` (default: rows, always enough) bounds
+        the entries written; bow_ptr and total stay exact."""
+        keep = []
+        v = self._bow_vocab(voc, keep)
+        ptr = np.ascontiguousarray(sets["row_ptr"], dtype=np.int32)
+        S = len(ptr) - 1
+        desc = np.ascontiguousarray(sets["desc"], dtype=np.uint8).reshape(-1, 32)
+        rows = len(desc)
+        cap = rows if capacity is None else int(capacity)
+        bptr = np.zeros(S + 1, np.int32); word = np.zeros(max(cap, 1), np.int32); value = np.zeros(max(cap, 1))
+        rw = np.full(max(rows, 1), -1, np.int32); rn = np.zeros(max(rows, 1), np.int32); tot = C.c_int64(0)
+        s = capi.BowTransformBatch(S, iptr(ptr), desc.ctypes.data_as(capi._bp), int(levelsup), cap, iptr(bptr), iptr(word), dptr(value),
+                                   C.pointer(tot), iptr(rw), iptr(rn))
+        self._check(lib().covgpu_bow_transform_batch(self._h, C.byref(v), C.byref(s)))
+        n = min(cap, int(tot.value))
+        return dict(bow_ptr=bptr, word=word[:n], value=value[:n], row_word=rw[:rows], row_node=rn[:rows], total=int(tot.value))
+
+    def bow_score_pairs(self, bow_ptr, word, value, a, b):
+        """L1Scoring::score of the pairs (a[i], b[i]) of the rows of a bow CSR (covgpu_bow_score_pairs). Returns float64 [len(a)]."""
+        ptr = np.ascontiguousarray(bow_ptr, dtype=np.int32); w = np.ascontiguousarray(word, dtype=np.int32)
+        v = np.ascontiguousarray(value, dtype=np.float64)
+        pa = np.ascontiguousarray(a, dtype=np.int32).ravel(); pb = np.ascontiguousarray(b, dtype=np.int32).ravel()
+        if len(pa) != len(pb):
+            raise ValueError("a and b differ in length")
+        out = np.zeros(max(len(pa), 1))
+        self._check(lib().covgpu_bow_score_pairs(self._h, len(ptr) - 1, iptr(ptr), iptr(w), dptr(v), len(pa), iptr(pa), iptr(pb), dptr(out)))
+        return out[:len(pa)]
+
+    def detect_candidates_batch(self, table: dict, db_order, query_kf, db_visible, mode: str = "covins", min_score=None,
+                                cap: Optional[int] = None, **opts):
+        """KeyframeDatabase::DetectCandidates for many queries (covgpu_detect_candidates_batch, DESIGN.md §4.13). `table`: id, client,
+        bow_ptr, word, value, nb_ptr, nb (table indices in the reference's neighbour order) and optionally invalid. Query q is
+        keyframe query_kf[q] against db_order[:db_visible[q]]. `min_score` [Q]: given directly instead of the reference score of
+        DetectLoop. `opts`: min_score_factor, min_loop_dist, exclude_kfs_with_id_less_than, inter_map_matches_only, scratch_kib (defaults:
+        covgpu_default_detect_opts(mode)). `cap` (default: len(db_order)) bounds the candidates kept per query. Returns
+        dict(candidates: list of arrays of table indices in the reference's order, acc_score: list of float32 arrays,
+        num_candidates, min_score, num_sharing, max_common_words, num_scored [Q])."""
+        m = {"covins": capi.DETECT_COVINS, "covins_g": capi.DETECT_COVINS_G}.get(mode, mode)
+        o = capi.DetectOpts()
+        lib().covgpu_default_detect_opts(C.byref(o), int(m))
+        for k, v in opts.items():
+            if k not in ("min_score_factor", "min_loop_dist", "exclude_kfs_with_id_less_than", "inter_map_matches_only", "scratch_kib"):
+                raise TypeError(f"unknown detect option {k}")
+            setattr(o, k, v)
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ravel()
+        kid, client, bptr, word, nptr, nb = (i32(table[k]) for k in ("id", "client", "bow_ptr", "word", "nb_ptr", "nb"))
+        value = np.ascontiguousarray(table["value"], dtype=np.float64).ravel()
+        inv = None if table.get("invalid") is None else np.ascontiguousarray(table["invalid"], dtype=np.uint8).ravel()
+        N = len(kid)
+        if len(client) != N or len(bptr) != N + 1 or len(nptr) != N + 1 or len(value) != len(word) or (inv is not None and len(inv) != N):
+            raise ValueError("table arrays differ in length")
+        db, qk, vis = i32(db_order), i32(query_kf), i32(db_visible)
+        Q = len(qk)
+        if len(vis) != Q:
+            raise ValueError("query_kf and db_visible differ in length")
+        ms = None if min_score is None else np.ascontiguousarray(min_score, dtype=np.float64).ravel()
+        if ms is not None and len(ms) != Q:
+            raise ValueError("min_score does not fit the queries")
+        cap = len(db) if cap is None else int(cap)
+        n = max(Q, 1)
+        nc = np.zeros(n, np.int32); cand = np.full((n, max(cap, 1)), -1, np.int32); acc = np.zeros((n, max(cap, 1)), np.float32)
+        mso = np.zeros(n); nsh = np.zeros(n, np.int32); mcw = np.zeros(n, np.int32); nsc = np.zeros(n, np.int32)
+        s = capi.DetectBatch(N, iptr(kid), iptr(client), iptr(bptr), iptr(word), dptr(value), iptr(nptr), iptr(nb),
+                             None if inv is None else inv.ctypes.data_as(capi._bp), len(db), iptr(db), Q, iptr(qk), iptr(vis), dptr(ms), cap,
+                             iptr(nc), iptr(cand), acc.ctypes.data_as(capi._fp), dptr(mso), iptr(nsh), iptr(mcw), iptr(nsc))
+        self._check(lib().covgpu_detect_candidates_batch(self._h, C.byref(s), C.byref(o)))
+        kept = np.minimum(nc[:Q], cap)
+        return dict(candidates=[cand[q, :kept[q]].copy() for q in range(Q)], acc_score=[acc[q, :kept[q]].copy() for q in range(Q)],
+                    num_candidates=nc[:Q], min_score=mso[:Q], num_sharing=nsh[:Q], max_common_words=mcw[:Q], num_scored=nsc[:Q])
 
     def p3p_batch(self, f, P):
         """covgpu_p3p_batch: f, P [n,4,3] -> (T [n,4,7] every solution, qx qy qz qw x y z, ascending v = s3/s1; nsol [n]; chosen [n], -1: none)."""

@@ -247,6 +247,35 @@ class SearchProjectionBatch(C.Structure):
                 ("claimed", _ip), ("remap_to", _ip), ("best_dist", _ip), ("nmatches", _ip)]
 
 
+BOW_L1_NORM = 0                                   # include/covgpu.h (DBoW2::ScoringType / WeightingType)
+BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
+DETECT_COVINS, DETECT_COVINS_G = 0, 1
+_lp = C.POINTER(C.c_int64)
+
+
+class BowVocab(C.Structure):
+    _fields_ = [("num_nodes", C.c_int32), ("num_words", C.c_int32), ("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32),
+                ("weighting", C.c_int32), ("parent", _ip), ("child_ptr", _ip), ("child", _ip), ("desc", _bp), ("word_id", _ip),
+                ("weight", _dp)]
+
+
+class BowTransformBatch(C.Structure):
+    _fields_ = [("num_sets", C.c_int32), ("row_ptr", _ip), ("desc", _bp), ("levelsup", C.c_int32), ("capacity", C.c_int32),
+                ("bow_ptr", _ip), ("word", _ip), ("value", _dp), ("total", _lp), ("row_word", _ip), ("row_node", _ip)]
+
+
+class DetectOpts(C.Structure):
+    _fields_ = [("min_score_factor", C.c_double), ("min_loop_dist", C.c_int32), ("exclude_kfs_with_id_less_than", C.c_int32),
+                ("inter_map_matches_only", C.c_int32), ("scratch_kib", C.c_int32)]
+
+
+class DetectBatch(C.Structure):
+    _fields_ = [("num_kf", C.c_int32), ("id", _ip), ("client", _ip), ("bow_ptr", _ip), ("word", _ip), ("value", _dp), ("nb_ptr", _ip),
+                ("nb", _ip), ("invalid", _bp), ("num_db", C.c_int32), ("db_order", _ip), ("num_queries", C.c_int32), ("query_kf", _ip),
+                ("db_visible", _ip), ("min_score_in", _dp), ("cap", C.c_int32), ("num_candidates", _ip), ("candidates", _ip),
+                ("acc_score", _fp), ("min_score", _dp), ("num_sharing", _ip), ("max_common_words", _ip), ("num_scored", _ip)]
+
+
 def declare(lib: C.CDLL, prefix: str) -> None:
     """Attach argtypes/restype for the entry points shared by libcovgpu (prefix 'covgpu_', with a context
     argument) and — test side only — the oracle (prefix 'covo_', no context)."""
@@ -287,6 +316,10 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("default_guided_opts", [C.POINTER(GuidedOpts), C.c_int32], None)
         d("search_se3_batch", [C.c_void_p, C.POINTER(SearchSe3Batch), C.POINTER(GuidedOpts)])
         d("search_projection_batch", [C.c_void_p, C.POINTER(SearchProjectionBatch), C.POINTER(GuidedOpts)])
+        d("bow_transform_batch", [C.c_void_p, C.POINTER(BowVocab), C.POINTER(BowTransformBatch)])
+        d("bow_score_pairs", [C.c_void_p, C.c_int32, _ip, _ip, _dp, C.c_int32, _ip, _ip, _dp])
+        d("default_detect_opts", [C.POINTER(DetectOpts), C.c_int32], None)
+        d("detect_candidates_batch", [C.c_void_p, C.POINTER(DetectBatch), C.POINTER(DetectOpts)])
         d("outlier_pass", [C.c_void_p, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])
         d("covisibility", [C.c_void_p, C.c_int32, C.c_int64, _ip, _ip, _ip, C.POINTER(C.c_int64)])
         d("gba_solve_multi", [OP, PP, RP, C.c_int32, _ip, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])

@@ -632,6 +632,29 @@ struct GuidedProjArgs {
 };
 void launch_guided_se3(const GuidedSe3Args& A, const GuidedOptsDev& O, int num_jobs, const int4* tiles, int num_tiles, hipStream_t st);
 void launch_guided_projection(const GuidedProjArgs& A, const GuidedOptsDev& O, int num_jobs, const int4* tiles, int num_tiles, hipStream_t st);
+// k_bow.hip: bag-of-words transform, L1 score and KeyframeDatabase::DetectCandidates. Device arrays throughout.
+struct BowVocabDev {
+  int num_nodes;
+  const int* child_ptr; const int* child; const uint4* desc; const int* word_id;   // per node; desc [nodes][2]
+  const double* word_weight;                                                      // [words] the leaf weight of each word
+};
+struct DetectOptsDev { int min_loop_dist, exclude_below, inter_only; };
+struct DetectDev {
+  int M;                                                           // database entries
+  const int* id; const int* client; const int* bow_ptr; const int* word; const double* value; const int* nb_ptr; const int* nb;
+  const int* db_order; const int* pos_of;                           // position -> keyframe, keyframe -> position or -1
+  int inv_words; const int* inv_ptr; const int* inv_pos;            // inverted index: word -> positions, ascending
+  const int* query_kf; const int* db_visible;
+  double* min_score; int* max_common; int* num_sharing; int* num_scored; int* num_candidates; int* candidates; float* acc_score;
+};
+void launch_bow_transform(const BowVocabDev& V, const unsigned char* desc, const int* row_ptr, int num_sets, int rows, int nid_level,
+                          int add_weight, int* row_word, int* row_node, int* out_word, double* out_value, int* count, hipStream_t st);
+void launch_bow_score_pairs(const int* bow_ptr, const int* word, const double* value, int num_pairs, const int* a, const int* b,
+                            double* score, hipStream_t st);
+void launch_bow_min_score(const DetectDev& D, int num_queries, const int* pair_off, const double* pair_score, double factor,
+                          hipStream_t st);
+void launch_bow_detect_chunk(const DetectDev& D, const DetectOptsDev& O, int q0, int nq, int cap, int hist_stride, int* common, int* first,
+                             double* score, float* acc, int* best, int* order, int* hist, hipStream_t st);
 void launch_reanchor(int K, const double* pose_old, const double* pose_new, double* vel, int L, const int* ref, double* lm,
                      hipStream_t st);
 

@@ -2491,3 +2491,282 @@ extern "C" int covgpu_pgo_reanchor(covgpu_context* c, int32_t K, const double* p
   for (void* p : tmp) (void)hipFree(p);
   return COVGPU_OK;
 }
+
+// ---- bag-of-words retrieval (k_bow.hip) ----
+namespace {
+
+// The first violation of a bow CSR over `rows` rows (word ids ascending and duplicate-free, values finite), or nullptr.
+const char* bow_csr_check(int rows, const int32_t* ptr, const int32_t* word, const double* value) {
+  if (rows < 0) return "negative row count";
+  if (rows == 0) return nullptr;
+  if (!ptr) return "NULL bow_ptr";
+  if (ptr[0] != 0) return "bow_ptr[0] != 0";
+  for (int r = 0; r < rows; ++r) if (ptr[r + 1] < ptr[r]) return "bow_ptr not monotone";
+  if (ptr[rows] > 0 && (!word || !value)) return "NULL word or value";
+  for (int r = 0; r < rows; ++r)
+    for (int i = ptr[r]; i < ptr[r + 1]; ++i) {
+      if (word[i] < 0) return "negative word id";
+      if (i > ptr[r] && word[i] <= word[i - 1]) return "word ids of a bow row not ascending and duplicate-free";
+      if (!std::isfinite(value[i])) return "non-finite bow value";
+    }
+  return nullptr;
+}
+
+// The first violation of the vocabulary's tree shape, or nullptr.
+const char* bow_vocab_check(const covgpu_bow_vocab_t* v) {
+  if (!v) return "NULL vocabulary";
+  if (v->scoring != COVGPU_BOW_L1_NORM) return "only L1_NORM scoring is supported";
+  if (v->weighting < COVGPU_BOW_TF_IDF || v->weighting > COVGPU_BOW_BINARY) return "unknown weighting";
+  const int N = v->num_nodes, W = v->num_words;
+  if (N < 2) return "the vocabulary has no node below the root";
+  if (W < 1 || W > COVGPU_BOW_MAX_WORDS) return "num_words is not in 1..COVGPU_BOW_MAX_WORDS";
+  if (v->k < 1 || v->L < 0) return "k < 1 or L < 0";
+  if (!v->parent || !v->child_ptr || !v->child || !v->desc || !v->word_id || !v->weight) return "NULL vocabulary array";
+  if (v->parent[0] != -1) return "parent[0] != -1";
+  for (int n = 1; n < N; ++n) if (v->parent[n] < 0 || v->parent[n] >= n) return "parent[n] is not in 0..n-1";
+  if (v->child_ptr[0] != 0) return "child_ptr[0] != 0";
+  for (int n = 0; n < N; ++n) if (v->child_ptr[n + 1] < v->child_ptr[n]) return "child_ptr not monotone";
+  if (v->child_ptr[N] != N - 1) return "child_ptr[num_nodes] != num_nodes - 1";
+  std::vector<uint8_t> seen(W, 0);
+  for (int n = 0; n < N; ++n) {
+    for (int i = v->child_ptr[n]; i < v->child_ptr[n + 1]; ++i) {
+      const int c = v->child[i];
+      if (c <= 0 || c >= N) return "child index out of range";
+      if (v->parent[c] != n) return "child lists inconsistent with parent";
+      if (i > v->child_ptr[n] && c <= v->child[i - 1]) return "children not in ascending (line) order";
+    }
+    const bool leaf = v->child_ptr[n + 1] == v->child_ptr[n];
+    if (leaf != (v->word_id[n] >= 0)) return "leaves are not exactly the nodes with a word id";
+    if (leaf) {
+      if (v->word_id[n] >= W) return "word id out of range";
+      if (seen[v->word_id[n]]) return "word ids are not a permutation of 0..num_words-1";
+      seen[v->word_id[n]] = 1;
+    }
+    if (!std::isfinite(v->weight[n])) return "non-finite weight";
+  }
+  for (int w = 0; w < W; ++w) if (!seen[w]) return "word ids are not a permutation of 0..num_words-1";
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" int covgpu_bow_transform_batch(covgpu_context* c, const covgpu_bow_vocab_t* v, const covgpu_bow_transform_batch_t* bt) {
+  auto bad = [](const char* m) { g_err = std::string("covgpu_bow_transform_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
+  if (!c) return bad("NULL context");
+  if (!bt) return bad("NULL batch");
+  if (const char* m = bow_vocab_check(v)) return bad(m);
+  const int S = bt->num_sets;
+  if (S < 0 || bt->capacity < 0) return bad("num_sets or capacity < 0");
+  if (S > 0 && (!bt->row_ptr || !bt->bow_ptr)) return bad("NULL row_ptr or bow_ptr");
+  if (S > 0 && bt->row_ptr[0] != 0) return bad("row_ptr[0] != 0");
+  for (int s = 0; s < S; ++s) {
+    if (bt->row_ptr[s + 1] < bt->row_ptr[s]) return bad("row_ptr not monotone");
+    if (bt->row_ptr[s + 1] - bt->row_ptr[s] > COVGPU_MATCH_MAX_ROWS) return bad("a set holds more than COVGPU_MATCH_MAX_ROWS rows");
+  }
+  const size_t R = S > 0 ? (size_t)bt->row_ptr[S] : 0;
+  if (R > 0 && !bt->desc) return bad("NULL desc");
+  if (bt->capacity > 0 && (!bt->word || !bt->value)) return bad("NULL word or value");
+  if (bt->total) *bt->total = 0;
+  if (S == 0) return COVGPU_OK;
+  const int N = v->num_nodes, W = v->num_words;
+  std::vector<double> ww(W);
+  for (int n = 0; n < N; ++n) if (v->word_id[n] >= 0) ww[v->word_id[n]] = v->weight[n];
+  HIPCHK(hipSetDevice(c->device));                                   // the first device call: every argument is checked above
+  GuidedUpload U{c};
+  BowVocabDev V{};
+  V.num_nodes = N;
+  HIPCHK(U.up(v->child_ptr, 4 * ((size_t)N + 1), (void**)&V.child_ptr)); HIPCHK(U.up(v->child, 4 * ((size_t)N - 1), (void**)&V.child));
+  HIPCHK(U.up(v->desc, 32 * (size_t)N, (void**)&V.desc)); HIPCHK(U.up(v->word_id, 4 * (size_t)N, (void**)&V.word_id));
+  HIPCHK(U.up(ww.data(), 8 * (size_t)W, (void**)&V.word_weight));
+  unsigned char* ddesc = nullptr;
+  int *dptr_ = nullptr, *drw = nullptr, *drn = nullptr, *dow = nullptr, *dcnt = nullptr;
+  double* dov = nullptr;
+  HIPCHK(U.up(bt->desc, 32 * R, (void**)&ddesc)); HIPCHK(U.up(bt->row_ptr, 4 * ((size_t)S + 1), (void**)&dptr_));
+  HIPCHK(U.alloc((void**)&drw, 4 * R)); HIPCHK(U.alloc((void**)&drn, 4 * R)); HIPCHK(U.alloc((void**)&dow, 4 * R));
+  HIPCHK(U.alloc((void**)&dov, 8 * R)); HIPCHK(U.alloc((void**)&dcnt, 4 * (size_t)S));
+  const int add_weight = v->weighting == COVGPU_BOW_TF_IDF || v->weighting == COVGPU_BOW_TF;
+  launch_bow_transform(V, ddesc, dptr_, S, (int)R, v->L - bt->levelsup, add_weight, drw, drn, dow, dov, dcnt, c->st);
+  HIPCHK(hipGetLastError());
+  // each set's words sit at its first row; the exact CSR is packed from one download
+  std::vector<int32_t> hw(R), hc(S);
+  std::vector<double> hv(R);
+  if (R) {
+    HIPCHK(hipMemcpyAsync(hw.data(), dow, 4 * R, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(hv.data(), dov, 8 * R, hipMemcpyDeviceToHost, c->st));
+    if (bt->row_word) HIPCHK(hipMemcpyAsync(bt->row_word, drw, 4 * R, hipMemcpyDeviceToHost, c->st));
+    if (bt->row_node) HIPCHK(hipMemcpyAsync(bt->row_node, drn, 4 * R, hipMemcpyDeviceToHost, c->st));
+  }
+  HIPCHK(hipMemcpyAsync(hc.data(), dcnt, 4 * (size_t)S, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  int64_t tot = 0;
+  bt->bow_ptr[0] = 0;
+  for (int s = 0; s < S; ++s) {
+    const int64_t room = std::max<int64_t>(0, std::min<int64_t>(hc[s], (int64_t)bt->capacity - tot));
+    if (room > 0) {
+      std::memcpy(bt->word + tot, hw.data() + bt->row_ptr[s], 4 * (size_t)room);
+      std::memcpy(bt->value + tot, hv.data() + bt->row_ptr[s], 8 * (size_t)room);
+    }
+    tot += hc[s];
+    bt->bow_ptr[s + 1] = (int32_t)tot;                                // tot <= rows <= 2^31 - 1
+  }
+  if (bt->total) *bt->total = tot;
+  return COVGPU_OK;
+}
+
+extern "C" int covgpu_bow_score_pairs(covgpu_context* c, int32_t num_vec, const int32_t* bow_ptr, const int32_t* word, const double* value,
+                                      int32_t num_pairs, const int32_t* a, const int32_t* b, double* score) {
+  auto bad = [](const char* m) { g_err = std::string("covgpu_bow_score_pairs: ") + m; return COVGPU_ERR_INVALID_ARG; };
+  if (!c) return bad("NULL context");
+  if (const char* m = bow_csr_check(num_vec, bow_ptr, word, value)) return bad(m);
+  if (num_pairs < 0) return bad("num_pairs < 0");
+  if (num_pairs > 0 && (!a || !b || !score)) return bad("NULL pair array");
+  for (int i = 0; i < num_pairs; ++i)
+    if (a[i] < 0 || a[i] >= num_vec || b[i] < 0 || b[i] >= num_vec) return bad("pair index out of range");
+  if (num_pairs == 0) return COVGPU_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t nnz = (size_t)bow_ptr[num_vec], P = (size_t)num_pairs;
+  GuidedUpload U{c};
+  int *dp = nullptr, *dw = nullptr, *da = nullptr, *db = nullptr;
+  double *dv = nullptr, *ds = nullptr;
+  HIPCHK(U.up(bow_ptr, 4 * ((size_t)num_vec + 1), (void**)&dp)); HIPCHK(U.up(word, 4 * nnz, (void**)&dw)); HIPCHK(U.up(value, 8 * nnz, (void**)&dv));
+  HIPCHK(U.up(a, 4 * P, (void**)&da)); HIPCHK(U.up(b, 4 * P, (void**)&db)); HIPCHK(U.alloc((void**)&ds, 8 * P));
+  launch_bow_score_pairs(dp, dw, dv, num_pairs, da, db, ds, c->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(score, ds, 8 * P, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return COVGPU_OK;
+}
+
+extern "C" void covgpu_default_detect_opts(covgpu_detect_opts* o, int32_t mode) {
+  if (!o) return;
+  o->min_score_factor = mode == COVGPU_DETECT_COVINS_G ? 0.7 : 0.8;  // placerec_gen_be.cpp / placerec_be.cpp:389
+  o->min_loop_dist = 100;                                            // config_backend.yaml:72-78
+  o->exclude_kfs_with_id_less_than = 7;
+  o->inter_map_matches_only = 0;
+  o->scratch_kib = 0;
+}
+
+extern "C" int covgpu_detect_candidates_batch(covgpu_context* c, const covgpu_detect_batch_t* bt, const covgpu_detect_opts* opts) {
+  auto bad = [](const char* m) { g_err = std::string("covgpu_detect_candidates_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
+  if (!c) return bad("NULL context");
+  if (!bt || !opts) return bad("NULL batch or options");
+  if (!std::isfinite(opts->min_score_factor)) return bad("non-finite min_score_factor");
+  if (opts->scratch_kib < 0) return bad("scratch_kib < 0");
+  const int N = bt->num_kf, M = bt->num_db, Q = bt->num_queries, cap = bt->cap;
+  if (N < 0 || M < 0 || Q < 0 || cap < 0) return bad("negative count");
+  if (N > 0 && (!bt->id || !bt->client || !bt->nb_ptr)) return bad("NULL keyframe array");
+  for (int k = 0; k < N; ++k) if (bt->id[k] < 0) return bad("negative keyframe id");
+  if (const char* m = bow_csr_check(N, bt->bow_ptr, bt->word, bt->value)) return bad(m);
+  if (N > 0 && bt->nb_ptr[0] != 0) return bad("nb_ptr[0] != 0");
+  for (int k = 0; k < N; ++k) if (bt->nb_ptr[k + 1] < bt->nb_ptr[k]) return bad("nb_ptr not monotone");
+  const size_t NB = N > 0 ? (size_t)bt->nb_ptr[N] : 0;
+  if (NB > 0 && !bt->nb) return bad("NULL nb");
+  for (size_t i = 0; i < NB; ++i) if (bt->nb[i] < 0 || bt->nb[i] >= N) return bad("neighbour index out of range");
+  if (M > 0 && !bt->db_order) return bad("NULL db_order");
+  std::vector<int32_t> pos_of(N > 0 ? N : 1, -1);
+  for (int p = 0; p < M; ++p) {
+    const int k = bt->db_order[p];
+    if (k < 0 || k >= N) return bad("db_order index out of range");
+    if (pos_of[k] >= 0) return bad("db_order repeats a keyframe");
+    pos_of[k] = p;
+  }
+  if (Q > 0 && (!bt->query_kf || !bt->db_visible || !bt->num_candidates)) return bad("NULL query array");
+  if (Q > 0 && cap > 0 && !bt->candidates) return bad("NULL candidates");
+  int max_words = 0;
+  size_t num_pairs = 0;
+  for (int q = 0; q < Q; ++q) {
+    const int k = bt->query_kf[q];
+    if (k < 0 || k >= N) return bad("query_kf out of range");
+    if (bt->db_visible[q] < 0 || bt->db_visible[q] > M) return bad("db_visible is not in 0..num_db");
+    if (bt->min_score_in && std::isnan(bt->min_score_in[q])) return bad("min_score_in is NaN");
+    max_words = std::max(max_words, bt->bow_ptr[k + 1] - bt->bow_ptr[k]);
+    num_pairs += (size_t)(bt->nb_ptr[k + 1] - bt->nb_ptr[k]);
+  }
+  if (num_pairs > (size_t)INT32_MAX) return bad("more than 2^31 - 1 query neighbours");
+  if (Q == 0) return COVGPU_OK;
+  // host side of the call: the reference-score pairs and the inverted index of the database (posting lists in insertion order)
+  std::vector<int32_t> pa, pb, poff(Q + 1, 0);
+  if (!bt->min_score_in) {
+    pa.reserve(num_pairs); pb.reserve(num_pairs);
+    for (int q = 0; q < Q; ++q) {
+      const int k = bt->query_kf[q];
+      for (int i = bt->nb_ptr[k]; i < bt->nb_ptr[k + 1]; ++i) {
+        if (bt->invalid && bt->invalid[bt->nb[i]]) continue;
+        pa.push_back(k); pb.push_back(bt->nb[i]);
+      }
+      poff[q + 1] = (int32_t)pa.size();
+    }
+  }
+  int inv_words = 0;
+  for (int p = 0; p < M; ++p) {
+    const int k = bt->db_order[p];
+    if (bt->bow_ptr[k + 1] > bt->bow_ptr[k]) inv_words = std::max(inv_words, bt->word[bt->bow_ptr[k + 1] - 1] + 1);
+  }
+  std::vector<int32_t> inv_ptr((size_t)inv_words + 1, 0);
+  for (int p = 0; p < M; ++p) {
+    const int k = bt->db_order[p];
+    for (int i = bt->bow_ptr[k]; i < bt->bow_ptr[k + 1]; ++i) ++inv_ptr[bt->word[i] + 1];
+  }
+  for (int w = 0; w < inv_words; ++w) {
+    if ((int64_t)inv_ptr[w + 1] + inv_ptr[w] > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 database words");
+    inv_ptr[w + 1] += inv_ptr[w];
+  }
+  std::vector<int32_t> inv_pos((size_t)inv_ptr[inv_words]), fill(inv_ptr.begin(), inv_ptr.end() - 1);
+  for (int p = 0; p < M; ++p) {
+    const int k = bt->db_order[p];
+    for (int i = bt->bow_ptr[k]; i < bt->bow_ptr[k + 1]; ++i) inv_pos[fill[bt->word[i]]++] = p;
+  }
+  HIPCHK(hipSetDevice(c->device));                                   // the first device call: every argument is checked above
+  GuidedUpload U{c};
+  DetectDev D{};
+  D.M = M; D.inv_words = inv_words;
+  const size_t nnz = N > 0 ? (size_t)bt->bow_ptr[N] : 0, Qs = (size_t)Q, caps = (size_t)cap;
+  HIPCHK(U.up(bt->id, 4 * (size_t)N, (void**)&D.id)); HIPCHK(U.up(bt->client, 4 * (size_t)N, (void**)&D.client));
+  HIPCHK(U.up(bt->bow_ptr, 4 * ((size_t)N + 1), (void**)&D.bow_ptr)); HIPCHK(U.up(bt->word, 4 * nnz, (void**)&D.word));
+  HIPCHK(U.up(bt->value, 8 * nnz, (void**)&D.value)); HIPCHK(U.up(bt->nb_ptr, 4 * ((size_t)N + 1), (void**)&D.nb_ptr));
+  HIPCHK(U.up(bt->nb, 4 * NB, (void**)&D.nb)); HIPCHK(U.up(bt->db_order, 4 * (size_t)M, (void**)&D.db_order));
+  HIPCHK(U.up(pos_of.data(), 4 * (size_t)N, (void**)&D.pos_of)); HIPCHK(U.up(inv_ptr.data(), 4 * inv_ptr.size(), (void**)&D.inv_ptr));
+  HIPCHK(U.up(inv_pos.data(), 4 * inv_pos.size(), (void**)&D.inv_pos)); HIPCHK(U.up(bt->query_kf, 4 * Qs, (void**)&D.query_kf));
+  HIPCHK(U.up(bt->db_visible, 4 * Qs, (void**)&D.db_visible));
+  if (bt->min_score_in) HIPCHK(U.up(bt->min_score_in, 8 * Qs, (void**)&D.min_score)); else HIPCHK(U.alloc((void**)&D.min_score, 8 * Qs));
+  int* counters = nullptr;                                           // max_common, num_sharing, num_scored, num_candidates
+  HIPCHK(U.alloc((void**)&counters, 16 * Qs));
+  HIPCHK(hipMemsetAsync(counters, 0, 16 * Qs, c->st));
+  D.max_common = counters; D.num_sharing = counters + Q; D.num_scored = counters + 2 * Qs; D.num_candidates = counters + 3 * Qs;
+  HIPCHK(U.alloc((void**)&D.candidates, 4 * Qs * caps)); HIPCHK(U.alloc((void**)&D.acc_score, 4 * Qs * caps));
+  if (cap > 0) { HIPCHK(hipMemsetAsync(D.candidates, 0xff, 4 * Qs * caps, c->st)); HIPCHK(hipMemsetAsync(D.acc_score, 0, 4 * Qs * caps, c->st)); }
+  if (!bt->min_score_in) {
+    int *dpa = nullptr, *dpb = nullptr, *dpo = nullptr;
+    double* dps = nullptr;
+    HIPCHK(U.up(pa.data(), 4 * pa.size(), (void**)&dpa)); HIPCHK(U.up(pb.data(), 4 * pb.size(), (void**)&dpb));
+    HIPCHK(U.up(poff.data(), 4 * poff.size(), (void**)&dpo)); HIPCHK(U.alloc((void**)&dps, 8 * pa.size()));
+    launch_bow_score_pairs(D.bow_ptr, D.word, D.value, (int)pa.size(), dpa, dpb, dps, c->st);
+    launch_bow_min_score(D, Q, dpo, dps, opts->min_score_factor, c->st);
+  }
+  // per-query scratch is 28 B per database entry; queries run in chunks that keep it within the budget
+  const size_t budget = (size_t)(opts->scratch_kib > 0 ? opts->scratch_kib : 65536) << 10;
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>(Qs, budget / (28 * std::max<size_t>(1, (size_t)M))));
+  const size_t cm = (size_t)chunk * (size_t)M;
+  const int hist_stride = max_words + 1;
+  int *common = nullptr, *first = nullptr, *best = nullptr, *order = nullptr, *hist = nullptr;
+  double* score = nullptr;
+  float* acc = nullptr;
+  HIPCHK(U.alloc((void**)&common, 4 * cm)); HIPCHK(U.alloc((void**)&first, 4 * cm)); HIPCHK(U.alloc((void**)&score, 8 * cm));
+  HIPCHK(U.alloc((void**)&acc, 4 * cm)); HIPCHK(U.alloc((void**)&best, 4 * cm)); HIPCHK(U.alloc((void**)&order, 4 * cm));
+  HIPCHK(U.alloc((void**)&hist, 4 * (size_t)chunk * (size_t)hist_stride));
+  const DetectOptsDev O{opts->min_loop_dist, opts->exclude_kfs_with_id_less_than, opts->inter_map_matches_only != 0};
+  for (int q0 = 0; q0 < Q; q0 += chunk)
+    launch_bow_detect_chunk(D, O, q0, std::min(chunk, Q - q0), cap, hist_stride, common, first, score, acc, best, order, hist, c->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(bt->num_candidates, D.num_candidates, 4 * Qs, hipMemcpyDeviceToHost, c->st));
+  if (bt->max_common_words) HIPCHK(hipMemcpyAsync(bt->max_common_words, D.max_common, 4 * Qs, hipMemcpyDeviceToHost, c->st));
+  if (bt->num_sharing) HIPCHK(hipMemcpyAsync(bt->num_sharing, D.num_sharing, 4 * Qs, hipMemcpyDeviceToHost, c->st));
+  if (bt->num_scored) HIPCHK(hipMemcpyAsync(bt->num_scored, D.num_scored, 4 * Qs, hipMemcpyDeviceToHost, c->st));
+  if (bt->min_score) HIPCHK(hipMemcpyAsync(bt->min_score, D.min_score, 8 * Qs, hipMemcpyDeviceToHost, c->st));
+  if (cap > 0) {
+    HIPCHK(hipMemcpyAsync(bt->candidates, D.candidates, 4 * Qs * caps, hipMemcpyDeviceToHost, c->st));
+    if (bt->acc_score) HIPCHK(hipMemcpyAsync(bt->acc_score, D.acc_score, 4 * Qs * caps, hipMemcpyDeviceToHost, c->st));
+  }
+  HIPCHK(hipStreamSynchronize(c->st));
+  return COVGPU_OK;
+}

@@ -619,6 +619,97 @@ void covgpu_default_guided_opts(covgpu_guided_opts*, int32_t mode);
 int  covgpu_search_se3_batch(covgpu_context*, const covgpu_search_se3_batch_t*, const covgpu_guided_opts*);
 int  covgpu_search_projection_batch(covgpu_context*, const covgpu_search_projection_batch_t*, const covgpu_guided_opts*);
 
+/* ---- Bag-of-words retrieval: DBoW2's transform and L1 score, and KeyframeDatabase::DetectCandidates ----
+ *
+ * The vocabulary is DBoW2's tree in flat form (covins_amd/vocio.py reads and writes the DBoW2 text format). Node 0 is the root, node ids
+ * are the line order of the text file, a node's children are in line order and word ids are leaf order. The tree may be irregular:
+ * leaves at different depths, nodes with one child, any k >= 1. Only L1_NORM scoring is supported; num_words is at most
+ * COVGPU_BOW_MAX_WORDS = 2^20 - 1, so that a (word, row) sort key of 20 + 12 bits never equals the all-ones key of a stopped row. */
+#define COVGPU_BOW_L1_NORM 0                     /* DBoW2::ScoringType */
+#define COVGPU_BOW_TF_IDF 0                      /* DBoW2::WeightingType */
+#define COVGPU_BOW_TF 1
+#define COVGPU_BOW_IDF 2
+#define COVGPU_BOW_BINARY 3
+#define COVGPU_BOW_MAX_WORDS ((1 << 20) - 1)
+typedef struct covgpu_bow_vocab_t {
+  int32_t num_nodes, num_words;
+  int32_t k, L;                                  /* the header's branching factor and depth; L - levelsup is the FeatureVector level */
+  int32_t scoring, weighting;
+  const int32_t* parent;                         /* [num_nodes] parent[0] = -1, parent[n] < n */
+  const int32_t* child_ptr;                      /* [num_nodes+1] */
+  const int32_t* child;                          /* [num_nodes-1] children of node n, ascending (line order) */
+  const uint8_t* desc;                           /* [num_nodes][32] (the root's row is not read) */
+  const int32_t* word_id;                        /* [num_nodes] -1 for an inner node */
+  const double*  weight;                         /* [num_nodes] */
+} covgpu_bow_vocab_t;
+
+/* transform(features, bow_vec, feat_vec, levelsup) of every descriptor set. Sets arrive in the row_ptr / desc layout of
+ * covgpu_match_batch_t, at most COVGPU_MATCH_MAX_ROWS rows each. bow_ptr is always exact; word / value receive the first `capacity`
+ * entries and *total the true count. row_word is -1 for a stopped word (weight <= 0); row_node is the node at depth L - levelsup
+ * (0 when that is <= 0; the leaf when the leaf lies above that depth, where the reference leaves the value uninitialised). */
+typedef struct covgpu_bow_transform_batch_t {
+  int32_t num_sets;
+  const int32_t* row_ptr;                        /* [num_sets+1] */
+  const uint8_t* desc;                           /* [rows][32] */
+  int32_t levelsup;                              /* the reference passes 4 */
+  int32_t capacity;                              /* entries of word / value */
+  int32_t* bow_ptr;                              /* out [num_sets+1] */
+  int32_t* word;                                 /* out [capacity] ascending within a set */
+  double*  value;                                /* out [capacity] */
+  int64_t* total;                                /* out, may be NULL */
+  int32_t* row_word;                             /* out [rows], may be NULL */
+  int32_t* row_node;                             /* out [rows], may be NULL */
+} covgpu_bow_transform_batch_t;
+int covgpu_bow_transform_batch(covgpu_context*, const covgpu_bow_vocab_t*, const covgpu_bow_transform_batch_t*);
+
+/* L1Scoring::score of pairs (a[i], b[i]) of the rows of a bow CSR (word ids ascending and duplicate-free within a row). */
+int covgpu_bow_score_pairs(covgpu_context*, int32_t num_vec, const int32_t* bow_ptr, const int32_t* word, const double* value,
+                           int32_t num_pairs, const int32_t* a, const int32_t* b, double* score);
+
+#define COVGPU_DETECT_COVINS 0
+#define COVGPU_DETECT_COVINS_G 1
+typedef struct covgpu_detect_opts {
+  double  min_score_factor;                      /* 0.8 (COVINS), 0.7 (COVINS-G) */
+  int32_t min_loop_dist;                         /* 100 */
+  int32_t exclude_kfs_with_id_less_than;         /* 7 */
+  int32_t inter_map_matches_only;                /* 0 */
+  int32_t scratch_kib;                           /* per-call budget of the per-query device scratch (28 B per database entry and
+                                                    query); queries run in chunks that fit it, at least one at a time. 0 = 65 536 */
+} covgpu_detect_opts;
+void covgpu_default_detect_opts(covgpu_detect_opts*, int32_t mode);
+
+/* One DetectCandidates per query over a keyframe table. Query q is keyframe query_kf[q] and sees the database entries
+ * db_order[0 : db_visible[q]] (table indices in insertion order), so one batch replays consecutive queries each followed by
+ * AddKeyframe. nb holds, per keyframe, the table indices of GetConnectedKeyframesByWeight(0) (COVINS) or
+ * GetConnectedNeighborKeyframes() (COVINS-G) in the reference's order. min_score_in NULL: the reference minimum score over the
+ * query's valid neighbours times min_score_factor. Each keyframe is expected to be queried once, as DetectLoop does. */
+typedef struct covgpu_detect_batch_t {
+  int32_t num_kf;
+  const int32_t* id;                             /* [num_kf] >= 0 */
+  const int32_t* client;                         /* [num_kf] */
+  const int32_t* bow_ptr;                        /* [num_kf+1] */
+  const int32_t* word;
+  const double*  value;
+  const int32_t* nb_ptr;                         /* [num_kf+1] */
+  const int32_t* nb;
+  const uint8_t* invalid;                        /* [num_kf] or NULL */
+  int32_t num_db;
+  const int32_t* db_order;                       /* [num_db] each keyframe at most once */
+  int32_t num_queries;
+  const int32_t* query_kf;                       /* [num_queries] */
+  const int32_t* db_visible;                     /* [num_queries] <= num_db */
+  const double*  min_score_in;                   /* [num_queries] or NULL */
+  int32_t cap;                                   /* candidates kept per query */
+  int32_t* num_candidates;                       /* out [num_queries] the true count */
+  int32_t* candidates;                           /* out [num_queries][cap] table indices in the reference's order, -1 padded */
+  float*   acc_score;                            /* out [num_queries][cap] accScore of the entry that gave the candidate */
+  double*  min_score;                            /* out [num_queries] */
+  int32_t* num_sharing;                          /* out [num_queries] size of lKFsSharingWords */
+  int32_t* max_common_words;                     /* out [num_queries] */
+  int32_t* num_scored;                           /* out [num_queries] nscores */
+} covgpu_detect_batch_t;
+int covgpu_detect_candidates_batch(covgpu_context*, const covgpu_detect_batch_t*, const covgpu_detect_opts*);
+
 #ifdef __cplusplus
 }
 #endif

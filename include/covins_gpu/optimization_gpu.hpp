@@ -316,6 +316,44 @@ struct Flat {  // owning storage behind one covgpu_problem
   }
 };
 
+// ---- what the bag-of-words retrieval (KeyframeDatabaseT) reads and writes, each through an optional trait with the COVINS member as
+//      the fallback: bow_vec_ (DBoW2::BowVector, a std::map<WordId, WordValue>), feat_vec_ (DBoW2::FeatureVector, a std::map<NodeId,
+//      std::vector<unsigned>>) and the covisibility neighbours in the reference's order.
+template <class Types, class K, class F>
+inline auto visit_bow(K& kf, F&& f, int) -> decltype(Types::visit_bow(kf, f), void()) { Types::visit_bow(kf, f); }
+template <class Types, class K, class F>
+inline void visit_bow(K& kf, F&& f, long) { for (const auto& e : kf.bow_vec_) f((int32_t)e.first, (double)e.second); }
+template <class Types, class K>
+inline auto set_bow(K& kf, size_t n, const int32_t* word, const double* value, int) -> decltype(Types::set_bow(kf, n, word, value), void()) {
+  Types::set_bow(kf, n, word, value);
+}
+template <class Types, class K>
+inline void set_bow(K& kf, size_t n, const int32_t* word, const double* value, long) {
+  kf.bow_vec_.clear();
+  for (size_t i = 0; i < n; ++i) kf.bow_vec_[word[i]] = value[i];
+}
+// per descriptor row its word (-1: stopped, no entry) and FeatureVector key: fv.addFeature(nid, i_feature) in row order
+template <class Types, class K>
+inline auto set_features(K& kf, size_t rows, const int32_t* row_word, const int32_t* row_node, int)
+    -> decltype(Types::set_features(kf, rows, row_word, row_node), void()) {
+  Types::set_features(kf, rows, row_word, row_node);
+}
+template <class Types, class K>
+inline void set_features(K& kf, size_t rows, const int32_t* row_word, const int32_t* row_node, long) {
+  kf.feat_vec_.clear();
+  for (size_t i = 0; i < rows; ++i) if (row_word[i] >= 0) kf.feat_vec_[row_node[i]].push_back((unsigned)i);
+}
+// GetConnectedKeyframesByWeight(0) (COVINS) or GetConnectedNeighborKeyframes() (COVINS-G), as kf_database.cpp:50-54 chooses
+template <class Types, class K>
+inline auto connected_keyframes(K& kf, bool covins_g, int) -> decltype(Types::connected_keyframes(kf, covins_g)) {
+  return Types::connected_keyframes(kf, covins_g);
+}
+template <class Types, class K>
+inline auto connected_keyframes(K& kf, bool covins_g, long) -> decltype(kf.GetConnectedKeyframesByWeight(0)) {
+  return covins_g ? kf.GetConnectedNeighborKeyframes() : kf.GetConnectedKeyframesByWeight(0);
+}
+
+
 }  // namespace detail
 
 // `Types` must provide (see tests/cpp/standin_map.hpp and INTEGRATION.md):
@@ -1299,6 +1337,189 @@ class LoopMatcherT {
     }
     return out;
   }
+};
+
+// ---- KeyframeDatabase with the reference's method names, the query batched on the GPU (covgpu_detect_candidates_batch, DESIGN.md
+// §4.13), plus the bag-of-words transform of arriving keyframes (keyframe_be.cpp:159-183) and the covisibility-consistency groups of
+// PlaceRecognition::DetectLoop (placerec_be.cpp:398-460). The database itself is a host-side insertion order; every call uploads what
+// it needs.
+struct BowVocabulary {                             // the flat form of covgpu_bow_vocab_t, owning its arrays
+  int32_t k = 0, L = 0, scoring = COVGPU_BOW_L1_NORM, weighting = COVGPU_BOW_TF_IDF, num_words = 0;
+  std::vector<int32_t> parent, child_ptr, child, word_id;
+  std::vector<uint8_t> desc;
+  std::vector<double> weight;
+  covgpu_bow_vocab_t view() const {
+    covgpu_bow_vocab_t v{};
+    v.num_nodes = (int32_t)parent.size(); v.num_words = num_words; v.k = k; v.L = L; v.scoring = scoring; v.weighting = weighting;
+    v.parent = parent.data(); v.child_ptr = child_ptr.data(); v.child = child.data(); v.desc = desc.data(); v.word_id = word_id.data();
+    v.weight = weight.data();
+    return v;
+  }
+};
+
+template <class Types>
+class KeyframeDatabaseT {
+ public:
+  using Keyframe = typename Types::Keyframe;
+  using KeyframePtr = std::shared_ptr<Keyframe>;
+  using KeyframeVector = std::vector<KeyframePtr>;
+
+  struct Query {
+    KeyframePtr kf;
+    size_t db_visible = 0;                         // the query sees the first db_visible keyframes added (DetectCandidatesBatch)
+    bool has_min_score = false;                    // false: the reference score of DetectLoop over kf's valid neighbours
+    double min_score = 0.0;                        // in when has_min_score, out otherwise
+    KeyframeVector candidates;                     // out, in the reference's order
+    std::vector<float> acc_score;                  // out
+  };
+
+  explicit KeyframeDatabaseT(int mode = COVGPU_DETECT_COVINS) : mode_(mode) { covgpu_default_detect_opts(&opts_, mode); }
+  covgpu_detect_opts& options() { return opts_; }
+  size_t max_candidates = (size_t)-1;              // candidates kept per query (the output arrays are queries x this, at most the database size)
+
+  void AddKeyframe(KeyframePtr kf) { order_.push_back(std::move(kf)); }
+  void EraseKeyframe(const KeyframePtr& kf) { order_.erase(std::remove(order_.begin(), order_.end(), kf), order_.end()); }
+  size_t size() const { return order_.size(); }
+
+  KeyframeVector DetectCandidates(KeyframePtr kf, double min_score) {
+    std::vector<Query> q(1);
+    q[0].kf = std::move(kf); q[0].db_visible = order_.size(); q[0].has_min_score = true; q[0].min_score = min_score;
+    DetectCandidatesBatch(q);
+    return q[0].candidates;
+  }
+
+  // Either every query brings its min_score or none does.
+  void DetectCandidatesBatch(std::vector<Query>& queries) {
+    const bool g = mode_ == COVGPU_DETECT_COVINS_G;
+    std::unordered_map<const Keyframe*, int32_t> index;
+    KeyframeVector rows;
+    auto row = [&](const KeyframePtr& kf) {
+      auto it = index.find(kf.get());
+      if (it != index.end()) return it->second;
+      index.emplace(kf.get(), (int32_t)rows.size());
+      rows.push_back(kf);
+      return (int32_t)rows.size() - 1;
+    };
+    std::vector<int32_t> db, qk, vis;
+    std::vector<double> ms;
+    for (const auto& kf : order_) db.push_back(row(kf));
+    bool given = !queries.empty() && queries[0].has_min_score;
+    for (const auto& q : queries) {
+      if (q.has_min_score != given) detail::fatal("DetectCandidatesBatch: min_score given for some queries only");
+      qk.push_back(row(q.kf)); vis.push_back((int32_t)q.db_visible); ms.push_back(q.min_score);
+    }
+    // neighbour lists: whole for the queries, the first 10 for the database entries (more are never read)
+    std::vector<std::vector<int32_t>> nbs(rows.size());
+    std::vector<uint8_t> is_query(rows.size(), 0);
+    for (int32_t k : qk) is_query[k] = 1;
+    const size_t first = rows.size();
+    std::vector<uint8_t> need_bow(first, 1);       // words of the database entries and the queries; other rows stay empty vectors
+    for (size_t k = 0; k < first; ++k) {
+      const auto con = detail::connected_keyframes<Types>(*rows[k], g, 0);
+      const size_t n = is_query[k] ? con.size() : std::min<size_t>(con.size(), 10);
+      std::vector<int32_t> l;
+      for (size_t i = 0; i < n; ++i) l.push_back(row(con[i]));
+      nbs.resize(rows.size());                     // (neighbours outside the database get a row and an empty list)
+      if (is_query[k] && !given) { need_bow.resize(rows.size(), 0); for (int32_t i : l) need_bow[i] = 1; }   // the reference score reads them
+      nbs[k] = std::move(l);
+    }
+    const size_t N = rows.size();
+    need_bow.resize(N, 0);
+    std::vector<int32_t> id(N), client(N), bptr(1, 0), word, nptr(1, 0), nb;
+    std::vector<double> value;
+    std::vector<uint8_t> invalid(N);
+    for (size_t k = 0; k < N; ++k) {
+      id[k] = (int32_t)rows[k]->id_.first; client[k] = (int32_t)rows[k]->id_.second; invalid[k] = rows[k]->IsInvalid() ? 1 : 0;
+      if (need_bow[k]) detail::visit_bow<Types>(*rows[k], [&](int32_t w, double v) { word.push_back(w); value.push_back(v); }, 0);
+      bptr.push_back((int32_t)word.size());
+      nb.insert(nb.end(), nbs[k].begin(), nbs[k].end());
+      nptr.push_back((int32_t)nb.size());
+    }
+    const size_t Q = queries.size(), cap = std::min(order_.size(), max_candidates);
+    std::vector<int32_t> nc(Q + 1), cand(Q * cap + 1);
+    std::vector<float> acc(Q * cap + 1);
+    std::vector<double> mso(Q + 1);
+    word.reserve(1); value.reserve(1); nb.reserve(1); db.reserve(1);
+    covgpu_detect_batch_t bt{};
+    bt.num_kf = (int32_t)N; bt.id = id.data(); bt.client = client.data(); bt.bow_ptr = bptr.data(); bt.word = word.data(); bt.value = value.data();
+    bt.nb_ptr = nptr.data(); bt.nb = nb.data(); bt.invalid = invalid.data(); bt.num_db = (int32_t)db.size(); bt.db_order = db.data();
+    bt.num_queries = (int32_t)Q; bt.query_kf = qk.data(); bt.db_visible = vis.data(); bt.min_score_in = given ? ms.data() : nullptr;
+    bt.cap = (int32_t)cap; bt.num_candidates = nc.data(); bt.candidates = cand.data(); bt.acc_score = acc.data(); bt.min_score = mso.data();
+    if (covgpu_detect_candidates_batch(OptimizationT<Types>::Context(), &bt, &opts_) != COVGPU_OK) detail::fatal(covgpu_last_error());
+    for (size_t q = 0; q < Q; ++q) {
+      queries[q].candidates.clear(); queries[q].acc_score.clear();
+      queries[q].min_score = mso[q];
+      for (size_t i = 0; i < std::min((size_t)nc[q], cap); ++i) {
+        queries[q].candidates.push_back(rows[cand[q * cap + i]]);
+        queries[q].acc_score.push_back(acc[q * cap + i]);
+      }
+    }
+  }
+
+  // voc->transform(descriptors_, bow_vec_, feat_vec_, levelsup) of every keyframe in one call
+  static void ComputeBoWBatch(const BowVocabulary& voc, const KeyframeVector& kfs, int levelsup = 4) {
+    std::vector<int32_t> ptr(1, 0);
+    std::vector<uint8_t> desc;
+    for (const auto& kf : kfs) {
+      int rows = 0; const uint8_t* data = nullptr;
+      if (!detail::descriptors<Types>(*kf, 0, &rows, &data, 0)) rows = 0;
+      desc.insert(desc.end(), data, data + 32 * (size_t)rows);
+      ptr.push_back(ptr.back() + rows);
+    }
+    const size_t R = (size_t)ptr.back(), S = kfs.size();
+    std::vector<int32_t> bptr(S + 1), word(R + 1), rw(R + 1), rn(R + 1);
+    std::vector<double> value(R + 1);
+    desc.reserve(1);
+    const covgpu_bow_vocab_t v = voc.view();
+    covgpu_bow_transform_batch_t bt{};
+    bt.num_sets = (int32_t)S; bt.row_ptr = ptr.data(); bt.desc = desc.data(); bt.levelsup = levelsup; bt.capacity = (int32_t)R;
+    bt.bow_ptr = bptr.data(); bt.word = word.data(); bt.value = value.data(); bt.row_word = rw.data(); bt.row_node = rn.data();
+    if (covgpu_bow_transform_batch(OptimizationT<Types>::Context(), &v, &bt) != COVGPU_OK) detail::fatal(covgpu_last_error());
+    for (size_t s = 0; s < S; ++s) {
+      detail::set_bow<Types>(*kfs[s], (size_t)(bptr[s + 1] - bptr[s]), &word[bptr[s]], &value[bptr[s]], 0);
+      detail::set_features<Types>(*kfs[s], (size_t)(ptr[s + 1] - ptr[s]), &rw[ptr[s]], &rn[ptr[s]], 0);
+    }
+  }
+
+  // mvConsistentGroups of DetectLoop: feed one query's candidates, get mvpEnoughConsistentCandidates. Sequential state of one detector.
+  class ConsistencyFilter {
+   public:
+    explicit ConsistencyFilter(int threshold = 3, int mode = COVGPU_DETECT_COVINS) : threshold_(threshold), g_(mode == COVGPU_DETECT_COVINS_G) {}
+    KeyframeVector Feed(const KeyframeVector& candidates) {
+      KeyframeVector enough;
+      if (candidates.empty()) { groups_.clear(); return enough; }
+      std::vector<std::pair<std::set<const Keyframe*>, int>> current;
+      std::vector<bool> used(groups_.size(), false);
+      for (const auto& cand : candidates) {
+        std::set<const Keyframe*> group;
+        for (const auto& k : detail::connected_keyframes<Types>(*cand, g_, 0)) group.insert(k.get());
+        group.insert(cand.get());
+        bool is_enough = false, for_some = false;
+        for (size_t i = 0; i < groups_.size(); ++i) {
+          bool consistent = false;
+          for (const Keyframe* k : group) if (groups_[i].first.count(k)) { consistent = true; break; }
+          if (!consistent) continue;
+          for_some = true;
+          const int n = groups_[i].second + 1;
+          if (!used[i]) { current.emplace_back(group, n); used[i] = true; }
+          if (n >= threshold_ && !is_enough) { enough.push_back(cand); is_enough = true; }
+        }
+        if (!for_some) current.emplace_back(group, 0);
+      }
+      groups_ = std::move(current);
+      return enough;
+    }
+    std::vector<int> Counters() const { std::vector<int> c; for (const auto& g : groups_) c.push_back(g.second); return c; }
+   private:
+    int threshold_;
+    bool g_;
+    std::vector<std::pair<std::set<const Keyframe*>, int>> groups_;
+  };
+
+ private:
+  int mode_;
+  covgpu_detect_opts opts_;
+  KeyframeVector order_;
 };
 
 }  // namespace covins_gpu
