@@ -245,8 +245,11 @@ static void nd_graph(int K, bool vi, int nchains, const int* chain_ptr, int npai
   for (auto& a : adj) { std::sort(a.begin(), a.end()); a.erase(std::unique(a.begin(), a.end()), a.end()); }
 }
 
+static bool nd_plan_finish(const std::vector<std::vector<int>>& adj, NdHostPlan& out);
+static bool nd_amalgamate(const std::vector<std::vector<int>>& adj, NdHostPlan& out);
+
 static bool nd_plan_build_mode(int top_mode, double group_frac, int K, bool vi, const std::vector<std::vector<int>>& adj, const std::vector<int>& chain_of,
-                               int leaf_dims, NdHostPlan& out) {
+                               int leaf_dims, bool merge, NdHostPlan& out) {
   out = NdHostPlan();
   out.K = K; out.vi = vi ? 1 : 0; out.nvar = 2 * K;
   out.vnode.assign(2 * (size_t)K, -1); out.voff.assign(2 * (size_t)K, 0); out.vord.assign(2 * (size_t)K, -1);
@@ -258,11 +261,6 @@ static bool nd_plan_build_mode(int top_mode, double group_frac, int K, bool vi, 
   bld.top_mode = top_mode; bld.group_frac = group_frac;
   bld.build(all, -1);
   const int nn = out.nnodes;
-  auto is_proper_ancestor = [&](int a, int n) {  // a above n?
-    if (out.depth[a] >= out.depth[n]) return false;
-    while (out.depth[n] > out.depth[a]) n = out.parent[n];
-    return n == a;
-  };
   // ---- panel balance. The levels (node heights) run one after the other and a level costs one serial panel chain per 256
   //      columns of its WIDEST front. Where the widest fronts of a level exceed a panel boundary by little, the excess
   //      unknowns move up into the parent's front (an ancestor's separator may always take more vertices: they leave the
@@ -304,10 +302,24 @@ static bool nd_plan_build_mode(int top_mode, double group_frac, int K, bool vi, 
       levc[l] = m - 1;
     }
   }
+  if (!nd_plan_finish(adj, out)) return false;
+  // ---- amalgamation: thin levels join the level above where the cost model says it pays (nd_amalgamate)
+  return merge ? nd_amalgamate(adj, out) : true;
+}
+
+// Everything that follows from the tree (parent / child / depth / own / own_dims / vnode / vord): the fronts' borders, the batches and their padded
+// orders, the flops. Called again on every tree the amalgamation tries.
+static bool nd_plan_finish(const std::vector<std::vector<int>>& adj, NdHostPlan& out) {
+  const int nn = out.nnodes;
+  auto is_proper_ancestor = [&](int a, int n) {  // a above n?
+    if (out.depth[a] >= out.depth[n]) return false;
+    while (out.depth[n] > out.depth[a]) n = out.parent[n];
+    return n == a;
+  };
   // ---- symbolic factorisation, children before parents (a child's index is always above its parent's)
   out.strct.assign(nn, {});
   out.st_dims.assign(nn, 0);
-  std::vector<int> stamp(2 * (size_t)K, -1);
+  std::vector<int> stamp((size_t)out.nvar, -1);
   for (int n = nn - 1; n >= 0; --n) {
     std::vector<int>& st = out.strct[n];
     auto add = [&](int w) { if (stamp[w] != n) { stamp[w] = n; st.push_back(w); } };
@@ -336,6 +348,7 @@ static bool nd_plan_build_mode(int top_mode, double group_frac, int K, bool vi, 
   out.lev_nodes.assign(out.nlev, {});
   for (int n = 0; n < nn; ++n) { out.slot[n] = (int)out.lev_nodes[out.level[n]].size(); out.lev_nodes[out.level[n]].push_back(n); }
   out.lev_nI.assign(out.nlev, 0); out.lev_nO.assign(out.nlev, 0); out.lev_ntot.assign(out.nlev, 0);
+  out.front_elems = 0; out.flops = 0;
   for (int l = 0; l < out.nlev; ++l) {
     int mo = 0, ms = 0;
     for (int n : out.lev_nodes[l]) { mo = std::max(mo, out.own_dims[n]); ms = std::max(ms, out.st_dims[n]); }
@@ -351,16 +364,139 @@ static bool nd_plan_build_mode(int top_mode, double group_frac, int K, bool vi, 
   return true;
 }
 
-// What one factorisation of the plan costs on the device, roughly (round 5 figures of one MI355X): the levels run one after the other, a level
-// costs one serial chain of ~140 us per 256 columns of its widest front plus ~40 us of transition, and the flops run at ~30 TFLOP/s beside them.
-static double nd_plan_cost(const NdHostPlan& hp) {
-  double t = hp.flops / 30e12;
-  for (int l = 0; l < hp.nlev; ++l) t += (hp.lev_nI[l] / 256) * 140e-6 + 40e-6;
+// ---- the cost model: what one factorisation of a plan costs on one MI355X, roughly: the serial chain of the levels (nd_chain_cost) plus the plan's
+// flops at kFlopRate. Refitted on the round-6 kernels from one COVGPU_TRACE_PANELS=1 run each of the 5-agent map, mh01 and the 12-agent map
+// (profiles/r07_merge_parent_marks_{mh12345,mh01,a12}.txt; the duration of every level, from the end of the level below to its own end, against the
+// plan's figures of that level):
+//   kFlopRate: the five top levels of the 12-agent map hold 94 % of its flops and run at 38 .. 45 TFLOP/s each (1.107e12 flops in 27.9 ms), its root,
+//     31 serial panels, at 29: 40 TFLOP/s. Round 5 assumed 30.
+//   the chain's constants: non-negative least squares over the 15 levels of the two latency-bound maps, flops at kFlopRate taken out first: 34 us per
+//     level, 45 us per panel of a level whose fronts have a border and 49 us per panel of a root level (the fit does not tell the two apart), and
+//     0.155 us per real column of the widest front in the panel — 85 / 89 us for a full panel. Residual 24 us rms per level; totals 2.50 ms modelled
+//     against 2.60 measured (5-agent map), 0.80 against 0.71 (mh01), 35.8 against 34.0 (12-agent map, which the fit of the chain never saw).
+//     Round 5's figures were 140 us per panel of 256 columns whatever it held, and 40 us per level.
+//   What the model leaves out: a level of one panel waits for the substitution and update of its border rows, which grow with the border and the
+//     number of fronts (5-agent map 128 .. 152 us measured against 103 .. 139 modelled; mh01 85 .. 96 against 96 .. 111), and a batch of more fronts
+//     than the device has compute units runs in rounds (bottom levels of the 12-agent map: twice the model).
+constexpr double kLevelS = 34e-6, kPanelBorderS = 45e-6, kPanelRootS = 49e-6, kPanelColS = 0.155e-6, kFlopRate = 40e12;
+// A merge is kept if it lowers the modelled cost by more than this. Two runs of one plan differ by up to 10 us in the duration of a level (the two
+// lines of each marks file): a modelled gain below twice that could not be told from no gain by the marks that the model was fitted on.
+// The model against the marks of the merged trees, which the fit never saw (profiles/r07_merge_marks_*): 5-agent map 2.41 ms modelled | 2.41 measured
+// (24 us rms per level), mh01 0.78 | 0.71. The modelled GAIN of merging is less sure than that: 5-agent map 97 us modelled against 184 measured (the
+// model charges the added flops in full although they run beside the chain, and underrates the one-panel levels of that map), mh01 26 us against 2
+// (it overrates that map's one-panel levels: 85 .. 96 us measured, 96 .. 111 modelled) — mh01's merge is a draw on the device (§5 of DESIGN.md), and
+// no margin separates the two maps in the right order: 35 us already costs the 5-agent map one of its two merges (50 us too, 70 us both) and leaves
+// mh01 merged on another leaf size. What the model lacks for that is a term for a level's last panel, whose border update the chain waits for.
+constexpr double kMergeMarginS = 20e-6;
+
+// The serial part: the levels run one after the other, and a level is a transition (extend-add on the chain's stream) plus one panel step per 256
+// columns of its WIDEST front; a panel step is paid by the real columns of that front in the panel (sixteen-column pivot steps) on top of a fixed
+// part, which is larger where the fronts carry a border (substitution and update of the border rows wait for the panel). Shared by nd_plan_cost and
+// nd_shard_cost.
+static double nd_level_cost(int widest_own, bool bordered) {
+  double t = kLevelS;
+  for (int c = 0; c < std::max(widest_own, 1); c += 256) t += (bordered ? kPanelBorderS : kPanelRootS) + kPanelColS * std::min(256, std::max(widest_own, 1) - c);
+  return t;
+}
+static double nd_front_flops(double m, double b) { return m * m * m / 3.0 + m * m * b + m * b * b; }
+static double nd_chain_cost(const NdHostPlan& hp) {
+  double t = 0.0;
+  for (int l = 0; l < hp.nlev; ++l) {
+    int mo = 1;
+    for (int n : hp.lev_nodes[l]) mo = std::max(mo, hp.own_dims[n]);
+    t += nd_level_cost(mo, hp.lev_nO[l] > 0);
+  }
+  return t;
+}
+static double nd_plan_cost(const NdHostPlan& hp) { return hp.flops / kFlopRate + nd_chain_cost(hp); }
+
+// COVGPU_ND_MERGE=0: no amalgamation, the trees of round 6
+bool nd_merge_enabled() {
+  const char* e = getenv("COVGPU_ND_MERGE");
+  return e == nullptr || atoi(e) != 0;
+}
+
+// Supernode amalgamation, a whole level at a time: every node of height l whose parent has height l + 1 joins that parent. The node's own variables
+// go in front of the parent's own (several children: in index order), its children become the parent's. Every node of height l + 1 has such a child,
+// so all of them come down to height l and the tree loses exactly one level. The merged front is [children's own | parent's own | parent's border]:
+// a child's border lies inside the parent's front, so no front elsewhere changes its set of variables. Nodes are renumbered by dropping the merged
+// ones: a re-attached grandchild's index was above its parent's, which was above the new parent's. Only the tree is rebuilt here (nd_plan_finish).
+static void nd_merge_level(NdHostPlan& out, int l) {
+  const int nn = out.nnodes;
+  std::vector<int> hgt(nn, 0), id(nn, -1);
+  for (int n = nn - 1; n >= 0; --n) for (int c : out.child[n]) hgt[n] = std::max(hgt[n], hgt[c] + 1);
+  std::vector<std::vector<int>> front(nn);
+  int kept = 0;
+  for (int n = 0; n < nn; ++n) {
+    const int p = out.parent[n];
+    if (hgt[n] == l && p >= 0 && hgt[p] == l + 1) front[p].insert(front[p].end(), out.own[n].begin(), out.own[n].end());
+    else id[n] = kept++;
+  }
+  NdHostPlan t;
+  t.K = out.K; t.vi = out.vi; t.nvar = out.nvar; t.nnodes = kept;
+  t.vnode.assign(out.vnode.size(), -1); t.voff.assign(out.voff.size(), 0); t.vord.assign(out.vord.size(), -1);
+  t.parent.resize(kept); t.depth.resize(kept); t.own.resize(kept); t.own_dims.resize(kept); t.child.assign(kept, {});
+  for (int n = 0; n < nn; ++n) {
+    if (id[n] < 0) continue;
+    const int m = id[n];
+    int p = out.parent[n];
+    if (p >= 0 && id[p] < 0) p = out.parent[p];   // (a merged node's parent has height l + 1: it stays)
+    t.parent[m] = p < 0 ? -1 : id[p];
+    t.depth[m] = p < 0 ? 0 : t.depth[id[p]] + 1;
+    if (p >= 0) t.child[id[p]].push_back(m);
+    t.own[m].swap(front[n]);
+    t.own[m].insert(t.own[m].end(), out.own[n].begin(), out.own[n].end());
+    int off = 0, ord = 0;
+    for (int v : t.own[m]) { t.vnode[v] = m; t.voff[v] = off; t.vord[v] = ord++; off += NdHostPlan::vdim(v); }
+    t.own_dims[m] = off;
+  }
+  out = std::move(t);
+}
+
+// nd_plan_cost of the tree that nd_merge_level(hp, l) would give, from the finished plan alone: a merged front has the own columns of the parent and of
+// its merged children and the parent's border, no other front changes, and a node of height h > l comes down to h - 1. No symbolic factorisation: a
+// trial is one pass over the nodes, so that planning stays near its old cost (the twelve candidates try every level in every round).
+static double nd_merge_trial_cost(const NdHostPlan& hp, int l) {
+  const int nn = hp.nnodes;
+  std::vector<int> add(nn, 0), mo(hp.nlev - 1, 1);
+  std::vector<char> merged(nn, 0), bordered(hp.nlev - 1, 0);
+  double flops = hp.flops;
+  for (int n = 0; n < nn; ++n) {
+    const int p = hp.parent[n];
+    if (hp.level[n] != l || p < 0 || hp.level[p] != l + 1) continue;
+    merged[n] = 1; add[p] += hp.own_dims[n];
+    flops -= nd_front_flops(hp.own_dims[n], hp.st_dims[n]);
+  }
+  for (int n = 0; n < nn; ++n) {
+    if (merged[n]) continue;
+    if (add[n]) flops += nd_front_flops(hp.own_dims[n] + add[n], hp.st_dims[n]) - nd_front_flops(hp.own_dims[n], hp.st_dims[n]);
+    const int h = hp.level[n] > l ? hp.level[n] - 1 : hp.level[n];
+    mo[h] = std::max(mo[h], hp.own_dims[n] + add[n]);
+    if (hp.st_dims[n] > 0) bordered[h] = 1;
+  }
+  double t = flops / kFlopRate;
+  for (int h = 0; h + 1 < hp.nlev; ++h) t += nd_level_cost(mo[h], bordered[h] != 0);
   return t;
 }
 
+// Greedy: of all levels, the merge that lowers nd_plan_cost most is kept if it lowers it by more than kMergeMarginS; repeated until none does.
+// Ties go to the lower level: deterministic, as every rank of a sharded solve must build the same plan. Only a kept merge rebuilds the tree.
+static bool nd_amalgamate(const std::vector<std::vector<int>>& adj, NdHostPlan& out) {
+  for (;;) {
+    double best_cost = nd_plan_cost(out) - kMergeMarginS;
+    int best = -1;
+    for (int l = 0; l + 1 < out.nlev; ++l) {
+      const double c = nd_merge_trial_cost(out, l);
+      if (c < best_cost) { best_cost = c; best = l; }
+    }
+    if (best < 0) return true;
+    nd_merge_level(out, best);
+    if (!nd_plan_finish(adj, out)) return false;
+  }
+}
+
 bool nd_plan_build(int K, bool vi, int nchains, const int* chain_ptr, int npairs, const int* pair_i, const int* pair_j, int nepairs,
-                   const int* epair_i, const int* epair_j, int leaf_dims, NdHostPlan& out, int top_mode) {
+                   const int* epair_i, const int* epair_j, int leaf_dims, NdHostPlan& out, int top_mode, bool allow_merge) {
   // Candidates: (how a region of three or more agents is cut) x (the order below which a region is not cut further). All are built — the coupling
   // graph once, the trees in host threads, milliseconds each — and the cheapest by nd_plan_cost is kept (ties: the first in the fixed order below).
   //   top: ONE cover of all cross-agent couplings (0) | two groups of agents, recursively (1). 5-agent map: 2.84e10 flops / 23 serial panels /
@@ -380,6 +516,12 @@ bool nd_plan_build(int K, bool vi, int nchains, const int* chain_ptr, int npairs
   nd_graph(K, vi, nchains, chain_ptr, npairs, pair_i, pair_j, nepairs, epair_i, epair_j, adj, chain_of);
   int forced = top_mode;
   if (const char* e = getenv("COVGPU_ND_TOP")) forced = atoi(e) != 0 ? 1 : 0;
+  // Amalgamation (nd_amalgamate) where the caller left the tree to the planner: every default candidate is merged before the candidates are compared, so
+  // the choice of the leaf size sees the merged trees. A forced leaf size keeps its tree, and so does a caller that passes the cut of the agents as an
+  // argument — covgpu_shard_plan: the tree of a shard plan is reproduced on one GPU by forcing its cut and leaf size, and must be that tree (the
+  // COVGPU_ND_TOP switch alone does not stop the merge). allow_merge = false: the pose graph, whose 6-dof fronts the model was never fitted on.
+  // COVGPU_ND_MERGE=0: never.
+  const bool merge = allow_merge && leaf_dims <= 0 && top_mode < 0 && nd_merge_enabled();
   std::vector<int> modes, leaves;
   if (nchains < 3 || forced == 0 || leaf_dims >= (1 << 29)) modes = {0};
   else if (forced == 1) modes = {1};
@@ -400,7 +542,7 @@ bool nd_plan_build(int K, bool vi, int nchains, const int* chain_ptr, int npairs
   //  created leave their candidates to the calling thread)
   auto run = [&](size_t i) {
     try {
-      cand[i].ok = nd_plan_build_mode(cand[i].mode, cand[i].frac, K, vi, adj, chain_of, cand[i].leaf, cand[i].hp);
+      cand[i].ok = nd_plan_build_mode(cand[i].mode, cand[i].frac, K, vi, adj, chain_of, cand[i].leaf, merge, cand[i].hp);
       if (cand[i].ok) cand[i].cost = nd_plan_cost(cand[i].hp);
     } catch (...) { cand[i].ok = false; }
   };
@@ -425,15 +567,14 @@ bool nd_plan_build(int K, bool vi, int nchains, const int* chain_ptr, int npairs
 
 double nd_shard_cost(const NdHostPlan& hp, int world) {
   const int nn = hp.nnodes;
-  double chain = 0.0;
-  for (int l = 0; l < hp.nlev; ++l) chain += (hp.lev_nI[l] / 256) * 140e-6 + 40e-6;
+  const double chain = nd_chain_cost(hp);
   if (hp.shard_policy == 1) {
     NdShardAcct a;
     nd_shard_account(hp, world, a);
     double busiest = 0.0;
     for (double f : a.rank_fl) busiest = std::max(busiest, f);
     constexpr double kCollLatency = 30e-6;   // ASSUMED per small all-reduce (not measured on xGMI)
-    return busiest / 30e12 + chain + (world > 1 ? 2.0 * (world - 1) / world * a.bytes / 150e9 + a.collectives * kCollLatency : 0.0);
+    return busiest / kFlopRate + chain + (world > 1 ? 2.0 * (world - 1) / world * a.bytes / 150e9 + a.collectives * kCollLatency : 0.0);
   }
   double top_fl = 0.0, exch = 0.0;
   std::vector<double> rank_fl(std::max(world, 1), 0.0);
@@ -444,7 +585,7 @@ double nd_shard_cost(const NdHostPlan& hp, int world) {
   }
   double busiest = 0.0;
   for (double f : rank_fl) busiest = std::max(busiest, f);
-  return (top_fl + busiest) / 30e12 + chain + (world > 1 ? 2.0 * (world - 1) / world * exch / 150e9 : 0.0);
+  return (top_fl + busiest) / kFlopRate + chain + (world > 1 ? 2.0 * (world - 1) / world * exch / 150e9 : 0.0);
 }
 
 // The top grows from `top` (an ancestor-closed set: the roots, or policy 1's seed) downwards, heaviest subtree first, until there are at least

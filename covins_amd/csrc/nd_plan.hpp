@@ -38,7 +38,10 @@ struct NdHostPlan {
 // positions are chain-major (solver.hip build_chains); pair / epair lists are keyframe pairs by position (i > j).
 // leaf_dims: a region of at most this many scalar unknowns is not cut further. Returns false on an inconsistent input.
 bool nd_plan_build(int K, bool vi, int nchains, const int* chain_ptr, int npairs, const int* pair_i, const int* pair_j, int nepairs,
-                   const int* epair_i, const int* epair_j, int leaf_dims, NdHostPlan& out, int top_mode = -1);
+                   const int* epair_i, const int* epair_j, int leaf_dims, NdHostPlan& out, int top_mode = -1, bool allow_merge = true);
+// allow_merge: thin levels may be merged into the level above (nd_plan.hip: nd_amalgamate) where leaf_dims <= 0 and top_mode < 0; false: never.
+// COVGPU_ND_MERGE (default 1; 0: the tree without amalgamation) as nd_plan_build reads it on every call
+bool nd_merge_enabled();
 // top_mode: how a region of three or more agents is cut — 0: ONE cover of all cross-agent couplings (its children: one region per agent;
 // the plan of a sharded solve) | 1: two groups of agents, recursively | -1: both are built and the cheaper one is kept (nd_plan.hip).
 
@@ -55,9 +58,10 @@ void nd_shard_assign_dist(NdHostPlan& hp, int world, double top_cap_bytes = 48.0
 // policy 1: the rank that applies the trailing update to tile row q of a top front (q counts the front's real interior tiles, then its border
 // tiles: 128 rows each) — deterministic from the plan; the node id staggers the rows of small fronts over the ranks
 inline int nd_tile_owner(int node, int q, int world) { return world > 0 ? (q + node) % world : 0; }
-// what one factorisation costs a rank of a sharded solve, roughly: the busiest rank's flops (nd_shard_account) at 30 TFLOP/s, the serial panel chains
-// of every level, and the ring all-reduces at 150 GB/s per link — policy 1 adds an ASSUMED 30 us per collective (one per panel of the top; nobody has
-// measured a small all-reduce on xGMI). Compares candidate shard plans (covgpu_shard_plan).
+// what one factorisation costs a rank of a sharded solve, roughly: the busiest rank's flops (nd_shard_account) at the rate of nd_plan.hip's cost model, the
+// serial panel chains of every level by that model's chain formula (shared with the single-GPU choice of the tree), and the ring all-reduces at 150 GB/s
+// per link — policy 1 adds an ASSUMED 30 us per collective (one per panel of the top; nobody has measured a small all-reduce on xGMI). Compares
+// candidate shard plans (covgpu_shard_plan).
 double nd_shard_cost(const NdHostPlan& hp, int world);
 // host accounting of a shard plan under its policy (covgpu_nd_plan_rank_flops / covgpu_nd_plan_exchange): flops of one factorisation per rank,
 // bytes all-reduced per linear solve and rank, collectives per linear solve. Sizes are the real (unpadded) front orders.

@@ -48,6 +48,7 @@ struct covgpu_profile_t {
 struct PlanCache {
   bool valid = false; int K = 0; bool vi = false; int leaf = 0;
   int top_env = -1; double frac_env = 0.0;   // COVGPU_ND_TOP / COVGPU_ND_GROUP_FRAC as nd_plan_build read them (-1 / 0: not set)
+  bool merge_env = true;                     // COVGPU_ND_MERGE likewise (nd_merge_enabled), and false for a pose graph
   std::vector<int> chain_ptr, pos_kf;
   std::vector<uint64_t> keys;   // sorted (position i << 32 | position j) of every covisible / loop-edge pair
   NdHostPlan hp;
@@ -625,7 +626,7 @@ extern "C" int covgpu_nd_plan_create_pgo(const covgpu_options* opt, const covgpu
     for (size_t q = 0; q < keys.size(); ++q) { ei[q] = (int)(keys[q] >> 32); ej[q] = (int)(keys[q] & 0xffffffffull); }
     covgpu_nd_plan* pl = new covgpu_nd_plan();
     pl->pos_kf = pos_kf;
-    if (!nd_plan_build(p->num_kf, false, (int)chain_ptr.size() - 1, chain_ptr.data(), 0, nullptr, nullptr, (int)ei.size(), ei.data(), ej.data(), nd_leaf_dims(leaf_dims), pl->hp, -1)) {
+    if (!nd_plan_build(p->num_kf, false, (int)chain_ptr.size() - 1, chain_ptr.data(), 0, nullptr, nullptr, (int)ei.size(), ei.data(), ej.data(), nd_leaf_dims(leaf_dims), pl->hp, -1, false)) {
       delete pl; g_err = "nested-dissection plan: a coupling joins two branches"; return (int)COVGPU_ERR_INVALID_ARG;
     }
     *out = pl;
@@ -645,7 +646,7 @@ extern "C" void covgpu_nd_plan_info(const covgpu_nd_plan* pl, int64_t* out) {
     if (h.parent[n] < 0) out[9] = std::max<int64_t>(out[9], h.own_dims[n]);
   }
   out[5] = (int64_t)h.front_elems; out[6] = (int64_t)h.flops;
-  out[10] = h.top_mode; out[11] = h.leaf; out[12] = h.group_frac100;   // which candidate tree (nd_plan_build): COVGPU_ND_TOP / COVGPU_ND_LEAF / COVGPU_ND_GROUP_FRAC (= out[12] / 100) reproduce it
+  out[10] = h.top_mode; out[11] = h.leaf; out[12] = h.group_frac100;   // which candidate tree (nd_plan_build): COVGPU_ND_TOP / COVGPU_ND_LEAF / COVGPU_ND_GROUP_FRAC (= out[12] / 100) reproduce it before the amalgamation: a shard plan and every plan with a forced leaf size exactly, a merged default plan not (a forced leaf size is never merged)
   out[13] = h.shard_policy;                                               // shard plans: 0 replicated top | 1 distributed top
 }
 extern "C" int32_t covgpu_nd_plan_rank_flops(const covgpu_nd_plan* pl, double* out) {
@@ -689,7 +690,7 @@ extern "C" int32_t covgpu_shard_plan(const covgpu_options* opt, const covgpu_pro
   if (world < 1) return 0;
   // Candidates (round 5): the tree with ONE separator of all agents at the top (its children, one region per agent, are the subtrees) and the tree with two
   // groups of agents at the top, each with the replicated top capped at 48 MiB (round 4's cap) and at 512 MiB of fronts; the cheapest by nd_shard_cost —
-  // (replicated top + busiest rank's subtrees) at 30 TFLOP/s + the panel chains + the ring all-reduce of the top — is kept. On the corrected 5-agent map the
+  // (replicated top + busiest rank's subtrees) at the flop rate of nd_plan.hip's cost model + the panel chains by its chain formula + the ring all-reduce of the top — is kept. On the corrected 5-agent map the
   // one-separator top is 3 726 unknowns = 61 % of the flops on every rank; the two-groups tree gives two ranks a 1 968-order top (10 %) and, with its two
   // second-level separators opened, four ranks a top of 45 %. COVGPU_SHARD_TREE = 0 / 1 forces the tree, COVGPU_SHARD_CAP_MIB the cap. Deterministic.
   // shard policy (options, COVGPU_SHARD_POLICY overrides for A/B runs): 0 the top replicated and all-reduced whole | 1 the top distributed — its fronts
@@ -1012,14 +1013,15 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
         const char *e_top = getenv("COVGPU_ND_TOP"), *e_frac = getenv("COVGPU_ND_GROUP_FRAC");
         const int top_env = e_top ? (atoi(e_top) != 0 ? 1 : 0) : -1;
         const double frac_env = e_frac ? std::max(2.0, atof(e_frac)) : 0.0;
-        const bool hit = pc.valid && pc.K == P.K && pc.vi == vi && pc.leaf == leaf && pc.top_env == top_env && pc.frac_env == frac_env && pc.chain_ptr == chain_ptr && pc.pos_kf == pos_kf &&
+        const bool merge_env = nd_merge_enabled() && !pgo;   // (the pose graph is never merged)
+        const bool hit = pc.valid && pc.K == P.K && pc.vi == vi && pc.leaf == leaf && pc.top_env == top_env && pc.frac_env == frac_env && pc.merge_env == merge_env && pc.chain_ptr == chain_ptr && pc.pos_kf == pos_kf &&
                          std::includes(pc.keys.begin(), pc.keys.end(), keys.begin(), keys.end());
         if (hit) nhp = pc.hp;
         else {
-          if (!nd_plan_build(P.K, vi, P.nchains, chain_ptr.data(), (int)h_pair_i.size(), h_pair_i.data(), h_pair_j.data(), P.nepairs, ei.data(), ej.data(), leaf, nhp)) {
+          if (!nd_plan_build(P.K, vi, P.nchains, chain_ptr.data(), (int)h_pair_i.size(), h_pair_i.data(), h_pair_j.data(), P.nepairs, ei.data(), ej.data(), leaf, nhp, -1, !pgo)) {
             g_err = "nested-dissection plan: a coupling joins two branches"; return COVGPU_ERR_INVALID_ARG;
           }
-          pc.valid = true; pc.K = P.K; pc.vi = vi; pc.leaf = leaf; pc.top_env = top_env; pc.frac_env = frac_env; pc.chain_ptr = chain_ptr; pc.pos_kf = pos_kf; pc.keys.swap(keys); pc.hp = nhp;
+          pc.valid = true; pc.K = P.K; pc.vi = vi; pc.leaf = leaf; pc.top_env = top_env; pc.frac_env = frac_env; pc.merge_env = merge_env; pc.chain_ptr = chain_ptr; pc.pos_kf = pos_kf; pc.keys.swap(keys); pc.hp = nhp;
         }
       }
       if (nhp.maxdepth > 64) { g_err = "nested-dissection plan: tree deeper than 64 levels"; return COVGPU_ERR_INVALID_ARG; }
