@@ -72,6 +72,12 @@ def pgo_partition(num_kf: int, edge_i, edge_j):
     return out, int(n)
 
 
+def lm_group(num_obs: int, num_lm: int) -> int:
+    """Host-only: lanes per landmark (4 | 8 | 16) the landmark-major kernels take for O observations on L landmarks (covgpu_lm_group:
+    the rule of the upload)."""
+    return int(lib().covgpu_lm_group(int(num_obs), int(num_lm)))
+
+
 def kernel_form_names():
     """Names of the kernel forms Context.kernel_forms() counts, in the library's order."""
     n = lib().covgpu_get_kernel_forms(None, None, 0)

@@ -306,6 +306,7 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("schur", [C.c_void_p, OP, PP, C.c_double, _dp, _dp, _dp])
         d("solve_reduced", [C.c_void_p, C.c_int32, _dp, _dp, _dp])
         d("pgo_partition", [C.c_int32, C.c_int32, _ip, _ip, _ip], C.c_int32)
+        d("lm_group", [C.c_int64, C.c_int32], C.c_int32)
         d("gn_step", [C.c_void_p, OP, PP, C.c_double, _dp, _dp, _dp])
         d("relpose_batch", [C.c_void_p, C.POINTER(RelposeBatch), C.c_double, C.c_int32])
         d("default_ransac_opts", [C.POINTER(RansacOpts)], None)

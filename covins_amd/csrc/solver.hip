@@ -308,6 +308,13 @@ extern "C" int32_t covgpu_reduced_dim(const covgpu_options* opt, const covgpu_pr
   return (opt->visual_only ? 6 : 15) * p->num_kf;
 }
 
+// lanes per landmark of the landmark-major kernels (k_visual.hip: k_lm_lin, k_lm_backsub, k_lm_outliers) from the mean track length O/L:
+// configs[4] (4.1): linearise+Schur 4.65 ms at 16 lanes, 4.24 at 8, 4.11 at 4; 5-agent map (10.0): 16 and 8 alike
+extern "C" int32_t covgpu_lm_group(int64_t num_obs, int32_t num_lm) {
+  const double mean_track = num_lm > 0 ? (double)num_obs / num_lm : 0.0;
+  return mean_track <= 5.0 ? 4 : (mean_track <= 8.0 ? 8 : 16);
+}
+
 extern "C" int32_t covgpu_pgo_partition(int32_t num_kf, int32_t num_edge, const int32_t* edge_i, const int32_t* edge_j, int32_t* block_of_kf) {
   for (int k = 0; k < num_kf; ++k) block_of_kf[k] = -1;
   for (int e = 0; e < num_edge; ++e)
@@ -792,10 +799,7 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
   P.I = vi ? p->num_imu : 0; P.E = p->num_edge;
   P.S = P.I ? p->imu_sample_ptr[P.I] : 0;
   P.vi = vi; P.D = vi ? 15 : 6; P.n = P.D * P.K;
-  {  // lanes per landmark of the landmark-major kernels, from the mean track length
-    const double mean_track = P.L > 0 ? (double)P.O / P.L : 0.0;
-    P.lm_group = mean_track <= 5.0 ? 4 : (mean_track <= 8.0 ? 8 : 16);   // configs[4] (4.1): linearise+Schur 4.65 ms at 16 lanes, 4.24 at 8, 4.11 at 4; 5-agent map (10.0): 16 and 8 alike
-  }
+  P.lm_group = covgpu_lm_group(P.O, P.L);   // lanes per landmark of the landmark-major kernels, from the mean track length
   P.npad = ((6 * P.K + kTile - 1) / kTile) * kTile;  // dense stage = pose-pose system only (k_struct.hip)
   P.N = P.n + 3 * P.L;
   // IMU chains -> chain-major keyframe order

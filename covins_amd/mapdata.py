@@ -105,8 +105,14 @@ class SlamMap:
     def erase_observations(self, obs_mask: np.ndarray) -> None:
         """kf->EraseLandmark + lm->EraseObservation for every flagged observation (opt_be.cpp:285-286)."""
         keep = ~obs_mask
-        counts = np.add.reduceat(keep.astype(np.int64), self.lm_obs_ptr[:-1]) if self.O else np.zeros(self.L, np.int64)
-        counts[np.diff(self.lm_obs_ptr) == 0] = 0
+        n = np.diff(self.lm_obs_ptr)
+        if self.O and n.min() > 0:
+            counts = np.add.reduceat(keep.astype(np.int64), self.lm_obs_ptr[:-1])
+        else:   # landmarks without observations: reduceat takes no empty segment, and none that starts at O (trailing landmarks an earlier call emptied)
+            counts = np.zeros(self.L, np.int64)
+            ne = np.flatnonzero(n > 0)
+            if len(ne):
+                counts[ne] = np.add.reduceat(keep.astype(np.int64), self.lm_obs_ptr[ne])
         rows = np.flatnonzero(keep)   # (one index list, three takes: a boolean mask is re-scanned by every indexing)
         self.obs_kf, self.obs_uv, self.obs_octave = self.obs_kf.take(rows), self.obs_uv.take(rows, axis=0), self.obs_octave.take(rows)
         self.lm_obs_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)

@@ -315,6 +315,11 @@ int covgpu_solve_reduced(covgpu_context* ctx, int32_t n, const double* S, const 
 
 int32_t covgpu_reduced_dim(const covgpu_options* opt, const covgpu_problem* p);
 
+/* Host-only: lanes per landmark (4 | 8 | 16) of the landmark-major kernels k_lm_lin, k_lm_backsub and k_lm_outliers for a problem of
+ * num_obs observations on num_lm landmarks — the rule covgpu_upload applies: mean track length O/L <= 5 -> 4, <= 8 -> 8, else 16
+ * (no landmarks: 4). DESIGN.md 4.1. */
+int32_t covgpu_lm_group(int64_t num_obs, int32_t num_lm);
+
 /* Host-only: the block partition of round 2's block-arrow pose-graph solve (PoseGraphOptimization's linear solver,
  * optimization_be.cpp:1024-1031; since round 6 the default is the multifrontal solve on the pose graph's own elimination
  * tree — DESIGN.md 4.8 — and this scheme runs with COVGPU_PGO_ND=0). block_of_kf[k] = block index (>= 0) of

@@ -166,3 +166,38 @@ def test_kernel_form_names_match_header():
     out = (C.c_int64 * len(names))()
     assert backend.lib().covgpu_get_kernel_forms(None, out, len(names)) == len(names) and not any(out)   # (no context: zeros)
     assert backend.lib().covgpu_kernel_form_name(len(names)) is None and backend.lib().covgpu_kernel_form_name(-1) is None
+
+
+def test_lm_group_boundaries():
+    """covgpu_lm_group, the rule the upload applies: lanes per landmark of k_lm_lin / k_lm_backsub / k_lm_outliers from the mean track length O/L —
+    both bounds belong to the narrower form, and a problem without landmarks does not divide."""
+    g = backend.lm_group
+    assert g(50, 10) == 4 and g(5, 1) == 4 and g(2, 1) == 4                    # O/L = 5.0 exactly (and below)
+    assert g(51, 10) == 8 and g(5 * 10**6 + 1, 10**6) == 8                     # just above 5
+    assert g(80, 10) == 8 and g(8, 1) == 8                                     # O/L = 8.0 exactly
+    assert g(81, 10) == 16 and g(8 * 10**6 + 1, 10**6) == 16 and g(10**9, 1) == 16   # just above 8
+    assert g(3 * 10**9, 10**9) == 4 and g(6 * 10**9, 10**9) == 8               # O beyond 2^31: the count is 64-bit
+    assert g(0, 0) == 4 and g(7, 0) == 4 and g(0, 5) == 4                      # L = 0: no division
+    assert backend.lib().covgpu_lm_group.restype is C.c_int32
+
+
+def test_erase_observations_with_landmarks_already_empty(tiny_map):
+    """Map.erase_observations on a map some of whose landmarks have no observation left — in the middle and at the END of the landmark list (an
+    earlier outlier round emptied them; the last one's segment starts at O): counts per landmark as by definition."""
+    m = tiny_map.copy()
+    n = np.diff(m.lm_obs_ptr)
+    lm_of = np.repeat(np.arange(m.L), n)
+    m.erase_observations(np.isin(lm_of, [3, m.L - 2, m.L - 1]))
+    n1 = np.diff(m.lm_obs_ptr)
+    assert n1[3] == n1[-2] == n1[-1] == 0 and m.lm_obs_ptr[-2] == m.O and np.array_equal(np.delete(n1, [3, m.L - 2, m.L - 1]), np.delete(n, [3, m.L - 2, m.L - 1]))
+    lm_of = np.repeat(np.arange(m.L), n1)
+    rng = np.random.default_rng(0)
+    mask = rng.random(m.O) < 0.3
+    mask[-1] = True; mask[m.lm_obs_ptr[4]] = True          # (the neighbours of the empty ones lose one each)
+    kf, uv = m.obs_kf.copy(), m.obs_uv.copy()
+    m.erase_observations(mask)
+    assert np.array_equal(np.diff(m.lm_obs_ptr), np.bincount(lm_of[~mask], minlength=m.L)) and m.lm_obs_ptr[-1] == m.O == (~mask).sum()
+    assert np.array_equal(m.obs_kf, kf[~mask]) and np.array_equal(m.obs_uv, uv[~mask])
+    m.erase_observations(np.ones(m.O, bool))               # ... down to a map without observations, and once more on that
+    m.erase_observations(np.zeros(0, bool))
+    assert m.O == 0 and not np.diff(m.lm_obs_ptr).any()
