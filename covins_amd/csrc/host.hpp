@@ -1,0 +1,122 @@
+// host.hpp — what the host files of libcovgpu (solver.hip, batch.hip) share: the context, the error plumbing of the extern "C"
+// entry points and the per-call device scratch. Host-only: no kernel file includes it.
+#pragma once
+#include <atomic>
+#include <memory>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "common.hpp"
+#include "nd_plan.hpp"
+
+// message of the calling thread's last failed call (covgpu_last_error); the one definition is in solver.hip
+__attribute__((visibility("hidden"))) extern thread_local std::string g_err;
+
+#define HIPCHK(expr)                                                                            \
+  do {                                                                                          \
+    hipError_t e_ = (expr);                                                                     \
+    if (e_ != hipSuccess) {                                                                     \
+      g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                                \
+      return e_ == hipErrorOutOfMemory ? COVGPU_ERR_OUT_OF_MEMORY : COVGPU_ERR_NO_DEVICE;       \
+    }                                                                                           \
+  } while (0)
+
+struct covgpu_profile_t {
+  double t_build_ms = 0, t_factor_ms = 0, t_syrk_ms = 0, syrk_flops = 0;
+  long n_build = 0, n_factor = 0, n_syrk = 0;
+};
+
+// elimination tree of the last single-GPU GBA upload and what it was built for (upload_impl)
+struct PlanCache {
+  bool valid = false; int K = 0; bool vi = false; int leaf = 0;
+  int top_env = -1; double frac_env = 0.0;   // COVGPU_ND_TOP / COVGPU_ND_GROUP_FRAC as nd_plan_build read them (-1 / 0: not set)
+  bool merge_env = true;                     // COVGPU_ND_MERGE likewise (nd_merge_enabled), and false for a pose graph
+  std::vector<int> chain_ptr, pos_kf;
+  std::vector<uint64_t> keys;   // sorted (position i << 32 | position j) of every covisible / loop-edge pair
+  covgpu::NdHostPlan hp;
+};
+
+constexpr int COVGPU_ERR_GATE_TIMEOUT = -1000;   // internal (solve_any): never returned through the C ABI
+struct covgpu_group;
+struct covgpu_context {
+  int device = 0;
+  hipStream_t st = nullptr;
+  covgpu::DevProblem P;
+  bool have = false, pgo = false;
+  std::vector<void*> allocs;
+  size_t alloc_bytes = 0;  // device bytes behind `allocs` (the footprint covgpu_get_layout reports)
+  double* h_scal = nullptr;  // pinned mirror of P.scal + flag
+  double* h_tr = nullptr;    // pinned mirror of P.tr (device-side trust region)
+  double* h_box = nullptr;   // pinned + mapped [TR_COUNT + 1]: the last kernel of an iteration posts P.tr and a sequence number here (k_tr_accept), the host polls it
+  double* d_box = nullptr;   // its device address (nullptr: not available — D2H copy + stream synchronisation)
+  double box_seq = 0.0;
+  int profiling = 0;
+  covgpu_profile_t prof;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  covgpu::CholAux chol;
+  covgpu::PgoPlan pgo_plan;  // block-arrow pose-graph solve (k_pgo.hip)
+  PlanCache plan_cache;  // elimination tree of the previous single-GPU GBA upload (reused when the new problem's couplings are a subset)
+  covgpu::NdDev nd;          // multifrontal GBA solve (k_front.hip)
+  // agent-sharded solve: the global plan (variables as 2 * IR keyframe + kind, node -> rank), this rank's
+  // identity and its collective
+  bool sharded = false;
+  int rank = 0, world = 1;
+  std::shared_ptr<covgpu::NdHostPlan> shard_plan;
+  struct Reducer* reducer = nullptr;
+  double* d_red = nullptr;     // [SC_COUNT + 2 world] scratch of the scalar all-reduce
+  double cur_damp = 0.0;       // damping of the system being built (the top unknowns get theirs after the all-reduce)
+  // a collective (or a scratch allocation of the linear solve) that failed while the iteration was being enqueued (broken / timed-out
+  // group barrier, scratch hipMalloc, non-zero ncclAllReduce): latched here, checked after the iteration's host synchronisation —
+  // the solve then returns an error instead of an estimate computed from un-reduced top fronts
+  bool coll_failed = false;
+  std::string coll_err;
+  covgpu_group* group = nullptr;   // the in-process group this context's reducer belongs to (aborted when this rank gives up)
+  int* d_pairkey = nullptr;    // [K] key of every keyframe in the covisible-pair numbering (chain position, -1: constant pose), kept for the second round of a call
+  std::vector<int> h_perm;     // [K] keyframe -> chain position of the resident problem
+  std::atomic<int>* peer_fail = nullptr;   // covgpu_gba_solve_multi: raised by any rank of the call that gave up; polled while waiting
+};
+
+#define RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
+// no C++ exception may cross the extern "C" boundary (std::bad_alloc from the host staging vectors, std::system_error from
+// std::thread): map them to status codes
+template <typename F>
+static int guarded(F&& body) {
+  try { return body(); }
+  catch (const std::bad_alloc&) { g_err = "host allocation failed"; return COVGPU_ERR_OUT_OF_MEMORY; }
+  catch (const std::exception& e) { g_err = std::string("host exception: ") + e.what(); return COVGPU_ERR_INVALID_ARG; }
+}
+
+// Every device buffer of one call: freed when the call returns, however it returns. Counts are in elements of T; an empty buffer is
+// still a valid pointer (16 B, which no kernel reads). Declare the host vectors that receive a fetch() BEFORE the scratch object:
+// its hipFree waits for the device, so on an error return the copies into them have drained before they are destroyed.
+struct DeviceScratch {
+  explicit DeviceScratch(hipStream_t st) : st(st) {}
+  DeviceScratch(const DeviceScratch&) = delete;
+  DeviceScratch& operator=(const DeviceScratch&) = delete;
+  ~DeviceScratch() { for (void* p : held) (void)hipFree(p); }
+  void adopt(void* d) { if (d) held.push_back(d); }   // a buffer somebody else allocated (k_pairs.hip's pair lists)
+  template <class T> hipError_t alloc(T** d, size_t count) {
+    *d = nullptr;
+    held.reserve(held.size() + 1);   // (a throwing push_back behind the hipMalloc would leak the buffer)
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, count ? count * sizeof(T) : 16);
+    if (e == hipSuccess) { held.push_back(p); *d = (T*)p; }
+    return e;
+  }
+  // alloc + asynchronous upload (T may be const-qualified: the device structs of common.hpp hold pointers to const)
+  template <class T> hipError_t upload(T** d, const std::remove_const_t<T>* host, size_t count) {
+    const hipError_t e = alloc(d, count);
+    return e != hipSuccess || !count ? e : hipMemcpyAsync((void*)*d, host, count * sizeof(T), hipMemcpyHostToDevice, st);
+  }
+  template <class T> hipError_t zeroed(T** d, size_t count) {
+    const hipError_t e = alloc(d, count);
+    return e != hipSuccess || !count ? e : hipMemsetAsync((void*)*d, 0, count * sizeof(T), st);
+  }
+  // asynchronous download; nothing to do for an empty buffer or an output the caller did not ask for
+  template <class T> hipError_t fetch(T* host, const T* d, size_t count) {
+    return count && host ? hipMemcpyAsync(host, d, count * sizeof(T), hipMemcpyDeviceToHost, st) : hipSuccess;
+  }
+  hipStream_t st;
+  std::vector<void*> held;
+};

@@ -1,4 +1,6 @@
-// solver.hip — host side of libcovgpu: context, HBM residency, trust-region driver, extern "C" entry points.
+// solver.hip — host side of libcovgpu's solver: context, HBM residency, trust-region driver and the extern "C" entry points of
+// the solve (upload, GBA / PGO solves single-GPU and sharded, plans, outlier pass, covisibility, the test entry points).
+// The stateless batch front end (relative pose, P3P RANSAC, matching, bag of words) is batch.hip; both share host.hpp.
 //
 // This is the thin extern "C" shim of BASELINE.json's north_star. It replaces what ceres::Solve does between
 // optimization_be.cpp:560-567 (GBA), :257-265 (GBA outlier round) and :1024-1031 (PGO): only scalars cross
@@ -22,77 +24,12 @@
 #include <thread>
 #include <vector>
 
-#include "common.hpp"
-#include "nd_plan.hpp"
+#include "host.hpp"
 
 using namespace covgpu;
 
-static thread_local std::string g_err;
+thread_local std::string g_err;
 extern "C" const char* covgpu_last_error(void) { return g_err.c_str(); }
-
-#define HIPCHK(expr)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) {                                                                     \
-      g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                                \
-      return e_ == hipErrorOutOfMemory ? COVGPU_ERR_OUT_OF_MEMORY : COVGPU_ERR_NO_DEVICE;       \
-    }                                                                                           \
-  } while (0)
-
-struct covgpu_profile_t {
-  double t_build_ms = 0, t_factor_ms = 0, t_syrk_ms = 0, syrk_flops = 0;
-  long n_build = 0, n_factor = 0, n_syrk = 0;
-};
-
-// elimination tree of the last single-GPU GBA upload and what it was built for (upload_impl)
-struct PlanCache {
-  bool valid = false; int K = 0; bool vi = false; int leaf = 0;
-  int top_env = -1; double frac_env = 0.0;   // COVGPU_ND_TOP / COVGPU_ND_GROUP_FRAC as nd_plan_build read them (-1 / 0: not set)
-  bool merge_env = true;                     // COVGPU_ND_MERGE likewise (nd_merge_enabled), and false for a pose graph
-  std::vector<int> chain_ptr, pos_kf;
-  std::vector<uint64_t> keys;   // sorted (position i << 32 | position j) of every covisible / loop-edge pair
-  NdHostPlan hp;
-};
-
-constexpr int COVGPU_ERR_GATE_TIMEOUT = -1000;   // internal (solve_any): never returned through the C ABI
-struct covgpu_group;
-struct covgpu_context {
-  int device = 0;
-  hipStream_t st = nullptr;
-  DevProblem P;
-  bool have = false, pgo = false;
-  std::vector<void*> allocs;
-  size_t alloc_bytes = 0;  // device bytes behind `allocs` (the footprint covgpu_get_layout reports)
-  double* h_scal = nullptr;  // pinned mirror of P.scal + flag
-  double* h_tr = nullptr;    // pinned mirror of P.tr (device-side trust region)
-  double* h_box = nullptr;   // pinned + mapped [TR_COUNT + 1]: the last kernel of an iteration posts P.tr and a sequence number here (k_tr_accept), the host polls it
-  double* d_box = nullptr;   // its device address (nullptr: not available — D2H copy + stream synchronisation)
-  double box_seq = 0.0;
-  int profiling = 0;
-  covgpu_profile_t prof;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  CholAux chol;
-  PgoPlan pgo_plan;  // block-arrow pose-graph solve (k_pgo.hip)
-  PlanCache plan_cache;  // elimination tree of the previous single-GPU GBA upload (reused when the new problem's couplings are a subset)
-  NdDev nd;          // multifrontal GBA solve (k_front.hip)
-  // agent-sharded solve: the global plan (variables as 2 * IR keyframe + kind, node -> rank), this rank's
-  // identity and its collective
-  bool sharded = false;
-  int rank = 0, world = 1;
-  std::shared_ptr<NdHostPlan> shard_plan;
-  struct Reducer* reducer = nullptr;
-  double* d_red = nullptr;     // [SC_COUNT + 2 world] scratch of the scalar all-reduce
-  double cur_damp = 0.0;       // damping of the system being built (the top unknowns get theirs after the all-reduce)
-  // a collective (or a scratch allocation of the linear solve) that failed while the iteration was being enqueued (broken / timed-out
-  // group barrier, scratch hipMalloc, non-zero ncclAllReduce): latched here, checked after the iteration's host synchronisation —
-  // the solve then returns an error instead of an estimate computed from un-reduced top fronts
-  bool coll_failed = false;
-  std::string coll_err;
-  covgpu_group* group = nullptr;   // the in-process group this context's reducer belongs to (aborted when this rank gives up)
-  int* d_pairkey = nullptr;    // [K] key of every keyframe in the covisible-pair numbering (chain position, -1: constant pose), kept for the second round of a call
-  std::vector<int> h_perm;     // [K] keyframe -> chain position of the resident problem
-  std::atomic<int>* peer_fail = nullptr;   // covgpu_gba_solve_multi: raised by any rank of the call that gave up; polled while waiting
-};
 
 // ---------------------------------------------------------------------------------------------------- collectives
 // sum (op 0) / max (op 1) of n device doubles over all ranks, in place, ENQUEUED on the stream (no host synchronisation in
@@ -277,13 +214,12 @@ extern "C" int covgpu_set_shard_rccl(covgpu_context* c, const covgpu_nd_plan* pl
 extern "C" int covgpu_allreduce_host(covgpu_context* c, double* host, int64_t n, int32_t op) {
   if (!c->reducer || n <= 0) return COVGPU_OK;
   HIPCHK(hipSetDevice(c->device));
+  DeviceScratch U(c->st);
   double* d = nullptr;
-  HIPCHK(hipMalloc((void**)&d, n * sizeof(double)));
-  HIPCHK(hipMemcpyAsync(d, host, n * sizeof(double), hipMemcpyHostToDevice, c->st));
+  HIPCHK(U.upload(&d, host, (size_t)n));
   const int rc = c->reducer->allreduce(d, (size_t)n, op, c->st);
-  HIPCHK(hipMemcpyAsync(host, d, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(U.fetch(host, d, (size_t)n));
   HIPCHK(hipStreamSynchronize(c->st));
-  (void)hipFree(d);
   if (rc != 0) { g_err = "all-reduce failed"; return COVGPU_ERR_NO_DEVICE; }
   return COVGPU_OK;
 }
@@ -449,16 +385,6 @@ static int dev_upload(covgpu_context* c, T** ptr, const T* host, size_t count) {
   else if (count) HIPCHK(hipMemsetAsync(*ptr, 0, count * sizeof(T), c->st));
   return COVGPU_OK;
 }
-#define RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
-// no C++ exception may cross the extern "C" boundary (std::bad_alloc from the host staging vectors, std::system_error from
-// std::thread): map them to status codes
-template <typename F>
-static int guarded(F&& body) {
-  try { return body(); }
-  catch (const std::bad_alloc&) { g_err = "host allocation failed"; return COVGPU_ERR_OUT_OF_MEMORY; }
-  catch (const std::exception& e) { g_err = std::string("host exception: ") + e.what(); return COVGPU_ERR_INVALID_ARG; }
-}
-
 static int validate(const covgpu_problem* p, bool pgo, bool vi) {
   auto bad = [](const char* m) { g_err = std::string("invalid problem: ") + m; return COVGPU_ERR_INVALID_ARG; };
   if (!p || p->num_kf <= 0) return bad("no keyframes");
@@ -858,14 +784,12 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
   RC(dev_alloc(c, &P.obs_lm, (size_t)P.O)); RC(dev_alloc(c, &P.obs_u, (size_t)P.O)); RC(dev_alloc(c, &P.obs_v, (size_t)P.O));
   RC(dev_alloc(c, &P.kf_obs_ptr, (size_t)P.K + 1)); RC(dev_alloc(c, &P.kf_obs_idx, (size_t)P.O));
   {
+    DeviceScratch U(c->st);
     double* d_uv = nullptr; int* d_iota = nullptr;
-    HIPCHK(hipMalloc((void**)&d_uv, std::max<size_t>((size_t)2 * P.O, 2) * sizeof(double)));
-    if (hipMalloc((void**)&d_iota, std::max<size_t>((size_t)P.O, 1) * sizeof(int)) != hipSuccess) { (void)hipFree(d_uv); g_err = "hipMalloc: out of memory"; return COVGPU_ERR_OUT_OF_MEMORY; }
-    hipError_t e = P.O ? hipMemcpyAsync(d_uv, p->obs_uv, (size_t)2 * P.O * sizeof(double), hipMemcpyHostToDevice, c->st) : hipSuccess;
+    HIPCHK(U.upload(&d_uv, p->obs_uv, (size_t)2 * P.O)); HIPCHK(U.alloc(&d_iota, (size_t)P.O));
     launch_obs_unpack(P.L, P.O, P.lm_obs_ptr, d_uv, P.obs_lm, P.obs_u, P.obs_v, d_iota, c->st);
-    const bool ok = e == hipSuccess && build_kf_lists_device(P.O, P.K, P.obs_kf, d_iota, P.kf_obs_ptr, P.kf_obs_idx, c->st);   // (ends with a stream synchronisation)
+    const bool ok = build_kf_lists_device(P.O, P.K, P.obs_kf, d_iota, P.kf_obs_ptr, P.kf_obs_idx, c->st);   // (ends with a stream synchronisation)
     (void)hipStreamSynchronize(c->st);
-    (void)hipFree(d_uv); (void)hipFree(d_iota);
     if (!ok) { g_err = "upload: device-side observation lists failed (allocation)"; return COVGPU_ERR_OUT_OF_MEMORY; }
   }
   tm("validate, chains, states, observation stream");
@@ -1829,17 +1753,13 @@ extern "C" int covgpu_outlier_pass(covgpu_context* c, double threshold, uint8_t*
   if (!c->have || c->pgo) { g_err = "covgpu_outlier_pass needs a resident GBA problem (call covgpu_gba_solve or covgpu_upload + covgpu_solve_resident first)"; return COVGPU_ERR_INVALID_ARG; }
   HIPCHK(hipSetDevice(c->device));
   const DevProblem& P = c->P;
+  unsigned long long hc[2] = {0, 0};   // (receives a fetch: declared before the scratch)
+  DeviceScratch U(c->st);
   unsigned char* de = nullptr; int* dl = nullptr; unsigned long long* dc = nullptr;
-  HIPCHK(hipMalloc((void**)&de, (size_t)std::max(P.O, 1))); HIPCHK(hipMalloc((void**)&dl, sizeof(int) * (size_t)std::max(P.L, 1)));
-  HIPCHK(hipMalloc((void**)&dc, 2 * sizeof(unsigned long long)));
-  HIPCHK(hipMemsetAsync(dc, 0, 2 * sizeof(unsigned long long), c->st));
+  HIPCHK(U.alloc(&de, (size_t)P.O)); HIPCHK(U.alloc(&dl, (size_t)P.L)); HIPCHK(U.zeroed(&dc, 2));
   launch_lm_outliers(P, threshold, de, dl, dc, c->st);
-  unsigned long long hc[2] = {0, 0};
-  if (P.O) HIPCHK(hipMemcpyAsync(obs_erase, de, (size_t)P.O, hipMemcpyDeviceToHost, c->st));
-  if (P.L) HIPCHK(hipMemcpyAsync(lm_left, dl, sizeof(int) * (size_t)P.L, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipMemcpyAsync(hc, dc, sizeof(hc), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(U.fetch(obs_erase, de, (size_t)P.O)); HIPCHK(U.fetch(lm_left, dl, (size_t)P.L)); HIPCHK(U.fetch(hc, dc, 2));
   HIPCHK(hipStreamSynchronize(c->st));
-  (void)hipFree(de); (void)hipFree(dl); (void)hipFree(dc);
   if (counts) { counts[0] = (int64_t)hc[0]; counts[1] = (int64_t)hc[1]; }
   return COVGPU_OK;
 }
@@ -1855,21 +1775,18 @@ extern "C" int covgpu_covisibility(covgpu_context* c, int32_t threshold, int64_t
     const DevProblem& P = c->P;
     std::vector<int> iota(P.K);
     for (int k = 0; k < P.K; ++k) iota[k] = k;
+    std::vector<int> pi, pj, pp;   // (receive a fetch: declared before the scratch)
+    DeviceScratch U(c->st);
     int* d_key = nullptr;
-    HIPCHK(hipMalloc((void**)&d_key, sizeof(int) * (size_t)P.K));
-    HIPCHK(hipMemcpyAsync(d_key, iota.data(), sizeof(int) * (size_t)P.K, hipMemcpyHostToDevice, c->st));
+    HIPCHK(U.upload(&d_key, iota.data(), iota.size()));
     PairLists pl;
     const bool ok = build_pairs_device(P.L, P.K, P.lm_obs_ptr, P.obs_kf, d_key, false, c->st, pl);
-    (void)hipFree(d_key);
     if (!ok) { g_err = "covgpu_covisibility: device allocation failed"; return (int)COVGPU_ERR_OUT_OF_MEMORY; }
-    std::vector<int> pi(pl.npairs), pj(pl.npairs), pp((size_t)pl.npairs + 1);
-    if (pl.npairs) {
-      HIPCHK(hipMemcpyAsync(pi.data(), pl.pair_i, sizeof(int) * (size_t)pl.npairs, hipMemcpyDeviceToHost, c->st));
-      HIPCHK(hipMemcpyAsync(pj.data(), pl.pair_j, sizeof(int) * (size_t)pl.npairs, hipMemcpyDeviceToHost, c->st));
-    }
-    HIPCHK(hipMemcpyAsync(pp.data(), pl.pair_ptr, sizeof(int) * ((size_t)pl.npairs + 1), hipMemcpyDeviceToHost, c->st));
+    for (int* q : {pl.pair_ptr, pl.pair_i, pl.pair_j}) U.adopt(q);   // allocated in k_pairs.hip, released with the rest
+    const size_t np = (size_t)pl.npairs;
+    pi.resize(np); pj.resize(np); pp.resize(np + 1);
+    HIPCHK(U.fetch(pi.data(), pl.pair_i, np)); HIPCHK(U.fetch(pj.data(), pl.pair_j, np)); HIPCHK(U.fetch(pp.data(), pl.pair_ptr, np + 1));
     HIPCHK(hipStreamSynchronize(c->st));
-    for (int* q : {pl.pair_ptr, pl.pair_i, pl.pair_j}) if (q) (void)hipFree(q);
     int64_t n = 0;
     for (int q = 0; q < pl.npairs; ++q) {
       const int w = pp[q + 1] - pp[q];
@@ -2013,766 +1930,17 @@ extern "C" int covgpu_solve_reduced(covgpu_context* c, int32_t n, const double* 
     if (r < n) { std::memcpy(&Sp[(size_t)r * npad], S + (size_t)r * n, (size_t)(r + 1) * sizeof(double)); bp[r] = b[r]; }
     else Sp[(size_t)r * npad + r] = 1.0;
   }
+  int flag = 0;   // (receives a fetch: declared, like Sp and bp, before the scratch)
+  DeviceScratch U(c->st);
   double *dS = nullptr, *db = nullptr, *dL = nullptr; int* df = nullptr;
-  HIPCHK(hipMalloc((void**)&dS, Sp.size() * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&db, bp.size() * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&dL, (size_t)(npad / kTile) * kTile * kTile * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&df, 4 * sizeof(int)));
-  HIPCHK(hipMemcpyAsync(dS, Sp.data(), Sp.size() * sizeof(double), hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(db, bp.data(), bp.size() * sizeof(double), hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemsetAsync(df, 0, 4 * sizeof(int), c->st));
+  HIPCHK(U.upload(&dS, Sp.data(), Sp.size())); HIPCHK(U.upload(&db, bp.data(), bp.size()));
+  HIPCHK(U.alloc(&dL, (size_t)(npad / kTile) * kTile * kTile)); HIPCHK(U.zeroed(&df, 4));
   {
     FormScope census(&c->chol.forms);
     dense_cholesky_solve_raw(dS, db, dL, df, npad, c->st, c->chol);
   }
-  int flag = 0;
-  HIPCHK(hipMemcpyAsync(x, db, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipMemcpyAsync(&flag, df, sizeof(int), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(U.fetch(x, db, (size_t)n)); HIPCHK(U.fetch(&flag, df, 1));
   HIPCHK(hipStreamSynchronize(c->st));
-  (void)hipFree(dS); (void)hipFree(db); (void)hipFree(dL); (void)hipFree(df);
   if (flag) { g_err = "reduced system is not positive definite"; return COVGPU_ERR_NUMERIC; }
-  return COVGPU_OK;
-}
-
-extern "C" int covgpu_relpose_batch(covgpu_context* c, const covgpu_relpose_batch_t* bt, double th_outlier, int32_t min_inliers) {
-  HIPCHK(hipSetDevice(c->device));
-  if (!bt || bt->num_pairs < 0 || (bt->num_pairs > 0 && (!bt->corr_ptr || !bt->T_ab || !bt->inliers || !bt->cam_a || !bt->cam_b || !bt->dist_type_a || !bt->dist_type_b))) {
-    g_err = "covgpu_relpose_batch: NULL array"; return COVGPU_ERR_INVALID_ARG;
-  }
-  const int B = bt->num_pairs;
-  if (B == 0) return COVGPU_OK;
-  for (int b = 0; b < B; ++b) if (bt->corr_ptr[b + 1] < bt->corr_ptr[b]) { g_err = "covgpu_relpose_batch: corr_ptr not monotone"; return COVGPU_ERR_INVALID_ARG; }
-  for (const int32_t* m : {bt->cam_model_a, bt->cam_model_b}) if (m) for (int b = 0; b < B; ++b) {
-    if (m[b] != COVGPU_CAM_PINHOLE && m[b] != COVGPU_CAM_UNIFIED) { g_err = "covgpu_relpose_batch: unknown camera model"; return COVGPU_ERR_INVALID_ARG; }
-  }
-  // per side: model and xi of every pair (xi 0 for pinhole rows); uploaded only if some camera of the batch is unified
-  std::vector<int32_t> hmA(B, COVGPU_CAM_PINHOLE), hmB(B, COVGPU_CAM_PINHOLE);
-  std::vector<double> hxA(B, 0.0), hxB(B, 0.0);
-  bool uni = false;
-  for (int side = 0; side < 2; ++side) {
-    const int32_t* m = side ? bt->cam_model_b : bt->cam_model_a;
-    const double* x = side ? bt->xi_b : bt->xi_a;
-    std::vector<int32_t>& hm = side ? hmB : hmA;
-    std::vector<double>& hx = side ? hxB : hxA;
-    if (!m) continue;
-    for (int b = 0; b < B; ++b) {
-      if (m[b] != COVGPU_CAM_UNIFIED) continue;
-      if (!x) { g_err = "covgpu_relpose_batch: unified camera without xi"; return COVGPU_ERR_INVALID_ARG; }
-      if (!std::isfinite(x[b]) || x[b] < 0.0) { g_err = "covgpu_relpose_batch: xi of a unified camera is negative or not finite"; return COVGPU_ERR_INVALID_ARG; }
-      hm[b] = COVGPU_CAM_UNIFIED; hx[b] = x[b]; uni = true;
-    }
-  }
-  const size_t C = (size_t)bt->corr_ptr[B];
-  if (C > 0 && (!bt->p_a || !bt->p_b || !bt->kp_a || !bt->kp_b || !bt->sigma_a || !bt->sigma_b || !bt->outlier)) { g_err = "covgpu_relpose_batch: NULL correspondence array"; return COVGPU_ERR_INVALID_ARG; }
-  std::vector<void*> tmp;
-  auto up = [&](const void* h, size_t bytes, void** d) -> hipError_t {
-    hipError_t e = hipMalloc(d, bytes ? bytes : 8);
-    if (e != hipSuccess) return e;
-    tmp.push_back(*d);
-    return bytes ? hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, c->st) : hipSuccess;
-  };
-  int *dptr_ = nullptr, *dda = nullptr, *ddb = nullptr, *din = nullptr;
-  double *dpB = nullptr, *dpA = nullptr, *dkA = nullptr, *dkB = nullptr, *dsA = nullptr, *dsB = nullptr, *dcA = nullptr, *dcB = nullptr, *dT = nullptr;
-  unsigned char* dout = nullptr;
-  HIPCHK(up(bt->corr_ptr, sizeof(int) * (B + 1), (void**)&dptr_));
-  HIPCHK(up(bt->p_b, 24 * C, (void**)&dpB)); HIPCHK(up(bt->p_a, 24 * C, (void**)&dpA));
-  HIPCHK(up(bt->kp_a, 16 * C, (void**)&dkA)); HIPCHK(up(bt->kp_b, 16 * C, (void**)&dkB));
-  HIPCHK(up(bt->sigma_a, 8 * C, (void**)&dsA)); HIPCHK(up(bt->sigma_b, 8 * C, (void**)&dsB));
-  HIPCHK(up(bt->cam_a, 64 * (size_t)B, (void**)&dcA)); HIPCHK(up(bt->cam_b, 64 * (size_t)B, (void**)&dcB));
-  HIPCHK(up(bt->dist_type_a, 4 * (size_t)B, (void**)&dda)); HIPCHK(up(bt->dist_type_b, 4 * (size_t)B, (void**)&ddb));
-  HIPCHK(up(bt->T_ab, 56 * (size_t)B, (void**)&dT));
-  int *dmA = nullptr, *dmB = nullptr;
-  double *dxA = nullptr, *dxB = nullptr;
-  if (uni) {
-    HIPCHK(up(hmA.data(), 4 * (size_t)B, (void**)&dmA)); HIPCHK(up(hmB.data(), 4 * (size_t)B, (void**)&dmB));
-    HIPCHK(up(hxA.data(), 8 * (size_t)B, (void**)&dxA)); HIPCHK(up(hxB.data(), 8 * (size_t)B, (void**)&dxB));
-  }
-  HIPCHK(hipMalloc((void**)&din, 4 * (size_t)B)); tmp.push_back(din);
-  HIPCHK(hipMalloc((void**)&dout, C ? C : 8)); tmp.push_back(dout);
-  launch_relpose(B, dptr_, dpB, dpA, dkA, dkB, dsA, dsB, dcA, dda, dcB, ddb, th_outlier, min_inliers, dT, dout, din, c->st, dmA, dxA, dmB, dxB);
-  HIPCHK(hipMemcpyAsync(bt->T_ab, dT, 56 * (size_t)B, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipMemcpyAsync(bt->inliers, din, 4 * (size_t)B, hipMemcpyDeviceToHost, c->st));
-  if (C) HIPCHK(hipMemcpyAsync(bt->outlier, dout, C, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  for (void* p : tmp) (void)hipFree(p);
-  return COVGPU_OK;
-}
-
-extern "C" void covgpu_default_ransac_opts(covgpu_ransac_opts* o) {
-  if (!o) return;
-  o->min_inliers = 6; o->max_iterations = 300; o->probability = 0.99; o->threshold = 25.0; o->seed = 0;   // config_backend.yaml:85-88
-}
-
-extern "C" int covgpu_abspose_ransac_batch(covgpu_context* c, const covgpu_abspose_batch_t* bt, const covgpu_ransac_opts* opts) {
-  HIPCHK(hipSetDevice(c->device));
-  auto bad = [](const char* m) { g_err = std::string("covgpu_abspose_ransac_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
-  if (!bt || !opts) return bad("NULL batch or options");
-  if (bt->num < 0) return bad("num < 0");
-  if (opts->max_iterations <= 0) return bad("max_iterations <= 0");
-  if (opts->max_iterations > 100000) return bad("max_iterations > 100000 (a candidate makes up to 11 max_iterations draws in one launch)");
-  if (!(opts->probability > 0.0 && opts->probability < 1.0)) return bad("probability outside (0, 1)");
-  if (!std::isfinite(opts->threshold) || !(opts->threshold > 0.0)) return bad("threshold not finite or not positive");
-  const int B = bt->num;
-  if (B == 0) return COVGPU_OK;
-  if (!bt->corr_ptr || !bt->T_wc || !bt->inliers) return bad("NULL array");
-  if (bt->corr_ptr[0] != 0) return bad("corr_ptr[0] != 0");
-  int max_n = 0;
-  for (int b = 0; b < B; ++b) {
-    if (bt->corr_ptr[b + 1] < bt->corr_ptr[b]) return bad("corr_ptr not monotone");
-    max_n = std::max(max_n, bt->corr_ptr[b + 1] - bt->corr_ptr[b]);
-  }
-  const size_t C = (size_t)bt->corr_ptr[B];
-  if (C > 0 && (!bt->bearing || !bt->point_w || !bt->sigma_angle || !bt->inlier)) return bad("NULL correspondence array");
-  for (size_t i = 0; i < 3 * C; ++i)
-    if (!std::isfinite(bt->bearing[i]) || !std::isfinite(bt->point_w[i])) return bad("non-finite bearing or point");
-  std::vector<uint64_t> seeds(B);
-  for (int b = 0; b < B; ++b) seeds[b] = bt->seed ? bt->seed[b] : opts->seed + (uint64_t)b;
-  std::vector<void*> tmp;
-  auto up = [&](const void* h, size_t bytes, void** d) -> hipError_t {
-    hipError_t e = hipMalloc(d, bytes ? bytes : 8);
-    if (e != hipSuccess) return e;
-    tmp.push_back(*d);
-    return bytes ? hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, c->st) : hipSuccess;
-  };
-  struct Free { std::vector<void*>& v; ~Free() { for (void* p : v) (void)hipFree(p); } } free_tmp{tmp};
-  int *dptr_ = nullptr, *din = nullptr, *dit = nullptr, *dbd = nullptr;
-  double *df = nullptr, *dP = nullptr, *ds = nullptr, *dT = nullptr;
-  unsigned long long* dseed = nullptr;
-  unsigned char* dmask = nullptr;
-  HIPCHK(up(bt->corr_ptr, sizeof(int) * (B + 1), (void**)&dptr_));
-  HIPCHK(up(bt->bearing, 24 * C, (void**)&df)); HIPCHK(up(bt->point_w, 24 * C, (void**)&dP)); HIPCHK(up(bt->sigma_angle, 8 * C, (void**)&ds));
-  HIPCHK(up(seeds.data(), 8 * (size_t)B, (void**)&dseed));
-  HIPCHK(up(bt->T_wc, 56 * (size_t)B, (void**)&dT));   // untouched rows come back as they went
-  HIPCHK(hipMalloc((void**)&dmask, C ? C : 8)); tmp.push_back(dmask);
-  HIPCHK(hipMalloc((void**)&din, 4 * (size_t)B)); tmp.push_back(din);
-  HIPCHK(hipMalloc((void**)&dit, 4 * (size_t)B)); tmp.push_back(dit);
-  HIPCHK(hipMalloc((void**)&dbd, 4 * (size_t)B)); tmp.push_back(dbd);
-  launch_abspose(B, dptr_, df, dP, ds, dseed, dT, dmask, din, dit, dbd, opts->min_inliers, opts->max_iterations, opts->probability, opts->threshold,
-                 max_n, c->st);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(bt->T_wc, dT, 56 * (size_t)B, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipMemcpyAsync(bt->inliers, din, 4 * (size_t)B, hipMemcpyDeviceToHost, c->st));
-  if (bt->iterations) HIPCHK(hipMemcpyAsync(bt->iterations, dit, 4 * (size_t)B, hipMemcpyDeviceToHost, c->st));
-  if (bt->best_draw) HIPCHK(hipMemcpyAsync(bt->best_draw, dbd, 4 * (size_t)B, hipMemcpyDeviceToHost, c->st));
-  if (C) HIPCHK(hipMemcpyAsync(bt->inlier, dmask, C, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return COVGPU_OK;
-}
-
-extern "C" int covgpu_p3p_batch(covgpu_context* c, int32_t n, const double* f, const double* P, double* T, int32_t* nsol, int32_t* chosen) {
-  HIPCHK(hipSetDevice(c->device));
-  if (n < 0) { g_err = "covgpu_p3p_batch: n < 0"; return COVGPU_ERR_INVALID_ARG; }
-  if (n == 0) return COVGPU_OK;
-  if (!f || !P || !T || !nsol || !chosen) { g_err = "covgpu_p3p_batch: NULL array"; return COVGPU_ERR_INVALID_ARG; }
-  for (size_t i = 0; i < (size_t)12 * n; ++i)
-    if (!std::isfinite(f[i]) || !std::isfinite(P[i])) { g_err = "covgpu_p3p_batch: non-finite bearing or point"; return COVGPU_ERR_INVALID_ARG; }
-  std::vector<void*> tmp;
-  struct Free { std::vector<void*>& v; ~Free() { for (void* p : v) (void)hipFree(p); } } free_tmp{tmp};
-  auto A = [&](void** p, size_t bytes) { hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) tmp.push_back(*p); return e; };
-  double *df, *dP, *dT; int *dn, *dc;
-  HIPCHK(A((void**)&df, 96 * (size_t)n)); HIPCHK(A((void**)&dP, 96 * (size_t)n)); HIPCHK(A((void**)&dT, 224 * (size_t)n));
-  HIPCHK(A((void**)&dn, 4 * (size_t)n)); HIPCHK(A((void**)&dc, 4 * (size_t)n));
-  HIPCHK(hipMemcpyAsync(df, f, 96 * (size_t)n, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(dP, P, 96 * (size_t)n, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemsetAsync(dT, 0, 224 * (size_t)n, c->st));
-  launch_p3p(n, df, dP, dT, dn, dc, c->st);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(T, dT, 224 * (size_t)n, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipMemcpyAsync(nsol, dn, 4 * (size_t)n, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipMemcpyAsync(chosen, dc, 4 * (size_t)n, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return COVGPU_OK;
-}
-
-extern "C" void covgpu_default_match_opts(covgpu_match_opts* o, int32_t mode) {
-  if (!o) return;
-  o->mode = mode;
-  o->dist_threshold = mode == COVGPU_MATCH_KNN2 ? 40.0f : 50.0f;   // img_match_thres (config_backend.yaml:38); LandmarkMatchingAlgorithm(50.0)
-  o->ratio = 0.8f;                                                 // ratio_thres (config_backend.yaml:39), KNN2 only
-}
-
-extern "C" int covgpu_match_batch(covgpu_context* c, const covgpu_match_batch_t* bt, const covgpu_match_opts* opts) {
-  auto bad = [](const char* m) { g_err = std::string("covgpu_match_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
-  if (!c) return bad("NULL context");
-  if (!bt || !opts) return bad("NULL batch or options");
-  if (opts->mode != COVGPU_MATCH_DENSE && opts->mode != COVGPU_MATCH_KNN2) return bad("unknown mode");
-  if (!std::isfinite(opts->dist_threshold) || !(opts->dist_threshold > 0.0f)) return bad("dist_threshold not finite or not positive");
-  if (!std::isfinite(opts->ratio) || !(opts->ratio > 0.0f)) return bad("ratio not finite or not positive");
-  const bool dense = opts->mode == COVGPU_MATCH_DENSE;
-  if (bt->num_sets < 0 || bt->num_jobs < 0) return bad("num_sets or num_jobs < 0");
-  if (!dense && bt->skip) return bad("skip must be NULL in KNN2");
-  if (bt->num_sets > 0 && !bt->row_ptr) return bad("NULL row_ptr");
-  if (bt->num_sets > 0 && bt->row_ptr[0] != 0) return bad("row_ptr[0] != 0");
-  for (int s = 0; s < bt->num_sets; ++s) {
-    if (bt->row_ptr[s + 1] < bt->row_ptr[s]) return bad("row_ptr not monotone");
-    if (bt->row_ptr[s + 1] - bt->row_ptr[s] > COVGPU_MATCH_MAX_ROWS) return bad("a set holds more than COVGPU_MATCH_MAX_ROWS rows");
-  }
-  const size_t R = bt->num_sets > 0 ? (size_t)bt->row_ptr[bt->num_sets] : 0;
-  if (R > 0 && !bt->desc) return bad("NULL desc");
-  const int J = bt->num_jobs;
-  if (J > 0 && (!bt->set_a || !bt->set_b || !bt->nmatches)) return bad("NULL job array");
-  std::vector<int32_t> off(J > 0 ? J : 1, 0);
-  size_t totalA = 0;
-  int maxA = 0, maxB = 0;
-  for (int j = 0; j < J; ++j) {
-    if (bt->set_a[j] < 0 || bt->set_a[j] >= bt->num_sets || bt->set_b[j] < 0 || bt->set_b[j] >= bt->num_sets) return bad("set index out of range");
-    const int nA = bt->row_ptr[bt->set_a[j] + 1] - bt->row_ptr[bt->set_a[j]];
-    off[j] = (int32_t)totalA;
-    totalA += (size_t)nA;
-    if (totalA > (size_t)INT32_MAX) return bad("more than 2^31 - 1 output rows");
-    maxA = std::max(maxA, nA);
-    maxB = std::max(maxB, bt->row_ptr[bt->set_b[j] + 1] - bt->row_ptr[bt->set_b[j]]);
-  }
-  if (totalA > 0 && !bt->match) return bad("NULL match");
-  if (J == 0) return COVGPU_OK;
-  const int tiles = (maxA + kMatchScanRows - 1) / kMatchScanRows;  // scan workgroups per job (launch_match): one 1-D grid of J * tiles
-  if ((int64_t)J * tiles > (int64_t)INT32_MAX) return bad("num_jobs * ceil(max query rows / 256) exceeds 2^31 - 1 workgroups");
-  HIPCHK(hipSetDevice(c->device));                                   // the first device call: every argument is checked above
-  int dcut = 0;                                                    // (float)d < dist_threshold  <=>  d < dcut, for d in 0..256
-  while (dcut <= 256 && (float)dcut < opts->dist_threshold) ++dcut;
-  std::vector<void*> tmp;
-  struct Free { std::vector<void*>& v; ~Free() { for (void* p : v) (void)hipFree(p); } } free_tmp{tmp};
-  auto A = [&](void** p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 16); if (e == hipSuccess) tmp.push_back(*p); return e; };
-  unsigned char *ddesc = nullptr, *dskip = nullptr;
-  int *dptr_ = nullptr, *dsa = nullptr, *dsb = nullptr, *doff = nullptr, *dlist = nullptr, *dmatch = nullptr, *ddist = nullptr, *dn = nullptr;
-  HIPCHK(A((void**)&ddesc, 32 * R));
-  if (R) HIPCHK(hipMemcpyAsync(ddesc, bt->desc, 32 * R, hipMemcpyHostToDevice, c->st));
-  if (dense && bt->skip) {
-    HIPCHK(A((void**)&dskip, R));
-    if (R) HIPCHK(hipMemcpyAsync(dskip, bt->skip, R, hipMemcpyHostToDevice, c->st));
-  }
-  HIPCHK(A((void**)&dptr_, 4 * ((size_t)bt->num_sets + 1)));
-  HIPCHK(hipMemcpyAsync(dptr_, bt->row_ptr, 4 * ((size_t)bt->num_sets + 1), hipMemcpyHostToDevice, c->st));
-  HIPCHK(A((void**)&dsa, 4 * (size_t)J)); HIPCHK(A((void**)&dsb, 4 * (size_t)J)); HIPCHK(A((void**)&doff, 4 * (size_t)J));
-  HIPCHK(hipMemcpyAsync(dsa, bt->set_a, 4 * (size_t)J, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(dsb, bt->set_b, 4 * (size_t)J, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(doff, off.data(), 4 * (size_t)J, hipMemcpyHostToDevice, c->st));
-  if (dense) HIPCHK(A((void**)&dlist, 16 * totalA));
-  HIPCHK(A((void**)&dmatch, 4 * totalA)); HIPCHK(A((void**)&ddist, 4 * totalA)); HIPCHK(A((void**)&dn, 4 * (size_t)J));
-  HIPCHK(hipMemsetAsync(dn, 0, 4 * (size_t)J, c->st));
-  launch_match(opts->mode, J, maxA, maxB, ddesc, dskip, dptr_, dsa, dsb, doff, dlist, dmatch, ddist, dn, dcut, opts->dist_threshold, opts->ratio,
-               c->st);
-  HIPCHK(hipGetLastError());
-  if (totalA) {
-    HIPCHK(hipMemcpyAsync(bt->match, dmatch, 4 * totalA, hipMemcpyDeviceToHost, c->st));
-    if (bt->dist) HIPCHK(hipMemcpyAsync(bt->dist, ddist, 4 * totalA, hipMemcpyDeviceToHost, c->st));
-  }
-  HIPCHK(hipMemcpyAsync(bt->nmatches, dn, 4 * (size_t)J, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return COVGPU_OK;
-}
-
-extern "C" void covgpu_default_guided_opts(covgpu_guided_opts* o, int32_t mode) {
-  if (!o) return;
-  o->th_low = 50;                                                  // desc_matching_th_low_ (feature_matcher_be.hpp)
-  o->radius = mode == COVGPU_GUIDED_PROJECTION ? 10.0 : 9.5;       // config_backend.yaml:45-50
-  o->scale_factor = 2.0; o->num_octaves = 1;                       // features::scale_factor, features::num_octaves
-  o->agreement = 0;
-}
-
-namespace {
-
-// Checks shared by the two guided entry points; the message of the first violation, or nullptr.
-const char* guided_check(const covgpu_keypoint_sets_t& s, const covgpu_guided_opts* o) {
-  if (!o) return "NULL options";
-  if (o->th_low < 0 || o->th_low > 255) return "th_low outside [0, 255]";
-  if (!std::isfinite(o->radius) || !(o->radius > 0.0)) return "radius not finite or not positive";
-  if (o->num_octaves < 1) return "num_octaves < 1";
-  if (o->num_octaves > 1 && (!std::isfinite(o->scale_factor) || !(o->scale_factor > 1.0))) return "scale_factor not finite or not above 1";
-  if (o->agreement != 0 && o->agreement != 1) return "agreement is neither 0 nor 1";
-  if (s.num_sets < 0) return "num_sets < 0";
-  if (s.num_sets > 0 && !s.row_ptr) return "NULL row_ptr";
-  if (s.num_sets > 0 && s.row_ptr[0] != 0) return "row_ptr[0] != 0";
-  for (int i = 0; i < s.num_sets; ++i) {
-    if (s.row_ptr[i + 1] < s.row_ptr[i]) return "row_ptr not monotone";
-    if (s.row_ptr[i + 1] - s.row_ptr[i] > COVGPU_MATCH_MAX_ROWS) return "a set holds more than COVGPU_MATCH_MAX_ROWS rows";
-  }
-  if (s.num_sets > 0 && !s.bounds) return "NULL bounds";
-  if (s.num_sets > 0 && s.row_ptr[s.num_sets] > 0 && (!s.kp || !s.level || !s.desc)) return "NULL keypoint array";
-  return nullptr;
-}
-
-// Device records of the keypoints: {x, y, level, visiting rank}. Grid order is ascending (cell_x, cell_y, index) with the cell of
-// AssignFeaturesToGrid (keyframe_base.cpp:134-139) clamped to the 64 x 48 grid; index order when the set has no grid. A taken keypoint
-// (SearchByProjection's vpMatched[idx] != NULL) gets level INT_MIN and so fails every level window.
-std::vector<int4> guided_records(const covgpu_keypoint_sets_t& s, const uint8_t* taken) {
-  const size_t R = s.num_sets > 0 ? (size_t)s.row_ptr[s.num_sets] : 0;
-  std::vector<int4> rec(R);
-  std::vector<int> cell, order;
-  for (int i = 0; i < s.num_sets; ++i) {
-    const int r0 = s.row_ptr[i], n = s.row_ptr[i + 1] - r0;
-    order.resize(n);
-    for (int k = 0; k < n; ++k) order[k] = k;
-    if (s.grid_inv && s.grid_inv[2 * i] > 0.0) {
-      cell.resize(n);
-      for (int k = 0; k < n; ++k) {
-        const double cx = std::round((double)s.kp[2 * (size_t)(r0 + k)] * s.grid_inv[2 * i]);
-        const double cy = std::round((double)s.kp[2 * (size_t)(r0 + k) + 1] * s.grid_inv[2 * i + 1]);
-        const int ix = cx >= 0.0 ? (cx <= 63.0 ? (int)cx : 63) : 0, iy = cy >= 0.0 ? (cy <= 47.0 ? (int)cy : 47) : 0;   // (a NaN goes to cell 0)
-        cell[k] = ix * 48 + iy;
-      }
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cell[a] < cell[b]; });
-    }
-    for (int rank = 0; rank < n; ++rank) {
-      const size_t r = (size_t)r0 + order[rank];
-      int4 e;
-      std::memcpy(&e.x, &s.kp[2 * r], 4); std::memcpy(&e.y, &s.kp[2 * r + 1], 4);
-      e.z = (taken && taken[r]) ? INT32_MIN : s.level[r];
-      e.w = rank;
-      rec[r] = e;
-    }
-  }
-  return rec;
-}
-
-struct GuidedUpload {
-  covgpu_context* c;
-  std::vector<void*> tmp;
-  ~GuidedUpload() { for (void* p : tmp) (void)hipFree(p); }
-  hipError_t alloc(void** p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 16); if (e == hipSuccess) tmp.push_back(*p); return e; }
-  hipError_t up(const void* h, size_t bytes, void** d) {
-    hipError_t e = alloc(d, bytes);
-    if (e != hipSuccess || !bytes) return e;
-    return hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, c->st);
-  }
-};
-
-}  // namespace
-
-extern "C" int covgpu_search_se3_batch(covgpu_context* c, const covgpu_search_se3_batch_t* bt, const covgpu_guided_opts* opts) {
-  auto bad = [](const char* m) { g_err = std::string("covgpu_search_se3_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
-  if (!c) return bad("NULL context");
-  if (!bt) return bad("NULL batch");
-  if (const char* m = guided_check(bt->sets, opts)) return bad(m);
-  const covgpu_keypoint_sets_t& s = bt->sets;
-  const int S = s.num_sets, J = bt->num_jobs;
-  const size_t R = S > 0 ? (size_t)s.row_ptr[S] : 0;
-  if (J < 0) return bad("num_jobs < 0");
-  if (S > 0 && !bt->K) return bad("NULL K");
-  if (R > 0 && (!bt->lm_pos || !bt->lm_max_distance || !bt->lm_desc || !bt->lm_free)) return bad("NULL landmark array");
-  if (J > 0 && (!bt->set_1 || !bt->set_2 || !bt->T12 || !bt->nfound)) return bad("NULL job array");
-  std::vector<int32_t> off1(J > 0 ? J : 1, 0), off2(J > 0 ? J : 1, 0);
-  std::vector<int4> tiles;
-  size_t tot1 = 0, tot2 = 0;
-  for (int j = 0; j < J; ++j) {
-    if (bt->set_1[j] < 0 || bt->set_1[j] >= S || bt->set_2[j] < 0 || bt->set_2[j] >= S) return bad("set index out of range");
-    for (int k = 0; k < 7; ++k) if (!std::isfinite(bt->T12[7 * (size_t)j + k])) return bad("non-finite T12");
-    const int n1 = s.row_ptr[bt->set_1[j] + 1] - s.row_ptr[bt->set_1[j]], n2 = s.row_ptr[bt->set_2[j] + 1] - s.row_ptr[bt->set_2[j]];
-    off1[j] = (int32_t)tot1; off2[j] = (int32_t)tot2;
-    tot1 += (size_t)n1; tot2 += (size_t)n2;
-    if (tot1 > (size_t)INT32_MAX || tot2 > (size_t)INT32_MAX) return bad("more than 2^31 - 1 output rows");
-    for (int dir = 0; dir < 2; ++dir)
-      for (int f = 0, n = dir ? n2 : n1; f < n; f += kGuidedScanPoints) tiles.push_back(make_int4(j, dir, f, std::min(kGuidedScanPoints, n - f)));
-    if (tiles.size() > (size_t)INT32_MAX) return bad("more than 2^31 - 1 scan workgroups");
-  }
-  if (tot1 > 0 && !bt->match) return bad("NULL match");
-  if (J == 0) return COVGPU_OK;
-  HIPCHK(hipSetDevice(c->device));                                   // the first device call: every argument is checked above
-  const std::vector<int4> rec = guided_records(s, nullptr);
-  GuidedUpload U{c};
-  GuidedSe3Args A{};
-  HIPCHK(U.up(rec.data(), 16 * R, (void**)&A.S.kpr)); HIPCHK(U.up(s.desc, 32 * R, (void**)&A.S.kdesc));
-  HIPCHK(U.up(s.row_ptr, 4 * ((size_t)S + 1), (void**)&A.S.row_ptr)); HIPCHK(U.up(s.bounds, 32 * (size_t)S, (void**)&A.S.bounds));
-  HIPCHK(U.up(bt->K, 32 * (size_t)S, (void**)&A.K)); HIPCHK(U.up(bt->lm_pos, 24 * R, (void**)&A.lm_pos));
-  HIPCHK(U.up(bt->lm_max_distance, 8 * R, (void**)&A.lm_maxd)); HIPCHK(U.up(bt->lm_desc, 32 * R, (void**)&A.lm_desc));
-  HIPCHK(U.up(bt->lm_free, R, (void**)&A.lm_free));
-  HIPCHK(U.up(bt->set_1, 4 * (size_t)J, (void**)&A.set_1)); HIPCHK(U.up(bt->set_2, 4 * (size_t)J, (void**)&A.set_2));
-  HIPCHK(U.up(bt->T12, 56 * (size_t)J, (void**)&A.T12));
-  HIPCHK(U.up(off1.data(), 4 * (size_t)J, (void**)&A.off1)); HIPCHK(U.up(off2.data(), 4 * (size_t)J, (void**)&A.off2));
-  int4* dtiles = nullptr;
-  HIPCHK(U.up(tiles.data(), 16 * tiles.size(), (void**)&dtiles));
-  HIPCHK(U.alloc((void**)&A.m1, 4 * tot1)); HIPCHK(U.alloc((void**)&A.m2, 4 * tot2)); HIPCHK(U.alloc((void**)&A.match, 4 * tot1));
-  HIPCHK(U.alloc((void**)&A.nfound, 4 * (size_t)J));
-  HIPCHK(hipMemsetAsync(A.nfound, 0, 4 * (size_t)J, c->st));
-  const GuidedOptsDev O{opts->th_low, opts->radius, opts->scale_factor, std::log(opts->scale_factor), opts->num_octaves, opts->agreement};
-  launch_guided_se3(A, O, J, dtiles, (int)tiles.size(), c->st);
-  HIPCHK(hipGetLastError());
-  if (tot1) HIPCHK(hipMemcpyAsync(bt->match, A.match, 4 * tot1, hipMemcpyDeviceToHost, c->st));
-  if (tot1 && bt->match1) HIPCHK(hipMemcpyAsync(bt->match1, A.m1, 4 * tot1, hipMemcpyDeviceToHost, c->st));
-  if (tot2 && bt->match2) HIPCHK(hipMemcpyAsync(bt->match2, A.m2, 4 * tot2, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipMemcpyAsync(bt->nfound, A.nfound, 4 * (size_t)J, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return COVGPU_OK;
-}
-
-extern "C" int covgpu_search_projection_batch(covgpu_context* c, const covgpu_search_projection_batch_t* bt, const covgpu_guided_opts* opts) {
-  auto bad = [](const char* m) { g_err = std::string("covgpu_search_projection_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
-  if (!c) return bad("NULL context");
-  if (!bt) return bad("NULL batch");
-  if (const char* m = guided_check(bt->sets, opts)) return bad(m);
-  const covgpu_keypoint_sets_t& s = bt->sets;
-  const int S = s.num_sets, J = bt->num_jobs;
-  const size_t R = S > 0 ? (size_t)s.row_ptr[S] : 0;
-  if (J < 0) return bad("num_jobs < 0");
-  if (S > 0 && (!bt->cam || !bt->dist_type)) return bad("NULL camera array");
-  for (int i = 0; i < S; ++i) {
-    if (bt->dist_type[i] != COVGPU_DIST_RADTAN && bt->dist_type[i] != COVGPU_DIST_EQUIDISTANT) return bad("unknown distortion type");
-    if (!bt->cam_model || bt->cam_model[i] == COVGPU_CAM_PINHOLE) continue;
-    if (bt->cam_model[i] != COVGPU_CAM_UNIFIED) return bad("unknown camera model");
-    if (!bt->xi) return bad("unified camera without xi");
-    if (!std::isfinite(bt->xi[i]) || bt->xi[i] < 0.0) return bad("xi of a unified camera is negative or not finite");
-  }
-  if (J > 0 && (!bt->set || !bt->T_cw || !bt->point_ptr || !bt->nmatches)) return bad("NULL job array");
-  if (J > 0 && bt->point_ptr[0] != 0) return bad("point_ptr[0] != 0");
-  std::vector<int4> tiles;
-  for (int j = 0; j < J; ++j) {
-    if (bt->set[j] < 0 || bt->set[j] >= S) return bad("set index out of range");
-    if (bt->point_ptr[j + 1] < bt->point_ptr[j]) return bad("point_ptr not monotone");
-    for (int k = 0; k < 7; ++k) if (!std::isfinite(bt->T_cw[7 * (size_t)j + k])) return bad("non-finite T_cw");
-    for (int f = 0, n = bt->point_ptr[j + 1] - bt->point_ptr[j]; f < n; f += kGuidedScanPoints)
-      tiles.push_back(make_int4(j, 0, f, std::min(kGuidedScanPoints, n - f)));
-  }
-  const size_t P = J > 0 ? (size_t)bt->point_ptr[J] : 0;
-  if (P > 0 && (!bt->p_w || !bt->normal || !bt->min_distance || !bt->max_distance || !bt->p_desc || !bt->claimed || !bt->remap_to))
-    return bad("NULL point array");
-  if (bt->existing_idx)
-    for (int j = 0; j < J; ++j) {
-      const int n = s.row_ptr[bt->set[j] + 1] - s.row_ptr[bt->set[j]];
-      for (int p = bt->point_ptr[j]; p < bt->point_ptr[j + 1]; ++p)
-        if (bt->existing_idx[p] < -1 || bt->existing_idx[p] >= n) return bad("existing_idx out of range");
-    }
-  if (J == 0) return COVGPU_OK;
-  HIPCHK(hipSetDevice(c->device));                                   // the first device call: every argument is checked above
-  const std::vector<int4> rec = guided_records(s, bt->taken);
-  GuidedUpload U{c};
-  GuidedProjArgs A{};
-  HIPCHK(U.up(rec.data(), 16 * R, (void**)&A.S.kpr)); HIPCHK(U.up(s.desc, 32 * R, (void**)&A.S.kdesc));
-  HIPCHK(U.up(s.row_ptr, 4 * ((size_t)S + 1), (void**)&A.S.row_ptr)); HIPCHK(U.up(s.bounds, 32 * (size_t)S, (void**)&A.S.bounds));
-  HIPCHK(U.up(bt->cam, 64 * (size_t)S, (void**)&A.cam)); HIPCHK(U.up(bt->dist_type, 4 * (size_t)S, (void**)&A.dist_type));
-  std::vector<double> xi(S, 0.0);                                    // 0 for the pinhole rows, whose xi is not read
-  if (bt->cam_model) {
-    for (int i = 0; i < S; ++i) if (bt->cam_model[i] == COVGPU_CAM_UNIFIED) xi[i] = bt->xi[i];
-    HIPCHK(U.up(bt->cam_model, 4 * (size_t)S, (void**)&A.cam_model)); HIPCHK(U.up(xi.data(), 8 * (size_t)S, (void**)&A.xi));
-  }
-  HIPCHK(U.up(bt->set, 4 * (size_t)J, (void**)&A.set)); HIPCHK(U.up(bt->T_cw, 56 * (size_t)J, (void**)&A.T_cw));
-  HIPCHK(U.up(bt->point_ptr, 4 * ((size_t)J + 1), (void**)&A.point_ptr));
-  HIPCHK(U.up(bt->p_w, 24 * P, (void**)&A.p_w)); HIPCHK(U.up(bt->normal, 24 * P, (void**)&A.normal));
-  HIPCHK(U.up(bt->min_distance, 8 * P, (void**)&A.min_d)); HIPCHK(U.up(bt->max_distance, 8 * P, (void**)&A.max_d));
-  HIPCHK(U.up(bt->p_desc, 32 * P, (void**)&A.p_desc));
-  if (bt->skip) HIPCHK(U.up(bt->skip, P, (void**)&A.skip));
-  if (bt->existing_idx) HIPCHK(U.up(bt->existing_idx, 4 * P, (void**)&A.existing));
-  int4* dtiles = nullptr;
-  HIPCHK(U.up(tiles.data(), 16 * tiles.size(), (void**)&dtiles));
-  HIPCHK(U.alloc((void**)&A.lists, 4 * kGuidedListCap * P)); HIPCHK(U.alloc((void**)&A.cnt, 4 * P)); HIPCHK(U.alloc((void**)&A.target, 8 * P));
-  HIPCHK(U.alloc((void**)&A.rad, 8 * P)); HIPCHK(U.alloc((void**)&A.lvl, 4 * P)); HIPCHK(U.alloc((void**)&A.dold, 4 * P));
-  HIPCHK(U.alloc((void**)&A.claimed, 4 * P)); HIPCHK(U.alloc((void**)&A.remap_to, 4 * P)); HIPCHK(U.alloc((void**)&A.best_dist, 4 * P));
-  HIPCHK(U.alloc((void**)&A.nmatches, 4 * (size_t)J));
-  const GuidedOptsDev O{opts->th_low, opts->radius, opts->scale_factor, std::log(opts->scale_factor), opts->num_octaves, opts->agreement};
-  launch_guided_projection(A, O, J, dtiles, (int)tiles.size(), c->st);
-  HIPCHK(hipGetLastError());
-  if (P) {
-    HIPCHK(hipMemcpyAsync(bt->claimed, A.claimed, 4 * P, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipMemcpyAsync(bt->remap_to, A.remap_to, 4 * P, hipMemcpyDeviceToHost, c->st));
-    if (bt->best_dist) HIPCHK(hipMemcpyAsync(bt->best_dist, A.best_dist, 4 * P, hipMemcpyDeviceToHost, c->st));
-  }
-  HIPCHK(hipMemcpyAsync(bt->nmatches, A.nmatches, 4 * (size_t)J, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return COVGPU_OK;
-}
-
-extern "C" int covgpu_pgo_reanchor(covgpu_context* c, int32_t K, const double* pose_old, const double* pose_new, double* velocity, int32_t L,
-                                   const int32_t* ref_kf, double* lm_pos) {
-  HIPCHK(hipSetDevice(c->device));
-  if (K < 0 || L < 0 || (K > 0 && (!pose_old || !pose_new)) || (L > 0 && (!ref_kf || !lm_pos))) { g_err = "covgpu_pgo_reanchor: NULL array"; return COVGPU_ERR_INVALID_ARG; }
-  for (int l = 0; l < L; ++l) if (ref_kf[l] >= K) { g_err = "covgpu_pgo_reanchor: ref_kf out of range"; return COVGPU_ERR_INVALID_ARG; }
-  double *dpo, *dpn, *dv = nullptr, *dl; int* dr;
-  std::vector<void*> tmp;
-  auto A = [&](void** p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 8); if (e == hipSuccess) tmp.push_back(*p); return e; };
-  HIPCHK(A((void**)&dpo, (size_t)7 * K * sizeof(double))); HIPCHK(A((void**)&dpn, (size_t)7 * K * sizeof(double)));
-  HIPCHK(A((void**)&dl, (size_t)3 * L * sizeof(double))); HIPCHK(A((void**)&dr, (size_t)L * sizeof(int)));
-  HIPCHK(hipMemcpyAsync(dpo, pose_old, (size_t)7 * K * sizeof(double), hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(dpn, pose_new, (size_t)7 * K * sizeof(double), hipMemcpyHostToDevice, c->st));
-  if (L) {
-    HIPCHK(hipMemcpyAsync(dl, lm_pos, (size_t)3 * L * sizeof(double), hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(dr, ref_kf, (size_t)L * sizeof(int), hipMemcpyHostToDevice, c->st));
-  }
-  if (velocity) {
-    HIPCHK(A((void**)&dv, (size_t)3 * K * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(dv, velocity, (size_t)3 * K * sizeof(double), hipMemcpyHostToDevice, c->st));
-  }
-  launch_reanchor(K, dpo, dpn, dv, L, dr, dl, c->st);
-  if (L) HIPCHK(hipMemcpyAsync(lm_pos, dl, (size_t)3 * L * sizeof(double), hipMemcpyDeviceToHost, c->st));
-  if (velocity) HIPCHK(hipMemcpyAsync(velocity, dv, (size_t)3 * K * sizeof(double), hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  for (void* p : tmp) (void)hipFree(p);
-  return COVGPU_OK;
-}
-
-// ---- bag-of-words retrieval (k_bow.hip) ----
-namespace {
-
-// The first violation of a bow CSR over `rows` rows (word ids ascending and duplicate-free, values finite), or nullptr.
-const char* bow_csr_check(int rows, const int32_t* ptr, const int32_t* word, const double* value) {
-  if (rows < 0) return "negative row count";
-  if (rows == 0) return nullptr;
-  if (!ptr) return "NULL bow_ptr";
-  if (ptr[0] != 0) return "bow_ptr[0] != 0";
-  for (int r = 0; r < rows; ++r) if (ptr[r + 1] < ptr[r]) return "bow_ptr not monotone";
-  if (ptr[rows] > 0 && (!word || !value)) return "NULL word or value";
-  for (int r = 0; r < rows; ++r)
-    for (int i = ptr[r]; i < ptr[r + 1]; ++i) {
-      if (word[i] < 0) return "negative word id";
-      if (i > ptr[r] && word[i] <= word[i - 1]) return "word ids of a bow row not ascending and duplicate-free";
-      if (!std::isfinite(value[i])) return "non-finite bow value";
-    }
-  return nullptr;
-}
-
-// The first violation of the vocabulary's tree shape, or nullptr.
-const char* bow_vocab_check(const covgpu_bow_vocab_t* v) {
-  if (!v) return "NULL vocabulary";
-  if (v->scoring != COVGPU_BOW_L1_NORM) return "only L1_NORM scoring is supported";
-  if (v->weighting < COVGPU_BOW_TF_IDF || v->weighting > COVGPU_BOW_BINARY) return "unknown weighting";
-  const int N = v->num_nodes, W = v->num_words;
-  if (N < 2) return "the vocabulary has no node below the root";
-  if (W < 1 || W > COVGPU_BOW_MAX_WORDS) return "num_words is not in 1..COVGPU_BOW_MAX_WORDS";
-  if (v->k < 1 || v->L < 0) return "k < 1 or L < 0";
-  if (!v->parent || !v->child_ptr || !v->child || !v->desc || !v->word_id || !v->weight) return "NULL vocabulary array";
-  if (v->parent[0] != -1) return "parent[0] != -1";
-  for (int n = 1; n < N; ++n) if (v->parent[n] < 0 || v->parent[n] >= n) return "parent[n] is not in 0..n-1";
-  if (v->child_ptr[0] != 0) return "child_ptr[0] != 0";
-  for (int n = 0; n < N; ++n) if (v->child_ptr[n + 1] < v->child_ptr[n]) return "child_ptr not monotone";
-  if (v->child_ptr[N] != N - 1) return "child_ptr[num_nodes] != num_nodes - 1";
-  std::vector<uint8_t> seen(W, 0);
-  for (int n = 0; n < N; ++n) {
-    for (int i = v->child_ptr[n]; i < v->child_ptr[n + 1]; ++i) {
-      const int c = v->child[i];
-      if (c <= 0 || c >= N) return "child index out of range";
-      if (v->parent[c] != n) return "child lists inconsistent with parent";
-      if (i > v->child_ptr[n] && c <= v->child[i - 1]) return "children not in ascending (line) order";
-    }
-    const bool leaf = v->child_ptr[n + 1] == v->child_ptr[n];
-    if (leaf != (v->word_id[n] >= 0)) return "leaves are not exactly the nodes with a word id";
-    if (leaf) {
-      if (v->word_id[n] >= W) return "word id out of range";
-      if (seen[v->word_id[n]]) return "word ids are not a permutation of 0..num_words-1";
-      seen[v->word_id[n]] = 1;
-    }
-    if (!std::isfinite(v->weight[n])) return "non-finite weight";
-  }
-  for (int w = 0; w < W; ++w) if (!seen[w]) return "word ids are not a permutation of 0..num_words-1";
-  return nullptr;
-}
-
-}  // namespace
-
-extern "C" int covgpu_bow_transform_batch(covgpu_context* c, const covgpu_bow_vocab_t* v, const covgpu_bow_transform_batch_t* bt) {
-  auto bad = [](const char* m) { g_err = std::string("covgpu_bow_transform_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
-  if (!c) return bad("NULL context");
-  if (!bt) return bad("NULL batch");
-  if (const char* m = bow_vocab_check(v)) return bad(m);
-  const int S = bt->num_sets;
-  if (S < 0 || bt->capacity < 0) return bad("num_sets or capacity < 0");
-  if (S > 0 && (!bt->row_ptr || !bt->bow_ptr)) return bad("NULL row_ptr or bow_ptr");
-  if (S > 0 && bt->row_ptr[0] != 0) return bad("row_ptr[0] != 0");
-  for (int s = 0; s < S; ++s) {
-    if (bt->row_ptr[s + 1] < bt->row_ptr[s]) return bad("row_ptr not monotone");
-    if (bt->row_ptr[s + 1] - bt->row_ptr[s] > COVGPU_MATCH_MAX_ROWS) return bad("a set holds more than COVGPU_MATCH_MAX_ROWS rows");
-  }
-  const size_t R = S > 0 ? (size_t)bt->row_ptr[S] : 0;
-  if (R > 0 && !bt->desc) return bad("NULL desc");
-  if (bt->capacity > 0 && (!bt->word || !bt->value)) return bad("NULL word or value");
-  if (bt->total) *bt->total = 0;
-  if (S == 0) return COVGPU_OK;
-  const int N = v->num_nodes, W = v->num_words;
-  std::vector<double> ww(W);
-  for (int n = 0; n < N; ++n) if (v->word_id[n] >= 0) ww[v->word_id[n]] = v->weight[n];
-  HIPCHK(hipSetDevice(c->device));                                   // the first device call: every argument is checked above
-  GuidedUpload U{c};
-  BowVocabDev V{};
-  V.num_nodes = N;
-  HIPCHK(U.up(v->child_ptr, 4 * ((size_t)N + 1), (void**)&V.child_ptr)); HIPCHK(U.up(v->child, 4 * ((size_t)N - 1), (void**)&V.child));
-  HIPCHK(U.up(v->desc, 32 * (size_t)N, (void**)&V.desc)); HIPCHK(U.up(v->word_id, 4 * (size_t)N, (void**)&V.word_id));
-  HIPCHK(U.up(ww.data(), 8 * (size_t)W, (void**)&V.word_weight));
-  unsigned char* ddesc = nullptr;
-  int *dptr_ = nullptr, *drw = nullptr, *drn = nullptr, *dow = nullptr, *dcnt = nullptr;
-  double* dov = nullptr;
-  HIPCHK(U.up(bt->desc, 32 * R, (void**)&ddesc)); HIPCHK(U.up(bt->row_ptr, 4 * ((size_t)S + 1), (void**)&dptr_));
-  HIPCHK(U.alloc((void**)&drw, 4 * R)); HIPCHK(U.alloc((void**)&drn, 4 * R)); HIPCHK(U.alloc((void**)&dow, 4 * R));
-  HIPCHK(U.alloc((void**)&dov, 8 * R)); HIPCHK(U.alloc((void**)&dcnt, 4 * (size_t)S));
-  const int add_weight = v->weighting == COVGPU_BOW_TF_IDF || v->weighting == COVGPU_BOW_TF;
-  launch_bow_transform(V, ddesc, dptr_, S, (int)R, v->L - bt->levelsup, add_weight, drw, drn, dow, dov, dcnt, c->st);
-  HIPCHK(hipGetLastError());
-  // each set's words sit at its first row; the exact CSR is packed from one download
-  std::vector<int32_t> hw(R), hc(S);
-  std::vector<double> hv(R);
-  if (R) {
-    HIPCHK(hipMemcpyAsync(hw.data(), dow, 4 * R, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipMemcpyAsync(hv.data(), dov, 8 * R, hipMemcpyDeviceToHost, c->st));
-    if (bt->row_word) HIPCHK(hipMemcpyAsync(bt->row_word, drw, 4 * R, hipMemcpyDeviceToHost, c->st));
-    if (bt->row_node) HIPCHK(hipMemcpyAsync(bt->row_node, drn, 4 * R, hipMemcpyDeviceToHost, c->st));
-  }
-  HIPCHK(hipMemcpyAsync(hc.data(), dcnt, 4 * (size_t)S, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  int64_t tot = 0;
-  bt->bow_ptr[0] = 0;
-  for (int s = 0; s < S; ++s) {
-    const int64_t room = std::max<int64_t>(0, std::min<int64_t>(hc[s], (int64_t)bt->capacity - tot));
-    if (room > 0) {
-      std::memcpy(bt->word + tot, hw.data() + bt->row_ptr[s], 4 * (size_t)room);
-      std::memcpy(bt->value + tot, hv.data() + bt->row_ptr[s], 8 * (size_t)room);
-    }
-    tot += hc[s];
-    bt->bow_ptr[s + 1] = (int32_t)tot;                                // tot <= rows <= 2^31 - 1
-  }
-  if (bt->total) *bt->total = tot;
-  return COVGPU_OK;
-}
-
-extern "C" int covgpu_bow_score_pairs(covgpu_context* c, int32_t num_vec, const int32_t* bow_ptr, const int32_t* word, const double* value,
-                                      int32_t num_pairs, const int32_t* a, const int32_t* b, double* score) {
-  auto bad = [](const char* m) { g_err = std::string("covgpu_bow_score_pairs: ") + m; return COVGPU_ERR_INVALID_ARG; };
-  if (!c) return bad("NULL context");
-  if (const char* m = bow_csr_check(num_vec, bow_ptr, word, value)) return bad(m);
-  if (num_pairs < 0) return bad("num_pairs < 0");
-  if (num_pairs > 0 && (!a || !b || !score)) return bad("NULL pair array");
-  for (int i = 0; i < num_pairs; ++i)
-    if (a[i] < 0 || a[i] >= num_vec || b[i] < 0 || b[i] >= num_vec) return bad("pair index out of range");
-  if (num_pairs == 0) return COVGPU_OK;
-  HIPCHK(hipSetDevice(c->device));
-  const size_t nnz = (size_t)bow_ptr[num_vec], P = (size_t)num_pairs;
-  GuidedUpload U{c};
-  int *dp = nullptr, *dw = nullptr, *da = nullptr, *db = nullptr;
-  double *dv = nullptr, *ds = nullptr;
-  HIPCHK(U.up(bow_ptr, 4 * ((size_t)num_vec + 1), (void**)&dp)); HIPCHK(U.up(word, 4 * nnz, (void**)&dw)); HIPCHK(U.up(value, 8 * nnz, (void**)&dv));
-  HIPCHK(U.up(a, 4 * P, (void**)&da)); HIPCHK(U.up(b, 4 * P, (void**)&db)); HIPCHK(U.alloc((void**)&ds, 8 * P));
-  launch_bow_score_pairs(dp, dw, dv, num_pairs, da, db, ds, c->st);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(score, ds, 8 * P, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return COVGPU_OK;
-}
-
-extern "C" void covgpu_default_detect_opts(covgpu_detect_opts* o, int32_t mode) {
-  if (!o) return;
-  o->min_score_factor = mode == COVGPU_DETECT_COVINS_G ? 0.7 : 0.8;  // placerec_gen_be.cpp / placerec_be.cpp:389
-  o->min_loop_dist = 100;                                            // config_backend.yaml:72-78
-  o->exclude_kfs_with_id_less_than = 7;
-  o->inter_map_matches_only = 0;
-  o->scratch_kib = 0;
-}
-
-extern "C" int covgpu_detect_candidates_batch(covgpu_context* c, const covgpu_detect_batch_t* bt, const covgpu_detect_opts* opts) {
-  auto bad = [](const char* m) { g_err = std::string("covgpu_detect_candidates_batch: ") + m; return COVGPU_ERR_INVALID_ARG; };
-  if (!c) return bad("NULL context");
-  if (!bt || !opts) return bad("NULL batch or options");
-  if (!std::isfinite(opts->min_score_factor)) return bad("non-finite min_score_factor");
-  if (opts->scratch_kib < 0) return bad("scratch_kib < 0");
-  const int N = bt->num_kf, M = bt->num_db, Q = bt->num_queries, cap = bt->cap;
-  if (N < 0 || M < 0 || Q < 0 || cap < 0) return bad("negative count");
-  if (N > 0 && (!bt->id || !bt->client || !bt->nb_ptr)) return bad("NULL keyframe array");
-  for (int k = 0; k < N; ++k) if (bt->id[k] < 0) return bad("negative keyframe id");
-  if (const char* m = bow_csr_check(N, bt->bow_ptr, bt->word, bt->value)) return bad(m);
-  if (N > 0 && bt->nb_ptr[0] != 0) return bad("nb_ptr[0] != 0");
-  for (int k = 0; k < N; ++k) if (bt->nb_ptr[k + 1] < bt->nb_ptr[k]) return bad("nb_ptr not monotone");
-  const size_t NB = N > 0 ? (size_t)bt->nb_ptr[N] : 0;
-  if (NB > 0 && !bt->nb) return bad("NULL nb");
-  for (size_t i = 0; i < NB; ++i) if (bt->nb[i] < 0 || bt->nb[i] >= N) return bad("neighbour index out of range");
-  if (M > 0 && !bt->db_order) return bad("NULL db_order");
-  std::vector<int32_t> pos_of(N > 0 ? N : 1, -1);
-  for (int p = 0; p < M; ++p) {
-    const int k = bt->db_order[p];
-    if (k < 0 || k >= N) return bad("db_order index out of range");
-    if (pos_of[k] >= 0) return bad("db_order repeats a keyframe");
-    pos_of[k] = p;
-  }
-  if (Q > 0 && (!bt->query_kf || !bt->db_visible || !bt->num_candidates)) return bad("NULL query array");
-  if (Q > 0 && cap > 0 && !bt->candidates) return bad("NULL candidates");
-  int max_words = 0;
-  size_t num_pairs = 0;
-  for (int q = 0; q < Q; ++q) {
-    const int k = bt->query_kf[q];
-    if (k < 0 || k >= N) return bad("query_kf out of range");
-    if (bt->db_visible[q] < 0 || bt->db_visible[q] > M) return bad("db_visible is not in 0..num_db");
-    if (bt->min_score_in && std::isnan(bt->min_score_in[q])) return bad("min_score_in is NaN");
-    max_words = std::max(max_words, bt->bow_ptr[k + 1] - bt->bow_ptr[k]);
-    num_pairs += (size_t)(bt->nb_ptr[k + 1] - bt->nb_ptr[k]);
-  }
-  if (num_pairs > (size_t)INT32_MAX) return bad("more than 2^31 - 1 query neighbours");
-  if (Q == 0) return COVGPU_OK;
-  // host side of the call: the reference-score pairs and the inverted index of the database (posting lists in insertion order)
-  std::vector<int32_t> pa, pb, poff(Q + 1, 0);
-  if (!bt->min_score_in) {
-    pa.reserve(num_pairs); pb.reserve(num_pairs);
-    for (int q = 0; q < Q; ++q) {
-      const int k = bt->query_kf[q];
-      for (int i = bt->nb_ptr[k]; i < bt->nb_ptr[k + 1]; ++i) {
-        if (bt->invalid && bt->invalid[bt->nb[i]]) continue;
-        pa.push_back(k); pb.push_back(bt->nb[i]);
-      }
-      poff[q + 1] = (int32_t)pa.size();
-    }
-  }
-  int inv_words = 0;
-  for (int p = 0; p < M; ++p) {
-    const int k = bt->db_order[p];
-    if (bt->bow_ptr[k + 1] > bt->bow_ptr[k]) inv_words = std::max(inv_words, bt->word[bt->bow_ptr[k + 1] - 1] + 1);
-  }
-  std::vector<int32_t> inv_ptr((size_t)inv_words + 1, 0);
-  for (int p = 0; p < M; ++p) {
-    const int k = bt->db_order[p];
-    for (int i = bt->bow_ptr[k]; i < bt->bow_ptr[k + 1]; ++i) ++inv_ptr[bt->word[i] + 1];
-  }
-  for (int w = 0; w < inv_words; ++w) {
-    if ((int64_t)inv_ptr[w + 1] + inv_ptr[w] > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 database words");
-    inv_ptr[w + 1] += inv_ptr[w];
-  }
-  std::vector<int32_t> inv_pos((size_t)inv_ptr[inv_words]), fill(inv_ptr.begin(), inv_ptr.end() - 1);
-  for (int p = 0; p < M; ++p) {
-    const int k = bt->db_order[p];
-    for (int i = bt->bow_ptr[k]; i < bt->bow_ptr[k + 1]; ++i) inv_pos[fill[bt->word[i]]++] = p;
-  }
-  HIPCHK(hipSetDevice(c->device));                                   // the first device call: every argument is checked above
-  GuidedUpload U{c};
-  DetectDev D{};
-  D.M = M; D.inv_words = inv_words;
-  const size_t nnz = N > 0 ? (size_t)bt->bow_ptr[N] : 0, Qs = (size_t)Q, caps = (size_t)cap;
-  HIPCHK(U.up(bt->id, 4 * (size_t)N, (void**)&D.id)); HIPCHK(U.up(bt->client, 4 * (size_t)N, (void**)&D.client));
-  HIPCHK(U.up(bt->bow_ptr, 4 * ((size_t)N + 1), (void**)&D.bow_ptr)); HIPCHK(U.up(bt->word, 4 * nnz, (void**)&D.word));
-  HIPCHK(U.up(bt->value, 8 * nnz, (void**)&D.value)); HIPCHK(U.up(bt->nb_ptr, 4 * ((size_t)N + 1), (void**)&D.nb_ptr));
-  HIPCHK(U.up(bt->nb, 4 * NB, (void**)&D.nb)); HIPCHK(U.up(bt->db_order, 4 * (size_t)M, (void**)&D.db_order));
-  HIPCHK(U.up(pos_of.data(), 4 * (size_t)N, (void**)&D.pos_of)); HIPCHK(U.up(inv_ptr.data(), 4 * inv_ptr.size(), (void**)&D.inv_ptr));
-  HIPCHK(U.up(inv_pos.data(), 4 * inv_pos.size(), (void**)&D.inv_pos)); HIPCHK(U.up(bt->query_kf, 4 * Qs, (void**)&D.query_kf));
-  HIPCHK(U.up(bt->db_visible, 4 * Qs, (void**)&D.db_visible));
-  if (bt->min_score_in) HIPCHK(U.up(bt->min_score_in, 8 * Qs, (void**)&D.min_score)); else HIPCHK(U.alloc((void**)&D.min_score, 8 * Qs));
-  int* counters = nullptr;                                           // max_common, num_sharing, num_scored, num_candidates
-  HIPCHK(U.alloc((void**)&counters, 16 * Qs));
-  HIPCHK(hipMemsetAsync(counters, 0, 16 * Qs, c->st));
-  D.max_common = counters; D.num_sharing = counters + Q; D.num_scored = counters + 2 * Qs; D.num_candidates = counters + 3 * Qs;
-  HIPCHK(U.alloc((void**)&D.candidates, 4 * Qs * caps)); HIPCHK(U.alloc((void**)&D.acc_score, 4 * Qs * caps));
-  if (cap > 0) { HIPCHK(hipMemsetAsync(D.candidates, 0xff, 4 * Qs * caps, c->st)); HIPCHK(hipMemsetAsync(D.acc_score, 0, 4 * Qs * caps, c->st)); }
-  if (!bt->min_score_in) {
-    int *dpa = nullptr, *dpb = nullptr, *dpo = nullptr;
-    double* dps = nullptr;
-    HIPCHK(U.up(pa.data(), 4 * pa.size(), (void**)&dpa)); HIPCHK(U.up(pb.data(), 4 * pb.size(), (void**)&dpb));
-    HIPCHK(U.up(poff.data(), 4 * poff.size(), (void**)&dpo)); HIPCHK(U.alloc((void**)&dps, 8 * pa.size()));
-    launch_bow_score_pairs(D.bow_ptr, D.word, D.value, (int)pa.size(), dpa, dpb, dps, c->st);
-    launch_bow_min_score(D, Q, dpo, dps, opts->min_score_factor, c->st);
-  }
-  // per-query scratch is 28 B per database entry; queries run in chunks that keep it within the budget
-  const size_t budget = (size_t)(opts->scratch_kib > 0 ? opts->scratch_kib : 65536) << 10;
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>(Qs, budget / (28 * std::max<size_t>(1, (size_t)M))));
-  const size_t cm = (size_t)chunk * (size_t)M;
-  const int hist_stride = max_words + 1;
-  int *common = nullptr, *first = nullptr, *best = nullptr, *order = nullptr, *hist = nullptr;
-  double* score = nullptr;
-  float* acc = nullptr;
-  HIPCHK(U.alloc((void**)&common, 4 * cm)); HIPCHK(U.alloc((void**)&first, 4 * cm)); HIPCHK(U.alloc((void**)&score, 8 * cm));
-  HIPCHK(U.alloc((void**)&acc, 4 * cm)); HIPCHK(U.alloc((void**)&best, 4 * cm)); HIPCHK(U.alloc((void**)&order, 4 * cm));
-  HIPCHK(U.alloc((void**)&hist, 4 * (size_t)chunk * (size_t)hist_stride));
-  const DetectOptsDev O{opts->min_loop_dist, opts->exclude_kfs_with_id_less_than, opts->inter_map_matches_only != 0};
-  for (int q0 = 0; q0 < Q; q0 += chunk)
-    launch_bow_detect_chunk(D, O, q0, std::min(chunk, Q - q0), cap, hist_stride, common, first, score, acc, best, order, hist, c->st);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(bt->num_candidates, D.num_candidates, 4 * Qs, hipMemcpyDeviceToHost, c->st));
-  if (bt->max_common_words) HIPCHK(hipMemcpyAsync(bt->max_common_words, D.max_common, 4 * Qs, hipMemcpyDeviceToHost, c->st));
-  if (bt->num_sharing) HIPCHK(hipMemcpyAsync(bt->num_sharing, D.num_sharing, 4 * Qs, hipMemcpyDeviceToHost, c->st));
-  if (bt->num_scored) HIPCHK(hipMemcpyAsync(bt->num_scored, D.num_scored, 4 * Qs, hipMemcpyDeviceToHost, c->st));
-  if (bt->min_score) HIPCHK(hipMemcpyAsync(bt->min_score, D.min_score, 8 * Qs, hipMemcpyDeviceToHost, c->st));
-  if (cap > 0) {
-    HIPCHK(hipMemcpyAsync(bt->candidates, D.candidates, 4 * Qs * caps, hipMemcpyDeviceToHost, c->st));
-    if (bt->acc_score) HIPCHK(hipMemcpyAsync(bt->acc_score, D.acc_score, 4 * Qs * caps, hipMemcpyDeviceToHost, c->st));
-  }
-  HIPCHK(hipStreamSynchronize(c->st));
   return COVGPU_OK;
 }

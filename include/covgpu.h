@@ -37,6 +37,10 @@ enum {
   COVGPU_ERR_NUMERIC = 4,       /* single linear solve not positive definite (covgpu_solve_reduced, covgpu_gn_step) */
   COVGPU_ERR_FATAL_MAP = 5      /* conditions on which the reference calls exit(-1)           */
 };
+/* The stateless batch calls (covgpu_relpose_batch, covgpu_abspose_ransac_batch, covgpu_p3p_batch, covgpu_match_batch,
+ * covgpu_search_se3_batch, covgpu_search_projection_batch, covgpu_pgo_reanchor, covgpu_bow_transform_batch, covgpu_bow_score_pairs,
+ * covgpu_detect_candidates_batch; covins_amd/csrc/batch.hip) share one convention: a NULL context is COVGPU_ERR_INVALID_ARG with the
+ * message "<function>: NULL context", and every argument is checked before any device work. */
 
 /* trust-region strategy (reference uses DOGLEG: optimization_be.cpp:261,564,1028;
  * BASELINE.json north_star asks for Levenberg-Marquardt as well) */

@@ -169,6 +169,28 @@ def test_library_defaults_and_argument_checks_need_no_device():
     assert backend.lib().covgpu_bow_score_pairs(None, 0, None, None, None, 0, None, None, None) == 1
 
 
+def test_every_batch_entry_point_rejects_a_null_context_by_name():
+    """The shared prologue of batch.hip: INVALID_ARG and "<function>: NULL context", whatever the other arguments are."""
+    import ctypes as C
+    lib = backend.lib()
+    calls = {
+        "covgpu_relpose_batch": (None, C.c_double(1.3), 12),
+        "covgpu_abspose_ransac_batch": (None, None),
+        "covgpu_p3p_batch": (0, None, None, None, None, None),
+        "covgpu_match_batch": (None, None),
+        "covgpu_search_se3_batch": (None, None),
+        "covgpu_search_projection_batch": (None, None),
+        "covgpu_pgo_reanchor": (0, None, None, None, 0, None, None),
+        "covgpu_bow_transform_batch": (None, None),
+        "covgpu_bow_score_pairs": (0, None, None, None, 0, None, None, None),
+        "covgpu_detect_candidates_batch": (None, None),
+    }
+    for name, args in calls.items():
+        assert getattr(lib, name)(None, *args) == 1, name               # COVGPU_ERR_INVALID_ARG
+        msg = lib.covgpu_last_error()
+        assert b"NULL context" in msg and name.encode() in msg, (name, msg)
+
+
 def test_facade_bow_shim_compiles():
     """KeyframeDatabaseT instantiates on the stand-in map (tests/test_gpu_bow.py drives it)."""
     lib = bu.bow_shim()

@@ -117,6 +117,12 @@ def test_score_pairs(ctx):
     assert len(ctx.bow_score_pairs(ptr, tab.word, tab.value, [], [])) == 0
 
 
+def test_score_of_two_empty_vectors_in_a_csr_without_entries(ctx):
+    """The word and value arrays are empty: their device buffers are the zero-sized ones, which the kernel never reads."""
+    got = ctx.bow_score_pairs(np.zeros(3, np.int32), np.zeros(0, np.int32), np.zeros(0), [0], [1])
+    assert got.shape == (1,) and got[0] == 0.0
+
+
 # ---------------------------------------------------------------- candidates
 
 KEYS = ("num_candidates", "min_score", "num_sharing", "max_common_words", "num_scored")

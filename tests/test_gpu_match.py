@@ -134,6 +134,13 @@ def test_edge_cases(ctx):
         _check(ctx, bt, mode)
 
 
+def test_dense_job_with_an_empty_query_set_and_no_skip_flags(ctx):
+    """No output row at all: the list, match and distance buffers of the call are the zero-sized ones."""
+    desc = np.random.default_rng(28).integers(0, 256, (3, 32), dtype=np.uint8)
+    r = ctx.match_batch(dict(row_ptr=np.array([0, 0, 3], np.int32), desc=desc), [0], [1], "dense")
+    assert list(r["nmatches"]) == [0] and len(r["match"]) == 0 and list(r["offset"]) == [0, 0]
+
+
 def test_invalid_arguments_are_rejected(ctx):
     rng = np.random.default_rng(29)
     sets = dict(row_ptr=np.array([0, 20, 35], np.int32), desc=rng.integers(0, 256, (35, 32), dtype=np.uint8))
