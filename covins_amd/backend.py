@@ -519,6 +519,60 @@ class Context:
         return dict(candidates=[cand[q, :kept[q]].copy() for q in range(Q)], acc_score=[acc[q, :kept[q]].copy() for q in range(Q)],
                     num_candidates=nc[:Q], min_score=mso[:Q], num_sharing=nsh[:Q], max_common_words=mcw[:Q], num_scored=nsc[:Q])
 
+    @staticmethod
+    def _prune_batch(lm_obs_ptr, obs_kf, kf_pred, kf_succ, kf_time, lm_invalid, kf_invalid, kf_first, kf_loop, kf_not_erase, capacity,
+                     opts, want_loop_ms=False):
+        """(PruneBatch, PruneOpts, outputs, keep-alive list) of one covgpu_prune_redundant call."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ravel()
+        flag = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint8).ravel()
+        ptr, okf, pred, succ = i32(lm_obs_ptr), i32(obs_kf), i32(kf_pred), i32(kf_succ)
+        time = np.ascontiguousarray(kf_time, dtype=np.float64).ravel()
+        K, L = len(pred), len(ptr) - 1
+        flags = [flag(a) for a in (lm_invalid, kf_invalid, kf_first, kf_loop, kf_not_erase)]
+        if L < 0 or len(succ) != K or len(time) != K or any(f is not None and len(f) != n for f, n in zip(flags, (L, K, K, K, K))):
+            raise ValueError("prune arrays differ in length")
+        if int(ptr[-1]) > len(okf):
+            raise ValueError("lm_obs_ptr runs past obs_kf")
+        o = capi.PruneOpts()
+        lib().covgpu_default_prune_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("th_red", "max_time_dist", "max_kfs", "max_rounds"):
+                raise TypeError(f"unknown prune option {k}")
+            setattr(o, k, -1 if k == "max_kfs" and v is None else v)
+        cap = K if capacity is None else int(capacity)
+        out = dict(round_kf=np.full(max(cap, 1), -1, np.int32), round_action=np.full(max(cap, 1), -1, np.int32),
+                   scal=np.zeros(3, np.int32), kf_pred=np.zeros(max(K, 1), np.int32), kf_succ=np.zeros(max(K, 1), np.int32),
+                   lm_nobs=np.zeros(max(L, 1), np.int32), red_num=np.zeros(max(K, 1), np.int32), red_den=np.zeros(max(K, 1), np.int32),
+                   loop_ms=np.zeros(1))
+        bp = lambda a: None if a is None else a.ctypes.data_as(capi._bp)
+        sc = out["scal"]
+        s = capi.PruneBatch(K, L, iptr(ptr), iptr(okf), *(bp(f) for f in flags), iptr(pred), iptr(succ), dptr(time), cap,
+                            iptr(out["round_kf"]), iptr(out["round_action"]), iptr(sc[0:1]), iptr(sc[1:2]), iptr(sc[2:3]),
+                            iptr(out["kf_pred"]), iptr(out["kf_succ"]), iptr(out["lm_nobs"]), iptr(out["red_num"]), iptr(out["red_den"]),
+                            dptr(out["loop_ms"]) if want_loop_ms else None)
+        return s, o, out, [ptr, okf, pred, succ, time, flags]
+
+    def prune_redundant(self, lm_obs_ptr, obs_kf, kf_pred, kf_succ, kf_time, lm_invalid=None, kf_invalid=None, kf_first=None, kf_loop=None,
+                        kf_not_erase=None, capacity: Optional[int] = None, loop_ms: bool = False, **opts):
+        """Map::RemoveRedundantData as one device call (covgpu_prune_redundant, DESIGN.md §4.14): the greedy loop over the redundancy
+        values, exact in integers. Observations are landmark-major (lm_obs_ptr [L+1], obs_kf [O] keyframe table indices); kf_pred /
+        kf_succ are table indices or -1; the flag arrays may be None (none set). `opts`: th_red (0.95), max_time_dist (1.0), max_kfs (None
+        or < 0: threshold mode), max_rounds (<= 0: K). `capacity` (default K) bounds the round records kept. Returns dict(round_kf,
+        round_action (0 erased, 1 time gate, 2 loop keyframe, 3 not_erase), num_rounds (the true count), removed (actions 0 + 3, the
+        reference's return value), stop_reason, kf_pred, kf_succ (the relinked chain), lm_nobs, red_num, red_den; loop_ms if asked for)."""
+        s, o, out, keep = self._prune_batch(lm_obs_ptr, obs_kf, kf_pred, kf_succ, kf_time, lm_invalid, kf_invalid, kf_first, kf_loop,
+                                            kf_not_erase, capacity, opts, loop_ms)
+        self._check(lib().covgpu_prune_redundant(self._h, C.byref(s), C.byref(o)))
+        K, L = s.num_kf, s.num_lm
+        n, removed, stop = (int(x) for x in out["scal"])
+        kept = min(n, s.capacity)
+        r = dict(round_kf=out["round_kf"][:kept].copy(), round_action=out["round_action"][:kept].copy(), num_rounds=n, removed=removed,
+                 stop_reason=stop, kf_pred=out["kf_pred"][:K], kf_succ=out["kf_succ"][:K], lm_nobs=out["lm_nobs"][:L],
+                 red_num=out["red_num"][:K], red_den=out["red_den"][:K])
+        if loop_ms:
+            r["loop_ms"] = float(out["loop_ms"][0])
+        return r
+
     def p3p_batch(self, f, P):
         """covgpu_p3p_batch: f, P [n,4,3] -> (T [n,4,7] every solution, qx qy qz qw x y z, ascending v = s3/s1; nsol [n]; chosen [n], -1: none)."""
         f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 4, 3)

@@ -276,6 +276,22 @@ class DetectBatch(C.Structure):
                 ("acc_score", _fp), ("min_score", _dp), ("num_sharing", _ip), ("max_common_words", _ip), ("num_scored", _ip)]
 
 
+class PruneBatch(C.Structure):
+    """covgpu_prune_t (include/covgpu.h): Map::RemoveRedundantData as one call, DESIGN.md §4.14."""
+    _fields_ = [("num_kf", C.c_int32), ("num_lm", C.c_int32), ("lm_obs_ptr", _ip), ("obs_kf", _ip), ("lm_invalid", _bp), ("kf_invalid", _bp),
+                ("kf_first", _bp), ("kf_loop", _bp), ("kf_not_erase", _bp), ("kf_pred", _ip), ("kf_succ", _ip), ("kf_time", _dp),
+                ("capacity", C.c_int32), ("round_kf", _ip), ("round_action", _ip), ("num_rounds", _ip), ("removed", _ip), ("stop_reason", _ip),
+                ("kf_pred_out", _ip), ("kf_succ_out", _ip), ("lm_nobs", _ip), ("red_num", _ip), ("red_den", _ip), ("loop_ms", _dp)]
+
+
+class PruneOpts(C.Structure):
+    _fields_ = [("th_red", C.c_double), ("max_time_dist", C.c_double), ("max_kfs", C.c_int32), ("max_rounds", C.c_int32)]
+
+
+PRUNE_ERASED, PRUNE_TIME_GATE, PRUNE_LOOP_KF, PRUNE_NOT_ERASE = 0, 1, 2, 3                       # round_action
+PRUNE_STOP_NO_CANDIDATES, PRUNE_STOP_THRESHOLD, PRUNE_STOP_MAX_KFS, PRUNE_STOP_MAX_ROUNDS = 0, 1, 2, 3   # stop_reason
+
+
 def declare(lib: C.CDLL, prefix: str) -> None:
     """Attach argtypes/restype for the entry points shared by libcovgpu (prefix 'covgpu_', with a context
     argument) and — test side only — the oracle (prefix 'covo_', no context)."""
@@ -321,6 +337,9 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("bow_score_pairs", [C.c_void_p, C.c_int32, _ip, _ip, _dp, C.c_int32, _ip, _ip, _dp])
         d("default_detect_opts", [C.POINTER(DetectOpts), C.c_int32], None)
         d("detect_candidates_batch", [C.c_void_p, C.POINTER(DetectBatch), C.POINTER(DetectOpts)])
+        d("default_prune_opts", [C.POINTER(PruneOpts)], None)
+        d("prune_check", [C.POINTER(PruneBatch), C.POINTER(PruneOpts)])
+        d("prune_redundant", [C.c_void_p, C.POINTER(PruneBatch), C.POINTER(PruneOpts)])
         d("outlier_pass", [C.c_void_p, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])
         d("covisibility", [C.c_void_p, C.c_int32, C.c_int64, _ip, _ip, _ip, C.POINTER(C.c_int64)])
         d("gba_solve_multi", [OP, PP, RP, C.c_int32, _ip, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])

@@ -2,7 +2,8 @@
 // run its kernels on the context's stream and hand the results back. Nothing here touches the resident problem of the solver
 // (solver.hip): a context lends its device and its stream only. Serves DESIGN.md §4.9 (relative pose, k_relpose.hip; the landmark
 // re-anchoring behind a pose-graph solve), §4.10 (P3P RANSAC, k_abspose.hip), §4.11 (descriptor matching, k_match.hip), §4.12
-// (guided matching, k_guided.hip) and §4.13 (bag-of-words transform, score and candidate query, k_bow.hip).
+// (guided matching, k_guided.hip), §4.13 (bag-of-words transform, score and candidate query, k_bow.hip) and §4.14 (redundant-keyframe
+// pruning, k_prune.hip).
 // Every entry point checks all its arguments before its first device call, holds its device buffers in one DeviceScratch
 // (host.hpp) and synchronises its stream once, at the end.
 #include <algorithm>
@@ -688,6 +689,111 @@ extern "C" int covgpu_detect_candidates_batch(covgpu_context* c, const covgpu_de
     HIPCHK(U.fetch(bt->min_score, D.min_score, Qs));
     HIPCHK(U.fetch(bt->candidates, D.candidates, Qs * caps)); HIPCHK(U.fetch(bt->acc_score, D.acc_score, Qs * caps));
     HIPCHK(hipStreamSynchronize(c->st));
+    return COVGPU_OK;
+  });
+}
+
+// ---- redundant-keyframe pruning (k_prune.hip) ----
+extern "C" void covgpu_default_prune_opts(covgpu_prune_opts* o) {
+  if (!o) return;
+  o->th_red = 0.95; o->max_time_dist = 1.0;                            // config_backend.yaml:58-59
+  o->max_kfs = -1; o->max_rounds = 0;
+}
+
+namespace {
+
+// The first violation of a prune call's arguments, or nullptr.
+const char* prune_check(const covgpu_prune_t* p, const covgpu_prune_opts* o) {
+  if (!p || !o) return "NULL problem or options";
+  if (!std::isfinite(o->th_red) || !std::isfinite(o->max_time_dist)) return "non-finite th_red or max_time_dist";
+  const int K = p->num_kf, L = p->num_lm;
+  if (K < 0 || L < 0 || p->capacity < 0) return "negative count";
+  if (!p->lm_obs_ptr) return "NULL lm_obs_ptr";
+  if (p->lm_obs_ptr[0] != 0) return "lm_obs_ptr[0] != 0";
+  for (int l = 0; l < L; ++l) if (p->lm_obs_ptr[l + 1] < p->lm_obs_ptr[l]) return "lm_obs_ptr not monotone";
+  const int O = p->lm_obs_ptr[L];
+  if (O > 0 && !p->obs_kf) return "NULL obs_kf";
+  for (int i = 0; i < O; ++i) if (p->obs_kf[i] < 0 || p->obs_kf[i] >= K) return "obs_kf out of range";
+  if (K > 0 && (!p->kf_pred || !p->kf_succ || !p->kf_time)) return "NULL keyframe array";
+  if (p->capacity > 0 && (!p->round_kf || !p->round_action)) return "NULL round array";
+  for (int k = 0; k < K; ++k) {
+    if (!std::isfinite(p->kf_time[k])) return "non-finite kf_time";
+    if (p->kf_pred[k] < -1 || p->kf_pred[k] >= K || p->kf_succ[k] < -1 || p->kf_succ[k] >= K) return "kf_pred or kf_succ out of range";
+  }
+  for (int k = 0; k < K; ++k) {
+    const int pr = p->kf_pred[k], su = p->kf_succ[k];
+    if ((pr >= 0 && p->kf_succ[pr] >= 0 && p->kf_succ[pr] != k) || (su >= 0 && p->kf_pred[su] >= 0 && p->kf_pred[su] != k))
+      return "kf_pred and kf_succ are not mutual";
+  }
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" int covgpu_prune_check(const covgpu_prune_t* p, const covgpu_prune_opts* o) {
+  return guarded([&]() -> int {
+    if (const char* m = prune_check(p, o)) { g_err = std::string("covgpu_prune_check: ") + m; return COVGPU_ERR_INVALID_ARG; }
+    return COVGPU_OK;
+  });
+}
+
+extern "C" int covgpu_prune_redundant(covgpu_context* c, const covgpu_prune_t* p, const covgpu_prune_opts* o) {
+  return batch_entry("covgpu_prune_redundant", c, [&](auto bad) -> int {
+    if (const char* m = prune_check(p, o)) return bad(m);
+    const int K = p->num_kf, L = p->num_lm;
+    const size_t Ks = (size_t)K, Ls = (size_t)L, Os = (size_t)p->lm_obs_ptr[L];
+    int valid0 = 0;
+    for (int k = 0; k < K; ++k) valid0 += !(p->kf_invalid && p->kf_invalid[k]);
+    if (p->loop_ms) *p->loop_ms = 0.0;
+    if (K == 0) {   // nothing to rank (and no observation: obs_kf has no valid value)
+      if (p->num_rounds) *p->num_rounds = 0;
+      if (p->removed) *p->removed = 0;
+      if (p->stop_reason) *p->stop_reason = o->max_kfs >= 0 ? 2 : 0;
+      if (p->lm_nobs) std::fill(p->lm_nobs, p->lm_nobs + L, 0);
+      return COVGPU_OK;
+    }
+    int32_t res[3] = {0, 0, 0};
+    HIPCHK(hipSetDevice(c->device));
+    struct Events {   // around the greedy loop, only when the caller asks for its time
+      hipEvent_t a = nullptr, b = nullptr;
+      ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    DeviceScratch U(c->st);
+    PruneDev D{};
+    D.K = K; D.L = L;
+    HIPCHK(U.upload(&D.lm_ptr, p->lm_obs_ptr, Ls + 1)); HIPCHK(U.upload(&D.obs_kf, p->obs_kf, Os));
+    if (p->lm_invalid) HIPCHK(U.upload(&D.lm_invalid, p->lm_invalid, Ls));
+    if (p->kf_invalid) HIPCHK(U.upload(&D.kf_invalid, p->kf_invalid, Ks));
+    if (p->kf_first) HIPCHK(U.upload(&D.kf_first, p->kf_first, Ks));
+    if (p->kf_loop) HIPCHK(U.upload(&D.kf_loop, p->kf_loop, Ks));
+    if (p->kf_not_erase) HIPCHK(U.upload(&D.kf_not_erase, p->kf_not_erase, Ks));
+    HIPCHK(U.upload(&D.time, p->kf_time, Ks));
+    HIPCHK(U.upload(&D.pred, p->kf_pred, Ks)); HIPCHK(U.upload(&D.succ, p->kf_succ, Ks));
+    HIPCHK(U.alloc(&D.kf_ptr, Ks + 1)); HIPCHK(U.alloc(&D.kf_lm, Os)); HIPCHK(U.alloc(&D.cnt, Ks));
+    HIPCHK(U.alloc(&D.lm_nobs, Ls));
+    HIPCHK(U.alloc(&D.num, Ks)); HIPCHK(U.alloc(&D.den, Ks)); HIPCHK(U.alloc(&D.live, Ks)); HIPCHK(U.alloc(&D.cand, Ks));
+    HIPCHK(U.alloc(&D.out_num, Ks)); HIPCHK(U.alloc(&D.out_den, Ks));
+    const int max_rounds = o->max_rounds > 0 ? std::min(o->max_rounds, K) : K;   // (a round takes a candidate: never more than K)
+    D.cap = std::min(p->capacity, max_rounds);
+    HIPCHK(U.alloc(&D.round_kf, (size_t)D.cap)); HIPCHK(U.alloc(&D.round_action, (size_t)D.cap));
+    HIPCHK(U.zeroed(&D.result, 3));
+    const PruneOptsDev OD{o->th_red, o->max_time_dist, o->max_kfs, o->max_rounds > 0 ? o->max_rounds : K, valid0};
+    launch_prune_setup(D, c->st);
+    if (p->loop_ms) { HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b)); HIPCHK(hipEventRecord(ev.a, c->st)); }
+    launch_prune_loop(D, OD, c->st);
+    if (p->loop_ms) HIPCHK(hipEventRecord(ev.b, c->st));
+    launch_prune_finish(D, c->st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(U.fetch(res, D.result, 3));
+    HIPCHK(U.fetch(p->round_kf, D.round_kf, (size_t)D.cap)); HIPCHK(U.fetch(p->round_action, D.round_action, (size_t)D.cap));
+    HIPCHK(U.fetch(p->kf_pred_out, D.pred, Ks)); HIPCHK(U.fetch(p->kf_succ_out, D.succ, Ks));
+    HIPCHK(U.fetch(p->lm_nobs, D.lm_nobs, Ls));
+    HIPCHK(U.fetch(p->red_num, D.out_num, Ks)); HIPCHK(U.fetch(p->red_den, D.out_den, Ks));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (p->loop_ms) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b)); *p->loop_ms = ms; }
+    if (p->num_rounds) *p->num_rounds = res[0];
+    if (p->removed) *p->removed = res[1];
+    if (p->stop_reason) *p->stop_reason = res[2];
     return COVGPU_OK;
   });
 }

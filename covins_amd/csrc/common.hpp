@@ -658,4 +658,24 @@ void launch_bow_detect_chunk(const DetectDev& D, const DetectOptsDev& O, int q0,
 void launch_reanchor(int K, const double* pose_old, const double* pose_new, double* vel, int L, const int* ref, double* lm,
                      hipStream_t st);
 
+// k_prune.hip: Map::RemoveRedundantData as an exact integer rule. Device arrays throughout; a flag array may be nullptr (none set).
+struct PruneDev {
+  int K, L;
+  const int* lm_ptr; const int* obs_kf;                               // landmark-major observation lists, as given
+  const unsigned char* lm_invalid;                                    // [L]
+  const unsigned char* kf_invalid; const unsigned char* kf_first; const unsigned char* kf_loop; const unsigned char* kf_not_erase;   // [K]
+  const double* time;                                                 // [K]
+  int* pred; int* succ;                                               // [K] working copies: relinked in place
+  int* kf_ptr; int* kf_lm; int* cnt;                                  // [K+1], [O], [K] the keyframe-major transpose, built by the set-up
+  int* lm_nobs;                                                       // [L] live observations
+  int* num; int* den; int* live; int* cand;                           // [K]
+  int* out_num; int* out_den;                                         // [K] num / den at the round that handled the keyframe, else the final ones
+  int* round_kf; int* round_action; int cap;                          // the first `cap` round records
+  int* result;                                                        // [3] rounds, removed (actions 0 + 3), stop reason
+};
+struct PruneOptsDev { double th_red, max_time_dist; int max_kfs, max_rounds, valid0; };   // max_rounds > 0; valid0: valid keyframes before round 0
+void launch_prune_setup(const PruneDev& P, hipStream_t st);
+void launch_prune_loop(const PruneDev& P, const PruneOptsDev& O, hipStream_t st);   // one workgroup, every round
+void launch_prune_finish(const PruneDev& P, hipStream_t st);
+
 }  // namespace covgpu

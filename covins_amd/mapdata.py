@@ -117,6 +117,44 @@ class SlamMap:
         self.obs_kf, self.obs_uv, self.obs_octave = self.obs_kf.take(rows), self.obs_uv.take(rows, axis=0), self.obs_octave.take(rows)
         self.lm_obs_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
 
+    def remove_keyframes(self, rounds) -> int:
+        """Keyframe::SetInvalid (keyframe_be.cpp:500-540) for the erased keyframes of a prune result, in round order. `rounds`: the dict
+        Context.prune_redundant returns, or (keyframe, action) pairs; only action 0 erases. Per keyframe: invalid, its observations
+        dropped, pred[succ] / succ[pred] relinked, and the successor's IMU buffer fused as Keyframe::FusePreintegration does (:413-440):
+        the removed keyframe's samples followed by its own, imu_first the removed keyframe's (the reading at the new predecessor), its
+        biases and calibration untouched. A landmark that lost an observation takes its first remaining observer as reference keyframe,
+        -1 when none is left (LandmarkBase::EraseObservation, landmark_base.cpp:105-110). Returns the number of keyframes erased."""
+        if isinstance(rounds, dict):
+            rounds = zip(rounds["round_kf"], rounds["round_action"])
+        erased = [int(k) for k, a in rounds if int(a) == 0]
+        if not erased:
+            return 0
+        chunks = [self.imu_samples[self.imu_ptr[k]:self.imu_ptr[k + 1]] for k in range(self.K)]
+        empty = self.imu_samples[:0]
+        for k in erased:
+            p, s = int(self.kf_pred[k]), int(self.kf_succ[k])
+            if self.kf_invalid[k] or p < 0 or s < 0:
+                raise ValueError(f"keyframe {k} cannot be erased: invalid already, or without predecessor or successor")
+            self.kf_invalid[k] = True
+            self.kf_succ[p], self.kf_pred[s] = s, p
+            chunks[s] = np.concatenate([chunks[k], chunks[s]])
+            chunks[k] = empty
+            self.imu_first[s] = self.imu_first[k]
+        self.imu_samples = np.concatenate(chunks) if self.K else self.imu_samples
+        self.imu_ptr = np.concatenate([[0], np.cumsum([len(c) for c in chunks])]).astype(self.imu_ptr.dtype)
+        gone = np.zeros(self.K, bool)
+        gone[erased] = True
+        mask = gone[self.obs_kf] if self.O else np.zeros(0, bool)
+        touched = np.zeros(self.L, bool)
+        touched[np.repeat(np.arange(self.L), np.diff(self.lm_obs_ptr))[mask]] = True
+        self.erase_observations(mask)
+        has = np.diff(self.lm_obs_ptr) > 0
+        first = np.full(self.L, -1, self.lm_ref_kf.dtype)
+        first[has] = self.obs_kf[self.lm_obs_ptr[:-1][has]]
+        touched |= (self.lm_ref_kf >= 0) & gone[np.maximum(self.lm_ref_kf, 0)]   # (a reference keyframe that is no listed observer)
+        self.lm_ref_kf = np.where(touched, first, self.lm_ref_kf)
+        return len(erased)
+
     def clean(self) -> int:
         """Map::Clean (map_be.cpp:448-454, 698-743): invalidate landmarks left with < 2 observations."""
         n = np.diff(self.lm_obs_ptr)

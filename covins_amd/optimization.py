@@ -173,3 +173,30 @@ class Optimization:
         finally:
             if own:
                 ctx.close()
+
+
+def remove_redundant_data(m: SlamMap, ctx: Optional[backend.Context] = None, th_red: float = 0.95, max_kfs: Optional[int] = None,
+                          max_time_dist: float = 1.0, kf_not_erase: Optional[np.ndarray] = None, info: Optional[dict] = None) -> int:
+    """Map::RemoveRedundantData(mapmanager, th_red, max_kfs) (map_be.cpp:745-811) over `SlamMap`: Map::Clean, the greedy loop over the
+    redundancy values as one device call (covgpu_prune_redundant), then SetInvalid of the erased keyframes in round
+    order (SlamMap.remove_keyframes). `max_kfs` None is the reference's numeric_limits<size_t>::max(): remove while the top value is
+    >= th_red; otherwise remove until max_kfs valid keyframes are left. `max_time_dist` is covins_params::mapping::
+    kf_culling_max_time_dist. The keyframes of the map's loop constraints are its loop keyframes (is_loop_kf_). Returns the
+    reference's count (erased keyframes plus those SetInvalid refused for not_erase_); `info` receives the call's result dict."""
+    own = ctx is None
+    ctx = ctx or backend.Context()
+    try:
+        m.clean()
+        loop = np.zeros(m.K, bool)
+        for l in m.loops:
+            loop[l.kf1] = loop[l.kf2] = True
+        r = ctx.prune_redundant(m.lm_obs_ptr, m.obs_kf, m.kf_pred, m.kf_succ, m.kf_time, lm_invalid=m.lm_invalid, kf_invalid=m.kf_invalid,
+                                kf_first=m.kf_id == 0, kf_loop=loop, kf_not_erase=kf_not_erase, th_red=th_red, max_kfs=max_kfs,
+                                max_time_dist=max_time_dist)
+        m.remove_keyframes(r)
+        if info is not None:
+            info.update(r)
+        return r["removed"]
+    finally:
+        if own:
+            ctx.close()

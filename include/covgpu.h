@@ -39,7 +39,7 @@ enum {
 };
 /* The stateless batch calls (covgpu_relpose_batch, covgpu_abspose_ransac_batch, covgpu_p3p_batch, covgpu_match_batch,
  * covgpu_search_se3_batch, covgpu_search_projection_batch, covgpu_pgo_reanchor, covgpu_bow_transform_batch, covgpu_bow_score_pairs,
- * covgpu_detect_candidates_batch; covins_amd/csrc/batch.hip) share one convention: a NULL context is COVGPU_ERR_INVALID_ARG with the
+ * covgpu_detect_candidates_batch, covgpu_prune_redundant; covins_amd/csrc/batch.hip) share one convention: a NULL context is COVGPU_ERR_INVALID_ARG with the
  * message "<function>: NULL context", and every argument is checked before any device work. */
 
 /* trust-region strategy (reference uses DOGLEG: optimization_be.cpp:261,564,1028;
@@ -718,6 +718,66 @@ typedef struct covgpu_detect_batch_t {
   int32_t* num_scored;                           /* out [num_queries] nscores */
 } covgpu_detect_batch_t;
 int covgpu_detect_candidates_batch(covgpu_context*, const covgpu_detect_batch_t*, const covgpu_detect_opts*);
+
+/* ---------------------------------------------------------------- redundant-keyframe pruning
+ * Map::RemoveRedundantData (map_be.cpp:745-811) on the device, as an exact integer rule.
+ *
+ * Value (Keyframe::ComputeRedundancyValue, keyframe_be.cpp:228-256): a landmark with n live observations is worth v(n) tenths, 0 for
+ * n <= 2, then 4, 7, 9 for n = 3, 4, 5 and 10 from 6 on. An observation is live while its keyframe is valid and not erased. Over the live
+ * observations of keyframe k on valid landmarks with n >= 2: num[k] = sum of v(n), den[k] = their number; the redundancy value is
+ * num / (10 den). A (keyframe, landmark) pair listed twice is counted as given.
+ * Candidates (:752-759), fixed before the first round: valid, not kf_first, with a predecessor and a successor.
+ * A round picks the candidate of largest value, compared as num_a * den_b > num_b * den_a in int64; den == 0 ranks after every den > 0 and
+ * equal values go to the lowest index. Before the pick is handled the call stops, in this order, with stop_reason 2 when max_kfs >= 0 and
+ * at most max_kfs valid keyframes are left, 0 when no candidate is left, 1 when max_kfs < 0 and the pick has den == 0 or
+ * (double)num / (double)(10 den) < th_red, 3 when max_rounds rounds have run. The pick always leaves the candidate list. It stays in the
+ * map with action 1 when time[succ] - time[pred] >= max_time_dist, else 2 when it is a loop keyframe, else 3 when kf_not_erase is set
+ * (SetInvalid refuses, keyframe_be.cpp:510, yet the reference's count includes it). Otherwise action 0, SetInvalid (:514-526): its
+ * observations stop being live, succ[pred] = succ, pred[succ] = pred, one valid keyframe less.
+ *
+ * Where this departs from the letter of the reference, each time as one outcome the reference can produce: (1) std::sort leaves the
+ * order of equal values to the implementation; (2) a 0/0 value is NaN there, under a comparator that is then no strict weak order;
+ * (3) the reference sums the doubles 0.4 / 0.7 / 0.9 / 1.0 in feature order, here the sums are integers.
+ * Map::Clean at the top of the reference function changes no value (a landmark with fewer than two observations never counts); the
+ * caller runs it, and lm_nobs tells which landmarks a later Clean drops. */
+typedef struct covgpu_prune_t {
+  int32_t num_kf, num_lm;
+  const int32_t* lm_obs_ptr;                     /* [num_lm+1] landmark-major, as covgpu_problem */
+  const int32_t* obs_kf;                         /* [lm_obs_ptr[num_lm]] keyframe table index */
+  const uint8_t* lm_invalid;                     /* [num_lm] or NULL = none */
+  const uint8_t* kf_invalid;                     /* [num_kf] or NULL = none */
+  const uint8_t* kf_first;                       /* [num_kf] id_.first == 0, or NULL = none */
+  const uint8_t* kf_loop;                        /* [num_kf] is_loop_kf_, or NULL = none */
+  const uint8_t* kf_not_erase;                   /* [num_kf] not_erase_, or NULL = none */
+  const int32_t* kf_pred;                        /* [num_kf] table index, -1 = none */
+  const int32_t* kf_succ;                        /* [num_kf] */
+  const double*  kf_time;                        /* [num_kf] seconds */
+  int32_t capacity;                              /* entries of round_kf / round_action */
+  /* out; each may be NULL */
+  int32_t* round_kf;                             /* [capacity] the keyframe of each round */
+  int32_t* round_action;                         /* [capacity] 0 erased, 1 time gate, 2 loop keyframe, 3 not_erase */
+  int32_t* num_rounds;                           /* the true count, also beyond capacity */
+  int32_t* removed;                              /* the reference's return value: actions 0 + 3 */
+  int32_t* stop_reason;                          /* 0 no candidates, 1 below threshold, 2 max_kfs reached, 3 max_rounds */
+  int32_t* kf_pred_out;                          /* [num_kf] the relinked chain */
+  int32_t* kf_succ_out;                          /* [num_kf] */
+  int32_t* lm_nobs;                              /* [num_lm] live observations left */
+  int32_t* red_num;                              /* [num_kf] for a handled keyframe: at the round it was handled */
+  int32_t* red_den;                              /* [num_kf] */
+  double*  loop_ms;                              /* device time of the greedy-loop kernel alone (HIP events around it) */
+} covgpu_prune_t;
+typedef struct covgpu_prune_opts {
+  double  th_red;                                /* 0.95 (config_backend.yaml:58) */
+  double  max_time_dist;                         /* 1.0 s (config_backend.yaml:59) */
+  int32_t max_kfs;                               /* < 0: threshold mode; else count mode: prune down to max_kfs valid keyframes */
+  int32_t max_rounds;                            /* <= 0: num_kf */
+} covgpu_prune_opts;
+void covgpu_default_prune_opts(covgpu_prune_opts*);
+/* The argument checks of covgpu_prune_redundant alone (no context, no device): COVGPU_OK or COVGPU_ERR_INVALID_ARG with the message.
+ * Rejected: NULL required arrays, lm_obs_ptr not starting at 0 or not monotone, obs_kf out of range, kf_pred / kf_succ out of range or
+ * not mutual (succ[pred[k]] == k and pred[succ[k]] == k wherever both exist), non-finite th_red, max_time_dist or kf_time. */
+int covgpu_prune_check(const covgpu_prune_t*, const covgpu_prune_opts*);
+int covgpu_prune_redundant(covgpu_context*, const covgpu_prune_t*, const covgpu_prune_opts*);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <map>
 #include <unordered_map>
 #include <memory>
@@ -1520,6 +1521,77 @@ class KeyframeDatabaseT {
   int mode_;
   covgpu_detect_opts opts_;
   KeyframeVector order_;
+};
+
+// ---- Map::RemoveRedundantData (map_be.cpp:745-811) ----
+// MapPruneT<Types>::RemoveRedundantData(map, database, th_red, max_kfs) has the reference's semantics and return value (the reference
+// takes the map manager and asks it for the database; here the caller passes the database). The map is flattened to one
+// covgpu_prune_t (keyframe table = GetKeyframesVec() order, observations landmark-major through detail::visit_observations), the whole
+// greedy loop runs in one covgpu_prune_redundant call (the exact integer rule and its three departures from the
+// letter of std::sort / NaN / double sums), and the erases are replayed in round order through the map's own
+// EraseKeyframeWithDatabase(kf, false, database). The caller holds the map as the reference does (its mtx_map_).
+// What Keyframe keeps privately is read through Types: timestamp(kf) [s], is_loop_kf(kf), not_erase(kf).
+template <class Types>
+class MapPruneT {
+ public:
+  using Map = typename Types::Map;
+  using Keyframe = typename Types::Keyframe;
+  using MapPtr = std::shared_ptr<Map>;
+  using KeyframePtr = std::shared_ptr<Keyframe>;
+
+  struct Round { KeyframePtr kf; int action; };   // action: 0 erased, 1 time gate, 2 loop keyframe, 3 not_erase (covgpu_prune_t)
+  static std::vector<Round>& last_rounds() { static thread_local std::vector<Round> v; return v; }
+  static double& max_time_dist() { static double v = 1.0; return v; }   // covins_params::mapping::kf_culling_max_time_dist
+
+  template <class DatabasePtr>
+  static auto RemoveRedundantData(MapPtr map, DatabasePtr database, double th_red,
+                                  size_t max_kfs = std::numeric_limits<size_t>::max()) -> size_t {
+    map->Clean();   // :747
+    auto keyframes = map->GetKeyframesVec();
+    auto landmarks = map->GetLandmarksVec();
+    const size_t K = keyframes.size();
+    std::unordered_map<const Keyframe*, int32_t> row;
+    row.reserve(2 * K + 16);
+    std::vector<uint8_t> kf_invalid(K), kf_first(K), kf_loop(K), kf_not_erase(K), lm_invalid;
+    std::vector<int32_t> pred(K, -1), succ(K, -1), obs_ptr{0}, obs_kf;
+    std::vector<double> time(K);
+    for (size_t k = 0; k < K; ++k) row[keyframes[k].get()] = (int32_t)k;
+    auto row_of = [&](const KeyframePtr& kf) { auto it = kf ? row.find(kf.get()) : row.end(); return it == row.end() ? -1 : it->second; };
+    for (size_t k = 0; k < K; ++k) {
+      Keyframe& kf = *keyframes[k];
+      kf_invalid[k] = kf.IsInvalid(); kf_first[k] = kf.id_.first == 0;
+      kf_loop[k] = Types::is_loop_kf(kf); kf_not_erase[k] = Types::not_erase(kf);
+      time[k] = Types::timestamp(kf);
+      pred[k] = row_of(kf.GetPredecessor()); succ[k] = row_of(kf.GetSuccessor());
+    }
+    for (auto& lm : landmarks) {
+      lm_invalid.push_back(lm->IsInvalid());
+      detail::visit_observations<Types>(*lm, [&](const KeyframePtr& kf, size_t) { const int32_t r = row_of(kf); if (r >= 0) obs_kf.push_back(r); }, 0);
+      obs_ptr.push_back((int32_t)obs_kf.size());
+    }
+    std::vector<int32_t> round_kf(K ? K : 1), round_action(K ? K : 1);
+    int32_t num_rounds = 0, removed = 0, stop = 0;
+    covgpu_prune_t p{};
+    p.num_kf = (int32_t)K; p.num_lm = (int32_t)landmarks.size();
+    p.lm_obs_ptr = obs_ptr.data(); p.obs_kf = obs_kf.data(); p.lm_invalid = lm_invalid.data();
+    p.kf_invalid = kf_invalid.data(); p.kf_first = kf_first.data(); p.kf_loop = kf_loop.data(); p.kf_not_erase = kf_not_erase.data();
+    p.kf_pred = pred.data(); p.kf_succ = succ.data(); p.kf_time = time.data();
+    p.capacity = (int32_t)K; p.round_kf = round_kf.data(); p.round_action = round_action.data();
+    p.num_rounds = &num_rounds; p.removed = &removed; p.stop_reason = &stop;
+    covgpu_prune_opts o;
+    covgpu_default_prune_opts(&o);
+    o.th_red = th_red; o.max_time_dist = max_time_dist();
+    if (max_kfs != std::numeric_limits<size_t>::max()) o.max_kfs = (int32_t)std::min<size_t>(max_kfs, (size_t)INT32_MAX);
+    if (covgpu_prune_redundant(OptimizationT<Types>::Context(), &p, &o) != COVGPU_OK) detail::fatal(covgpu_last_error());
+    std::vector<Round>& rounds = last_rounds();
+    rounds.clear();
+    for (int32_t r = 0; r < num_rounds; ++r) {
+      rounds.push_back({keyframes[round_kf[r]], round_action[r]});
+      // action 3 too: the reference calls the erase, SetInvalid refuses (keyframe_be.cpp:510), and the call is counted (:776-777)
+      if (round_action[r] == 0 || round_action[r] == 3) map->EraseKeyframeWithDatabase(keyframes[round_kf[r]], false, database);
+    }
+    return (size_t)removed;
+  }
 };
 
 }  // namespace covins_gpu
