@@ -573,6 +573,60 @@ class Context:
             r["loop_ms"] = float(out["loop_ms"][0])
         return r
 
+    @staticmethod
+    def _refresh_batch(lm_obs_ptr, obs_kf, obs_desc, obs_octave, lm_ref_obs, lm_pos, kf_center, kf_invalid, lm_invalid, opts,
+                       want_kernel_ms=False):
+        """(LandmarkRefresh, LandmarkRefreshOpts, outputs, keep-alive list) of one covgpu_landmark_refresh call."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ravel()
+        flag = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint8).ravel()
+        ptr, okf, ooc, ref = i32(lm_obs_ptr), i32(obs_kf), i32(obs_octave), i32(lm_ref_obs)
+        pos = np.ascontiguousarray(lm_pos, dtype=np.float64).reshape(-1, 3)
+        cen = np.ascontiguousarray(kf_center, dtype=np.float64).reshape(-1, 3)
+        desc = None if obs_desc is None else np.ascontiguousarray(obs_desc, dtype=np.uint8).reshape(-1, 32)
+        kinv, linv = flag(kf_invalid), flag(lm_invalid)
+        K, L = len(cen), len(ptr) - 1
+        if L < 0 or len(ref) != L or len(pos) != L or len(ooc) != len(okf) or (desc is not None and len(desc) != len(okf)) or \
+                (kinv is not None and len(kinv) != K) or (linv is not None and len(linv) != L):
+            raise ValueError("landmark-refresh arrays differ in length")
+        if int(ptr[-1]) > len(okf):
+            raise ValueError("lm_obs_ptr runs past obs_kf")
+        o = capi.LandmarkRefreshOpts()
+        lib().covgpu_default_landmark_refresh_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("scale_factor", "num_octaves"):
+                raise TypeError(f"unknown landmark-refresh option {k}")
+            setattr(o, k, v)
+        n = max(L, 1)
+        out = dict(lm_desc_obs=np.full(n, -1, np.int32), lm_desc=np.zeros((n, 32), np.uint8), lm_normal=np.zeros((n, 3)),
+                   lm_min_distance=np.zeros(n), lm_max_distance=np.zeros(n), lm_status=np.zeros(n, np.int32),
+                   form_count=np.zeros(capi.LMR_FORMS, np.int32), kernel_ms=np.zeros(1))
+        bp = lambda a: None if a is None else a.ctypes.data_as(capi._bp)
+        s = capi.LandmarkRefresh(K, L, iptr(ptr), iptr(okf), bp(desc), iptr(ooc), iptr(ref), dptr(pos), dptr(cen), bp(kinv), bp(linv),
+                                 iptr(out["lm_desc_obs"]), bp(out["lm_desc"]), dptr(out["lm_normal"]), dptr(out["lm_min_distance"]),
+                                 dptr(out["lm_max_distance"]), iptr(out["lm_status"]), iptr(out["form_count"]),
+                                 dptr(out["kernel_ms"]) if want_kernel_ms else None)
+        return s, o, out, [ptr, okf, ooc, ref, pos, cen, desc, kinv, linv]
+
+    def refresh_landmarks(self, lm_obs_ptr, obs_kf, obs_desc, obs_octave, lm_ref_obs, lm_pos, kf_center, kf_invalid=None, lm_invalid=None,
+                          kernel_ms: bool = False, **opts):
+        """Landmark::ComputeDescriptor and Landmark::UpdateNormal for every landmark as one device call (covgpu_landmark_refresh,
+        DESIGN.md §4.15). Observations are landmark-major in the order given (lm_obs_ptr [L+1], obs_kf [O] keyframe table indices);
+        obs_desc [O,32] the observing keypoints' ORB rows or None (no descriptors asked for), obs_octave [O], lm_ref_obs [L] the position
+        of the reference keyframe's observation in the landmark's list or -1, kf_center [K,3] the camera centres. `opts`: scale_factor
+        (2.0), num_octaves (1). Returns dict(lm_desc_obs, lm_desc (both None without obs_desc), lm_normal, lm_min_distance,
+        lm_max_distance, lm_status (bit 0 no valid observer, 1 no reference, 2 invalid landmark), form_count; kernel_ms if asked for)."""
+        s, o, out, keep = self._refresh_batch(lm_obs_ptr, obs_kf, obs_desc, obs_octave, lm_ref_obs, lm_pos, kf_center, kf_invalid,
+                                              lm_invalid, opts, kernel_ms)
+        self._check(lib().covgpu_landmark_refresh(self._h, C.byref(s), C.byref(o)))
+        L = s.num_lm
+        r = {k: out[k][:L] for k in ("lm_normal", "lm_min_distance", "lm_max_distance", "lm_status")}
+        has = obs_desc is not None
+        r.update(lm_desc_obs=out["lm_desc_obs"][:L] if has else None, lm_desc=out["lm_desc"][:L] if has else None,
+                 form_count=out["form_count"])
+        if kernel_ms:
+            r["kernel_ms"] = float(out["kernel_ms"][0])
+        return r
+
     def p3p_batch(self, f, P):
         """covgpu_p3p_batch: f, P [n,4,3] -> (T [n,4,7] every solution, qx qy qz qw x y z, ascending v = s3/s1; nsol [n]; chosen [n], -1: none)."""
         f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 4, 3)

@@ -288,6 +288,22 @@ class PruneOpts(C.Structure):
     _fields_ = [("th_red", C.c_double), ("max_time_dist", C.c_double), ("max_kfs", C.c_int32), ("max_rounds", C.c_int32)]
 
 
+class LandmarkRefresh(C.Structure):
+    """covgpu_landmark_refresh_t (include/covgpu.h): Landmark::ComputeDescriptor + UpdateNormal for every landmark, DESIGN.md §4.15."""
+    _fields_ = [("num_kf", C.c_int32), ("num_lm", C.c_int32), ("lm_obs_ptr", _ip), ("obs_kf", _ip), ("obs_desc", _bp), ("obs_octave", _ip),
+                ("lm_ref_obs", _ip), ("lm_pos", _dp), ("kf_center", _dp), ("kf_invalid", _bp), ("lm_invalid", _bp),
+                ("lm_desc_obs", _ip), ("lm_desc", _bp), ("lm_normal", _dp), ("lm_min_distance", _dp), ("lm_max_distance", _dp),
+                ("lm_status", _ip), ("form_count", _ip), ("kernel_ms", _dp)]
+
+
+class LandmarkRefreshOpts(C.Structure):
+    _fields_ = [("scale_factor", C.c_double), ("num_octaves", C.c_int32)]
+
+
+LMR_NO_OBSERVER, LMR_NO_REFERENCE, LMR_INVALID = 1, 2, 4                                         # lm_status bits
+LMR_FORMS = 6                                                                                    # form_count: 4, 8, 16, 32, 64 lanes, long
+
+
 PRUNE_ERASED, PRUNE_TIME_GATE, PRUNE_LOOP_KF, PRUNE_NOT_ERASE = 0, 1, 2, 3                       # round_action
 PRUNE_STOP_NO_CANDIDATES, PRUNE_STOP_THRESHOLD, PRUNE_STOP_MAX_KFS, PRUNE_STOP_MAX_ROUNDS = 0, 1, 2, 3   # stop_reason
 
@@ -340,6 +356,10 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("default_prune_opts", [C.POINTER(PruneOpts)], None)
         d("prune_check", [C.POINTER(PruneBatch), C.POINTER(PruneOpts)])
         d("prune_redundant", [C.c_void_p, C.POINTER(PruneBatch), C.POINTER(PruneOpts)])
+        d("default_landmark_refresh_opts", [C.POINTER(LandmarkRefreshOpts)], None)
+        d("landmark_refresh_limits", [_ip], None)
+        d("landmark_refresh_check", [C.POINTER(LandmarkRefresh), C.POINTER(LandmarkRefreshOpts)])
+        d("landmark_refresh", [C.c_void_p, C.POINTER(LandmarkRefresh), C.POINTER(LandmarkRefreshOpts)])
         d("outlier_pass", [C.c_void_p, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])
         d("covisibility", [C.c_void_p, C.c_int32, C.c_int64, _ip, _ip, _ip, C.POINTER(C.c_int64)])
         d("gba_solve_multi", [OP, PP, RP, C.c_int32, _ip, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])

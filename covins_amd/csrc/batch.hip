@@ -2,8 +2,8 @@
 // run its kernels on the context's stream and hand the results back. Nothing here touches the resident problem of the solver
 // (solver.hip): a context lends its device and its stream only. Serves DESIGN.md §4.9 (relative pose, k_relpose.hip; the landmark
 // re-anchoring behind a pose-graph solve), §4.10 (P3P RANSAC, k_abspose.hip), §4.11 (descriptor matching, k_match.hip), §4.12
-// (guided matching, k_guided.hip), §4.13 (bag-of-words transform, score and candidate query, k_bow.hip) and §4.14 (redundant-keyframe
-// pruning, k_prune.hip).
+// (guided matching, k_guided.hip), §4.13 (bag-of-words transform, score and candidate query, k_bow.hip), §4.14 (redundant-keyframe
+// pruning, k_prune.hip) and §4.15 (landmark descriptors, normals and scale ranges, k_lmrefresh.hip).
 // Every entry point checks all its arguments before its first device call, holds its device buffers in one DeviceScratch
 // (host.hpp) and synchronises its stream once, at the end.
 #include <algorithm>
@@ -794,6 +794,113 @@ extern "C" int covgpu_prune_redundant(covgpu_context* c, const covgpu_prune_t* p
     if (p->num_rounds) *p->num_rounds = res[0];
     if (p->removed) *p->removed = res[1];
     if (p->stop_reason) *p->stop_reason = res[2];
+    return COVGPU_OK;
+  });
+}
+
+// ---- landmark refresh (k_lmrefresh.hip) ----
+extern "C" void covgpu_default_landmark_refresh_opts(covgpu_landmark_refresh_opts* o) {
+  if (!o) return;
+  o->scale_factor = 2.0; o->num_octaves = 1;                          // config_backend.yaml:31-32
+}
+
+extern "C" void covgpu_landmark_refresh_limits(int32_t out[4]) {
+  if (!out) return;
+  out[0] = kLmrGroupMax; out[1] = 64; out[2] = kLmrLongThreads; out[3] = kLmrStage;
+}
+
+static_assert(kLmrGroupMax == COVGPU_LMR_GROUP_MAX && kLmrLongThreads == COVGPU_LMR_LONG_THREADS && kLmrStage == COVGPU_LMR_STAGE &&
+              kLmrForms == COVGPU_LMR_FORMS && COVGPU_LMR_WAVE == 64, "covgpu.h names the limits of k_lmrefresh.hip");
+
+namespace {
+
+// The first violation of a landmark-refresh call's arguments, or nullptr.
+const char* lm_refresh_check(const covgpu_landmark_refresh_t* p, const covgpu_landmark_refresh_opts* o) {
+  if (!p || !o) return "NULL problem or options";
+  if (!std::isfinite(o->scale_factor) || !(o->scale_factor > 0.0)) return "scale_factor not finite or not positive";
+  if (o->num_octaves < 1 || o->num_octaves > 64) return "num_octaves outside [1, 64]";
+  const int K = p->num_kf, L = p->num_lm;
+  if (K < 0 || L < 0) return "negative count";
+  if (!p->lm_obs_ptr) return "NULL lm_obs_ptr";
+  if (p->lm_obs_ptr[0] != 0) return "lm_obs_ptr[0] != 0";
+  for (int l = 0; l < L; ++l) if (p->lm_obs_ptr[l + 1] < p->lm_obs_ptr[l]) return "lm_obs_ptr not monotone";
+  const int O = p->lm_obs_ptr[L];
+  if (O > 0 && (!p->obs_kf || !p->obs_octave)) return "NULL obs_kf or obs_octave";
+  if (L > 0 && (!p->lm_ref_obs || !p->lm_pos)) return "NULL lm_ref_obs or lm_pos";
+  if (K > 0 && !p->kf_center) return "NULL kf_center";
+  for (int i = 0; i < O; ++i) if (p->obs_kf[i] < 0 || p->obs_kf[i] >= K) return "obs_kf out of range";
+  for (int l = 0; l < L; ++l) {
+    const int r = p->lm_ref_obs[l], m = p->lm_obs_ptr[l + 1] - p->lm_obs_ptr[l];
+    if (r < -1 || r >= m) return "lm_ref_obs outside its landmark's list";
+    if (r >= 0) { const int oc = p->obs_octave[p->lm_obs_ptr[l] + r]; if (oc < 0 || oc >= 64) return "octave of a reference observation outside [0, 64)"; }
+  }
+  for (size_t i = 0; i < 3 * (size_t)L; ++i) if (!std::isfinite(p->lm_pos[i])) return "non-finite lm_pos";
+  for (size_t i = 0; i < 3 * (size_t)K; ++i) if (!std::isfinite(p->kf_center[i])) return "non-finite kf_center";
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" int covgpu_landmark_refresh_check(const covgpu_landmark_refresh_t* p, const covgpu_landmark_refresh_opts* o) {
+  return guarded([&]() -> int {
+    if (const char* m = lm_refresh_check(p, o)) { g_err = std::string("covgpu_landmark_refresh_check: ") + m; return COVGPU_ERR_INVALID_ARG; }
+    return COVGPU_OK;
+  });
+}
+
+extern "C" int covgpu_landmark_refresh(covgpu_context* c, const covgpu_landmark_refresh_t* p, const covgpu_landmark_refresh_opts* o) {
+  return batch_entry("covgpu_landmark_refresh", c, [&](auto bad) -> int {
+    if (const char* m = lm_refresh_check(p, o)) return bad(m);
+    const int K = p->num_kf, L = p->num_lm;
+    const size_t Ks = (size_t)K, Ls = (size_t)L, Os = (size_t)p->lm_obs_ptr[L];
+    // the form of every landmark from the length of its list; an invalid landmark is skipped by the narrowest
+    static const int kLanes[kLmrForms] = {4, 8, 16, 32, 64, 0};
+    std::vector<int32_t> form(Ls), start(kLmrForms + 1, 0), list(Ls);
+    for (int l = 0; l < L; ++l) {
+      const int m = p->lm_invalid && p->lm_invalid[l] ? 0 : p->lm_obs_ptr[l + 1] - p->lm_obs_ptr[l];
+      int f = 0;
+      while (f < kLmrForms - 1 && m > kLanes[f]) ++f;
+      form[l] = f; ++start[f + 1];
+    }
+    if (p->form_count) for (int f = 0; f < kLmrForms; ++f) p->form_count[f] = start[f + 1];
+    if (p->kernel_ms) *p->kernel_ms = 0.0;
+    if (L == 0) return COVGPU_OK;
+    for (int f = 0; f < kLmrForms; ++f) start[f + 1] += start[f];
+    { std::vector<int32_t> at(start.begin(), start.end() - 1); for (int l = 0; l < L; ++l) list[at[form[l]]++] = l; }
+    double scale[64];
+    for (int l = 0; l < 64; ++l) scale[l] = std::pow(o->scale_factor, l);   // the device never calls pow
+    HIPCHK(hipSetDevice(c->device));
+    struct Events {   // around the kernels, only when the caller asks for their time
+      hipEvent_t a = nullptr, b = nullptr;
+      ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    DeviceScratch U(c->st);
+    LmRefreshDev D{};
+    int* dlist = nullptr;
+    HIPCHK(U.upload(&D.lm_ptr, p->lm_obs_ptr, Ls + 1)); HIPCHK(U.upload(&D.obs_kf, p->obs_kf, Os));
+    HIPCHK(U.upload(&D.obs_octave, p->obs_octave, Os));
+    if (p->obs_desc) HIPCHK(U.upload(&D.obs_desc, reinterpret_cast<const uint4*>(p->obs_desc), 2 * Os));
+    HIPCHK(U.upload(&D.ref_obs, p->lm_ref_obs, Ls)); HIPCHK(U.upload(&D.pos, p->lm_pos, 3 * Ls));
+    HIPCHK(U.upload(&D.center, p->kf_center, 3 * Ks));
+    if (p->kf_invalid) HIPCHK(U.upload(&D.kf_invalid, p->kf_invalid, Ks));
+    if (p->lm_invalid) HIPCHK(U.upload(&D.lm_invalid, p->lm_invalid, Ls));
+    HIPCHK(U.upload(&D.scale, scale, 64));
+    D.num_octaves = o->num_octaves;
+    HIPCHK(U.upload(&dlist, list.data(), Ls));
+    HIPCHK(U.alloc(&D.desc_obs, Ls)); HIPCHK(U.alloc(&D.desc, 2 * Ls));
+    HIPCHK(U.alloc(&D.normal, 3 * Ls)); HIPCHK(U.alloc(&D.min_dist, Ls)); HIPCHK(U.alloc(&D.max_dist, Ls)); HIPCHK(U.alloc(&D.status, Ls));
+    if (p->kernel_ms) { HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b)); HIPCHK(hipEventRecord(ev.a, c->st)); }
+    for (int f = 0; f < kLmrForms; ++f) launch_lm_refresh(D, kLanes[f], dlist + start[f], start[f + 1] - start[f], c->st);
+    if (p->kernel_ms) HIPCHK(hipEventRecord(ev.b, c->st));
+    HIPCHK(hipGetLastError());
+    if (p->obs_desc) {
+      HIPCHK(U.fetch(p->lm_desc_obs, D.desc_obs, Ls));
+      HIPCHK(U.fetch(reinterpret_cast<uint4*>(p->lm_desc), D.desc, 2 * Ls));
+    }
+    HIPCHK(U.fetch(p->lm_normal, D.normal, 3 * Ls)); HIPCHK(U.fetch(p->lm_min_distance, D.min_dist, Ls));
+    HIPCHK(U.fetch(p->lm_max_distance, D.max_dist, Ls)); HIPCHK(U.fetch(p->lm_status, D.status, Ls));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (p->kernel_ms) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b)); *p->kernel_ms = ms; }
     return COVGPU_OK;
   });
 }

@@ -678,4 +678,24 @@ void launch_prune_setup(const PruneDev& P, hipStream_t st);
 void launch_prune_loop(const PruneDev& P, const PruneOptsDev& O, hipStream_t st);   // one workgroup, every round
 void launch_prune_finish(const PruneDev& P, hipStream_t st);
 
+// k_lmrefresh.hip: Landmark::ComputeDescriptor + Landmark::UpdateNormal for every landmark. Device arrays throughout.
+constexpr int kLmrGroupMax = 64;        // longest observation list of the lane-group forms (4, 8, 16, 32, 64 lanes); the long form from 65
+constexpr int kLmrLongThreads = 256;    // workgroup of the long form: one landmark, four wavefronts, one row per wavefront at a time
+constexpr int kLmrStage = 512;          // descriptors of one landmark the long form stages in LDS; the rest is read from global memory
+constexpr int kLmrForms = 6;            // form_count: 4, 8, 16, 32, 64 lanes, long
+struct LmRefreshDev {
+  const int* lm_ptr; const int* obs_kf;                               // landmark-major observation lists, as given
+  const uint4* obs_desc;                                              // [O][2] or nullptr: descriptors not asked for
+  const int* obs_octave;                                              // [O]
+  const int* ref_obs;                                                 // [L] position in the landmark's list, -1 = none
+  const double* pos; const double* center;                            // [L][3], [K][3]
+  const unsigned char* kf_invalid; const unsigned char* lm_invalid;   // [K], [L] or nullptr
+  const double* scale; int num_octaves;                               // [64] scale_factor^l, tabulated by the host
+  int* desc_obs; uint4* desc;                                         // [L], [L][2] (written only with obs_desc)
+  double* normal; double* min_dist; double* max_dist;                 // [L][3], [L], [L]
+  int* status;                                                        // [L]
+};
+// the landmarks list[0..count) through the form of `lanes` lanes per landmark (4 | 8 | 16 | 32 | 64: lists of at most `lanes`), 0 = long form
+void launch_lm_refresh(const LmRefreshDev& D, int lanes, const int* list, int count, hipStream_t st);
+
 }  // namespace covgpu

@@ -148,21 +148,36 @@ def _pose_mat(p: np.ndarray) -> np.ndarray:
     return T
 
 
-def load_map(path: str) -> SlamMap:
-    """What Map::LoadFromFile builds (map_be.cpp:508-696), as the struct-of-arrays SlamMap: keyframes sorted by
-    (id, client) (typedefs_base.hpp:178), predecessor / successor links, raw IMU samples per keyframe (samples with dt == 0
-    skipped like keyframe_be.cpp:199-202), landmark observations with the keypoint each one refers to, reference keyframes,
-    loop constraints; every keyframe is flagged is_loaded_ (map_be.cpp:583)."""
+def _read_sorted(path: str):
+    """The keyframe and landmark archives of a saved map, each sorted by (id, client), and the keyframe table row of every keyframe id:
+    the order load_map and load_observation_features share."""
     def files(sub):
         d = os.path.join(path, sub)
         return sorted(os.path.join(d, f) for f in os.listdir(d)) if os.path.isdir(d) else []
     kfs = [read_keyframe(open(f, "rb").read()) for f in files("keyframes")]
     lms = [read_landmark(open(f, "rb").read()) for f in files("mappoints")]
-    md = read_mapdata(open(os.path.join(path, "mapdata.txt"), "rb").read())
     kfs.sort(key=lambda k: k["id"])
     lms.sort(key=lambda l: l["id"])
+    return kfs, lms, {k["id"]: i for i, k in enumerate(kfs)}
+
+
+def _observations(lm: dict, row: Dict[Tuple, int]):
+    """(keyframe table row, feature index) of a landmark's observations in key order, without those whose keyframe is missing."""
+    for kid, feat in lm["observations"]:
+        i = row.get(kid)
+        if i is None:
+            continue   # "if(!kf) continue" (map_be.cpp:655-657)
+        yield i, feat
+
+
+def load_map(path: str) -> SlamMap:
+    """What Map::LoadFromFile builds (map_be.cpp:508-696), as the struct-of-arrays SlamMap: keyframes sorted by
+    (id, client) (typedefs_base.hpp:178), predecessor / successor links, raw IMU samples per keyframe (samples with dt == 0
+    skipped like keyframe_be.cpp:199-202), landmark observations with the keypoint each one refers to, reference keyframes,
+    loop constraints; every keyframe is flagged is_loaded_ (map_be.cpp:583)."""
+    kfs, lms, row = _read_sorted(path)
+    md = read_mapdata(open(os.path.join(path, "mapdata.txt"), "rb").read())
     K = len(kfs)
-    row = {k["id"]: i for i, k in enumerate(kfs)}
     # cameras: one row per distinct (client, calibration)
     cams: List[Tuple] = []
     cam_rows: Dict[Tuple, int] = {}
@@ -196,10 +211,7 @@ def load_map(path: str) -> SlamMap:
         chunks.append(s); imu_ptr[i + 1] = imu_ptr[i] + len(s)
     obs_kf, obs_uv, obs_oct, ptr = [], [], [], [0]
     for lm in lms:
-        for kid, feat in lm["observations"]:
-            i = row.get(kid)
-            if i is None:
-                continue   # "if(!kf) continue" (map_be.cpp:655-657)
+        for i, feat in _observations(lm, row):
             obs_kf.append(i); obs_uv.append(kfs[i]["keypoints_distorted"][feat]); obs_oct.append(int(kfs[i]["keypoints_aors"][feat][1]))
         ptr.append(len(obs_kf))
     loops = []
@@ -228,6 +240,21 @@ def load_map(path: str) -> SlamMap:
         obs_octave=np.array(obs_oct, np.int32), loops=loops,
         cam_model=np.array([c["cam_model"] for _, c in cams], np.int32) if omni else None,
         cam_xi=np.array([c["intrinsics"][0] if c["cam_model"] == 1 else 0.0 for _, c in cams], np.float64) if omni else None)
+
+
+def load_observation_features(path: str) -> Tuple[np.ndarray, np.ndarray]:
+    """(obs_desc [O,32] uint8, obs_feat [O] int32) of a saved map in exactly load_map's observation order: for every observation the ORB
+    row of the observing keypoint, kf->descriptors_.row(feat_idx), and the feature index. What Landmark::ComputeDescriptor reads after
+    Map::LoadFromFile (map_be.cpp:660); the input of optimization.refresh_landmarks."""
+    kfs, lms, row = _read_sorted(path)
+    desc, feats = [], []
+    for lm in lms:
+        for i, feat in _observations(lm, row):
+            d = kfs[i]["descriptors"]
+            if feat < 0 or feat >= len(d) or d.shape[1] != 32:
+                raise ValueError(f"keyframe {kfs[i]['id']}: no 32-byte descriptor row for feature {feat}")
+            desc.append(d[feat]); feats.append(feat)
+    return np.array(desc, np.uint8).reshape(-1, 32), np.array(feats, np.int32)
 
 
 # ------------------------------------------------------------------------------------------------ writer (fixtures / tests)

@@ -200,3 +200,48 @@ def remove_redundant_data(m: SlamMap, ctx: Optional[backend.Context] = None, th_
     finally:
         if own:
             ctx.close()
+
+
+def refresh_landmarks(m: SlamMap, obs_desc: Optional[np.ndarray], ctx: Optional[backend.Context] = None, scale_factor: float = 2.0,
+                      num_octaves: int = 1, info: Optional[dict] = None) -> Dict[str, np.ndarray]:
+    """Landmark::ComputeDescriptor and Landmark::UpdateNormal (landmark_be.cpp:49-92, 185-220) for every landmark of `m` as one device
+    call (covgpu_landmark_refresh, DESIGN.md §4.15), as Map::LoadFromFile runs them per landmark (map_be.cpp:660-661). `obs_desc`
+    [O,32]: the observing keypoints' ORB rows in the map's observation order (mapio.load_observation_features), or None to refresh
+    the normals and distances only. The camera centres are the translations of kf_pose (x) cam_extr[kf_cam] (GetPoseTwc), the
+    reference observation of a landmark is the first one of lm_ref_kf in its list. Returns the attributes the guided matching reads,
+    in the layout of its inputs: lm_desc [L,32] (None without obs_desc), lm_normal [L,3], lm_mind [L], lm_maxd [L], plus lm_desc_obs
+    and lm_status; `info` receives the call's result dict."""
+    own = ctx is None
+    ctx = ctx or backend.Context()
+    try:
+        center = kf_centers(m)
+        r = ctx.refresh_landmarks(m.lm_obs_ptr, m.obs_kf, obs_desc, m.obs_octave, reference_observations(m), m.lm_pos, center,
+                                  kf_invalid=m.kf_invalid, lm_invalid=m.lm_invalid, scale_factor=scale_factor, num_octaves=num_octaves)
+        if info is not None:
+            info.update(r)
+        return dict(lm_desc=r["lm_desc"], lm_normal=r["lm_normal"], lm_mind=r["lm_min_distance"], lm_maxd=r["lm_max_distance"],
+                    lm_desc_obs=r["lm_desc_obs"], lm_status=r["lm_status"])
+    finally:
+        if own:
+            ctx.close()
+
+
+def kf_centers(m: SlamMap) -> np.ndarray:
+    """[K,3] camera centres: the translation of T_ws * T_sc (Keyframe::GetPoseTwc), t_ws + R_ws t_sc."""
+    from scipy.spatial.transform import Rotation as R
+    if m.K == 0:
+        return np.zeros((0, 3))
+    t_sc = np.asarray(m.cam_extr, np.float64)[np.asarray(m.kf_cam, np.int64), 4:]
+    return np.ascontiguousarray(m.kf_pose[:, 4:] + R.from_quat(m.kf_pose[:, :4]).apply(t_sc))
+
+
+def reference_observations(m: SlamMap) -> np.ndarray:
+    """[L] position of lm_ref_kf's (first) observation inside each landmark's list, -1 when it has none."""
+    ref = np.full(m.L, -1, np.int32)
+    if m.O == 0:
+        return ref
+    obs_lm = np.repeat(np.arange(m.L), np.diff(m.lm_obs_ptr))
+    hit = np.flatnonzero(np.asarray(m.obs_kf) == np.asarray(m.lm_ref_kf)[obs_lm])
+    pos = (hit - np.asarray(m.lm_obs_ptr)[obs_lm[hit]]).astype(np.int32)
+    ref[obs_lm[hit[::-1]]] = pos[::-1]          # reversed: the first hit of a landmark is written last
+    return ref

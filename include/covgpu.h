@@ -39,7 +39,7 @@ enum {
 };
 /* The stateless batch calls (covgpu_relpose_batch, covgpu_abspose_ransac_batch, covgpu_p3p_batch, covgpu_match_batch,
  * covgpu_search_se3_batch, covgpu_search_projection_batch, covgpu_pgo_reanchor, covgpu_bow_transform_batch, covgpu_bow_score_pairs,
- * covgpu_detect_candidates_batch, covgpu_prune_redundant; covins_amd/csrc/batch.hip) share one convention: a NULL context is COVGPU_ERR_INVALID_ARG with the
+ * covgpu_detect_candidates_batch, covgpu_prune_redundant, covgpu_landmark_refresh; covins_amd/csrc/batch.hip) share one convention: a NULL context is COVGPU_ERR_INVALID_ARG with the
  * message "<function>: NULL context", and every argument is checked before any device work. */
 
 /* trust-region strategy (reference uses DOGLEG: optimization_be.cpp:261,564,1028;
@@ -778,6 +778,65 @@ void covgpu_default_prune_opts(covgpu_prune_opts*);
  * not mutual (succ[pred[k]] == k and pred[succ[k]] == k wherever both exist), non-finite th_red, max_time_dist or kf_time. */
 int covgpu_prune_check(const covgpu_prune_t*, const covgpu_prune_opts*);
 int covgpu_prune_redundant(covgpu_context*, const covgpu_prune_t*, const covgpu_prune_opts*);
+
+/* ---------------------------------------------------------------- landmark refresh
+ * Landmark::ComputeDescriptor (landmark_be.cpp:49-92) and Landmark::UpdateNormal (:185-220) for every landmark of a map in one call: the
+ * representative descriptor, the viewing normal and the scale-invariance distances that the guided matching reads.
+ *
+ * Order: a landmark's observations are taken in the order given. The reference iterates a std::map keyed by shared_ptr address
+ * (typedefs_base.hpp:187), so its order — and with it its tie-break and its summation order — is an accident of the allocator; the
+ * order given is one outcome the reference can produce. This is the one departure from the letter of the reference.
+ * Candidates: the landmark's observations whose keyframe is valid, in list order; n is their number. A keyframe listed twice counts twice.
+ * Descriptor: d(i, j) is the Hamming distance over 256 bits, d(i, i) = 0. The median of row i is its element of rank (n - 1) / 2
+ * (integer division) in ascending order, the self-distance included (distances[0.5 * (num_desc - 1)]). The choice is the lowest i whose
+ * median is strictly smallest (<, :86). lm_desc_obs is the chosen observation's position in the landmark's own list (not among the
+ * candidates), -1 when n = 0; lm_desc its 32 bytes, zeros when -1 (the reference leaves descriptor_ as it was).
+ * Normal: for each candidate in list order v = lm_pos - kf_center, u = v / sqrt((v.x v.x + v.y v.y) + v.z v.z);
+ * normal = (((0 + u_0) + u_1) + ...) / (double)n. Distances: dist = the same norm of lm_pos - kf_center[keyframe of the reference
+ * observation] (not asked whether it is valid, as in the reference), max_distance = dist * scale[level], min_distance = max_distance /
+ * scale[num_octaves - 1], level = obs_octave of the reference observation, scale[l] = std::pow(scale_factor, l) tabulated on the host.
+ * Every operation is an IEEE double operation on its own: no fused multiply-add.
+ * lm_status: bit 0 no valid observer (the reference divides 0 by 0; here the normal is 0), bit 1 no reference observation (the
+ * reference exits; here the distances are 0), bit 2 the landmark is invalid: skipped, status 4 and every other output 0 / -1. */
+#define COVGPU_LMR_GROUP_MAX 64                  /* longest observation list of the lane-group forms; the long form starts one above */
+#define COVGPU_LMR_WAVE 64                       /* the long form strides a row over one wavefront ... */
+#define COVGPU_LMR_LONG_THREADS 256              /* ... of a workgroup of this size, which also is its chunk of the normal's sum ... */
+#define COVGPU_LMR_STAGE 512                     /* ... and keeps this many descriptors of the landmark in LDS */
+#define COVGPU_LMR_FORMS 6                       /* form_count: lists of <= 4, 8, 16, 32, 64 (lane groups of that width), longer (long form) */
+typedef struct covgpu_landmark_refresh_t {
+  int32_t num_kf, num_lm;
+  const int32_t* lm_obs_ptr;                     /* [num_lm+1] landmark-major, as covgpu_prune_t */
+  const int32_t* obs_kf;                         /* [O = lm_obs_ptr[num_lm]] keyframe table index */
+  const uint8_t* obs_desc;                       /* [O][32] the observing keypoint's ORB row, or NULL: no descriptors asked for */
+  const int32_t* obs_octave;                     /* [O] (int)keypoints_aors_[feat](1) */
+  const int32_t* lm_ref_obs;                     /* [num_lm] position of the reference keyframe's observation in the landmark's list, -1 = none */
+  const double*  lm_pos;                         /* [num_lm][3] */
+  const double*  kf_center;                      /* [num_kf][3] translation of GetPoseTwc() */
+  const uint8_t* kf_invalid;                     /* [num_kf] or NULL = none */
+  const uint8_t* lm_invalid;                     /* [num_lm] or NULL = none */
+  /* out; each may be NULL */
+  int32_t* lm_desc_obs;                          /* [num_lm]; not written when obs_desc is NULL */
+  uint8_t* lm_desc;                              /* [num_lm][32]; not written when obs_desc is NULL */
+  double*  lm_normal;                            /* [num_lm][3] */
+  double*  lm_min_distance;                      /* [num_lm] */
+  double*  lm_max_distance;                      /* [num_lm] */
+  int32_t* lm_status;                            /* [num_lm] bit mask, see above */
+  int32_t* form_count;                           /* [COVGPU_LMR_FORMS] landmarks that took each kernel form; an invalid landmark takes the first */
+  double*  kernel_ms;                            /* device time of the kernels alone (HIP events around them) */
+} covgpu_landmark_refresh_t;
+typedef struct covgpu_landmark_refresh_opts {
+  double  scale_factor;                          /* 2.0 (config_backend.yaml:31) */
+  int32_t num_octaves;                           /* 1 (config_backend.yaml:32) */
+} covgpu_landmark_refresh_opts;
+void covgpu_default_landmark_refresh_opts(covgpu_landmark_refresh_opts*);
+/* {COVGPU_LMR_GROUP_MAX, COVGPU_LMR_WAVE, COVGPU_LMR_LONG_THREADS, COVGPU_LMR_STAGE} as the library was built */
+void covgpu_landmark_refresh_limits(int32_t out[4]);
+/* The argument checks of covgpu_landmark_refresh alone (no context, no device): COVGPU_OK or COVGPU_ERR_INVALID_ARG with the message.
+ * Rejected: NULL required arrays, lm_obs_ptr not starting at 0 or not monotone, obs_kf out of range, lm_ref_obs outside its landmark's
+ * list, a reference observation whose octave is outside [0, 64), num_octaves outside [1, 64], a non-finite or non-positive
+ * scale_factor, non-finite positions or centres. */
+int covgpu_landmark_refresh_check(const covgpu_landmark_refresh_t*, const covgpu_landmark_refresh_opts*);
+int covgpu_landmark_refresh(covgpu_context*, const covgpu_landmark_refresh_t*, const covgpu_landmark_refresh_opts*);
 
 #ifdef __cplusplus
 }

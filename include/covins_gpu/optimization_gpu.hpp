@@ -20,6 +20,7 @@
 // spelling differs between the real COVINS classes and a stand-in (see INTEGRATION.md for the COVINS binding).
 #pragma once
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -188,6 +189,32 @@ inline auto remap_landmark(const KP& kf, const LP& lm, size_t now, size_t to, in
 }
 template <class Types, class KP, class LP>
 inline void remap_landmark(const KP& kf, const LP& lm, size_t now, size_t to, long) { kf->RemapLandmark(lm, now, to); }
+
+// ---- what LandmarkRefreshT writes and reads beyond the above.
+// descriptor_ of a landmark (32 bytes): Types::set_landmark_descriptor(landmark, bytes32); normal_, min_distance_, max_distance_:
+// Types::set_landmark_scale(landmark, normal3, min, max). LandmarkBase keeps these members protected and offers no setter, so there is
+// no COVINS member to fall back on: a binding that instantiates LandmarkRefreshT supplies both.
+template <class Types, class L>
+inline auto set_landmark_descriptor(L& lm, const uint8_t* d, int) -> decltype(Types::set_landmark_descriptor(lm, d), void()) {
+  Types::set_landmark_descriptor(lm, d);
+}
+template <class Types, class L>
+inline void set_landmark_descriptor(L&, const uint8_t*, long) {
+  static_assert(sizeof(L) == 0, "LandmarkRefreshT needs Types::set_landmark_descriptor(landmark, bytes32)");
+}
+template <class Types, class L>
+inline auto set_landmark_scale(L& lm, const double* n, double mn, double mx, int) -> decltype(Types::set_landmark_scale(lm, n, mn, mx), void()) {
+  Types::set_landmark_scale(lm, n, mn, mx);
+}
+template <class Types, class L>
+inline void set_landmark_scale(L&, const double*, double, double, long) {
+  static_assert(sizeof(L) == 0, "LandmarkRefreshT needs Types::set_landmark_scale(landmark, normal3, min, max)");
+}
+// camera centre of a keyframe, the translation of GetPoseTwc(): Types::camera_center(keyframe, out3), else the member
+template <class Types, class K>
+inline auto camera_center(K& kf, double* c, int) -> decltype(Types::camera_center(kf, c), void()) { Types::camera_center(kf, c); }
+template <class Types, class K>
+inline void camera_center(K& kf, double* c, long) { const auto T = kf.GetPoseTwc(); c[0] = T(0, 3); c[1] = T(1, 3); c[2] = T(2, 3); }
 
 // RANSAC seed of a (query, candidate) keyframe pair from their ids: a candidate's draws do not depend on the batch it is verified in
 template <class K>
@@ -1591,6 +1618,112 @@ class MapPruneT {
       if (round_action[r] == 0 || round_action[r] == 3) map->EraseKeyframeWithDatabase(keyframes[round_kf[r]], false, database);
     }
     return (size_t)removed;
+  }
+};
+
+// ---- Landmark::ComputeDescriptor (landmark_be.cpp:49-92) + Landmark::UpdateNormal (:185-220) for many landmarks ----
+// LandmarkRefreshT<Types>::Refresh(map) / Refresh(landmarks) replaces the serial loops that call the two member functions per landmark
+// (map_be.cpp:660-661 after a load, communicator_be.cpp:190-198 for a received keyframe's landmarks, placerec_be.cpp:279, 495, 500 after
+// a fusion): the landmarks are flattened to one covgpu_landmark_refresh_t — observations in the order detail::visit_observations
+// yields them, each with its keyframe's descriptor row (detail::descriptors) and octave (keypoints_aors_[feat](1)), camera centres
+// from GetPoseTwc() — one covgpu_landmark_refresh call runs, and the results are written back through
+// Types::set_landmark_descriptor / Types::set_landmark_scale. The one departure from the letter of the reference is the order: the
+// reference's std::map is keyed by shared_ptr address, so its tie-break and summation order are the allocator's; here they are the
+// visit's, one outcome the reference can produce. A landmark without a valid observer keeps its descriptor (ComputeDescriptor
+// returns early); UpdateNormal exits on a landmark without reference keyframe or without observations, and so does this, with the
+// reference's message, before anything is written. Invalid landmarks are skipped. The caller holds the map as the reference does.
+template <class Types>
+class LandmarkRefreshT {
+ public:
+  using Map = typename Types::Map;
+  using Keyframe = typename Types::Keyframe;
+  using Landmark = typename Types::Landmark;
+  using MapPtr = std::shared_ptr<Map>;
+  using KeyframePtr = std::shared_ptr<Keyframe>;
+  using LandmarkPtr = std::shared_ptr<Landmark>;
+
+  struct Params { double scale_factor = 2.0; int num_octaves = 1; };   // covins_params::features::scale_factor / num_octaves
+  static Params& params() { static Params p; return p; }
+  // landmarks per kernel form of the calling thread's last call (covgpu_landmark_refresh_t::form_count)
+  static std::array<int32_t, COVGPU_LMR_FORMS>& last_forms() { static thread_local std::array<int32_t, COVGPU_LMR_FORMS> f{}; return f; }
+
+  static void Refresh(MapPtr map) { Refresh(map->GetLandmarksVec()); }
+
+  static void Refresh(const std::vector<LandmarkPtr>& landmarks) {
+    const size_t L = landmarks.size();
+    std::unordered_map<const Keyframe*, int32_t> row;
+    std::vector<uint8_t> kf_invalid, lm_invalid(L), obs_desc;
+    std::vector<const uint8_t*> kf_desc;
+    std::vector<int> kf_rows;
+    std::vector<double> center, pos(3 * L);
+    std::vector<int32_t> obs_ptr{0}, obs_kf, obs_octave, ref_obs(L, -1);
+    auto row_of = [&](Keyframe& kf) -> int32_t {
+      auto it = row.find(&kf);
+      if (it != row.end()) return it->second;
+      const int32_t r = (int32_t)kf_invalid.size();
+      row.emplace(&kf, r);
+      kf_invalid.push_back(kf.IsInvalid());
+      double c[3];
+      detail::camera_center<Types>(kf, c, 0);
+      center.insert(center.end(), c, c + 3);
+      int rows = 0; const uint8_t* data = nullptr;
+      if (!detail::descriptors<Types>(kf, 0, &rows, &data, 0)) { rows = 0; data = nullptr; }
+      kf_rows.push_back(rows); kf_desc.push_back(data);
+      return r;
+    };
+    for (size_t l = 0; l < L; ++l) {
+      Landmark& lm = *landmarks[l];
+      lm_invalid[l] = lm.IsInvalid();
+      const auto p = lm.GetWorldPos();
+      pos[3 * l] = p[0]; pos[3 * l + 1] = p[1]; pos[3 * l + 2] = p[2];
+      const KeyframePtr ref = lm.GetReferenceKeyframe();
+      const int32_t first = obs_ptr.back();
+      detail::visit_observations<Types>(lm, [&](const KeyframePtr& kf, size_t feat) {
+        if (!kf) return;
+        const int32_t r = row_of(*kf);
+        if (ref && kf.get() == ref.get() && ref_obs[l] < 0) ref_obs[l] = (int32_t)obs_kf.size() - first;
+        obs_kf.push_back(r);
+        obs_octave.push_back(feat < kf->keypoints_aors_.size() ? (int32_t)kf->keypoints_aors_[feat][1] : -1);
+        const size_t at = obs_desc.size();
+        obs_desc.resize(at + 32, 0);
+        if (!kf_invalid[r]) {   // (ComputeDescriptor reads the rows of valid keyframes only)
+          if (!kf_desc[r] || feat >= (size_t)kf_rows[r]) detail::fatal("LandmarkRefreshT: an observation without a descriptor row");
+          std::memcpy(&obs_desc[at], kf_desc[r] + 32 * feat, 32);
+        }
+      }, 0);
+      obs_ptr.push_back((int32_t)obs_kf.size());
+    }
+    const size_t K = kf_invalid.size();
+    std::vector<int32_t> desc_obs(L ? L : 1), status(L ? L : 1);
+    std::vector<uint8_t> desc(32 * (L ? L : 1));
+    std::vector<double> normal(3 * (L ? L : 1)), mind(L ? L : 1), maxd(L ? L : 1);
+    covgpu_landmark_refresh_t p{};
+    p.num_kf = (int32_t)K; p.num_lm = (int32_t)L;
+    p.lm_obs_ptr = obs_ptr.data(); p.obs_kf = obs_kf.data(); p.obs_desc = obs_desc.data(); p.obs_octave = obs_octave.data();
+    p.lm_ref_obs = ref_obs.data(); p.lm_pos = pos.data(); p.kf_center = center.data();
+    p.kf_invalid = kf_invalid.data(); p.lm_invalid = lm_invalid.data();
+    p.lm_desc_obs = desc_obs.data(); p.lm_desc = desc.data(); p.lm_normal = normal.data();
+    p.lm_min_distance = mind.data(); p.lm_max_distance = maxd.data(); p.lm_status = status.data();
+    p.form_count = last_forms().data();
+    uint8_t none = 0;
+    if (obs_desc.empty()) p.obs_desc = &none;   // (no observation at all: still "descriptors asked for")
+    covgpu_landmark_refresh_opts o;
+    covgpu_default_landmark_refresh_opts(&o);
+    o.scale_factor = params().scale_factor; o.num_octaves = params().num_octaves;
+    if (covgpu_landmark_refresh(OptimizationT<Types>::Context(), &p, &o) != COVGPU_OK) detail::fatal(covgpu_last_error());
+    for (size_t l = 0; l < L; ++l) {
+      if (status[l] & 4) continue;
+      if (status[l] & 2) {   // landmark_be.cpp:188-191
+        const std::string m = "LM (" + std::to_string(landmarks[l]->id_.first) + "," + std::to_string(landmarks[l]->id_.second) + "): no ref-KF";
+        detail::fatal(m.c_str());
+      }
+      if (status[l] & 1) detail::fatal("no obervations");   // :192-195 (the reference's spelling)
+    }
+    for (size_t l = 0; l < L; ++l) {
+      if (status[l] & 4) continue;
+      if (desc_obs[l] >= 0) detail::set_landmark_descriptor<Types>(*landmarks[l], &desc[32 * l], 0);
+      detail::set_landmark_scale<Types>(*landmarks[l], &normal[3 * l], mind[l], maxd[l], 0);
+    }
   }
 };
 
