@@ -172,7 +172,11 @@ class FlatProblem:
         assert self.lm_obs_ptr.shape[0] == L + 1 and self.lm_obs_ptr[0] == 0 and self.lm_obs_ptr[-1] == O
         assert np.all(np.diff(self.lm_obs_ptr) >= 0)
         assert self.obs_uv.shape[0] == O and self.obs_sigma.shape[0] == O
-        if O: assert self.obs_kf.min() >= 0 and self.obs_kf.max() < K
+        if O:
+            assert self.obs_kf.min() >= 0 and self.obs_kf.max() < K
+            # one observation per (landmark, keyframe), as the library's validation: the pair lists skip a keyframe paired with itself
+            obs_lm = np.repeat(np.arange(L, dtype=np.int64), np.diff(self.lm_obs_ptr))
+            assert np.unique(obs_lm * K + self.obs_kf).shape[0] == O, "landmark observed twice by one keyframe"
         assert self.kf_cam.min() >= 0 and self.kf_cam.max() < self.A
         assert self.imu_kf_j.shape[0] == I and self.imu_sample_ptr.shape[0] == I + 1 and self.imu_first.shape[0] == I
         assert self.imu_sample_ptr[-1] == self.imu_samples.shape[0]

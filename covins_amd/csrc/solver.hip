@@ -398,6 +398,15 @@ static int validate(const covgpu_problem* p, bool pgo, bool vi) {
     if (p->num_lm > 0 && (p->lm_obs_ptr[0] != 0 || p->lm_obs_ptr[p->num_lm] != p->num_obs)) return bad("lm_obs_ptr does not span the observations");
     for (int l = 0; l < p->num_lm; ++l) if (p->lm_obs_ptr[l + 1] < p->lm_obs_ptr[l]) return bad("lm_obs_ptr not monotone");
     for (int o = 0; o < p->num_obs; ++o) if (p->obs_kf[o] < 0 || p->obs_kf[o] >= K) return bad("obs_kf out of range");
+    {  // one observation per (landmark, keyframe): the pair lists skip a keyframe paired with itself, so the cross terms of two observations
+       // of one landmark by one keyframe would be missing from that keyframe's diagonal block of the reduced system
+      std::vector<int> stamp(K, -1);
+      for (int l = 0; l < p->num_lm; ++l)
+        for (int o = p->lm_obs_ptr[l]; o < p->lm_obs_ptr[l + 1]; ++o) {
+          if (stamp[p->obs_kf[o]] == l) return bad("landmark observed twice by one keyframe");
+          stamp[p->obs_kf[o]] = l;
+        }
+    }
     if (p->num_cam <= 0 || !p->cam_extr || !p->cam_intr || !p->cam_dist || !p->cam_dist_type) return bad("NULL camera array");
     for (int k = 0; k < K; ++k) if (p->kf_cam[k] < 0 || p->kf_cam[k] >= p->num_cam) return bad("kf_cam out of range");
     for (int a = 0; a < p->num_cam; ++a) if (p->cam_dist_type[a] != COVGPU_DIST_RADTAN && p->cam_dist_type[a] != COVGPU_DIST_EQUIDISTANT) return bad("unknown distortion type");

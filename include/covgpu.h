@@ -105,7 +105,10 @@ typedef struct covgpu_problem {
   const int32_t* cam_dist_type;  /* [A]    */
 
   /* landmarks + observations. Observations are grouped by landmark (the reference's iteration
-   * order, opt_be.cpp:432-530): those of landmark l are [lm_obs_ptr[l], lm_obs_ptr[l+1]). */
+   * order, opt_be.cpp:432-530): those of landmark l are [lm_obs_ptr[l], lm_obs_ptr[l+1]), in any keyframe order.
+   * A landmark has at most ONE observation per keyframe (the reference keys a landmark's observations by keyframe): two
+   * observations of a landmark by the same keyframe are COVGPU_ERR_INVALID_ARG ("landmark observed twice by one keyframe") —
+   * the covisible-pair lists never pair a keyframe with itself, so their cross terms would be missing from the reduced system. */
   double*        lm_pos;         /* [L][3]  in/out  world position                 */
   const int32_t* lm_obs_ptr;     /* [L+1]                                          */
   const int32_t* obs_kf;         /* [O]                                            */
