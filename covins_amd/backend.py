@@ -143,6 +143,149 @@ class ConsistencyFilter:
         return enough
 
 
+class BowDb:
+    """The resident keyframe database of one context (covgpu_bowdb): the vocabulary, the bow vectors and the inverted
+    index stay on the device across calls. Keyframes are named by slots, dense non-negative numbers chosen by the caller. Made by
+    Context.bowdb(); calls on one context are serialised by the caller."""
+
+    def __init__(self, ctx: "Context", voc: Optional[dict] = None, mode="covins", **opts):
+        self._ctx, self._h = ctx, C.c_void_p()
+        m = {"covins": capi.DETECT_COVINS, "covins_g": capi.DETECT_COVINS_G}.get(mode, mode)
+        o = capi.BowDbOpts()
+        lib().covgpu_default_bowdb_opts(C.byref(o), int(m))
+        for k, v in opts.items():
+            if k in ("min_score_factor", "min_loop_dist", "exclude_kfs_with_id_less_than", "inter_map_matches_only", "scratch_kib"):
+                setattr(o.detect, k, v)
+            elif k in ("levelsup", "tail_limit", "reserve_kf", "reserve_words", "num_words"):
+                setattr(o, k, int(v))
+            else:
+                raise TypeError(f"unknown bowdb option {k}")
+        self.levelsup = int(o.levelsup)
+        keep = []
+        v = None if voc is None else C.byref(Context._bow_vocab(voc, keep))
+        ctx._check(lib().covgpu_bowdb_create(ctx._h, v, C.byref(o), C.byref(self._h)))
+
+    def _check(self, rc: int):
+        self._ctx._check(rc)
+
+    def close(self):
+        if self._h and self._ctx._h:               # (a closed context has destroyed its databases)
+            lib().covgpu_bowdb_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _i32(a):
+        return np.ascontiguousarray(a, dtype=np.int32).ravel()
+
+    def _meta(self, slot, id, client):
+        s, i, c = self._i32(slot), self._i32(id), self._i32(client)
+        if len(i) != len(s) or len(c) != len(s):
+            raise ValueError("slot, id and client differ in length")
+        return s, i, c
+
+    def put(self, slot, id, client, bow_ptr, word, value):
+        """Stores vectors computed elsewhere: a bow CSR with one row per slot (covgpu_bowdb_put)."""
+        s, i, c = self._meta(slot, id, client)
+        ptr, w = self._i32(bow_ptr), self._i32(word)
+        v = np.ascontiguousarray(value, dtype=np.float64).ravel()
+        if len(ptr) != len(s) + 1 or len(v) != len(w) or (len(s) and int(ptr[-1]) > len(w)):
+            raise ValueError("bow arrays do not fit the slots")
+        self._check(lib().covgpu_bowdb_put(self._h, len(s), iptr(s), iptr(i), iptr(c), iptr(ptr), iptr(w), dptr(v)))
+
+    def put_descriptors(self, slot, id, client, sets: dict, want: bool = False):
+        """Transforms descriptor sets (row_ptr [S+1], desc [rows,32]) against the resident vocabulary and stores the vectors without a
+        round trip (covgpu_bowdb_put_descriptors). want: also download them; returns what Context.bow_transform_batch returns."""
+        s, i, c = self._meta(slot, id, client)
+        ptr = self._i32(sets["row_ptr"])
+        desc = np.ascontiguousarray(sets["desc"], dtype=np.uint8).reshape(-1, 32)
+        S, rows = len(ptr) - 1, len(desc)
+        if S != len(s) or (S > 0 and int(ptr[-1]) > rows):
+            raise ValueError("descriptor sets do not fit the slots")
+        bt = capi.BowTransformBatch(S, iptr(ptr), desc.ctypes.data_as(capi._bp), self.levelsup, 0, None, None, None, None, None, None)
+        if want:
+            bptr = np.zeros(S + 1, np.int32); word = np.zeros(max(rows, 1), np.int32); value = np.zeros(max(rows, 1))
+            rw = np.full(max(rows, 1), -1, np.int32); rn = np.zeros(max(rows, 1), np.int32); tot = C.c_int64(0)
+            bt.capacity, bt.bow_ptr, bt.word, bt.value, bt.total = rows, iptr(bptr), iptr(word), dptr(value), C.pointer(tot)
+            bt.row_word, bt.row_node = iptr(rw), iptr(rn)
+        self._check(lib().covgpu_bowdb_put_descriptors(self._h, iptr(s), iptr(i), iptr(c), C.byref(bt)))
+        if want:
+            n = int(tot.value)
+            return dict(bow_ptr=bptr, word=word[:n], value=value[:n], row_word=rw[:rows], row_node=rn[:rows], total=n)
+        return None
+
+    def set_neighbours(self, slot, neighbours):
+        """The connected keyframes (slots, the reference's order) of each slot; the first ten are kept."""
+        s = self._i32(slot)
+        if len(neighbours) != len(s):
+            raise ValueError("one neighbour list per slot")
+        ptr = np.zeros(len(s) + 1, np.int32); ptr[1:] = np.cumsum([len(x) for x in neighbours])
+        nb = self._i32(np.concatenate([self._i32(x) for x in neighbours] + [np.zeros(0, np.int32)]))
+        self._check(lib().covgpu_bowdb_set_neighbours(self._h, len(s), iptr(s), iptr(ptr), iptr(nb)))
+
+    def set_invalid(self, slot, flag):
+        s = self._i32(slot); f = np.ascontiguousarray(flag, dtype=np.uint8).ravel()
+        if len(f) != len(s):
+            raise ValueError("one flag per slot")
+        self._check(lib().covgpu_bowdb_set_invalid(self._h, len(s), iptr(s), f.ctypes.data_as(capi._bp)))
+
+    def add(self, slot):
+        """AddKeyframe: the slots join the insertion order at its end."""
+        s = self._i32(slot)
+        self._check(lib().covgpu_bowdb_add(self._h, len(s), iptr(s)))
+
+    def erase(self, slot):
+        """EraseKeyframe: slots that are not in the index are skipped."""
+        s = self._i32(slot)
+        self._check(lib().covgpu_bowdb_erase(self._h, len(s), iptr(s)))
+
+    def query(self, query_slot, connected, min_score=None, cap: Optional[int] = None):
+        """DetectCandidates of the stored slots query_slot against the database as it is; connected[q]: the query's whole connected
+        list (slots, the reference's order). Returns what Context.detect_candidates_batch returns, candidates as slots. cap defaults
+        to the number of live entries."""
+        qs = self._i32(query_slot)
+        Q = len(qs)
+        if len(connected) != Q:
+            raise ValueError("one connected list per query")
+        cptr = np.zeros(Q + 1, np.int32); cptr[1:] = np.cumsum([len(x) for x in connected])
+        con = self._i32(np.concatenate([self._i32(x) for x in connected] + [np.zeros(0, np.int32)]))
+        ms = None if min_score is None else np.ascontiguousarray(min_score, dtype=np.float64).ravel()
+        if ms is not None and len(ms) != Q:
+            raise ValueError("min_score does not fit the queries")
+        cap = self.stats()["live"] if cap is None else int(cap)
+        n = max(Q, 1)
+        nc = np.zeros(n, np.int32); cand = np.full((n, max(cap, 1)), -1, np.int32); acc = np.zeros((n, max(cap, 1)), np.float32)
+        mso = np.zeros(n); nsh = np.zeros(n, np.int32); mcw = np.zeros(n, np.int32); nsc = np.zeros(n, np.int32)
+        s = capi.BowDbQuery(Q, iptr(qs), iptr(cptr), iptr(con), dptr(ms), cap, iptr(nc), iptr(cand), acc.ctypes.data_as(capi._fp), dptr(mso),
+                            iptr(nsh), iptr(mcw), iptr(nsc))
+        self._check(lib().covgpu_bowdb_query(self._h, C.byref(s)))
+        kept = np.minimum(nc[:Q], cap)
+        return dict(candidates=[cand[q, :kept[q]].copy() for q in range(Q)], acc_score=[acc[q, :kept[q]].copy() for q in range(Q)],
+                    num_candidates=nc[:Q], min_score=mso[:Q], num_sharing=nsh[:Q], max_common_words=mcw[:Q], num_scored=nsc[:Q])
+
+    def compact(self):
+        """Rebuilds the base index now: erased positions and dead pool words go."""
+        self._check(lib().covgpu_bowdb_compact(self._h))
+
+    def order(self):
+        """The live slots in insertion order."""
+        n = C.c_int32(0)
+        out = np.zeros(max(self.stats()["live"], 1), np.int32)
+        self._check(lib().covgpu_bowdb_order(self._h, len(out), iptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def stats(self) -> dict:
+        """covgpu_bowdb_stats by name (capi.BOWDB_STATS); h2d_bytes / d2h_bytes are those of the last call."""
+        out = (C.c_int64 * 16)()
+        self._check(lib().covgpu_bowdb_stats(self._h, out))
+        return {k: int(out[i]) for i, k in enumerate(capi.BOWDB_STATS)}
+
+
 class Context:
     """One solver context = one HIP stream + HBM workspace (covgpu_create / covgpu_destroy)."""
 
@@ -430,6 +573,12 @@ class Context:
                                        None if ex is None else iptr(ex), iptr(claimed), iptr(remap), iptr(bd), iptr(nm))
         self._check(lib().covgpu_search_projection_batch(self._h, C.byref(s), C.byref(o)))
         return dict(claimed=claimed[:P], remap_to=remap[:P], best_dist=bd[:P], nmatches=nm[:J])
+
+    def bowdb(self, voc: Optional[dict] = None, **opts) -> "BowDb":
+        """A resident keyframe database on this context (covgpu_bowdb_create). voc: a vocabulary as covins_amd/vocio.py
+        reads it, or None for a handle that only takes ready vectors (put). opts: mode ("covins" | "covins_g"), the detect options of
+        detect_candidates_batch, levelsup, tail_limit, reserve_kf, reserve_words, num_words."""
+        return BowDb(self, voc, **opts)
 
     @staticmethod
     def _bow_vocab(voc: dict, keep: list):

@@ -280,6 +280,22 @@ class DetectBatch(C.Structure):
                 ("acc_score", _fp), ("min_score", _dp), ("num_sharing", _ip), ("max_common_words", _ip), ("num_scored", _ip)]
 
 
+class BowDbOpts(C.Structure):
+    """covgpu_bowdb_opts (include/covgpu.h): the resident keyframe database, DESIGN.md §4.16."""
+    _fields_ = [("detect", DetectOpts), ("levelsup", C.c_int32), ("tail_limit", C.c_int32), ("reserve_kf", C.c_int32),
+                ("reserve_words", C.c_int32), ("num_words", C.c_int32)]
+
+
+class BowDbQuery(C.Structure):
+    _fields_ = [("num_queries", C.c_int32), ("query_slot", _ip), ("con_ptr", _ip), ("con", _ip), ("min_score_in", _dp), ("cap", C.c_int32),
+                ("num_candidates", _ip), ("candidates", _ip), ("acc_score", _fp), ("min_score", _dp), ("num_sharing", _ip),
+                ("max_common_words", _ip), ("num_scored", _ip)]
+
+
+BOWDB_STATS = ("stored", "live", "positions", "base_postings", "tail", "rebuilds", "h2d_bytes", "d2h_bytes", "device_bytes", "pool_used",
+               "pool_dead", "slot_capacity", "position_capacity", "pool_capacity", "growths")   # covgpu_bowdb_stats out[0..14]
+
+
 class PruneBatch(C.Structure):
     """covgpu_prune_t (include/covgpu.h): Map::RemoveRedundantData as one call, DESIGN.md §4.14."""
     _fields_ = [("num_kf", C.c_int32), ("num_lm", C.c_int32), ("lm_obs_ptr", _ip), ("obs_kf", _ip), ("lm_invalid", _bp), ("kf_invalid", _bp),
@@ -357,6 +373,19 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("bow_score_pairs", [C.c_void_p, C.c_int32, _ip, _ip, _dp, C.c_int32, _ip, _ip, _dp])
         d("default_detect_opts", [C.POINTER(DetectOpts), C.c_int32], None)
         d("detect_candidates_batch", [C.c_void_p, C.POINTER(DetectBatch), C.POINTER(DetectOpts)])
+        d("default_bowdb_opts", [C.POINTER(BowDbOpts), C.c_int32], None)
+        d("bowdb_create", [C.c_void_p, C.POINTER(BowVocab), C.POINTER(BowDbOpts), C.POINTER(C.c_void_p)])
+        d("bowdb_destroy", [C.c_void_p], None)
+        d("bowdb_put", [C.c_void_p, C.c_int32, _ip, _ip, _ip, _ip, _ip, _dp])
+        d("bowdb_put_descriptors", [C.c_void_p, _ip, _ip, _ip, C.POINTER(BowTransformBatch)])
+        d("bowdb_set_neighbours", [C.c_void_p, C.c_int32, _ip, _ip, _ip])
+        d("bowdb_set_invalid", [C.c_void_p, C.c_int32, _ip, _bp])
+        d("bowdb_add", [C.c_void_p, C.c_int32, _ip])
+        d("bowdb_erase", [C.c_void_p, C.c_int32, _ip])
+        d("bowdb_query", [C.c_void_p, C.POINTER(BowDbQuery)])
+        d("bowdb_compact", [C.c_void_p])
+        d("bowdb_order", [C.c_void_p, C.c_int32, _ip, _ip])
+        d("bowdb_stats", [C.c_void_p, C.POINTER(C.c_int64)])
         d("default_prune_opts", [C.POINTER(PruneOpts)], None)
         d("prune_check", [C.POINTER(PruneBatch), C.POINTER(PruneOpts)])
         d("prune_redundant", [C.c_void_p, C.POINTER(PruneBatch), C.POINTER(PruneOpts)])

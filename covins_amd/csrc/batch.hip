@@ -425,7 +425,7 @@ extern "C" int covgpu_pgo_reanchor(covgpu_context* c, int32_t K, const double* p
 }
 
 // ---- bag-of-words retrieval (k_bow.hip) ----
-namespace {
+// (the two checks are shared with bowdb.hip: declared in host.hpp)
 
 // The first violation of a bow CSR over `rows` rows (word ids ascending and duplicate-free, values finite), or nullptr.
 const char* bow_csr_check(int rows, const int32_t* ptr, const int32_t* word, const double* value) {
@@ -479,8 +479,6 @@ const char* bow_vocab_check(const covgpu_bow_vocab_t* v) {
   for (int w = 0; w < W; ++w) if (!seen[w]) return "word ids are not a permutation of 0..num_words-1";
   return nullptr;
 }
-
-}  // namespace
 
 extern "C" int covgpu_bow_transform_batch(covgpu_context* c, const covgpu_bow_vocab_t* v, const covgpu_bow_transform_batch_t* bt) {
   return batch_entry("covgpu_bow_transform_batch", c, [&](auto bad) -> int {
@@ -557,7 +555,7 @@ extern "C" int covgpu_bow_score_pairs(covgpu_context* c, int32_t num_vec, const 
     double *dv = nullptr, *ds = nullptr;
     HIPCHK(U.upload(&dp, bow_ptr, (size_t)num_vec + 1)); HIPCHK(U.upload(&dw, word, nnz)); HIPCHK(U.upload(&dv, value, nnz));
     HIPCHK(U.upload(&da, a, P)); HIPCHK(U.upload(&db, b, P)); HIPCHK(U.alloc(&ds, P));
-    launch_bow_score_pairs(dp, dw, dv, num_pairs, da, db, ds, c->st);
+    launch_bow_score_pairs(dp, dp + 1, dw, dv, num_pairs, da, db, ds, c->st);
     HIPCHK(hipGetLastError());
     HIPCHK(U.fetch(score, ds, P));
     HIPCHK(hipStreamSynchronize(c->st));
@@ -649,9 +647,12 @@ extern "C" int covgpu_detect_candidates_batch(covgpu_context* c, const covgpu_de
     D.M = M; D.inv_words = inv_words;
     const size_t nnz = N > 0 ? (size_t)bt->bow_ptr[N] : 0, Ns = (size_t)N, Qs = (size_t)Q, caps = (size_t)cap;
     HIPCHK(U.upload(&D.id, bt->id, Ns)); HIPCHK(U.upload(&D.client, bt->client, Ns));
-    HIPCHK(U.upload(&D.bow_ptr, bt->bow_ptr, Ns + 1)); HIPCHK(U.upload(&D.word, bt->word, nnz));
-    HIPCHK(U.upload(&D.value, bt->value, nnz)); HIPCHK(U.upload(&D.nb_ptr, bt->nb_ptr, Ns + 1));
-    HIPCHK(U.upload(&D.nb, bt->nb, NB)); HIPCHK(U.upload(&D.db_order, bt->db_order, (size_t)M));
+    HIPCHK(U.upload(&D.vec_beg, bt->bow_ptr, Ns + 1)); HIPCHK(U.upload(&D.word, bt->word, nnz));
+    HIPCHK(U.upload(&D.value, bt->value, nnz)); HIPCHK(U.upload(&D.nb_beg, bt->nb_ptr, Ns + 1));
+    HIPCHK(U.upload(&D.nb, bt->nb, NB));
+    D.vec_end = D.vec_beg + 1; D.nb_end = D.nb_beg + 1;                // a CSR pointer array as (begin, end)
+    D.con_beg = D.nb_beg; D.con_end = D.nb_end; D.con = D.nb;          // a query's connected list is its row of the table
+    HIPCHK(U.upload(&D.db_order, bt->db_order, (size_t)M));
     HIPCHK(U.upload(&D.pos_of, pos_of.data(), Ns)); HIPCHK(U.upload(&D.inv_ptr, inv_ptr.data(), inv_ptr.size()));
     HIPCHK(U.upload(&D.inv_pos, inv_pos.data(), inv_pos.size())); HIPCHK(U.upload(&D.query_kf, bt->query_kf, Qs));
     HIPCHK(U.upload(&D.db_visible, bt->db_visible, Qs));
@@ -666,7 +667,7 @@ extern "C" int covgpu_detect_candidates_batch(covgpu_context* c, const covgpu_de
       double* dps = nullptr;
       HIPCHK(U.upload(&dpa, pa.data(), pa.size())); HIPCHK(U.upload(&dpb, pb.data(), pb.size()));
       HIPCHK(U.upload(&dpo, poff.data(), poff.size())); HIPCHK(U.alloc(&dps, pa.size()));
-      launch_bow_score_pairs(D.bow_ptr, D.word, D.value, (int)pa.size(), dpa, dpb, dps, c->st);
+      launch_bow_score_pairs(D.vec_beg, D.vec_end, D.word, D.value, (int)pa.size(), dpa, dpb, dps, c->st);
       launch_bow_min_score(D, Q, dpo, dps, opts->min_score_factor, c->st);
     }
     // per-query scratch is 28 B per database entry; queries run in chunks that keep it within the budget

@@ -639,22 +639,55 @@ struct BowVocabDev {
   const double* word_weight;                                                      // [words] the leaf weight of each word
 };
 struct DetectOptsDev { int min_loop_dist, exclude_below, inter_only; };
+// Keyframe k's bow vector is word / value [vec_beg[k], vec_end[k]) and its neighbour list nb [nb_beg[k], nb_end[k]): the stateless
+// entry point passes a CSR pointer array p as (p, p + 1), the resident database (k_bowdb.hip) keeps a begin and an end per slot.
 struct DetectDev {
-  int M;                                                           // database entries
-  const int* id; const int* client; const int* bow_ptr; const int* word; const double* value; const int* nb_ptr; const int* nb;
+  int M;                                                           // database positions
+  const int* id; const int* client; const int* vec_beg; const int* vec_end; const int* word; const double* value;
+  const int* nb_beg; const int* nb_end; const int* nb;
+  // the query's connected keyframes con [con_beg[i], con_end[i]): i is the query's keyframe, or the query number if con_by_query
+  const int* con_beg; const int* con_end; const int* con; int con_by_query;
   const int* db_order; const int* pos_of;                           // position -> keyframe, keyframe -> position or -1
-  int inv_words; const int* inv_ptr; const int* inv_pos;            // inverted index: word -> positions, ascending
+  const unsigned char* dead;                                        // [M] an erased position (resident database), or nullptr: none
+  int tail;                                                         // the positions [M - tail, M) are not in the inverted index
+  int inv_words; const int* inv_ptr; const int* inv_pos;            // inverted index: word -> positions
   const int* query_kf; const int* db_visible;
   double* min_score; int* max_common; int* num_sharing; int* num_scored; int* num_candidates; int* candidates; float* acc_score;
 };
 void launch_bow_transform(const BowVocabDev& V, const unsigned char* desc, const int* row_ptr, int num_sets, int rows, int nid_level,
                           int add_weight, int* row_word, int* row_node, int* out_word, double* out_value, int* count, hipStream_t st);
-void launch_bow_score_pairs(const int* bow_ptr, const int* word, const double* value, int num_pairs, const int* a, const int* b,
-                            double* score, hipStream_t st);
+void launch_bow_score_pairs(const int* vec_beg, const int* vec_end, const int* word, const double* value, int num_pairs, const int* a,
+                            const int* b, double* score, hipStream_t st);
 void launch_bow_min_score(const DetectDev& D, int num_queries, const int* pair_off, const double* pair_score, double factor,
                           hipStream_t st);
 void launch_bow_detect_chunk(const DetectDev& D, const DetectOptsDev& O, int q0, int nq, int cap, int hist_stride, int* common, int* first,
                              double* score, float* acc, int* best, int* order, int* hist, hipStream_t st);
+// k_bowdb.hip: the resident keyframe database. Per slot: id, client, the vector's range in the pool, the position in
+// the insertion order or -1, a row of kBowDbNeighbours neighbour slots. Per position: the slot and the erased flag.
+constexpr int kBowDbNeighbours = 10;    // kf_database.cpp:141-142: the first ten connected keyframes of an entry
+struct BowDbDev {
+  int* id; int* client; int* vec_beg; int* vec_end; int* pos_of; int* nb_beg; int* nb_end; int* nb;
+  int* db_order; unsigned char* dead;
+  int* word; double* value;             // the vector pool
+};
+void launch_bowdb_tail_count(const DetectDev& D, int q0, int nq, int* common, int* first, hipStream_t st);
+void launch_bowdb_store_meta(const BowDbDev& B, int n, const int* slot, const int* id, const int* client, const int* beg, const int* end,
+                             hipStream_t st);
+void launch_bowdb_gather(int num_sets, const int* row_ptr, const int* count, const int* dst, const int* src_word, const double* src_value,
+                         int* pool_word, double* pool_value, hipStream_t st);
+void launch_bowdb_set_neighbours(const BowDbDev& B, int n, const int* slot, const int* rows, const int* count, hipStream_t st);
+void launch_bowdb_add(const BowDbDev& B, int n, const int* slot, int p0, hipStream_t st);
+void launch_bowdb_erase(const BowDbDev& B, int n, const int* slot, hipStream_t st);
+size_t bowdb_scan_tmp_ints(int n_out);  // ints of scratch launch_bowdb_scan needs for n_out outputs
+// exclusive scan: out[i] = in[0] + ... + in[i - 1] for i < n_out, in[i] = 0 from n_in on; in may be out
+void launch_bowdb_scan(const int* in, int n_in, int* out, int n_out, int* tmp, hipStream_t st);
+// rebuild, step by step: new_pos [P + 1] and new_order [live] (pos_of follows); new_beg [slots + 1] and the compacted pool (the slots'
+// ranges follow); word_count [words] += the live entries' words; inv_pos filled through cursor [words], a copy of the scanned counts
+void launch_bowdb_renumber(const BowDbDev& B, int P, int* new_pos, int* new_order, int* scan_tmp, hipStream_t st);
+void launch_bowdb_compact_pool(const BowDbDev& B, int num_slots, int* new_beg, int* new_word, double* new_value, int* scan_tmp,
+                               hipStream_t st);
+void launch_bowdb_histogram(const BowDbDev& B, int live, int* word_count, hipStream_t st);
+void launch_bowdb_scatter(const BowDbDev& B, int live, int* cursor, int* inv_pos, hipStream_t st);
 void launch_reanchor(int K, const double* pose_old, const double* pose_new, double* vel, int L, const int* ref, double* lm,
                      hipStream_t st);
 

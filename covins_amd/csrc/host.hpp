@@ -1,4 +1,4 @@
-// host.hpp — what the host files of libcovgpu (solver.hip, batch.hip) share: the context, the error plumbing of the extern "C"
+// host.hpp — what the host files of libcovgpu (solver.hip, batch.hip, bowdb.hip) share: the context, the error plumbing of the extern "C"
 // entry points and the per-call device scratch. Host-only: no kernel file includes it.
 #pragma once
 #include <atomic>
@@ -75,7 +75,12 @@ struct covgpu_context {
   int* d_pairkey = nullptr;    // [K] key of every keyframe in the covisible-pair numbering (chain position, -1: constant pose), kept for the second round of a call
   std::vector<int> h_perm;     // [K] keyframe -> chain position of the resident problem
   std::atomic<int>* peer_fail = nullptr;   // covgpu_gba_solve_multi: raised by any rank of the call that gave up; polled while waiting
+  std::vector<covgpu_bowdb*> bowdbs;       // resident keyframe databases of this context (bowdb.hip): destroyed with it
 };
+
+// argument checks of the bag-of-words entry points (batch.hip), shared with the resident database (bowdb.hip): the first violation, or nullptr
+__attribute__((visibility("hidden"))) const char* bow_csr_check(int rows, const int32_t* ptr, const int32_t* word, const double* value);
+__attribute__((visibility("hidden"))) const char* bow_vocab_check(const covgpu_bow_vocab_t* v);
 
 #define RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 // no C++ exception may cross the extern "C" boundary (std::bad_alloc from the host staging vectors, std::system_error from

@@ -6,7 +6,8 @@
 //
 // Transform: k_bow_descend walks the tree, one thread per descriptor (its row in 8 VGPRs, the lowest node ids staged in LDS);
 // k_bow_reduce, one workgroup per set, sorts (word, row) keys in LDS, forms each word's sum in row order and the norm in word order.
-// Query: k_bow_count walks the inverted index of the database with integer counters; k_bow_filter applies the per-keyframe filters
+// Query: k_bow_count walks the inverted index of the database with integer counters (the resident database of k_bowdb.hip counts the
+// positions outside its index beside it); k_bow_filter applies the per-keyframe filters
 // and takes maxCommonWords; k_bow_score_entries scores the entries above the common-word cut; k_bow_accumulate adds the scores of
 // the first 10 neighbours; k_bow_select orders the retained entries by (first common word, insertion position) with a counting
 // sort and replays the dedup in one lane.
@@ -152,12 +153,12 @@ __device__ double bow_score(const int* word, const double* value, int a0, int a1
   return -s / 2.0;
 }
 
-__global__ __launch_bounds__(kThreads) void k_bow_score_pairs(const int* bow_ptr, const int* word, const double* value, int num_pairs,
-                                                              const int* pa, const int* pb, double* score) {
+__global__ __launch_bounds__(kThreads) void k_bow_score_pairs(const int* vec_beg, const int* vec_end, const int* word, const double* value,
+                                                              int num_pairs, const int* pa, const int* pb, double* score) {
   const int i = blockIdx.x * kThreads + (int)threadIdx.x;
   if (i >= num_pairs) return;
   const int a = pa[i], b = pb[i];
-  score[i] = bow_score(word, value, bow_ptr[a], bow_ptr[a + 1], bow_ptr[b], bow_ptr[b + 1]);
+  score[i] = bow_score(word, value, vec_beg[a], vec_end[a], vec_beg[b], vec_end[b]);
 }
 
 // placerec_be.cpp:374-389: float minScore = 1; the float of each valid neighbour's score; min_score = (double)minScore * factor.
@@ -182,9 +183,9 @@ __global__ __launch_bounds__(kThreads) void k_bow_init(int n, int* common, int* 
 }
 
 __global__ __launch_bounds__(kThreads) void k_bow_mark_connected(DetectDev D, int q0, int* common) {
-  const int qc = blockIdx.x, kf = D.query_kf[q0 + qc];
-  for (int i = D.nb_ptr[kf] + (int)threadIdx.x; i < D.nb_ptr[kf + 1]; i += kThreads) {
-    const int p = D.pos_of[D.nb[i]];
+  const int qc = blockIdx.x, c = D.con_by_query ? q0 + qc : D.query_kf[q0 + qc];
+  for (int i = D.con_beg[c] + (int)threadIdx.x; i < D.con_end[c]; i += kThreads) {
+    const int p = D.pos_of[D.con[i]];
     if (p >= 0) common[(size_t)qc * D.M + p] = kConnected;
   }
 }
@@ -194,7 +195,7 @@ constexpr int kCountSlices = 4;                   // workgroups per query in k_b
 __global__ __launch_bounds__(kThreads) void k_bow_count(DetectDev D, int q0, int* common, int* first) {
   const int qc = blockIdx.x / kCountSlices, slice = blockIdx.x % kCountSlices;
   const int q = q0 + qc, kf = D.query_kf[q], vis = D.db_visible[q];
-  const int w0 = D.bow_ptr[kf], nw = D.bow_ptr[kf + 1] - w0;
+  const int w0 = D.vec_beg[kf], nw = D.vec_end[kf] - w0;
   int* cm = common + (size_t)qc * D.M;
   int* fs = first + (size_t)qc * D.M;
   for (int j = slice; j < nw; j += kCountSlices) {
@@ -213,7 +214,9 @@ __global__ __launch_bounds__(kThreads) void k_bow_filter(DetectDev D, DetectOpts
   const int qc = (int)(i / D.M), p = (int)(i % D.M), q = q0 + qc;
   int c = common[i];
   if (c == 0) return;
-  if (c > 0) {
+  if (D.dead && D.dead[p]) {
+    c = 0;                                        // an erased position: its postings stay in the index until the next rebuild
+  } else if (c > 0) {
     const int kq = D.query_kf[q], ki = D.db_order[p];
     const int idq = D.id[kq], idi = D.id[ki];
     const bool same = D.client[kq] == D.client[ki];
@@ -233,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void k_bow_score_entries(DetectDev D, int
   const int qc = (int)(i / D.M), p = (int)(i % D.M), q = q0 + qc;
   if (common[i] <= min_common_words(D.max_common[q])) return;       // common > 0 here: max_common >= 1 where any entry shares
   const int kq = D.query_kf[q], ki = D.db_order[p];
-  score[i] = bow_score(D.word, D.value, D.bow_ptr[kq], D.bow_ptr[kq + 1], D.bow_ptr[ki], D.bow_ptr[ki + 1]);
+  score[i] = bow_score(D.word, D.value, D.vec_beg[kq], D.vec_end[kq], D.vec_beg[ki], D.vec_end[ki]);
   atomicAdd(&D.num_scored[q], 1);
 }
 
@@ -248,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void k_bow_accumulate(DetectDev D, int q0
   if (common[i] <= cut || !(score[i] >= D.min_score[q])) { acc[i] = -1.0f; best[i] = -1; return; }
   float best_score = (float)score[i], a = (float)score[i];
   int bp = p;
-  const int ki = D.db_order[p], n0 = D.nb_ptr[ki], n1 = min(D.nb_ptr[ki + 1], n0 + 10), vis = D.db_visible[q];
+  const int ki = D.db_order[p], n0 = D.nb_beg[ki], n1 = min(D.nb_end[ki], n0 + 10), vis = D.db_visible[q];
   for (int e = n0; e < n1; ++e) {
     const int p2 = D.pos_of[D.nb[e]];
     if (p2 < 0 || p2 >= vis || common[base + p2] <= cut) continue;  // loop_query_ == kf->id_ && loop_words_ > minCommonWords
@@ -272,7 +275,7 @@ __global__ __launch_bounds__(kThreads) void k_bow_select(DetectDev D, int q0, in
   int* first = first_all + base;
   int* order = order_all + base;
   int* hist = hist_all + (size_t)qc * hist_stride;
-  const int kq = D.query_kf[q], nw = D.bow_ptr[kq + 1] - D.bow_ptr[kq];
+  const int kq = D.query_kf[q], nw = D.vec_end[kq] - D.vec_beg[kq];
   float m = -INFINITY;
   for (int p = tid; p < vis; p += kThreads)
     if (best[p] >= 0) m = fmaxf(m, acc[p]);
@@ -338,10 +341,11 @@ void launch_bow_transform(const BowVocabDev& V, const unsigned char* desc, const
                        out_value, count);
 }
 
-void launch_bow_score_pairs(const int* bow_ptr, const int* word, const double* value, int num_pairs, const int* a, const int* b,
-                            double* score, hipStream_t st) {
+void launch_bow_score_pairs(const int* vec_beg, const int* vec_end, const int* word, const double* value, int num_pairs, const int* a,
+                            const int* b, double* score, hipStream_t st) {
   if (num_pairs > 0)
-    hipLaunchKernelGGL(k_bow_score_pairs, dim3(blocks(num_pairs)), dim3(kThreads), 0, st, bow_ptr, word, value, num_pairs, a, b, score);
+    hipLaunchKernelGGL(k_bow_score_pairs, dim3(blocks(num_pairs)), dim3(kThreads), 0, st, vec_beg, vec_end, word, value, num_pairs, a, b,
+                       score);
 }
 
 void launch_bow_min_score(const DetectDev& D, int num_queries, const int* pair_off, const double* pair_score, double factor,
@@ -359,6 +363,7 @@ void launch_bow_detect_chunk(const DetectDev& D, const DetectOptsDev& O, int q0,
   hipLaunchKernelGGL(k_bow_init, dim3(blocks(n)), dim3(kThreads), 0, st, (int)n, common, first);
   hipLaunchKernelGGL(k_bow_mark_connected, dim3(nq), dim3(kThreads), 0, st, D, q0, common);
   hipLaunchKernelGGL(k_bow_count, dim3(nq * kCountSlices), dim3(kThreads), 0, st, D, q0, common, first);
+  launch_bowdb_tail_count(D, q0, nq, common, first, st);   // the positions outside the index (resident database only)
   hipLaunchKernelGGL(k_bow_filter, dim3(blocks(n)), dim3(kThreads), 0, st, D, O, q0, nq, common);
   hipLaunchKernelGGL(k_bow_score_entries, dim3(blocks(n)), dim3(kThreads), 0, st, D, q0, nq, common, score);
   hipLaunchKernelGGL(k_bow_accumulate, dim3(blocks(n)), dim3(kThreads), 0, st, D, q0, nq, common, score, acc, best);

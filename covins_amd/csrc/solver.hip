@@ -307,6 +307,7 @@ static void free_problem(covgpu_context* c) {
 extern "C" void covgpu_destroy(covgpu_context* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
+  while (!c->bowdbs.empty()) covgpu_bowdb_destroy(c->bowdbs.back());   // (each removes itself from the list)
   free_problem(c);
   for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
   c->chol.destroy();

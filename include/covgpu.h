@@ -722,6 +722,79 @@ typedef struct covgpu_detect_batch_t {
 } covgpu_detect_batch_t;
 int covgpu_detect_candidates_batch(covgpu_context*, const covgpu_detect_batch_t*, const covgpu_detect_opts*);
 
+/* ---- The resident keyframe database ----
+ *
+ * A covgpu_bowdb keeps the vocabulary, the bow vectors of the keyframes it was given and the inverted index of the keyframes that are
+ * in the database on the device across calls, so that a query uploads the query's own lists only. A query returns exactly what
+ * covgpu_detect_candidates_batch returns on the table of the stored slots with db_order = the live slots in insertion order,
+ * db_visible = all of them, nb of the query = its con list, nb of an entry = its stored first ten neighbours.
+ *
+ * Keyframes are named by slots: dense non-negative numbers below COVGPU_BOWDB_MAX_SLOTS chosen by the caller, as a table index is for
+ * the stateless call; the per-slot arrays (68 B a slot) reach up to the largest slot ever named, as a put, a neighbour or a connected
+ * keyframe. A slot is `stored` once it has a vector and `live` while it is in the index. The handle belongs to its context
+ * (covgpu_destroy destroys it) and works on the context's stream; calls on one context are serialised by the caller, as the reference's
+ * mtx_ does. An argument error (COVGPU_ERR_INVALID_ARG, with a message) leaves the handle as it was. Every buffer grows by doubling
+ * with device-to-device copies. */
+#define COVGPU_BOWDB_MAX_SLOTS (1 << 24)
+typedef struct covgpu_bowdb covgpu_bowdb;
+typedef struct covgpu_bowdb_opts {
+  covgpu_detect_opts detect;
+  int32_t levelsup;                              /* of put_descriptors; the reference passes 4 */
+  int32_t tail_limit;                            /* an add that leaves more positions than this outside the base index rebuilds it */
+  int32_t reserve_kf;                            /* initial capacity in slots and positions */
+  int32_t reserve_words;                         /* initial capacity of the vector pool, in (word, value) pairs */
+  int32_t num_words;                             /* word ids are below this; used without a vocabulary, 0 = COVGPU_BOW_MAX_WORDS */
+} covgpu_bowdb_opts;
+void covgpu_default_bowdb_opts(covgpu_bowdb_opts*, int32_t mode);   /* detect: covgpu_default_detect_opts(mode); 4, 256, 1024, 2^18, 0 */
+/* vocab may be NULL: the handle then takes vectors through covgpu_bowdb_put only. opts NULL: the defaults of COVGPU_DETECT_COVINS. */
+int  covgpu_bowdb_create(covgpu_context*, const covgpu_bow_vocab_t* vocab, const covgpu_bowdb_opts* opts, covgpu_bowdb** out);
+void covgpu_bowdb_destroy(covgpu_bowdb*);
+/* Stores n vectors computed elsewhere (the checks of a bow CSR, word ids below num_words). A slot that is live is refused; a stored
+ * slot that is not live gets the new vector. No slot twice in one call. */
+int covgpu_bowdb_put(covgpu_bowdb*, int32_t n, const int32_t* slot, const int32_t* id, const int32_t* client, const int32_t* bow_ptr,
+                     const int32_t* word, const double* value);
+/* The same from descriptor sets, through the transform kernels against the resident vocabulary; the vectors stay on the device.
+ * bt->num_sets sets go to slot[0 : num_sets]; bt->levelsup must be the handle's. Every output of bt may be NULL and is downloaded only
+ * if it is not (word / value: the first bt->capacity entries). */
+int covgpu_bowdb_put_descriptors(covgpu_bowdb*, const int32_t* slot, const int32_t* id, const int32_t* client,
+                                 const covgpu_bow_transform_batch_t* bt);
+/* The connected keyframes (slots, the reference's order) of n slots; the first ten of each are kept (kf_database.cpp:141-142). */
+int covgpu_bowdb_set_neighbours(covgpu_bowdb*, int32_t n, const int32_t* slot, const int32_t* nb_ptr, const int32_t* nb);
+/* IsInvalid() of n slots, for the reference minimum score. */
+int covgpu_bowdb_set_invalid(covgpu_bowdb*, int32_t n, const int32_t* slot, const uint8_t* flag);
+/* AddKeyframe: the slots join the insertion order at its end. A slot without a vector is refused. A slot that is live is refused too:
+ * the reference would list it twice and count its words twice, which no caller of it does. */
+int covgpu_bowdb_add(covgpu_bowdb*, int32_t n, const int32_t* slot);
+/* EraseKeyframe: a slot that is not live is skipped, as in the reference. The vector stays stored (it may be a query's neighbour). */
+int covgpu_bowdb_erase(covgpu_bowdb*, int32_t n, const int32_t* slot);
+typedef struct covgpu_bowdb_query_t {
+  int32_t num_queries;
+  const int32_t* query_slot;                     /* [num_queries] stored slots */
+  const int32_t* con_ptr;                        /* [num_queries+1] or NULL = no connected keyframes */
+  const int32_t* con;                            /* the query's whole connected list: slots, the reference's order */
+  const double*  min_score_in;                   /* [num_queries] or NULL: the reference minimum score; every connected slot that is
+                                                    not invalid must then be stored */
+  int32_t cap;
+  int32_t* num_candidates;                       /* out, as covgpu_detect_batch_t; candidates are slots */
+  int32_t* candidates;
+  float*   acc_score;
+  double*  min_score;
+  int32_t* num_sharing;
+  int32_t* max_common_words;
+  int32_t* num_scored;
+} covgpu_bowdb_query_t;
+/* All queries of one call see the same database state. */
+int covgpu_bowdb_query(covgpu_bowdb*, const covgpu_bowdb_query_t*);
+/* Rebuilds the base index now: erased positions and dead pool words go, the tail joins the base. */
+int covgpu_bowdb_compact(covgpu_bowdb*);
+/* The live slots in insertion order: the first `capacity` into slots, the true number into *count. */
+int covgpu_bowdb_order(covgpu_bowdb*, int32_t capacity, int32_t* slots, int32_t* count);
+/* out[0] stored slots, [1] live entries, [2] positions including erased ones, [3] postings in the base index, [4] positions in the tail,
+ * [5] rebuilds so far, [6] host-to-device and [7] device-to-host bytes of the last call on the handle other than this one (after create:
+ * the vocabulary upload), [8] device bytes held, [9] pool words in use, [10] pool words dead, [11] slot
+ * capacity, [12] position capacity, [13] pool capacity, [14] buffer growths so far, [15] 0. */
+int covgpu_bowdb_stats(covgpu_bowdb*, int64_t out[16]);
+
 /* ---------------------------------------------------------------- redundant-keyframe pruning
  * Map::RemoveRedundantData (map_be.cpp:745-811) on the device, as an exact integer rule.
  *

@@ -1370,7 +1370,7 @@ class LoopMatcherT {
 // ---- KeyframeDatabase with the reference's method names, the query batched on the GPU (covgpu_detect_candidates_batch, DESIGN.md
 // §4.13), plus the bag-of-words transform of arriving keyframes (keyframe_be.cpp:159-183) and the covisibility-consistency groups of
 // PlaceRecognition::DetectLoop (placerec_be.cpp:398-460). The database itself is a host-side insertion order; every call uploads what
-// it needs.
+// it needs. ResidentKeyframeDatabaseT below keeps the database on the device instead.
 struct BowVocabulary {                             // the flat form of covgpu_bow_vocab_t, owning its arrays
   int32_t k = 0, L = 0, scoring = COVGPU_BOW_L1_NORM, weighting = COVGPU_BOW_TF_IDF, num_words = 0;
   std::vector<int32_t> parent, child_ptr, child, word_id;
@@ -1548,6 +1548,215 @@ class KeyframeDatabaseT {
   int mode_;
   covgpu_detect_opts opts_;
   KeyframeVector order_;
+};
+
+// ---- KeyframeDatabase kept on the device across calls (covgpu_bowdb): the reference's method names on a resident
+// vocabulary, vector pool and inverted index. A query uploads the query's own lists; AddKeyframe / EraseKeyframe change the index in
+// place. Keyframes are mapped to the handle's slots in the order this class first meets them. One object per context; its calls are
+// serialised by the caller, as the reference's mtx_ does. KeyframeDatabaseT above is untouched and remains the stateless form.
+//
+// track_connections (default true): before each query the first ten connected keyframes and IsInvalid() of every live entry are read
+// again and sent (40 B + 1 flag per entry), which is exact whatever happened to the covisibility graph. false: the class relies on
+// TouchConnections(kf), which the integrator calls where the reference calls UpdateCovisibilityConnections or SetInvalid on kf.
+template <class Types>
+class ResidentKeyframeDatabaseT {
+ public:
+  using Keyframe = typename Types::Keyframe;
+  using KeyframePtr = std::shared_ptr<Keyframe>;
+  using KeyframeVector = std::vector<KeyframePtr>;
+
+  struct Query {
+    KeyframePtr kf;
+    bool has_min_score = false;                    // false: the reference score of DetectLoop over kf's valid neighbours
+    double min_score = 0.0;                        // in when has_min_score, out otherwise
+    KeyframeVector candidates;                     // out, in the reference's order
+    std::vector<float> acc_score;                  // out
+  };
+
+  // voc may be nullptr: ComputeBoW is then unavailable and vectors come from bow_vec_ (StoreBoW). Its arrays are read here only.
+  explicit ResidentKeyframeDatabaseT(const BowVocabulary* voc = nullptr, int mode = COVGPU_DETECT_COVINS) : mode_(mode) {
+    covgpu_default_bowdb_opts(&opts_, mode);
+    if (voc) { voc_ = *voc; have_voc_ = true; }
+  }
+  ResidentKeyframeDatabaseT(const ResidentKeyframeDatabaseT&) = delete;
+  ResidentKeyframeDatabaseT& operator=(const ResidentKeyframeDatabaseT&) = delete;
+  ~ResidentKeyframeDatabaseT() { Close(); }
+  void Close() { if (db_) covgpu_bowdb_destroy(db_); db_ = nullptr; }   // before the context goes (covgpu_destroy frees the handle too)
+  covgpu_bowdb_opts& options() { return opts_; }   // read when the handle is made, at the first call that needs the device
+  bool track_connections = true;
+  size_t max_candidates = (size_t)-1;
+
+  int32_t Slot(const KeyframePtr& kf) {
+    auto it = slot_.find(kf.get());
+    if (it != slot_.end()) return it->second;
+    slot_.emplace(kf.get(), (int32_t)kfs_.size());
+    kfs_.push_back(kf); stored_.push_back(0); live_.push_back(0);
+    return (int32_t)kfs_.size() - 1;
+  }
+  size_t size() const { return num_live_; }
+  KeyframeVector Order() {                         // the live keyframes in insertion order, read back from the device
+    std::vector<int32_t> s(num_live_ + 1);
+    int32_t n = 0;
+    check(covgpu_bowdb_order(handle(), (int32_t)num_live_, s.data(), &n));
+    KeyframeVector out;
+    for (int32_t i = 0; i < n; ++i) out.push_back(kfs_[s[i]]);
+    return out;
+  }
+
+  // voc->transform(descriptors_, bow_vec_, feat_vec_, levelsup) of every keyframe in one call; the vectors also stay on the device
+  void ComputeBoW(const KeyframeVector& kfs) {
+    std::vector<int32_t> ptr(1, 0), slot, id, client;
+    std::vector<uint8_t> desc;
+    for (const auto& kf : kfs) {
+      int rows = 0; const uint8_t* data = nullptr;
+      if (!detail::descriptors<Types>(*kf, 0, &rows, &data, 0)) rows = 0;
+      desc.insert(desc.end(), data, data + 32 * (size_t)rows);
+      ptr.push_back(ptr.back() + rows);
+      slot.push_back(Slot(kf)); id.push_back((int32_t)kf->id_.first); client.push_back((int32_t)kf->id_.second);
+    }
+    const size_t R = (size_t)ptr.back(), S = kfs.size();
+    std::vector<int32_t> bptr(S + 1), word(R + 1), rw(R + 1), rn(R + 1);
+    std::vector<double> value(R + 1);
+    desc.reserve(1);
+    covgpu_bow_transform_batch_t bt{};
+    bt.num_sets = (int32_t)S; bt.row_ptr = ptr.data(); bt.desc = desc.data(); bt.levelsup = opts_.levelsup; bt.capacity = (int32_t)R;
+    bt.bow_ptr = bptr.data(); bt.word = word.data(); bt.value = value.data(); bt.row_word = rw.data(); bt.row_node = rn.data();
+    check(covgpu_bowdb_put_descriptors(handle(), slot.data(), id.data(), client.data(), &bt));
+    for (size_t s = 0; s < S; ++s) {
+      detail::set_bow<Types>(*kfs[s], (size_t)(bptr[s + 1] - bptr[s]), &word[bptr[s]], &value[bptr[s]], 0);
+      detail::set_features<Types>(*kfs[s], (size_t)(ptr[s + 1] - ptr[s]), &rw[ptr[s]], &rn[ptr[s]], 0);
+      stored_[slot[s]] = 1;
+    }
+  }
+  // the keyframes' bow_vec_ as they are (computed elsewhere), for those not stored yet
+  void StoreBoW(const KeyframeVector& kfs) {
+    std::vector<int32_t> slot, id, client, bptr(1, 0), word;
+    std::vector<double> value;
+    for (const auto& kf : kfs) {
+      const int32_t s = Slot(kf);
+      if (stored_[s] == 1 || stored_[s] == 2) continue;
+      stored_[s] = 2;                              // (listed once)
+      slot.push_back(s); id.push_back((int32_t)kf->id_.first); client.push_back((int32_t)kf->id_.second);
+      detail::visit_bow<Types>(*kf, [&](int32_t w, double v) { word.push_back(w); value.push_back(v); }, 0);
+      bptr.push_back((int32_t)word.size());
+    }
+    if (slot.empty()) return;
+    word.reserve(1); value.reserve(1);
+    check(covgpu_bowdb_put(handle(), (int32_t)slot.size(), slot.data(), id.data(), client.data(), bptr.data(), word.data(), value.data()));
+    for (int32_t s : slot) stored_[s] = 1;
+  }
+
+  void AddKeyframe(const KeyframePtr& kf) {
+    const int32_t s = Slot(kf);
+    StoreBoW({kf});
+    if (!track_connections) TouchConnections(kf);
+    check(covgpu_bowdb_add(handle(), 1, &s));
+    live_[s] = 1; ++num_live_;
+  }
+  void EraseKeyframe(const KeyframePtr& kf) {
+    auto it = slot_.find(kf.get());
+    if (it == slot_.end() || !live_[it->second]) return;
+    check(covgpu_bowdb_erase(handle(), 1, &it->second));
+    live_[it->second] = 0; --num_live_;
+  }
+  // the first ten connected keyframes and IsInvalid() of kf, as the device keeps them
+  void TouchConnections(const KeyframePtr& kf) { send_connections({Slot(kf)}); }
+
+  KeyframeVector DetectCandidates(KeyframePtr kf, double min_score) {
+    std::vector<Query> q(1);
+    q[0].kf = std::move(kf); q[0].has_min_score = true; q[0].min_score = min_score;
+    DetectCandidatesBatch(q);
+    return q[0].candidates;
+  }
+
+  // Every query sees the database as it is. Either every query brings its min_score or none does.
+  void DetectCandidatesBatch(std::vector<Query>& queries) {
+    const bool g = mode_ == COVGPU_DETECT_COVINS_G;
+    const size_t Q = queries.size();
+    if (Q == 0) return;
+    const bool given = queries[0].has_min_score;
+    std::vector<int32_t> qs, cptr(1, 0), con, flag_slot;
+    std::vector<double> ms;
+    std::vector<uint8_t> flag;
+    KeyframeVector need;
+    for (const auto& q : queries) {
+      if (q.has_min_score != given) detail::fatal("DetectCandidatesBatch: min_score given for some queries only");
+      need.push_back(q.kf);
+      for (const auto& n : detail::connected_keyframes<Types>(*q.kf, g, 0)) {
+        con.push_back(Slot(n));
+        if (!given) {                              // the reference score reads the valid neighbours' vectors
+          flag_slot.push_back(con.back()); flag.push_back(n->IsInvalid() ? 1 : 0);
+          if (!n->IsInvalid()) need.push_back(n);
+        }
+      }
+      cptr.push_back((int32_t)con.size()); ms.push_back(q.min_score);
+    }
+    StoreBoW(need);
+    for (const auto& q : queries) qs.push_back(Slot(q.kf));
+    if (!flag_slot.empty()) check(covgpu_bowdb_set_invalid(handle(), (int32_t)flag_slot.size(), flag_slot.data(), flag.data()));
+    if (track_connections) {
+      std::vector<int32_t> all;
+      for (size_t s = 0; s < live_.size(); ++s) if (live_[s]) all.push_back((int32_t)s);
+      send_connections(all);
+    }
+    const size_t cap = std::min(num_live_, max_candidates);
+    std::vector<int32_t> nc(Q + 1), cand(Q * cap + 1);
+    std::vector<float> acc(Q * cap + 1);
+    std::vector<double> mso(Q + 1);
+    con.reserve(1);
+    covgpu_bowdb_query_t bq{};
+    bq.num_queries = (int32_t)Q; bq.query_slot = qs.data(); bq.con_ptr = cptr.data(); bq.con = con.data();
+    bq.min_score_in = given ? ms.data() : nullptr; bq.cap = (int32_t)cap;
+    bq.num_candidates = nc.data(); bq.candidates = cand.data(); bq.acc_score = acc.data(); bq.min_score = mso.data();
+    check(covgpu_bowdb_query(handle(), &bq));
+    for (size_t q = 0; q < Q; ++q) {
+      queries[q].candidates.clear(); queries[q].acc_score.clear();
+      queries[q].min_score = mso[q];
+      for (size_t i = 0; i < std::min((size_t)nc[q], cap); ++i) {
+        queries[q].candidates.push_back(kfs_[cand[q * cap + i]]);
+        queries[q].acc_score.push_back(acc[q * cap + i]);
+      }
+    }
+  }
+
+  void Stats(int64_t out[16]) { check(covgpu_bowdb_stats(handle(), out)); }
+
+ private:
+  static void check(int rc) { if (rc != COVGPU_OK) detail::fatal(covgpu_last_error()); }
+  covgpu_bowdb* handle() {
+    if (!db_) {
+      covgpu_bow_vocab_t v{};
+      if (have_voc_) v = voc_.view();
+      check(covgpu_bowdb_create(OptimizationT<Types>::Context(), have_voc_ ? &v : nullptr, &opts_, &db_));
+    }
+    return db_;
+  }
+  void send_connections(const std::vector<int32_t>& slots) {
+    if (slots.empty()) return;
+    const bool g = mode_ == COVGPU_DETECT_COVINS_G;
+    std::vector<int32_t> ptr(1, 0), nb;
+    std::vector<uint8_t> flag;
+    for (size_t i = 0; i < slots.size(); ++i) {    // (Slot() may grow kfs_: no reference into it is held)
+      const KeyframePtr kf = kfs_[slots[i]];
+      const auto con = detail::connected_keyframes<Types>(*kf, g, 0);
+      for (size_t j = 0; j < std::min<size_t>(con.size(), 10); ++j) nb.push_back(Slot(con[j]));
+      ptr.push_back((int32_t)nb.size());
+      flag.push_back(kf->IsInvalid() ? 1 : 0);
+    }
+    nb.reserve(1);
+    check(covgpu_bowdb_set_neighbours(handle(), (int32_t)slots.size(), slots.data(), ptr.data(), nb.data()));
+    check(covgpu_bowdb_set_invalid(handle(), (int32_t)slots.size(), slots.data(), flag.data()));
+  }
+
+  int mode_;
+  covgpu_bowdb_opts opts_;
+  BowVocabulary voc_;
+  bool have_voc_ = false;
+  covgpu_bowdb* db_ = nullptr;
+  std::unordered_map<const Keyframe*, int32_t> slot_;
+  KeyframeVector kfs_;                             // slot -> keyframe
+  std::vector<uint8_t> stored_, live_;
+  size_t num_live_ = 0;
 };
 
 // ---- Map::RemoveRedundantData (map_be.cpp:745-811) ----
