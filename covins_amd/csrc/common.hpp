@@ -26,6 +26,7 @@
 
 namespace covgpu {
 
+constexpr int kEdgeRec = 132;  // doubles per edge of k_edge_build's record: Hii(36) Hjj(36) Hij(36) gi(6) gj(6) diag i(6) diag j(6)
 constexpr int kTile = 128;  // panel width / tile edge of the dense reduced-system factorisation
 
 struct DevProblem {
@@ -60,6 +61,7 @@ struct DevProblem {
   int npairs;
   int *pair_ptr, *pair_i, *pair_j;          // [npairs+1], [npairs] chain-major positions, i > j
   int *pair_oa, *pair_ob;                   // [sum] observation of keyframe i / keyframe j of each common landmark
+  int *pair_order;                          // [npairs rounded up to 512] the pair every slot of k_pair_blocks works on (-1: none): the list order, inside every 512, by falling length
   double *obsZ;                             // [O][18] per-observation Z = (Jp^T Jl) R with Hll^-1 = R R^T: the one record of the landmark elimination (k_visual.hip),
                                             // KEYFRAME-major (slot obs_zpos[o]): the records a covisible pair reads lie in its two keyframes' 60-KB blocks (L2)
   double *lmRT;                             // [L][9] per landmark: lower factor R (6) | t = R^T g_l (3)
@@ -208,6 +210,7 @@ inline int env_int(const char* name, int fallback) {
   return e != nullptr ? atoi(e) : fallback;
 }
 // ---- launchers (each enqueues on `st`, no synchronisation)
+size_t pair_order_slots(int npairs);   // entries of DevProblem::pair_order (allocated by the caller of launch_kobs_build, which fills it)
 void launch_kobs_build(const DevProblem& P, int* pair_oa, int* pair_ob, size_t nent, hipStream_t st);  // upload: keyframe-major copies, Z slots, pair lists -> Z slots
 void launch_lm_lin(const DevProblem& P, double mu, hipStream_t st, DevSignal sig = DevSignal());   // landmark-major linearisation: records, H_ll, g_l, cost partials
 void launch_lm_build(const DevProblem& P, double mu, hipStream_t st, hipEvent_t pose_system_cleared = nullptr, hipStream_t side = nullptr,
@@ -236,6 +239,7 @@ void launch_part_clear(const DevProblem& P, int slot0, int nslots, hipStream_t s
 void launch_part_finish(const DevProblem& P, int slot0, int nslots, hipStream_t st);
 void launch_imu_gather(const DevProblem& P, int which, hipStream_t st);  // which: 0 pose dims, 1 speed-bias dims, 2 both
 void launch_edge_gather(const DevProblem& P, hipStream_t st);
+void launch_pose_finish(const DevProblem& P, double mu, hipStream_t st);  // visual-inertial: k_imu_gather(0) + k_edge_gather_kf + k_edge_gather_pair + k_finalize_diag(0) in one launch (k_dense.hip)
 // structured solve of the damped reduced system: speed-bias chains -> dense pose system -> back-substitution.
 // Solution (IR layout, D per keyframe) is written to dst[0..n).
 struct PgoPlan;

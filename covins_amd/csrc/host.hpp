@@ -70,6 +70,7 @@ struct covgpu_context {
   // group barrier, scratch hipMalloc, non-zero ncclAllReduce): latched here, checked after the iteration's host synchronisation —
   // the solve then returns an error instead of an estimate computed from un-reduced top fronts
   bool coll_failed = false;
+  bool edge_beside_imu = false;  // a loop edge joins two neighbouring chain positions: its pair block may be an IMU factor's cross block too (enqueue_build)
   std::string coll_err;
   covgpu_group* group = nullptr;   // the in-process group this context's reducer belongs to (aborted when this rank gives up)
   int* d_pairkey = nullptr;    // [K] key of every keyframe in the covisible-pair numbering (chain position, -1: constant pose), kept for the second round of a call

@@ -16,7 +16,6 @@ namespace covgpu {
 using namespace covdev;
 
 // per-edge normal-equation pieces, written with plain stores: Hii(36) Hjj(36) Hij(36) gi(6) gj(6) hdi(6) hdj(6)
-constexpr int kEdgeRec = 132;
 __global__ __launch_bounds__(64) void k_edge_build(DevProblem P) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   double cost = 0.0;

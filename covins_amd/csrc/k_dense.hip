@@ -44,6 +44,81 @@ __global__ __launch_bounds__(256) void k_finalize_diag(DevProblem P, double mu, 
   if (which != 1 && !P.nd && q < P.npad - 6 * P.K) P.Sred[(size_t)pad * P.npad + pad] = 1.0;
 }
 
+// Visual-inertial problems, behind the landmark passes on the main stream: what k_imu_gather(which = 0), k_edge_gather_kf, k_edge_gather_pair and
+// k_finalize_diag(which = 0) do in four launches (each a link of the chain between the pair pass and the factorisation), in one. Two blockIdx segments:
+//   [0, nb_kf)   one wave per keyframe, one lane per entry it owns: the 15 entries below the diagonal of its pose block (lanes 0..14), the six rows — diagonal
+//                entry, gradient, right-hand side, diag(J^T J) — (lanes 15..20) and the 36 entries of the block pose_pos x pose_(pos-1) of the IMU factor
+//                that ends here (lanes 21..56; exactly 0: none). Per entry the additions keep their order: visual (stored by k_kf_reduce / k_pair_blocks),
+//                inertial (the two role slots added first), loop edges (summed from 0 in list order, added only where the keyframe has edges), then the
+//                rule of k_finalize_diag on the diagonal: the row's lane forms diag(J^T J) from the same three contributions, stores it once and damps
+//                with it — rows of another rank (P.nd_vown) are left alone, h == 0 becomes an identity row with bred = 0.
+//   the rest     the body of k_edge_gather_pair, one thread per entry of a loop-edge pair block. (The host takes this kernel only where no such block is
+//                a pose_pos x pose_(pos-1) block: solver.hip: enqueue_build.)
+__global__ __launch_bounds__(256) void k_pose_finish(DevProblem P, double mu, int nb_kf) {
+  if ((int)blockIdx.x >= nb_kf) {
+    const int t = ((int)blockIdx.x - nb_kf) * 256 + threadIdx.x;
+    const int pr = t / 36, q = t - 36 * pr;
+    if (pr >= P.nepairs) return;
+    const int r = q / 6, c = q - 6 * r;
+    double acc = 0.0;
+    for (int s2 = P.epair_ptr[pr]; s2 < P.epair_ptr[pr + 1]; ++s2) {
+      const int ent = P.epair_ent[s2], e = ent >> 1, tr = ent & 1;
+      const double* h = P.edgeOut + (size_t)kEdgeRec * e + 72;   // Hij: rows = dims of edge_i, cols = dims of edge_j
+      acc += tr ? h[6 * c + r] : h[6 * r + c];
+    }
+    *c_entry(P, P.epair_i[pr], P.epair_j[pr], r, c) += acc;
+    return;
+  }
+  const int kf = (int)blockIdx.x * 4 + (threadIdx.x >> 6), e = threadIdx.x & 63;
+  if (kf >= P.K || e >= 57) return;
+  const int pos = P.perm[kf];
+  const size_t K = (size_t)P.K, s0 = (size_t)pos, s1 = K + pos;
+  const int ea = P.E > 0 ? P.kf_edge_ptr[kf] : 0, eb = P.E > 0 ? P.kf_edge_ptr[kf + 1] : 0;
+  // k_edge_gather_kf's sum of entry q over the keyframe's edges: q < 36 block entry | < 42 gradient | < 48 diag(J^T J)
+  auto edge_sum = [&](int q) {
+    double acc = 0.0;
+    for (int s2 = ea; s2 < eb; ++s2) {
+      const int ent = P.kf_edge_ent[s2], ed = ent >> 1, role = ent & 1;
+      const double* o = P.edgeOut + (size_t)kEdgeRec * ed;
+      acc += (q < 36) ? o[36 * role + q] : (q < 42 ? o[108 + 6 * role + (q - 36)] : o[120 + 6 * role + (q - 42)]);
+    }
+    return acc;
+  };
+  if (e < 21) {
+    int r, c;
+    if (e < 15) { r = 1; while (r * (r + 1) / 2 <= e) ++r; c = e - r * (r - 1) / 2; }
+    else { r = e - 15; c = r; }
+    const int q = 6 * r + c;
+    double* d = c_entry(P, pos, pos, r, c);
+    double dv = *d;
+    dv += P.imuCd[36 * s0 + q] + P.imuCd[36 * s1 + q];
+    if (ea != eb) dv += edge_sum(q);
+    if (e >= 15) {
+      const size_t row = (size_t)15 * kf + r;
+      double g = P.grad[row], b = P.bred[row], h = P.hdiag[row];
+      const double v = P.imuG[30 * s0 + r] + P.imuG[30 * s1 + r];
+      g += v; b -= v;
+      h += P.imuG[30 * s0 + 15 + r] + P.imuG[30 * s1 + 15 + r];
+      if (ea != eb) {
+        const double acc = edge_sum(36 + r);
+        g += acc; b -= acc;
+        h += edge_sum(42 + r);
+      }
+      const int own = P.nd_vown != nullptr ? P.nd_vown[2 * pos] : 1;
+      if (own == 1) {
+        if (h == 0.0) { dv = 1.0; b = 0.0; }
+        else { const double cl = clamp_diag(h); dv += mu * cl * cl; }
+      }
+      P.grad[row] = g; P.bred[row] = b; P.hdiag[row] = h;
+    }
+    *d = dv;
+  } else {
+    const int q = e - 21, r = q / 6, c = q - 6 * r;
+    const double x = P.imuCd[36 * (2 * K + pos) + q];  // pose_pos x pose_(pos-1) of the factor ending here (exactly 0: none)
+    if (x != 0.0) *c_entry(P, pos, pos - 1, r, c) += x;
+  }
+}
+
 // fixed-order sum of one slot's partials -> scal[slot]
 // (1024 threads, four independent partial sums each: with 256 threads walking ~73 partials apiece in one dependent chain
 //  this tiny kernel took 20 us, five times per trust-region iteration)
@@ -251,6 +326,10 @@ static inline int vec_grid(int n) {
   return b < 1 ? 1 : (b > 2048 ? 2048 : b);
 }
 
+void launch_pose_finish(const DevProblem& P, double mu, hipStream_t st) {
+  const int nb_kf = (P.K + 3) / 4, nb_pair = P.E > 0 ? (36 * P.nepairs + 255) / 256 : 0;
+  hipLaunchKernelGGL(k_pose_finish, dim3(nb_kf + nb_pair), dim3(256), 0, st, P, mu, nb_kf);
+}
 void launch_finalize_diag(const DevProblem& P, double mu, int which, hipStream_t st) {
   const int cnt = P.n > P.npad ? P.n : P.npad;
   hipLaunchKernelGGL(k_finalize_diag, dim3((cnt + 255) / 256), dim3(256), 0, st, P, mu, which);

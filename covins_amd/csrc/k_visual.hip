@@ -19,7 +19,10 @@
 //                  right-hand side, diag(J^T J).
 //   k_pair_blocks  sixteen lanes per covisible keyframe pair (host-built lists, static per problem), lanes over the common
 //                  landmarks: C[i,j] = -sum Z_i Z_j^T with plain stores. Every entry has exactly one writer and a fixed
-//                  summation order: two solves of the same problem are bit-identical. (The first version accumulated the
+//                  summation order: two solves of the same problem are bit-identical. The sixteen lanes load a trip's records together,
+//                  consecutive lanes consecutive 16 bytes, through LDS; the pairs of an XCD chunk are dealt to its slots by falling
+//                  length (DevProblem::pair_order). k_lm_lin writes the records the same way, through a per-wave LDS tile.
+//                  (The first version accumulated the
 //                  6x6 blocks with FP64 atomics: 11.1 ms and run-to-run rounding differences; these three passes take
 //                  0.66 ms on the 5-agent map.)
 //   obs_*          one thread per observation over the SoA stream (cost, J*v products, test dumps).
@@ -165,18 +168,39 @@ __global__ __launch_bounds__(kBuildThreads) void k_lm_lin(DevProblem P, double m
     P.cost_part[blockIdx.x] = c4;
   }
 
-  for (int c = 0; c < nchunk; ++c) {
-    const int a = c * G + lane;
-    if (a >= nobs) continue;
-    if (nchunk > 1) {  // multi-chunk landmark: this chunk's Jacobians were overwritten above
-      kf = P.obs_kf[o0 + a];
-      eval_obs<true, UNI>(P, P.pose, P.lm, o0 + a, kf, l, e);
-    }
-    double Z[18];
-    z_of(e, R, Z);
-    double2* zo = reinterpret_cast<double2*>(P.obsZ + 18 * (size_t)P.obs_zpos[o0 + a]);  // 144-byte record, 16-byte aligned, in its keyframe's block
+  // The records leave as whole cache lines: every lane puts its Z into the wave's LDS tile (64 records of 144 B), then lane q of the wave
+  // stores 16-byte segment 64 m + q (m = 0..8) of the tile — part (64 m + q) % 9 of the record of lane (64 m + q) / 9, consecutive lanes
+  // on consecutive 16 bytes — to that record's slot, handed round by shuffle; lanes without an observation hand out -1 and their
+  // segments are skipped. The groups of a wave walk their chunks in step (wave barriers): as many as its longest landmark has.
+  // (Before: nine 16-byte stores per lane to its own scattered record — 64 partial lines per store instruction; same bytes.)
+  __shared__ __attribute__((aligned(16))) double2 ztile[kBuildThreads / 64][64 * 9];
+  double2* tile = ztile[threadIdx.x >> 6];
+  const int wl = threadIdx.x & 63;
+  int wchunk = nchunk;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) zo[k] = double2{Z[2 * k], Z[2 * k + 1]};
+  for (int off = G; off < 64; off <<= 1) wchunk = max(wchunk, __shfl_xor(wchunk, off, 64));
+  for (int c = 0; c < wchunk; ++c) {
+    const int a = c * G + lane;
+    int zp = -1;
+    if (a < nobs) {
+      if (nchunk > 1) {  // multi-chunk landmark: this chunk's Jacobians were overwritten above
+        kf = P.obs_kf[o0 + a];
+        eval_obs<true, UNI>(P, P.pose, P.lm, o0 + a, kf, l, e);
+      }
+      double Z[18];
+      z_of(e, R, Z);
+      zp = P.obs_zpos[o0 + a];  // 144-byte record, 16-byte aligned, in its keyframe's block
+#pragma unroll
+      for (int k = 0; k < 9; ++k) tile[9 * wl + k] = double2{Z[2 * k], Z[2 * k + 1]};
+    }
+    group_sync();
+#pragma unroll
+    for (int m = 0; m < 9; ++m) {
+      const int s2 = 64 * m + wl, rec = s2 / 9, part = s2 - 9 * rec;
+      const int zr = __shfl(zp, rec, 64);
+      if (zr >= 0) reinterpret_cast<double2*>(P.obsZ)[9 * (size_t)zr + part] = tile[s2];
+    }
+    group_sync();   // the tile is free for the next chunk
   }
 }
 
@@ -258,14 +282,63 @@ __global__ __launch_bounds__(64) void k_kf_reduce(DevProblem P) {
 }
 
 // Sixteen lanes per covisible keyframe pair (eight pairs per workgroup): C[i,j] = -sum over the common landmarks of Z_i Z_j^T.
-// Lanes run over the common LANDMARKS (lane g takes terms g, g+16, ...: each a 6x3 times 3x6 product from two contiguous
-// 144-byte records), the 36 partial sums of every lane go through LDS and lane g adds entries g, g+16, g+32 in lane order.
+// Lanes run over the common LANDMARKS (lane g takes terms g, g+16, ...: each a 6x3 times 3x6 product of two 144-byte records),
+// the 36 partial sums of every lane go through LDS and lane g adds entries g, g+16, g+32 in lane order.
+// The records travel as whole cache lines: a trip is sixteen terms, its record list the (up to) sixteen records of the row
+// keyframe followed by the sixteen of the column keyframe, and lane q of the pair's sixteen loads 16-byte segment 16 m + q
+// (m = 0..8) of either half — part (16 m + q) % 9 of record (16 m + q) / 9, consecutive lanes on consecutive 16 bytes — into
+// registers, from there into LDS, and every lane reads its own two records back (144-byte stride). The slots of the trip are read
+// coalesced (lane q: term q) and handed round by shuffle. The next trip's segments are in flight while this one is multiplied.
+// The staging buffer is the pair's own slice of sp, which is needed behind the loop only: only the pair's lanes (one wave) touch it.
+// (Before: every lane fetched its own records as nine 16-byte loads each — 64 lanes of a load instruction in 64 different
+//  records; same terms, same order of additions, same bits.)
 // (The first version had lane = block entry, 36 of 64 lanes busy, every lane walking all common landmarks in sequence:
 // 0.78 ms on the 5-agent map, the longest kernel of the linearisation.)
 constexpr int kPairLanes = 16, kPairsPerWg = 8;
 constexpr int kPairChunk = 64;   // consecutive workgroups (of kPairsPerWg pairs) that one XCD takes together
-__global__ __launch_bounds__(kPairLanes * kPairsPerWg) void k_pair_blocks(DevProblem P) {
-  __shared__ double sp[kPairsPerWg][36][kPairLanes + 1];
+constexpr int kPairSeg = 9 * kPairLanes;   // 16-byte segments of one half (sixteen records) of a trip's record list
+static_assert(2 * kPairSeg * 2 <= 36 * (kPairLanes + 1), "a trip's records fit the pair's slice of the reduction buffer");
+static_assert((36 * (kPairLanes + 1)) % 2 == 0, "the slices are 16-byte aligned");
+// the trips of one pair as lane g of its sixteen sees them
+constexpr int kPairSort = kPairChunk * kPairsPerWg;   // slots that are sorted together: the pairs of one XCD chunk (its keyframe blocks stay the same)
+// upload: DevProblem::pair_order. One workgroup per kPairSort consecutive pairs of the list: slot r of the chunk gets the pair of rank r by falling number of
+// common landmarks (ties: list order); slots behind the last pair get -1. Every pair keeps its own terms and order of additions: its block does not depend
+// on the slot that computes it.
+__global__ __launch_bounds__(kPairSort) void k_pair_order(DevProblem P) {
+  __shared__ int cnt[kPairSort];
+  const int t = threadIdx.x, p = blockIdx.x * kPairSort + t;
+  const int mine = p < P.npairs ? P.pair_ptr[p + 1] - P.pair_ptr[p] : -1;
+  cnt[t] = mine;
+  __syncthreads();
+  int rank = 0;
+  for (int u = 0; u < kPairSort; ++u) { const int o = cnt[u]; rank += (o > mine || (o == mine && u < t)) ? 1 : 0; }
+  P.pair_order[blockIdx.x * kPairSort + rank] = p < P.npairs ? p : -1;
+}
+struct PairTrips {
+  const int *pair_oa, *pair_ob;
+  const double2* Zs;   // record of slot z: segments 9 z .. 9 z + 8
+  int e0, e1, g;
+  // this lane's term of trip t: its two slots (-> the shuffles of fetch)
+  COV_DEV void slots(int t, int& oa, int& ob) const {
+    const int e = e0 + kPairLanes * t + g;
+    oa = e < e1 ? pair_oa[e] : 0; ob = e < e1 ? pair_ob[e] : 0;
+  }
+  // issues this lane's segments of trip t, only segments of whole valid records (terms below e1); returns the segments per half
+  COV_DEV int fetch(int t, int oa, int ob, double2 (&ra)[9], double2 (&rb)[9]) const {
+    const int left = e1 - e0 - kPairLanes * t;
+    const int nseg = 9 * (left < 0 ? 0 : (left > kPairLanes ? kPairLanes : left));
+#pragma unroll
+    for (int m = 0; m < 9; ++m) {
+      const int s = kPairLanes * m + g, rec = s / 9, part = s - 9 * rec;
+      const int za = __shfl(oa, rec, kPairLanes), zb = __shfl(ob, rec, kPairLanes);
+      ra[m] = s < nseg ? Zs[9 * (size_t)za + part] : double2{0.0, 0.0};
+      rb[m] = s < nseg ? Zs[9 * (size_t)zb + part] : double2{0.0, 0.0};
+    }
+    return nseg;
+  }
+};
+__global__ __launch_bounds__(kPairLanes * kPairsPerWg, 2) void k_pair_blocks(DevProblem P) {
+  __shared__ __attribute__((aligned(16))) double sp[kPairsPerWg][36][kPairLanes + 1];
   const int grp = threadIdx.x / kPairLanes, g = threadIdx.x % kPairLanes;
   // XCD-aware order (round 5): workgroup b runs on XCD b % 8 (observed dispatch order; placement affects speed only). The pair list is sorted by
   // (row keyframe, column keyframe) in chain order, and the two keyframes' record blocks (60 KB each) are what a pair reads: with consecutive
@@ -277,38 +350,58 @@ __global__ __launch_bounds__(kPairLanes * kPairsPerWg) void k_pair_blocks(DevPro
   const int nblk = (P.npairs + kPairsPerWg - 1) / kPairsPerWg;
   const int kx = (int)blockIdx.x >> 3, xcd = (int)blockIdx.x & 7;
   const int lb = ((kx / kPairChunk) * 8 + xcd) * kPairChunk + kx % kPairChunk;
-  const int p = lb * kPairsPerWg + grp;
-  const bool ok = lb < nblk && p < P.npairs;
+  // which pair this slot works on: inside every kPairSort consecutive slots the pairs are dealt by falling length (k_pair_order), so that the four pairs of
+  // a wave, which walk their trips in step, and the two waves of a workgroup, which holds its LDS until both are through, are of a length
+  const int p = lb < nblk ? P.pair_order[lb * kPairsPerWg + grp] : -1;
+  const bool ok = p >= 0;
   const int e0 = ok ? P.pair_ptr[p] : 0, e1 = ok ? P.pair_ptr[p + 1] : 0;
   double acc[36];
 #pragma unroll
   for (int k = 0; k < 36; ++k) acc[k] = 0.0;
-  // two common landmarks per lane and trip: four 144-byte records in flight instead of two (the pass runs at the latency of these
-  // scattered reads); the second one of an odd tail reads the first again with weight zero
-  for (int e = e0 + g; e < e1; e += 2 * kPairLanes) {
-    const int e2 = e + kPairLanes;
-    const bool two = e2 < e1;
-    const double2* y = reinterpret_cast<const double2*>(P.obsZ + 18 * (size_t)P.pair_oa[e]);
-    const double2* w = reinterpret_cast<const double2*>(P.obsZ + 18 * (size_t)P.pair_ob[e]);
-    const double2* y2 = reinterpret_cast<const double2*>(P.obsZ + 18 * (size_t)P.pair_oa[two ? e2 : e]);
-    const double2* w2 = reinterpret_cast<const double2*>(P.obsZ + 18 * (size_t)P.pair_ob[two ? e2 : e]);
-    double yv[18], wv[18], yu[18], wu[18];
+  // the trips of the four pairs of a wave run in step (wave barriers): as many as its longest pair has, a pair that is through idles
+  int ntrip = (e1 - e0 + kPairLanes - 1) / kPairLanes;
+  ntrip = max(ntrip, __shfl_xor(ntrip, 16, 64));
+  ntrip = max(ntrip, __shfl_xor(ntrip, 32, 64));
+  double2* stage = reinterpret_cast<double2*>(&sp[grp][0][0]);   // [2][kPairSeg]: row keyframe's records, column keyframe's
+  double2 ra[9], rb[9];
+  const PairTrips T{P.pair_oa, P.pair_ob, reinterpret_cast<const double2*>(P.obsZ), e0, e1, g};
+  int oa = 0, ob = 0, nseg = 0;
+  if (ntrip > 0) {
+    T.slots(0, oa, ob);
+    nseg = T.fetch(0, oa, ob, ra, rb);
+    T.slots(1, oa, ob);
+  }
+  for (int t = 0; t < ntrip; ++t) {
 #pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const double2 a2 = y[k], b2 = w[k], c2 = y2[k], d2 = w2[k];
-      yv[2 * k] = a2.x; yv[2 * k + 1] = a2.y; wv[2 * k] = b2.x; wv[2 * k + 1] = b2.y;
-      yu[2 * k] = c2.x; yu[2 * k + 1] = c2.y; wu[2 * k] = d2.x; wu[2 * k + 1] = d2.y;
+    for (int m = 0; m < 9; ++m) {
+      const int s = kPairLanes * m + g;
+      if (s < nseg) { stage[s] = ra[m]; stage[kPairSeg + s] = rb[m]; }
     }
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int c = 0; c < 6; ++c) acc[6 * r + c] += yv[3 * r] * wv[3 * c] + yv[3 * r + 1] * wv[3 * c + 1] + yv[3 * r + 2] * wv[3 * c + 2];
-    if (two) {
-#pragma unroll
-      for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) acc[6 * r + c] += yu[3 * r] * wu[3 * c] + yu[3 * r + 1] * wu[3 * c + 1] + yu[3 * r + 2] * wu[3 * c + 2];
+    group_sync();
+    const bool mine = 9 * g < nseg;   // this lane has a term in this trip
+    if (t + 1 < ntrip) {
+      nseg = T.fetch(t + 1, oa, ob, ra, rb);
+      T.slots(t + 2, oa, ob);
     }
+    if (mine) {
+      const double2* y = stage + 9 * g;
+      const double* w = reinterpret_cast<const double*>(stage + kPairSeg + 9 * g);
+      double yv[18];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) { const double2 a2 = y[k]; yv[2 * k] = a2.x; yv[2 * k + 1] = a2.y; }
+      // (the column keyframe's record in two halves of three rows: the whole of it beside the next trip's segments costs registers the kernel does not have)
+#pragma unroll
+      for (int hc = 0; hc < 6; hc += 3) {
+        double wv[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wv[k] = w[3 * hc + k];
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) acc[6 * r + hc + c] += yv[3 * r] * wv[3 * c] + yv[3 * r + 1] * wv[3 * c + 1] + yv[3 * r + 2] * wv[3 * c + 2];
+      }
+    }
+    group_sync();   // every lane has read its records: the next trip (or the partial sums) may overwrite them
   }
 #pragma unroll
   for (int k = 0; k < 36; ++k) sp[grp][k][g] = acc[k];
@@ -323,6 +416,11 @@ __global__ __launch_bounds__(kPairLanes * kPairsPerWg) void k_pair_blocks(DevPro
   }
 }
 
+// (Measured, round 8, 5-agent map, kernel trace of 70 passes, beside k_kf_reduce on the side stream: 270-272 us before; 264 us with the cooperative
+//  gathers alone — the 144-byte records straddle two 128-byte lines each whoever loads them, and the nine partial reads of a lane mostly hit in L1:
+//  the pass moves the same lines and was not waiting for the load instructions; 244-252 us with the pairs of a chunk dealt by falling length as well:
+//  in list order a wave walks as many trips as its longest pair has — 128 000 wave-trips on this map where 101 000 do — and a workgroup holds its
+//  39 KB of LDS until its longest pair is through.)
 // (Measured and dropped, round 4: one workgroup per keyframe i with i's records staged once in LDS (57.6 KB) so that only the partner's
 //  records travel per common landmark — bit-identical, half the scattered reads, and SLOWER: 0.52 instead of 0.27 ms. One or two
 //  workgroups per CU (77 KB of LDS each) cannot keep enough partner reads in flight; eight waves per CU with every read in flight can.)
@@ -480,7 +578,9 @@ void launch_kobs_build(const DevProblem& P, int* pair_oa, int* pair_ob, size_t n
   if (P.O == 0) return;
   hipLaunchKernelGGL(k_kobs_build, dim3((P.O + 255) / 256), dim3(256), 0, st, P);
   if (nent > 0) hipLaunchKernelGGL(k_remap_idx, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, st, nent, pair_oa, pair_ob, (const int*)P.obs_zpos);
+  if (P.npairs > 0) hipLaunchKernelGGL(k_pair_order, dim3((unsigned)(pair_order_slots(P.npairs) / kPairSort)), dim3(kPairSort), 0, st, P);
 }
+size_t pair_order_slots(int npairs) { return ((size_t)npairs + kPairSort - 1) / kPairSort * kPairSort; }
 void launch_lm_backsub(const DevProblem& P, const double* dp, double* out_all, hipStream_t st) {
   if (P.L == 0) return;
   with_uni(P, [&](auto U) { with_group(P.lm_group, [&](auto G) {

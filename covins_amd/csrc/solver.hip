@@ -825,6 +825,7 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
     }
     RC(dev_alloc(c, &P.obsZ, (size_t)18 * P.O)); RC(dev_alloc(c, &P.lmRT, (size_t)9 * P.L));
     RC(dev_alloc(c, &P.kobs, (size_t)3 * P.O)); RC(dev_alloc(c, &P.kobs_lm, (size_t)P.O)); RC(dev_alloc(c, &P.obs_zpos, (size_t)P.O));
+    if (P.npairs) RC(dev_alloc(c, &P.pair_order, pair_order_slots(P.npairs)));
     launch_kobs_build(P, P.pair_oa, P.pair_ob, pl.nent, c->st);
     RC(dev_alloc(c, &P.cost_part, (size_t)(P.L / 4 + 64)));
     HIPCHK(hipStreamSynchronize(c->st));
@@ -916,6 +917,8 @@ static int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgp
     }
     eptr.push_back(P.E);
     P.nepairs = (int)ei.size();
+    c->edge_beside_imu = false;
+    for (size_t q = 0; q < ei.size(); ++q) if (ei[q] - ej[q] == 1) c->edge_beside_imu = true;
     RC(dev_upload(c, &P.kf_edge_ptr, kptr.data(), kptr.size())); RC(dev_upload(c, &P.kf_edge_ent, kent.data(), kent.size()));
     RC(dev_upload(c, &P.epair_ptr, eptr.data(), eptr.size())); RC(dev_upload(c, &P.epair_i, ei.data(), ei.size()));
     RC(dev_upload(c, &P.epair_j, ej.data(), ej.size())); RC(dev_upload(c, &P.epair_ent, eent.data(), eent.size()));
@@ -1144,9 +1147,16 @@ static void enqueue_build(covgpu_context* c, double mu) {
   if (forked) launch_part_finish(P, SC_COST, 1, side);
   c->chol.record(c->chol.ev_kf, side, 4);
   c->chol.wait(c->st, c->chol.ev_kf);
-  launch_imu_gather(P, 0, c->st);  // pose-dimension part: adds onto the blocks k_kf_reduce assigned (fixed order: visual, inertial, loop)
-  launch_edge_gather(P, c->st);
-  launch_finalize_diag(P, mu, P.vi ? 0 : 2, c->st);
+  // pose-dimension part: adds onto the blocks k_kf_reduce assigned (fixed order: visual, inertial, loop), then the damping. Visual-inertial: one launch
+  // (k_pose_finish: every entry gets the same operands in the same order from ONE thread). Not where a loop edge joins two neighbouring chain positions:
+  // that pair block can be an IMU factor's cross block as well, and the two additions onto it are ordered by the launches only. Visual-only problems and
+  // pose graphs (no inertial part, both halves of the damping, the padding rows of the dense matrix) keep their launches too.
+  if (P.vi && !c->edge_beside_imu) launch_pose_finish(P, mu, c->st);
+  else {
+    launch_imu_gather(P, 0, c->st);
+    launch_edge_gather(P, c->st);
+    launch_finalize_diag(P, mu, P.vi ? 0 : 2, c->st);
+  }
   if (!forked) launch_part_finish(P, SC_COST, 1, c->st);
   if (c->profiling) (void)hipEventRecord(c->ev[1], c->st);
 }
@@ -1522,6 +1532,8 @@ static int gba_two_round_impl(covgpu_context* c, const covgpu_options* opt, covg
       if (!build_pairs_device(P.L, P.K, P.lm_obs_ptr, P.obs_kf, c->d_pairkey, true, c->st, pl)) { g_err = "covisible pair lists: device allocation failed"; return (int)COVGPU_ERR_OUT_OF_MEMORY; }
       for (int* q : {pl.pair_ptr, pl.pair_i, pl.pair_j, pl.pair_oa, pl.pair_ob}) if (q) c->allocs.push_back(q);
       P.npairs = pl.npairs; P.pair_ptr = pl.pair_ptr; P.pair_i = pl.pair_i; P.pair_j = pl.pair_j; P.pair_oa = pl.pair_oa; P.pair_ob = pl.pair_ob;
+      P.pair_order = nullptr;
+      if (P.npairs) RC(dev_alloc(c, &P.pair_order, pair_order_slots(P.npairs)));
       launch_kobs_build(P, P.pair_oa, P.pair_ob, pl.nent, c->st);
     }
     // (the reductions store one partial sum per wave into fixed slots and never clear them: fewer observations = fewer waves, and the

@@ -47,7 +47,7 @@ for row in csv.DictReader(open(os.path.join("$out", "${tag}_pmc_hbm_traffic.csv"
         out["potrf_calls"] = int(row["Calls"])
 # counter traffic of the whole linearise + landmark-Schur pass per trust-region iteration (bench.py: roofline_build.traffic)
 BUILD = ("k_lm_lin", "k_kf_reduce", "k_pair_blocks", "k_imu_build", "k_imu_gather", "k_edge_build", "k_edge_gather_kf", "k_edge_gather_pair",
-         "k_finalize_diag", "k_zero_many", "k_nd_zero", "k_cost_finish")
+         "k_finalize_diag", "k_pose_finish", "k_zero_many", "k_nd_zero", "k_cost_finish")
 its = 0; bbytes = 0.0; parts = {}
 for row in csv.DictReader(open(os.path.join("$out", "${tag}_pmc_hbm_traffic.csv"))):
     nm = row["Name"].split("(")[0].replace("void covgpu::", "").replace("covgpu::", "").split("<")[0]
