@@ -476,6 +476,39 @@ class Context:
         self._check(lib().covgpu_match_batch(self._h, C.byref(s), C.byref(o)))
         return dict(match=match[:tot], dist=dist[:tot], nmatches=nm[:J], offset=off)
 
+    def match_float_batch(self, sets: dict, set_a, set_b, **opts):
+        """Batched L2 matching of float (SIFT) descriptors of COVINS-G's loop candidates (covgpu_match_float_batch):
+        knnMatch(k = 2) + distance and ratio tests, exact search. `sets`: dict with row_ptr [num_sets+1] and desc [rows,dim] float32 (dim
+        from desc's last axis, or sets["dim"] where desc has no rows). Job j matches set set_a[j] (query) against set set_b[j] (train).
+        `opts`: dist_threshold, ratio, mode (defaults: covgpu_default_match_float_opts). Returns the dict of match_batch, dist in float32."""
+        o = capi.MatchOpts()
+        lib().covgpu_default_match_float_opts(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("dist_threshold", "ratio", "mode"):
+                raise TypeError(f"unknown match option {k}")
+            setattr(o, k, {"dense": capi.MATCH_DENSE, "knn2": capi.MATCH_KNN2}.get(v, v) if k == "mode" else v)
+        ptr = np.ascontiguousarray(sets["row_ptr"], dtype=np.int32)
+        S = len(ptr) - 1
+        desc = np.ascontiguousarray(sets["desc"], dtype=np.float32)
+        dim = int(sets["dim"]) if sets.get("dim") is not None else (int(desc.shape[-1]) if desc.ndim == 2 else 0)
+        sa = np.ascontiguousarray(set_a, dtype=np.int32).ravel()
+        sb = np.ascontiguousarray(set_b, dtype=np.int32).ravel()
+        J = len(sa)
+        if len(sb) != J:
+            raise ValueError("set_a and set_b differ in length")
+        if dim > 0 and S >= 0 and desc.size != int(ptr[-1]) * dim:
+            raise ValueError("desc does not hold row_ptr[-1] rows of dim floats")
+        ok = S >= 0 and np.all((sa >= 0) & (sa < S))
+        nA = (ptr[sa + 1] - ptr[sa]) if ok and J else np.zeros(J, np.int32)
+        off = np.zeros(J + 1, np.int64); off[1:] = np.cumsum(np.maximum(nA, 0))
+        tot = int(off[-1])
+        match = np.full(max(tot, 1), -1, np.int32); dist = np.full(max(tot, 1), -1, np.float32); nm = np.zeros(max(J, 1), np.int32)
+        dbuf = desc if desc.size else np.zeros(1, np.float32)
+        s = capi.MatchFloatBatch(S, iptr(ptr), dim, dbuf.ctypes.data_as(capi._fp), J, iptr(sa), iptr(sb), iptr(match),
+                                 dist.ctypes.data_as(capi._fp), iptr(nm))
+        self._check(lib().covgpu_match_float_batch(self._h, C.byref(s), C.byref(o)))
+        return dict(match=match[:tot], dist=dist[:tot], nmatches=nm[:J], offset=off)
+
     @staticmethod
     def _guided_opts(mode, opts):
         o = capi.GuidedOpts()

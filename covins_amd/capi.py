@@ -229,6 +229,12 @@ GUIDED_SE3, GUIDED_PROJECTION = 0, 1   # include/covgpu.h
 _fp = C.POINTER(C.c_float)
 
 
+class MatchFloatBatch(C.Structure):
+    """covgpu_match_float_batch_t (include/covgpu.h): L2 matching of float (SIFT) descriptors, DESIGN.md §4.17."""
+    _fields_ = [("num_sets", C.c_int32), ("row_ptr", _ip), ("dim", C.c_int32), ("desc", _fp), ("num_jobs", C.c_int32), ("set_a", _ip),
+                ("set_b", _ip), ("match", _ip), ("dist", _fp), ("nmatches", _ip)]
+
+
 class GuidedOpts(C.Structure):
     _fields_ = [("th_low", C.c_int32), ("radius", C.c_double), ("scale_factor", C.c_double), ("num_octaves", C.c_int32),
                 ("agreement", C.c_int32)]
@@ -366,6 +372,10 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("p3p_batch", [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _ip])
         d("default_match_opts", [C.POINTER(MatchOpts), C.c_int32], None)
         d("match_batch", [C.c_void_p, C.POINTER(MatchBatch), C.POINTER(MatchOpts)])
+        d("default_match_float_opts", [C.POINTER(MatchOpts)], None)
+        d("match_float_limits", [_ip], None)
+        d("match_float_batch", [C.c_void_p, C.POINTER(MatchFloatBatch), C.POINTER(MatchOpts)])
+        d("match_float_check", [C.POINTER(MatchFloatBatch), C.POINTER(MatchOpts)])
         d("default_guided_opts", [C.POINTER(GuidedOpts), C.c_int32], None)
         d("search_se3_batch", [C.c_void_p, C.POINTER(SearchSe3Batch), C.POINTER(GuidedOpts)])
         d("search_projection_batch", [C.c_void_p, C.POINTER(SearchProjectionBatch), C.POINTER(GuidedOpts)])

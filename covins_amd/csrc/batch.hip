@@ -3,7 +3,8 @@
 // (solver.hip): a context lends its device and its stream only. Serves DESIGN.md §4.9 (relative pose, k_relpose.hip; the landmark
 // re-anchoring behind a pose-graph solve), §4.10 (P3P RANSAC, k_abspose.hip), §4.11 (descriptor matching, k_match.hip), §4.12
 // (guided matching, k_guided.hip), §4.13 (bag-of-words transform, score and candidate query, k_bow.hip), §4.14 (redundant-keyframe
-// pruning, k_prune.hip) and §4.15 (landmark descriptors, normals and scale ranges, k_lmrefresh.hip).
+// pruning, k_prune.hip), §4.15 (landmark descriptors, normals and scale ranges, k_lmrefresh.hip) and §4.17 (float descriptor matching,
+// k_matchf.hip).
 // Every entry point checks all its arguments before its first device call, holds its device buffers in one DeviceScratch
 // (host.hpp) and synchronises its stream once, at the end.
 #include <algorithm>
@@ -206,6 +207,94 @@ extern "C" int covgpu_match_batch(covgpu_context* c, const covgpu_match_batch_t*
     HIPCHK(U.alloc(&dmatch, totalA)); HIPCHK(U.alloc(&ddist, totalA)); HIPCHK(U.zeroed(&dn, (size_t)J));
     launch_match(opts->mode, J, maxA, maxB, ddesc, dskip, dptr_, dsa, dsb, doff, dlist, dmatch, ddist, dn, dcut, opts->dist_threshold, opts->ratio,
                  c->st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(U.fetch(bt->match, dmatch, totalA)); HIPCHK(U.fetch(bt->dist, ddist, totalA)); HIPCHK(U.fetch(bt->nmatches, dn, (size_t)J));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return COVGPU_OK;
+  });
+}
+
+extern "C" void covgpu_default_match_float_opts(covgpu_match_opts* o) {
+  if (!o) return;
+  o->mode = COVGPU_MATCH_KNN2;
+  o->dist_threshold = 500.0f;                                      // img_match_thres, "use 500 for SIFT" (config_backend.yaml:38)
+  o->ratio = 0.8f;                                                 // ratio_thres (config_backend.yaml:39)
+}
+
+extern "C" void covgpu_match_float_limits(int32_t out[4]) {
+  if (!out) return;
+  out[0] = COVGPU_MATCH_MAX_ROWS; out[1] = kMatchFloatMaxDim; out[2] = kMatchFloatTileRows; out[3] = kMatchFloatChunkRows;
+}
+
+namespace {
+
+// What covgpu_match_float_batch derives from its arguments while it checks them.
+struct MatchFloatPlan { size_t rows = 0, total_a = 0; int max_a = 0; std::vector<int32_t> off; };
+
+// All checks of covgpu_match_float_batch; the message of the first violation, or nullptr.
+const char* match_float_check(const covgpu_match_float_batch_t* bt, const covgpu_match_opts* opts, MatchFloatPlan& P) {
+  if (!bt || !opts) return "NULL batch or options";
+  if (opts->mode != COVGPU_MATCH_KNN2) return "mode must be COVGPU_MATCH_KNN2";
+  if (!std::isfinite(opts->dist_threshold) || !(opts->dist_threshold > 0.0f)) return "dist_threshold not finite or not positive";
+  if (!std::isfinite(opts->ratio) || !(opts->ratio > 0.0f)) return "ratio not finite or not positive";
+  if (bt->dim <= 0 || bt->dim % 4 != 0 || bt->dim > kMatchFloatMaxDim) return "dim must be a positive multiple of 4 up to 256";
+  if (bt->num_sets < 0 || bt->num_jobs < 0) return "num_sets or num_jobs < 0";
+  if (bt->num_sets > 0 && !bt->row_ptr) return "NULL row_ptr";
+  if (bt->num_sets > 0 && bt->row_ptr[0] != 0) return "row_ptr[0] != 0";
+  for (int s = 0; s < bt->num_sets; ++s) {
+    if (bt->row_ptr[s + 1] < bt->row_ptr[s]) return "row_ptr not monotone";
+    if (bt->row_ptr[s + 1] - bt->row_ptr[s] > COVGPU_MATCH_MAX_ROWS) return "a set holds more than COVGPU_MATCH_MAX_ROWS rows";
+  }
+  P.rows = bt->num_sets > 0 ? (size_t)bt->row_ptr[bt->num_sets] : 0;
+  if (P.rows > 0 && !bt->desc) return "NULL desc";
+  const int J = bt->num_jobs;
+  if (J > 0 && (!bt->set_a || !bt->set_b || !bt->nmatches)) return "NULL job array";
+  P.off.assign(J > 0 ? J : 1, 0);
+  for (int j = 0; j < J; ++j) {
+    if (bt->set_a[j] < 0 || bt->set_a[j] >= bt->num_sets || bt->set_b[j] < 0 || bt->set_b[j] >= bt->num_sets) return "set index out of range";
+    const int nA = bt->row_ptr[bt->set_a[j] + 1] - bt->row_ptr[bt->set_a[j]];
+    P.off[j] = (int32_t)P.total_a;
+    P.total_a += (size_t)nA;
+    if (P.total_a > (size_t)INT32_MAX) return "more than 2^31 - 1 output rows";
+    P.max_a = std::max(P.max_a, nA);
+  }
+  if (P.total_a > 0 && !bt->match) return "NULL match";
+  const int tiles = (P.max_a + kMatchFloatTileRows - 1) / kMatchFloatTileRows;   // scan workgroups per job (launch_matchf)
+  if ((int64_t)J * tiles > (int64_t)INT32_MAX) return "num_jobs * ceil(max query rows / 128) exceeds 2^31 - 1 workgroups";
+  // a NaN would leave the order by (distance, index) undefined, and |x|^2 has to stay finite in float32
+  for (size_t i = 0; i < P.rows * (size_t)bt->dim; ++i)
+    if (!(std::fabs(bt->desc[i]) <= kMatchFloatMaxAbs)) return "descriptor value not finite or above 1e18 in magnitude";
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" int covgpu_match_float_check(const covgpu_match_float_batch_t* bt, const covgpu_match_opts* opts) {
+  return guarded([&]() -> int {
+    MatchFloatPlan P;
+    if (const char* m = match_float_check(bt, opts, P)) { g_err = std::string("covgpu_match_float_check: ") + m; return COVGPU_ERR_INVALID_ARG; }
+    return COVGPU_OK;
+  });
+}
+
+extern "C" int covgpu_match_float_batch(covgpu_context* c, const covgpu_match_float_batch_t* bt, const covgpu_match_opts* opts) {
+  return batch_entry("covgpu_match_float_batch", c, [&](auto bad) -> int {
+    MatchFloatPlan P;
+    if (const char* m = match_float_check(bt, opts, P)) return bad(m);
+    const int J = bt->num_jobs;
+    if (J == 0) return COVGPU_OK;
+    const size_t R = P.rows, totalA = P.total_a;
+    HIPCHK(hipSetDevice(c->device));
+    DeviceScratch U(c->st);
+    float *ddesc = nullptr, *dnorm = nullptr, *ddist = nullptr;
+    int *dptr_ = nullptr, *dsa = nullptr, *dsb = nullptr, *doff = nullptr, *dmatch = nullptr, *dn = nullptr;
+    HIPCHK(U.upload(&ddesc, bt->desc, R * (size_t)bt->dim));         // every set once, however many jobs name it
+    HIPCHK(U.alloc(&dnorm, R));
+    HIPCHK(U.upload(&dptr_, bt->row_ptr, (size_t)bt->num_sets + 1));
+    HIPCHK(U.upload(&dsa, bt->set_a, (size_t)J)); HIPCHK(U.upload(&dsb, bt->set_b, (size_t)J)); HIPCHK(U.upload(&doff, P.off.data(), (size_t)J));
+    HIPCHK(U.alloc(&dmatch, totalA)); HIPCHK(U.alloc(&ddist, totalA)); HIPCHK(U.zeroed(&dn, (size_t)J));
+    launch_matchf_norms((int)R, bt->dim, ddesc, dnorm, c->st);
+    launch_matchf(J, P.max_a, bt->dim, ddesc, dnorm, dptr_, dsa, dsb, doff, dmatch, ddist, dn, opts->dist_threshold, opts->ratio, c->st);
     HIPCHK(hipGetLastError());
     HIPCHK(U.fetch(bt->match, dmatch, totalA)); HIPCHK(U.fetch(bt->dist, ddist, totalA)); HIPCHK(U.fetch(bt->nmatches, dn, (size_t)J));
     HIPCHK(hipStreamSynchronize(c->st));

@@ -37,7 +37,7 @@ enum {
   COVGPU_ERR_NUMERIC = 4,       /* single linear solve not positive definite (covgpu_solve_reduced, covgpu_gn_step) */
   COVGPU_ERR_FATAL_MAP = 5      /* conditions on which the reference calls exit(-1)           */
 };
-/* The stateless batch calls (covgpu_relpose_batch, covgpu_abspose_ransac_batch, covgpu_p3p_batch, covgpu_match_batch,
+/* The stateless batch calls (covgpu_relpose_batch, covgpu_abspose_ransac_batch, covgpu_p3p_batch, covgpu_match_batch, covgpu_match_float_batch,
  * covgpu_search_se3_batch, covgpu_search_projection_batch, covgpu_pgo_reanchor, covgpu_bow_transform_batch, covgpu_bow_score_pairs,
  * covgpu_detect_candidates_batch, covgpu_prune_redundant, covgpu_landmark_refresh; covins_amd/csrc/batch.hip) share one convention: a NULL context is COVGPU_ERR_INVALID_ARG with the
  * message "<function>: NULL context", and every argument is checked before any device work. */
@@ -533,6 +533,35 @@ typedef struct { int32_t mode; float dist_threshold; float ratio; } covgpu_match
 /* DENSE: 50 (placerec_be.cpp:85); KNN2: 40, 0.8 (config_backend.yaml:38-39). ratio is read in KNN2 only but must be finite and positive. */
 void covgpu_default_match_opts(covgpu_match_opts*, int32_t mode);
 int  covgpu_match_batch(covgpu_context*, const covgpu_match_batch_t*, const covgpu_match_opts*);
+
+/* ---------------------------------------------------------------- loop-candidate float descriptor matching
+ * COVINS-G with feat.type SIFT: knnMatch(k = 2) over descriptors_add_ as `dim`-float rows under the L2 norm + distance test + ratio
+ * test (placerec_gen_be.cpp:82-114, RelNonCentralPosSolver.cpp:303-340). Sets and jobs as in covgpu_match_batch_t. All in float32:
+ *   d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 dot(a, b)),  |x|^2 and dot k-ordered fmaf chains from 0,  d = sqrtf(d2) correctly rounded.
+ * Per job the two nearest train rows of every query row by (d2, index), equal distances keeping the lower index first; A row a matches
+ * its nearest b1 iff B has >= 2 rows, d1 <= dist_threshold and d1 < ratio * d2 (float32 comparisons). Matches are emitted in ascending
+ * a. This is the exact search (cv::BFMatcher(NORM_L2)); the reference's cv::FlannBasedMatcher approximates it and is not reproducible.
+ * For integer-valued rows 0..255 (OpenCV's SIFT) at dim <= 128 every intermediate is an exact integer below 2^24, so d2 is the exact
+ * sum of squared differences. match[] = local B row or -1, dist[] = d1 of a match or -1, nmatches[j] = the number of matches of job j.
+ * mode must be COVGPU_MATCH_KNN2; dim is a positive multiple of 4 up to limits[1]; every set holds at most limits[0] rows;
+ * num_jobs * ceil(max rows(set_a[j]) / limits[2]) may not exceed 2^31 - 1; every descriptor value is finite and at most 1e18 in
+ * magnitude (a NaN would leave the order undefined). All arguments (the context included) are checked before any device work; zero jobs
+ * and empty sets are valid. A set is uploaded once, however many jobs name it. */
+typedef struct covgpu_match_float_batch_t {
+  int32_t num_sets;         const int32_t* row_ptr;      /* [num_sets+1], monotone, row_ptr[0] == 0 */
+  int32_t dim;              const float* desc;           /* [rows][dim] */
+  int32_t num_jobs;         const int32_t* set_a;        /* [num_jobs] query set */   const int32_t* set_b; /* [num_jobs] train set */
+  int32_t* match;           /* [sum of rows(set_a[j])] out: local B row or -1 */
+  float*   dist;            /* same length, out, or NULL: d1 of a match, -1 otherwise */
+  int32_t* nmatches;        /* [num_jobs] out */
+} covgpu_match_float_batch_t;
+/* KNN2, 500, 0.8 (config_backend.yaml:38-39, "use 500 for SIFT") */
+void covgpu_default_match_float_opts(covgpu_match_opts*);
+/* out = {max rows per set (4096), max dim, query rows per workgroup tile, train rows per staged chunk} */
+void covgpu_match_float_limits(int32_t out[4]);
+int  covgpu_match_float_batch(covgpu_context*, const covgpu_match_float_batch_t*, const covgpu_match_opts*);
+/* The argument checks of covgpu_match_float_batch alone, without a context or a device ("covgpu_match_float_check: <message>"). */
+int  covgpu_match_float_check(const covgpu_match_float_batch_t*, const covgpu_match_opts*);
 
 /* ---------------------------------------------------------------- loop-candidate guided matching
  * FeatureMatcher::SearchBySE3 (feature_matcher_be.cpp:293-498) and FeatureMatcher::SearchByProjection (:168-291), many jobs per call.

@@ -228,6 +228,23 @@ inline void fatal(const char* msg) {  // the reference prints COUTFATAL and exit
   std::exit(-1);
 }
 
+// float descriptor matrix of a keyframe (COVINS-G with feat.type SIFT: descriptors_add_ as `dim`-float rows) through the optional trait
+// Types::descriptors_f32(keyframe, &rows, &dim, &data) (false: none); without it descriptors_add_ read as a continuous CV_32F cv::Mat
+// (rows, cols, data). A non-empty matrix of another type is fatal: the reference's FLANN matcher throws on it.
+template <class Types, class K>
+inline auto descriptors_f32(K& kf, int* rows, int* dim, const float** data, int)
+    -> decltype(Types::descriptors_f32(kf, rows, dim, data), bool()) {
+  return Types::descriptors_f32(kf, rows, dim, data);
+}
+template <class Types, class K>
+inline bool descriptors_f32(K& kf, int* rows, int* dim, const float** data, long) {
+  const auto& M = kf.descriptors_add_;
+  constexpr int kCv32F = 5;                                            // CV_32FC1 (opencv2/core/hal/interface.h)
+  if (M.rows > 0 && (M.type() != kCv32F || !M.isContinuous())) fatal("descriptors_add_ is not a continuous CV_32F matrix (feat.type SIFT)");
+  *rows = M.rows; *dim = M.cols; *data = reinterpret_cast<const float*>(M.data);
+  return true;
+}
+
 // rotation matrix (rows/cols 0..2 of any (r,c)-indexable) -> Hamilton quaternion x,y,z,w (what Eigen::Quaterniond(R) yields)
 template <class M>
 inline void rot_to_quat(const M& T, double* q) {
@@ -1133,7 +1150,8 @@ class Se3SolverT {
 //      query keyframe in ONE library call. MatchLandmarksBatch is COVINS's LandmarkMatchingAlgorithm(50) + estd2::DenseMatcher(8)
 //      over descriptors_ (placerec_be.cpp:84-90; rows without a valid landmark skipped, as LandmarkMatchingAlgorithm::doSetup does);
 //      MatchImagesBatch is COVINS-G's BFMatcher(NORM_HAMMING).knnMatch(k = 2) + distance and ratio tests over descriptors_add_
-//      (placerec_gen_be.cpp:82-114). Each returns, per candidate, the match list in the reference's order (ascending idxB for the
+//      (placerec_gen_be.cpp:82-114); MatchImagesFloatBatch is its SIFT branch (L2 over float rows, covgpu_match_float_batch, DESIGN.md
+//      §4.17) and MatchImagePairsBatch takes any list of keyframe pairs, for both feature types. Each returns, per candidate, the match list in the reference's order (ascending idxB for the
 //      former, ascending idxA for the latter); its size is ComputeSE3's nmatches. Invalid candidates are the caller's to drop first.
 template <class Types>
 class LoopMatcherT {
@@ -1290,6 +1308,29 @@ class LoopMatcherT {
     return run(query, candidates, o, 1);
   }
 
+  // ---- float (SIFT) descriptors and arbitrary pair lists (covgpu_match_float_batch). Member templates for the
+  //      reason given above: the float path reads cols / type() / isContinuous() of descriptors_add_ unless the binding has the trait
+  //      Types::descriptors_f32. Call them without template arguments.
+  // The SIFT branch of ComputeSE3 (placerec_gen_be.cpp:86-114): knnMatch(k = 2) over descriptors_add_ under the L2 norm + distance and
+  // ratio tests, the exact search that the reference's FlannBasedMatcher approximates. Returns what MatchImagesBatch returns.
+  template <class Binding = Types>
+  static std::vector<Matches> MatchImagesFloatBatch(const KeyframePtr& query, const std::vector<KeyframePtr>& candidates,
+                                                    float img_match_thres = 500.0f, float ratio_thres = 0.8f) {
+    std::vector<std::pair<KeyframePtr, KeyframePtr>> pairs;
+    for (const KeyframePtr& c : candidates) pairs.emplace_back(query, c);
+    return run_pairs<Binding>(pairs, true, img_match_thres, ratio_thres);
+  }
+  // Any list of (query, train) keyframe pairs in ONE library call, every distinct keyframe uploaded once: what
+  // RelNonCentralPosSolver::findMatches needs for its grid of query / candidate predecessors (RelNonCentralPosSolver.cpp:82-144,
+  // :303-340). feature_type is covins_params::features::type: "ORB" goes to covgpu_match_batch (mode KNN2), "SIFT" to
+  // covgpu_match_float_batch; anything else is the reference's fatal path. One match list per pair, ascending idxA.
+  template <class Binding = Types>
+  static std::vector<Matches> MatchImagePairsBatch(const std::vector<std::pair<KeyframePtr, KeyframePtr>>& pairs, const std::string& feature_type,
+                                                   float img_match_thres, float ratio_thres = 0.8f) {
+    if (feature_type != "ORB" && feature_type != "SIFT") detail::fatal("Wrong Feature Type: Only ORB or SIFT is supported currently");
+    return run_pairs<Binding>(pairs, feature_type == "SIFT", img_match_thres, ratio_thres);
+  }
+
  private:
   // keypoint sets of the guided matching: keypoints_distorted_, (int)keypoints_aors_[i][1], descriptors_ rows, bounds and grid state
   struct KpSets {
@@ -1328,6 +1369,73 @@ class LoopMatcherT {
     const GuidedParams& g = guided_params();
     o.th_low = g.th_low; o.radius = th; o.scale_factor = g.scale_factor; o.num_octaves = g.num_octaves; o.agreement = g.agreement;
     return o;
+  }
+
+  template <class Binding>
+  static std::vector<Matches> run_pairs(const std::vector<std::pair<KeyframePtr, KeyframePtr>>& pairs, bool is_float, float thr, float ratio) {
+    const size_t J = pairs.size();
+    std::vector<Matches> out(J);
+    if (J == 0) return out;
+    std::map<const Keyframe*, int32_t> set_of;                         // every distinct keyframe is one set
+    std::vector<int32_t> ptr(1, 0), sa(J), sb(J), off(J + 1, 0);
+    std::vector<uint8_t> desc8;
+    std::vector<float> descf;
+    int dim = 0;
+    auto add = [&](Keyframe& kf) -> int32_t {
+      const auto it = set_of.find(&kf);
+      if (it != set_of.end()) return it->second;
+      int rows = 0;
+      if (is_float) {
+        int d = 0; const float* data = nullptr;
+        if (!detail::descriptors_f32<Binding>(kf, &rows, &d, &data, 0)) rows = 0;
+        if (rows > 0) {
+          if (dim == 0) dim = d;
+          if (d != dim) detail::fatal("float descriptors of different lengths in one batch");
+          descf.insert(descf.end(), data, data + (size_t)rows * (size_t)d);
+        }
+      } else {
+        const uint8_t* data = nullptr;
+        if (!detail::descriptors<Binding>(kf, 1, &rows, &data, 0)) rows = 0;
+        desc8.insert(desc8.end(), data, data + 32 * (size_t)rows);
+      }
+      ptr.push_back(ptr.back() + rows);
+      return set_of[&kf] = (int32_t)ptr.size() - 2;
+    };
+    for (size_t j = 0; j < J; ++j) {
+      sa[j] = add(*pairs[j].first); sb[j] = add(*pairs[j].second);
+      off[j + 1] = off[j] + (ptr[sa[j] + 1] - ptr[sa[j]]);
+    }
+    const size_t total = (size_t)off[J];
+    std::vector<int32_t> match(total + 1), nm(J);
+    std::vector<int32_t> disti(is_float ? 1 : total + 1);
+    std::vector<float> distf(is_float ? total + 1 : 1);
+    covgpu_match_opts o;
+    int rc;
+    if (is_float) {
+      covgpu_default_match_float_opts(&o);
+      o.dist_threshold = thr; o.ratio = ratio;
+      descf.reserve(1);                                                // non-NULL data() for empty sets
+      covgpu_match_float_batch_t bt{};
+      bt.num_sets = (int32_t)ptr.size() - 1; bt.row_ptr = ptr.data(); bt.dim = dim > 0 ? dim : 4; bt.desc = descf.data();
+      bt.num_jobs = (int32_t)J; bt.set_a = sa.data(); bt.set_b = sb.data(); bt.match = match.data(); bt.dist = distf.data(); bt.nmatches = nm.data();
+      rc = covgpu_match_float_batch(OptimizationT<Types>::Context(), &bt, &o);
+    } else {
+      covgpu_default_match_opts(&o, COVGPU_MATCH_KNN2);
+      o.dist_threshold = thr; o.ratio = ratio;
+      desc8.reserve(1);
+      covgpu_match_batch_t bt{};
+      bt.num_sets = (int32_t)ptr.size() - 1; bt.row_ptr = ptr.data(); bt.desc = desc8.data(); bt.skip = nullptr;
+      bt.num_jobs = (int32_t)J; bt.set_a = sa.data(); bt.set_b = sb.data(); bt.match = match.data(); bt.dist = disti.data(); bt.nmatches = nm.data();
+      rc = covgpu_match_batch(OptimizationT<Types>::Context(), &bt, &o);
+    }
+    if (rc != COVGPU_OK) detail::fatal(covgpu_last_error());
+    for (size_t j = 0; j < J; ++j) {
+      Matches& r = out[j];
+      r.reserve((size_t)nm[j]);
+      for (int32_t i = off[j]; i < off[j + 1]; ++i)
+        if (match[i] >= 0) r.push_back(Match{(size_t)(i - off[j]), (size_t)match[i], is_float ? (double)distf[i] : (double)disti[i]});
+    }
+    return out;
   }
 
   static std::vector<Matches> run(const KeyframePtr& query, const std::vector<KeyframePtr>& candidates, const covgpu_match_opts& o, int which) {
