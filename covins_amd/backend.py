@@ -809,6 +809,57 @@ class Context:
             r["kernel_ms"] = float(out["kernel_ms"][0])
         return r
 
+    @staticmethod
+    def _voc_train_batch(row_ptr, desc, k, L, weighting, seed, opts, node_capacity=None, want_row_word=False):
+        """(VocTrain, VocTrainOpts, outputs, keep-alive list) of one covgpu_voc_train call."""
+        ptr = np.ascontiguousarray(row_ptr, dtype=np.int32).ravel()
+        d = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        if len(ptr) < 1 or (len(ptr) > 1 and int(ptr[-1]) > len(d)):
+            raise ValueError("row_ptr runs past desc")
+        o = capi.VocTrainOpts()
+        lib().covgpu_default_voc_train_opts(C.byref(o))
+        o.k, o.L, o.weighting, o.seed = int(k), int(L), int(weighting), int(seed) & ((1 << 64) - 1)
+        for name, v in opts.items():
+            if name not in ("scoring", "max_iterations", "scratch_kib"):
+                raise TypeError(f"unknown vocabulary-training option {name}")
+            setattr(o, name, int(v))
+        rows = len(d)
+        if node_capacity is None:                                  # every node the k-ary tree of depth L can have, or what the rows can fill
+            full = sum(int(k) ** i for i in range(int(L) + 1)) if 2 <= int(k) <= 32 and 1 <= int(L) <= 20 else 1
+            node_capacity = min(full, 2 * rows + 64)
+        n = max(int(node_capacity), 1)
+        out = dict(num_nodes=np.zeros(1, np.int32), num_words=np.zeros(1, np.int32), parent=np.full(n, -2, np.int32),
+                   desc=np.zeros((n, 32), np.uint8), word_id=np.full(n, -2, np.int32), weight=np.full(n, -1.0),
+                   row_word=np.full(max(rows, 1), -2, np.int32) if want_row_word else None, stats=np.zeros(8, np.int64))
+        s = capi.VocTrain(len(ptr) - 1, iptr(ptr), d.ctypes.data_as(capi._bp), int(node_capacity), iptr(out["num_nodes"]),
+                          iptr(out["num_words"]), iptr(out["parent"]), out["desc"].ctypes.data_as(capi._bp), iptr(out["word_id"]),
+                          dptr(out["weight"]), None if out["row_word"] is None else iptr(out["row_word"]),
+                          out["stats"].ctypes.data_as(capi._lp))
+        return s, o, out, [ptr, d]
+
+    def train_vocabulary(self, row_ptr, desc, k, L, weighting=capi.BOW_TF_IDF, seed=0, node_capacity=None, row_word=False, **opts):
+        """DBoW2's TemplatedVocabulary::create(training_features, k, L, weighting, L1_NORM) on the device (covgpu_voc_train, DESIGN.md
+        §4.18). Descriptor sets as for bow_transform_batch: row_ptr [S+1], desc [rows,32]; empty sets count as documents. `opts`:
+        scoring, max_iterations (100), scratch_kib. Returns (voc, stats): voc is the flat form of covins_amd/vocio.py, usable by bowdb,
+        bow_transform_batch and vocio.write_text; stats maps capi.VOCTRAIN_STATS to ints, plus row_word (the transform leaf of every
+        training row) if asked for. Without node_capacity a tree that outgrows the guess (emptied clusters only) is trained again with
+        the count the first call reported."""
+        from . import vocio
+        s, o, out, keep = self._voc_train_batch(row_ptr, desc, k, L, weighting, seed, opts, node_capacity, row_word)
+        rc = lib().covgpu_voc_train(self._h, C.byref(s), C.byref(o))
+        if rc != 0 and node_capacity is None and int(out["num_nodes"][0]) > s.node_capacity:
+            s, o, out, keep = self._voc_train_batch(row_ptr, desc, k, L, weighting, seed, opts, int(out["num_nodes"][0]), row_word)
+            rc = lib().covgpu_voc_train(self._h, C.byref(s), C.byref(o))
+        self._check(rc)
+        N = int(out["num_nodes"][0])
+        voc = vocio.from_nodes(o.k, o.L, o.scoring, o.weighting, out["parent"][1:N], out["word_id"][1:N] >= 0, out["desc"][1:N],
+                               out["weight"][1:N])
+        assert voc["num_words"] == int(out["num_words"][0]) and np.array_equal(voc["word_id"], out["word_id"][:N])
+        stats = {name: int(v) for name, v in zip(capi.VOCTRAIN_STATS, out["stats"])}
+        if row_word:
+            stats["row_word"] = out["row_word"][:len(keep[1])]
+        return voc, stats
+
     def p3p_batch(self, f, P):
         """covgpu_p3p_batch: f, P [n,4,3] -> (T [n,4,7] every solution, qx qy qz qw x y z, ascending v = s3/s1; nsol [n]; chosen [n], -1: none)."""
         f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 4, 3)

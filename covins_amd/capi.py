@@ -330,6 +330,22 @@ LMR_NO_OBSERVER, LMR_NO_REFERENCE, LMR_INVALID = 1, 2, 4                        
 LMR_FORMS = 6                                                                                    # form_count: 4, 8, 16, 32, 64 lanes, long
 
 
+class VocTrain(C.Structure):
+    """covgpu_voc_train_t (include/covgpu.h): TemplatedVocabulary::create, DESIGN.md §4.18."""
+    _fields_ = [("num_sets", C.c_int32), ("row_ptr", _ip), ("desc", _bp), ("node_capacity", C.c_int32), ("num_nodes", _ip),
+                ("num_words", _ip), ("parent", _ip), ("desc_out", _bp), ("word_id", _ip), ("weight", _dp), ("row_word", _ip),
+                ("stats", _lp)]
+
+
+class VocTrainOpts(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("scoring", C.c_int32), ("seed", C.c_uint64),
+                ("max_iterations", C.c_int32), ("scratch_kib", C.c_int32)]
+
+
+VOCTRAIN_STATS = ("iterations", "max_node_iterations", "nodes_at_cap", "emptied_clusters", "short_seeded_nodes", "levels", "h2d_bytes",
+                  "d2h_bytes")                                                                   # covgpu_voc_train_t::stats[0..7]
+
+
 PRUNE_ERASED, PRUNE_TIME_GATE, PRUNE_LOOP_KF, PRUNE_NOT_ERASE = 0, 1, 2, 3                       # round_action
 PRUNE_STOP_NO_CANDIDATES, PRUNE_STOP_THRESHOLD, PRUNE_STOP_MAX_KFS, PRUNE_STOP_MAX_ROUNDS = 0, 1, 2, 3   # stop_reason
 
@@ -403,6 +419,10 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("landmark_refresh_limits", [_ip], None)
         d("landmark_refresh_check", [C.POINTER(LandmarkRefresh), C.POINTER(LandmarkRefreshOpts)])
         d("landmark_refresh", [C.c_void_p, C.POINTER(LandmarkRefresh), C.POINTER(LandmarkRefreshOpts)])
+        d("default_voc_train_opts", [C.POINTER(VocTrainOpts)], None)
+        d("voc_train_limits", [_ip], None)
+        d("voc_train_check", [C.POINTER(VocTrain), C.POINTER(VocTrainOpts)])
+        d("voc_train", [C.c_void_p, C.POINTER(VocTrain), C.POINTER(VocTrainOpts)])
         d("outlier_pass", [C.c_void_p, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])
         d("covisibility", [C.c_void_p, C.c_int32, C.c_int64, _ip, _ip, _ip, C.POINTER(C.c_int64)])
         d("gba_solve_multi", [OP, PP, RP, C.c_int32, _ip, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])

@@ -744,4 +744,40 @@ struct LmRefreshDev {
 // the landmarks list[0..count) through the form of `lanes` lanes per landmark (4 | 8 | 16 | 32 | 64: lists of at most `lanes`), 0 = long form
 void launch_lm_refresh(const LmRefreshDev& D, int lanes, const int* list, int count, hipStream_t st);
 
+// k_voctrain.hip: one level of the hierarchical k-means of TemplatedVocabulary::create. Device arrays throughout.
+constexpr int kVtWaveMax = 256;         // a segment (the rows of one node) of at most this many rows is worked by one wavefront
+constexpr int kVtTile = 2048;           // rows of one workgroup's tile; a longer segment spreads over several workgroups
+constexpr int kVtMaxK = 32;             // largest branching factor (k x 256 bit counters in LDS)
+constexpr int kVtThreads = 256;
+struct VocTrainDev {
+  int k;
+  const uint4* desc;                                                  // [rows][2] the training rows, as given
+  const int* perm; int* perm_out;                                     // [rows] position -> row, grouped by segment, before / after the level
+  int* min_d; int* assoc;                                             // [rows] by position: k-means++ minimum distance, cluster
+  int num_seg;                                                        // the level's segments; per segment:
+  const int* seg_beg; const int* seg_n; const unsigned long long* seg_key;   // first position, rows, the node's key (D1)
+  const int* seg_tile0; const int* seg_ntiles;                        // its tiles (none for a segment of at most k rows)
+  const int* seg_slot;                                                // its slot in gcnt / gsize if it has several tiles, else -1
+  const int4* tiles;                                                  // (segment, first position, end position, -): wide ones first
+  int* ncent; int* draws; int* seed_done; int* done; int* iters; int* changed;
+  double* cut; int* pick_tile; unsigned long long* pick_base;         // the current seeding round: cut_d, the tile of the crossing, the sum before it
+  unsigned* tile_sum; int* tile_cnt;                                  // [tiles], [tiles][k]
+  uint4* cent; int* sizes;                                            // [segments][k][2] centres, [segments][k] group sizes
+  int num_slots; const int* slot_seg; int* gcnt; int* gsize;          // [slots][k][256], [slots][k]: zero before launch_vt_means
+  long long* stats;                                                   // [8] as covgpu_voc_train_t::stats; the kernels count [3] and [4]
+  int* any;                                                           // raised by an association that did not repeat
+};
+size_t vt_means_lds_bytes(int k, int group);
+// tiles [0, wide) are worked by workgroups of kVtThreads, the `narrow` ones behind them by one wavefront each
+void launch_vt_begin(const VocTrainDev& D, hipStream_t st);
+void launch_vt_seed_round(const VocTrainDev& D, int wide, int narrow, int first_round, hipStream_t st);
+void launch_vt_means(const VocTrainDev& D, int wide, int narrow, hipStream_t st);
+void launch_vt_assoc(const VocTrainDev& D, int wide, int narrow, int first, hipStream_t st);
+void launch_vt_partition(const VocTrainDev& D, int wide, int narrow, hipStream_t st);
+// Ni[w] += 1 per (set, word) met first among the rows [r0, r1) of the sets from set0 on; bitmap [sets][words32] zero before
+void launch_vt_unique_words(const int* row_set, const int* row_word, int r0, int r1, int set0, int words32, unsigned* bitmap, int* ni,
+                            hipStream_t st);
+// k_bow.hip's tree descent alone: the leaf's word id of every row, whatever its weight (V.word_weight may be nullptr)
+void launch_bow_descend(const BowVocabDev& V, const unsigned char* desc, int rows, int* row_word, int* row_node, hipStream_t st);
+
 }  // namespace covgpu

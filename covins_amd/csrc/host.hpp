@@ -1,4 +1,4 @@
-// host.hpp — what the host files of libcovgpu (solver.hip, batch.hip, bowdb.hip) share: the context, the error plumbing of the extern "C"
+// host.hpp — what the host files of libcovgpu (solver.hip, batch.hip, bowdb.hip, voctrain.hip) share: the context, the error plumbing of the extern "C"
 // entry points and the per-call device scratch. Host-only: no kernel file includes it.
 #pragma once
 #include <atomic>

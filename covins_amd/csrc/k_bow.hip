@@ -61,7 +61,7 @@ __global__ __launch_bounds__(kThreads) void k_bow_descend(BowVocabDev V, const u
   } while (V.word_id[node] < 0);
   if (nid < 0) nid = node;                        // the leaf lies above nid_level (irregular tree): the leaf itself
   const int w = V.word_id[node];
-  row_word[r] = V.word_weight[w] > 0.0 ? w : -1;  // a stopped word is dropped
+  row_word[r] = !V.word_weight || V.word_weight[w] > 0.0 ? w : -1;   // a stopped word is dropped (no weights: vocabulary training)
   row_node[r] = nid;
 }
 
@@ -339,6 +339,12 @@ void launch_bow_transform(const BowVocabDev& V, const unsigned char* desc, const
   if (num_sets > 0)
     hipLaunchKernelGGL(k_bow_reduce, dim3(num_sets), dim3(kThreads), 0, st, row_ptr, row_word, V.word_weight, add_weight, out_word,
                        out_value, count);
+}
+
+void launch_bow_descend(const BowVocabDev& V, const unsigned char* desc, int rows, int* row_word, int* row_node, hipStream_t st) {
+  if (rows > 0)
+    hipLaunchKernelGGL(k_bow_descend, dim3(blocks(rows)), dim3(kThreads), 0, st, V, reinterpret_cast<const uint4*>(desc), rows, 0,
+                       row_word, row_node);
 }
 
 void launch_bow_score_pairs(const int* vec_beg, const int* vec_end, const int* word, const double* value, int num_pairs, const int* a,

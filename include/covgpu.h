@@ -39,7 +39,8 @@ enum {
 };
 /* The stateless batch calls (covgpu_relpose_batch, covgpu_abspose_ransac_batch, covgpu_p3p_batch, covgpu_match_batch, covgpu_match_float_batch,
  * covgpu_search_se3_batch, covgpu_search_projection_batch, covgpu_pgo_reanchor, covgpu_bow_transform_batch, covgpu_bow_score_pairs,
- * covgpu_detect_candidates_batch, covgpu_prune_redundant, covgpu_landmark_refresh; covins_amd/csrc/batch.hip) share one convention: a NULL context is COVGPU_ERR_INVALID_ARG with the
+ * covgpu_detect_candidates_batch, covgpu_prune_redundant, covgpu_landmark_refresh; covins_amd/csrc/batch.hip; covgpu_voc_train;
+ * covins_amd/csrc/voctrain.hip) share one convention: a NULL context is COVGPU_ERR_INVALID_ARG with the
  * message "<function>: NULL context", and every argument is checked before any device work. */
 
 /* trust-region strategy (reference uses DOGLEG: optimization_be.cpp:261,564,1028;
@@ -942,6 +943,59 @@ void covgpu_landmark_refresh_limits(int32_t out[4]);
  * scale_factor, non-finite positions or centres. */
 int covgpu_landmark_refresh_check(const covgpu_landmark_refresh_t*, const covgpu_landmark_refresh_opts*);
 int covgpu_landmark_refresh(covgpu_context*, const covgpu_landmark_refresh_t*, const covgpu_landmark_refresh_opts*);
+
+/* ---- Vocabulary training: DBoW2's TemplatedVocabulary::create for ORB descriptors under L1 scoring ----
+ *
+ * create(training_features, k, L, weighting, scoring): hierarchical k-means (k-means++ seeding, FORB::meanValue centres, FORB::distance
+ * association with the first minimum winning), createWords and setNodeWeights. Node ids are the reference's (the children of a node get
+ * consecutive ids when the node is processed, nodes are processed depth first), word ids are leaf order. All of it is integer work, so
+ * the result is defined bit for bit; tests/voctrain_ref.py restates it. Deliberate departures from the reference:
+ *   D1 random numbers are counter based: key(root) = seed, key(child c) = splitmix64(key(node) + 1 + c); draw j of a node is
+ *      r = splitmix64(splitmix64(key(node)) + j), u = (r >> 11) * 2^-53; j counts every draw of the node. The first centre is row
+ *      min(int(u n), n - 1); a further centre is the first row whose inclusive prefix sum of minimum distances, as a double, is
+ *      >= cut_d = u * dist_sum (redrawn while 0.0, at most 64 times), the last row if there is none.
+ *   D2 a cluster that loses all its members keeps its previous centre and stays a node (a leaf with an empty group).
+ *   D3 the k-means loop of one node runs at most max_iterations associations; stats[2] counts the nodes it cut short.
+ *   D4 zero descriptor rows, k < 2, L < 1 and k^L > COVGPU_BOW_MAX_WORDS are COVGPU_ERR_INVALID_ARG; so are k > COVGPU_VOCTRAIN_MAX_K and
+ *      a scratch_kib below one set's word bitmap, ceil(k^L / 8192) KiB, and more than 2^31 - 1 - COVGPU_VOCTRAIN_TILE rows.
+ * Sets arrive in the row_ptr / desc layout of covgpu_bow_transform_batch_t, without its limit on the rows of a set; empty sets are
+ * allowed and count in NDocs. The outputs are the per-node arrays of covgpu_bow_vocab_t; child_ptr / child are left to the caller
+ * (vocio.from_nodes, CreateVocabulary of the C++ facade): they follow from parent. If the tree has more than node_capacity nodes the
+ * call returns COVGPU_ERR_INVALID_ARG, *num_nodes holds the count needed and no other output is written. */
+#define COVGPU_VOCTRAIN_MAX_K 32                 /* largest branching factor: the kernels keep k x 256 bit counters in LDS */
+#define COVGPU_VOCTRAIN_WAVE_MAX 256             /* a node of at most this many rows is worked by one wavefront ... */
+#define COVGPU_VOCTRAIN_TILE 2048                /* ... a larger one by workgroups of COVGPU_VOCTRAIN_THREADS over tiles of this many rows */
+#define COVGPU_VOCTRAIN_THREADS 256
+typedef struct covgpu_voc_train_t {
+  int32_t num_sets;
+  const int32_t* row_ptr;                        /* [num_sets+1] */
+  const uint8_t* desc;                           /* [rows][32] */
+  int32_t node_capacity;                         /* entries of parent / desc / word_id / weight */
+  int32_t* num_nodes;                            /* out: nodes of the tree, the root included */
+  int32_t* num_words;                            /* out */
+  int32_t* parent;                               /* out [node_capacity] parent[0] = -1 */
+  uint8_t* desc_out;                             /* out [node_capacity][32] the root's row is zero */
+  int32_t* word_id;                              /* out [node_capacity] -1 for an inner node and the root */
+  double*  weight;                               /* out [node_capacity] 0 for an inner node */
+  int32_t* row_word;                             /* out [rows] or NULL: the transform leaf (word id) of every training row */
+  int64_t* stats;                                /* out [8] or NULL: k-means associations summed; most of one node; nodes cut short by
+                                                  * max_iterations; centre updates that met an empty group (D2); nodes seeded with fewer
+                                                  * than k centres; levels worked; bytes to the device; bytes from it */
+} covgpu_voc_train_t;
+typedef struct covgpu_voc_train_opts {
+  int32_t k, L;                                  /* 10, 5 */
+  int32_t weighting, scoring;                    /* COVGPU_BOW_TF_IDF, COVGPU_BOW_L1_NORM */
+  uint64_t seed;                                 /* 0 */
+  int32_t max_iterations;                        /* 100 (D3) */
+  int32_t scratch_kib;                           /* 65536: device bytes of the per-set word bitmaps behind the weights */
+} covgpu_voc_train_opts;
+void covgpu_default_voc_train_opts(covgpu_voc_train_opts*);
+/* {COVGPU_VOCTRAIN_WAVE_MAX, COVGPU_VOCTRAIN_TILE, COVGPU_VOCTRAIN_MAX_K, COVGPU_VOCTRAIN_THREADS} as the library was built. A node of
+ * at most k rows takes no k-means at all: k is the third size at which the path changes. */
+void covgpu_voc_train_limits(int32_t out[4]);
+/* The argument checks of covgpu_voc_train alone (no context, no device): COVGPU_OK or COVGPU_ERR_INVALID_ARG with the message. */
+int covgpu_voc_train_check(const covgpu_voc_train_t*, const covgpu_voc_train_opts*);
+int covgpu_voc_train(covgpu_context*, const covgpu_voc_train_t*, const covgpu_voc_train_opts*);
 
 #ifdef __cplusplus
 }

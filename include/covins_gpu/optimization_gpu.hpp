@@ -1493,6 +1493,62 @@ struct BowVocabulary {                             // the flat form of covgpu_bo
   }
 };
 
+// ---- TemplatedVocabulary::create(training_features, k, L, weighting, scoring) on the device (covgpu_voc_train), with
+// DBoW2's argument order and the seed of the counter-based draws behind it. A descriptor is anything with 32 bytes behind data() (a
+// std::array<uint8_t, 32>) or behind a data member (a cv::Mat row). The result is the flat vocabulary KeyframeDatabaseT::ComputeBoWBatch
+// and ResidentKeyframeDatabaseT take; stats, if given, receives the eight counters of covgpu_voc_train_t::stats.
+namespace detail {
+template <class D>
+inline auto orb_row(const D& d, int) -> decltype(static_cast<const uint8_t*>(d.data())) { return d.data(); }
+template <class D>
+inline auto orb_row(const D& d, long) -> decltype(static_cast<const uint8_t*>(d.data)) { return d.data; }
+}  // namespace detail
+
+template <class Types, class D>
+inline BowVocabulary CreateVocabulary(const std::vector<std::vector<D>>& training_features, int k, int L,
+                                      int weighting = COVGPU_BOW_TF_IDF, int scoring = COVGPU_BOW_L1_NORM, uint64_t seed = 0,
+                                      int64_t* stats = nullptr, int max_iterations = 0) {
+  std::vector<int32_t> ptr(1, 0);
+  std::vector<uint8_t> desc;
+  for (const auto& set : training_features) {
+    for (const auto& d : set) { const uint8_t* b = detail::orb_row(d, 0); desc.insert(desc.end(), b, b + 32); }
+    ptr.push_back(ptr.back() + (int32_t)set.size());
+  }
+  desc.reserve(1);
+  covgpu_voc_train_opts o;
+  covgpu_default_voc_train_opts(&o);
+  o.k = k; o.L = L; o.weighting = weighting; o.scoring = scoring; o.seed = seed;
+  if (max_iterations > 0) o.max_iterations = max_iterations;
+  const size_t R = (size_t)ptr.back();
+  size_t full = 1, level = 1;                      // every node of a full tree, as far as the rows can fill it
+  for (int l = 0; l < L && full <= 2 * R + 64; ++l) { level *= (size_t)(k > 1 ? k : 2); full += level; }
+  size_t cap = std::min(full, 2 * R + 64);
+  BowVocabulary voc;
+  for (int attempt = 0;; ++attempt) {
+    voc.parent.assign(cap, 0); voc.word_id.assign(cap, 0); voc.desc.assign(32 * cap, 0); voc.weight.assign(cap, 0.0);
+    int32_t num_nodes = 0, num_words = 0;
+    covgpu_voc_train_t t{};
+    t.num_sets = (int32_t)training_features.size(); t.row_ptr = ptr.data(); t.desc = desc.data(); t.node_capacity = (int32_t)cap;
+    t.num_nodes = &num_nodes; t.num_words = &num_words; t.parent = voc.parent.data(); t.desc_out = voc.desc.data();
+    t.word_id = voc.word_id.data(); t.weight = voc.weight.data(); t.stats = stats;
+    const int rc = covgpu_voc_train(OptimizationT<Types>::Context(), &t, &o);
+    if (rc != COVGPU_OK && attempt == 0 && (size_t)num_nodes > cap) { cap = (size_t)num_nodes; continue; }   // emptied clusters outgrew the guess
+    if (rc != COVGPU_OK) detail::fatal(covgpu_last_error());
+    const size_t N = (size_t)num_nodes;
+    voc.parent.resize(N); voc.word_id.resize(N); voc.desc.resize(32 * N); voc.weight.resize(N);
+    voc.k = k; voc.L = L; voc.scoring = scoring; voc.weighting = weighting; voc.num_words = num_words;
+    break;
+  }
+  // the children of a node have consecutive ids, so the child lists follow from parent
+  const size_t N = voc.parent.size();
+  voc.child_ptr.assign(N + 1, 0); voc.child.assign(N - 1, 0);
+  for (size_t n = 1; n < N; ++n) ++voc.child_ptr[(size_t)voc.parent[n] + 1];
+  for (size_t n = 0; n < N; ++n) voc.child_ptr[n + 1] += voc.child_ptr[n];
+  std::vector<int32_t> at(voc.child_ptr.begin(), voc.child_ptr.end() - 1);
+  for (size_t n = 1; n < N; ++n) voc.child[(size_t)at[(size_t)voc.parent[n]]++] = (int32_t)n;
+  return voc;
+}
+
 template <class Types>
 class KeyframeDatabaseT {
  public:
