@@ -252,7 +252,7 @@ void launch_zero_system(const DevProblem& P, hipStream_t st);       // every sma
 enum KernelForm {
   KF_POTRF_PANEL = 0, KF_POTRF_PANEL_FRONTS, KF_POTRF_PANEL4, KF_POTRF_PANEL4_FRONTS, KF_POTRF_SKIPPED,
   KF_TRSM_SUB4_4, KF_TRSM_SUB4_8, KF_TRSM_SUB4_12, KF_TRSM_SUB4_16,
-  KF_GEMM_TRI_FULL, KF_GEMM_TRI_QUAD, KF_GEMM_TRI_GRID, KF_GEMM_RECT_FULL, KF_GEMM_RECT_QUAD,
+  KF_GEMM_TRI_FULL, KF_GEMM_TRI_QUAD, KF_GEMM_TRI_GRID, KF_GEMM_RECT_FULL, KF_GEMM_RECT_QUAD, KF_DIAG_UPDATE,
   KF_BULK_ONE_LAUNCH, KF_BULK_TWO_LAUNCHES, KF_LAST_UPDATE_WHOLE, KF_LAST_UPDATE_SPLIT, KF_PANEL_ONE_TILE, KF_KD_CUT, KF_KD_ZERO, KF_GEMM_BETA0,
   KF_BWD_FRONT, KF_BWD_PIPE, KF_BWD_PIPE64, KF_BWD_TREE, KF_BWD_TREE64, KF_BWD_GIVEN, KF_BWD_STEP_SUB,
   KF_ND_EXTEND_REC, KF_ND_EXTEND, KF_ND_EXTEND_SPLIT,

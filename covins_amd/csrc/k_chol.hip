@@ -62,7 +62,7 @@ constexpr int PFF = 1;   // chunks in flight in registers: full tiles
 constexpr int PFQ = 2;   // quarter forms. Round 4: 4 (+2 % on a map whose trailing updates were ~300 workgroups: one per CU). Round 5, corrected map
                          // (~1 000 workgroups per launch): two chunks in flight are 138 VGPRs instead of 210 — three workgroups per CU instead of two:
                          // 233.9 / 233.5 against 231.8 / 231.2 it/s
-constexpr int PFR = 2;   // the 64x64 RECT form (a dozen workgroups on the serial chain: the next panel's diagonal block)
+constexpr int PFR = 2;   // the 64x64 RECT form (look-ahead of the next panel's rows; the next diagonal block of a one-matrix solve — the fronts' is k_diag_update)
 
 enum { MODE_SYRK_TRI = 0, MODE_SYRK_RECT = 1, MODE_TRSM = 2 };
 
@@ -285,6 +285,85 @@ template <int MODE>
 __global__ __launch_bounds__(256, 2) void k_gemm_abt(GemmArgs g) { gemm_abt_body<MODE, kTile, kTile, KC, PFF>(g); }
 template <int MODE, int TSA, int TSB>
 __global__ __launch_bounds__(256, 2) void k_gemm_abt_q(GemmArgs g) { gemm_abt_body<MODE, TSA, TSB, KCQ, (MODE == MODE_SYRK_RECT ? PFR : PFQ)>(g); }
+
+// The look-ahead update of the NEXT panel's diagonal block (at most 256 x 256, K = the panel just factored) sits on the serial chain between
+// two factorisations. As 64x64 quadrants (k_gemm_abt_q<RECT>) it was a dozen workgroups of 256 MFMAs per wave whose K = 256 arrived in eight
+// chunks with two in flight: four dependent memory round trips with nothing else to run on those CUs. Here: one workgroup per 32x32 sub-block of
+// the block's lower triangle (36 for two tiles, 10 for one), one 16x16 accumulator per wave (64 MFMAs), and EVERY chunk of both operands issued
+// before the first is consumed — one memory latency. The chunks pass through two alternating LDS buffers (one barrier per chunk: the barrier of
+// chunk c + 1 is behind every wave's reads of chunk c). The arithmetic of an element is gemm_abt_body's: the accumulator starts from C and takes
+// v_mfma_f64_16x16x4 over ascending k with the same lane -> k mapping and a negated A fragment, so the bits are the quadrant kernel's. The 64x64
+// quadrants ABOVE the diagonal of the two diagonal tiles, which the quadrant kernel also updated and nobody reads, are left alone.
+constexpr int kDiagSub = 32;                       // sub-block edge
+constexpr int kDiagChunks = 2 * kTile / KCQ;       // K chunks of a 256-column panel
+__global__ __launch_bounds__(256, 2) void k_diag_update(GemmArgs g) {
+  constexpr int LDQ = KCQ + kLdsPad;
+  __builtin_amdgcn_s_setprio(3);   // on the serial chain, beside bulk waves (as the quarter forms)
+  const int batch = blockIdx.y;
+  int bi = 0, bj = blockIdx.x;     // sub-block (bi, bj), bj <= bi: blockIdx.x = bi (bi + 1) / 2 + bj
+  while (bj > bi) { bj -= bi + 1; ++bi; }
+  const int ti = bi / (kTile / kDiagSub), tj = bj / (kTile / kDiagSub);
+  if (g.live != nullptr) {  // wave-uniform early exits on padding, as gemm_abt_body
+    if (!tile_live(g, batch, g.kcol0 / kTile)) return;
+    if (!tile_live(g, batch, g.ra0 / kTile + ti)) return;
+    if (!tile_live(g, batch, g.rb0 / kTile + tj)) return;
+  }
+  int kend = g.KD;
+  if (g.own != nullptr) {
+    const int real = g.own[batch] - g.kcol0;
+    if (real <= 0) return;
+    kend = min(kend, ((real + KCQ - 1) / KCQ) * KCQ);
+  }
+  __shared__ __attribute__((aligned(16))) double sbuf[2][2 * kDiagSub][LDQ];   // [buffer][A rows | B rows][chunk]
+  double* const Mb = g.M + (g.btab != nullptr ? (size_t)g.btab[2 * batch] : (size_t)batch * g.bsM);
+  const size_t ld = g.btab != nullptr ? (size_t)g.btab[2 * batch + 1] : g.ld;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const char* Ag = reinterpret_cast<const char*>(Mb + (size_t)(g.ra0 + bi * kDiagSub) * ld + g.kcol0);
+  const char* Bg = reinterpret_cast<const char*>(Mb + (size_t)(g.rb0 + bj * kDiagSub) * ld + g.kcol0);
+  char* Cg = reinterpret_cast<char*>(Mb + (size_t)(g.ra0 + bi * kDiagSub) * ld + (size_t)(g.cc0 + bj * kDiagSub));
+  const unsigned ldab = (unsigned)(ld * sizeof(double));
+  // staging map: 16 lanes cover one 32-double row segment, 16 rows per pass, two passes per operand
+  constexpr int LPR = KCQ / 2, RPP = 256 / LPR, NPS = kDiagSub / RPP;
+  const int c2 = (tid % LPR) * 2, rbase = tid / LPR;
+  const unsigned offa = (unsigned)rbase * ldab + (unsigned)c2 * 8u;
+  const int fr = lane & 15, fk = lane >> 4;
+  const unsigned offc = (unsigned)(wr * 16 + fk) * ldab + (unsigned)(wc * 16 + fr) * 8u;
+  v4f64 acc;   // (loaded in FRONT of the operands: loads return in order, and the first chunk's products need it)
+#pragma unroll
+  for (int rg = 0; rg < 4; ++rg) acc[rg] = *reinterpret_cast<const double*>(Cg + offc + (unsigned)(4 * rg) * ldab);
+  __builtin_amdgcn_sched_barrier(0);   // (the scheduler otherwise sinks these four loads behind the operands')
+  double2 pa[kDiagChunks][NPS], pb[kDiagChunks][NPS];
+#pragma unroll
+  for (int c = 0; c < kDiagChunks; ++c) {
+    // (straight-line: a chunk beyond kend re-reads the last real one — in bounds, in cache, never consumed — instead of a branch per chunk,
+    //  behind which the compiler waits for EVERY load in flight before the first product)
+    const size_t kcb = (size_t)min(c * KCQ, kend - KCQ) * sizeof(double);   // uniform
+#pragma unroll
+    for (int it = 0; it < NPS; ++it) {
+      pa[c][it] = *reinterpret_cast<const double2*>(Ag + kcb + (size_t)(RPP * it) * ldab + offa);
+      pb[c][it] = *reinterpret_cast<const double2*>(Bg + kcb + (size_t)(RPP * it) * ldab + offa);
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);   // (every load is issued before the first chunk is awaited)
+#pragma unroll
+  for (int c = 0; c < kDiagChunks; ++c) {
+    if (c * KCQ >= kend) break;
+    double (*sA)[LDQ] = sbuf[c & 1];
+    double (*sB)[LDQ] = sbuf[c & 1] + kDiagSub;
+#pragma unroll
+    for (int it = 0; it < NPS; ++it) {
+      sA[rbase + RPP * it][c2] = -pa[c][it].x; sA[rbase + RPP * it][c2 + 1] = -pa[c][it].y;
+      sB[rbase + RPP * it][c2] = pb[c][it].x; sB[rbase + RPP * it][c2 + 1] = pb[c][it].y;
+    }
+    lds_only_barrier();
+#pragma unroll
+    for (int kk = 0; kk < KCQ; kk += 4)
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sA[wr * 16 + fr][kk + fk], sB[wc * 16 + fr][kk + fk], acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int rg = 0; rg < 4; ++rg) *reinterpret_cast<double*>(Cg + offc + (unsigned)(4 * rg) * ldab) = acc[rg];
+}
 
 // The single-workgroup potrf (133 KB LDS + 174 VGPRs x 256 threads: needs an EMPTY CU) starves for the whole duration
 // of a bulk trailing update when every CU holds two bulk workgroups: 400-800 us instead of ~100 us (profiles/r01q,
@@ -547,7 +626,7 @@ thread_local FormCensus* t_forms = nullptr;
 const char* const kFormNames[KF_COUNT] = {
   "k_potrf_panel", "k_potrf_panel.fronts", "k_potrf_panel4", "k_potrf_panel4.fronts", "potrf_skipped",
   "k_trsm_sub4<4>", "k_trsm_sub4<8>", "k_trsm_sub4<12>", "k_trsm_sub4<16>",
-  "k_gemm_abt.tri", "k_gemm_abt_q.tri", "k_gemm_abt.tri_grid", "k_gemm_abt.rect", "k_gemm_abt_q.rect",
+  "k_gemm_abt.tri", "k_gemm_abt_q.tri", "k_gemm_abt.tri_grid", "k_gemm_abt.rect", "k_gemm_abt_q.rect", "k_diag_update",
   "bulk_one_launch", "bulk_two_launches", "last_update_whole", "last_update_split", "panel_one_tile", "kd_cut", "kd_zero", "gemm_beta0",
   "k_bwd_front", "k_bwd_pipe", "k_bwd_pipe64", "k_bwd_tree", "k_bwd_tree64", "k_bwd_given", "k_bwd_step_sub",
   "k_nd_extend_rec", "k_nd_extend", "nd_extend_split",
@@ -595,6 +674,17 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
     form_hit(quad ? KF_GEMM_RECT_QUAD : KF_GEMM_RECT_FULL);
     if (quad) hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_RECT, 64, 64>), dim3(ntc, r1 - r0, 4 * nbt), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), s2, g);
     else hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_RECT>, dim3(ntc, r1 - r0, nbt), dim3(256), lds_gemm, s2, g);
+  };
+  // the same update of the diagonal block of tile rows / columns [u0, u0 + uw) on the chain's stream. Fronts of a tree take k_diag_update; the
+  // one-matrix solves keep the quadrant form (at three and four tiles this is their only RECT launch, and their census says so:
+  // tests/test_gpu_parity.py::test_mfma_cholesky_solve_forms). The bits are the same either way.
+  auto diag = [&](int u0, int uw, int kt0, int KD, hipStream_t s2) {
+    if (bt.tab == nullptr) { rect(u0, u0 + uw, u0, uw, kt0, KD, s2, true); return; }
+    if (uw <= 0 || KD <= 0) return;
+    GemmArgs g{S, ld, kt0 * kTile, KD, u0 * kTile, u0 * kTile, u0 * kTile, uw, nullptr, nullptr, nullptr, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, nullptr, bt.tab, bt.own_dims};
+    const int nb = uw * (kTile / kDiagSub);
+    form_hit(KF_DIAG_UPDATE);
+    hipLaunchKernelGGL(k_diag_update, dim3(nb * (nb + 1) / 2, nbt), dim3(256), 0, s2, g);
   };
 
   // Four streams (timeline analysis in profiles/r01y_timeline_*.csv: once the trailing matrix is small the period of
@@ -864,7 +954,7 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
       if (P + 1 < NP) {
         const int u0 = t0 + 2, uw = (T - u0 >= 2) ? 2 : 1;
         if (P >= 1 && !waitedA) wait(M, eA[P - 1]);          // bulk(P-1) was the previous writer of these tiles (its first launch)
-        rect(u0, u0 + uw, u0, uw, t0, kd(P), M, true);
+        diag(u0, uw, t0, kd(P), M);
         if (trace2) ax.mark(M, 100 * (P + 1) + 3);   // next diagonal block updated
       }
       // (A bulk launched at the same instant as the next diagonal update takes every workgroup slot first and the chain waits

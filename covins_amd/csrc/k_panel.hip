@@ -203,9 +203,11 @@ COV_DEV void panel_out(const double* pan, double* sRhs, const double* rs, double
 //                         L and y leave ONE STEP BEHIND (panel_out), in the solve phase.
 //   waves 4, 8, 12        (SIMD 0, beside the chain wave, which takes every issue slot there during its sweep) help to fill LDS and exit.
 // The diagonal-block sweep of wave 0 is described at its place in the loop; the rest of the panel is X_ij = T_ij Dinv_j^T, 4 MFMAs per
-// tile. (Round 1 found the product with a 128x128 explicit inverse too inaccurate for this system; a 16x16 block inverse formed by
-// substitution is the standard blocked-TRSM building block and tests/test_gpu_parity.py::test_mfma_cholesky_ill_conditioned_blocks and
-// the full-size parity tests hold with it.)
+// tile. (What round 1 found too inaccurate for this system was ITS wide inverse: 128x128, formed inside the factorisation and applied
+// to every row below. That finding is about that inverse, not about wide explicit inverses as such: the backward pass applies 64x64 inverses
+// built from these 16x16 ones by two doubling steps — k_bwd_pipe64 — and holds the same tests. A 16x16 block inverse formed by substitution
+// is the standard blocked-TRSM building block; tests/test_gpu_parity.py::test_mfma_cholesky_ill_conditioned_blocks and the full-size
+// parity tests hold with it.)
 // Round 6: (i) every front factors only ITS OWN real 16-column blocks of the panel (`own`: the launch-wide nb is the widest front's; a front's
 // further blocks are identity padding — L = I, block inverses = I, y = 0 are in place and stay), and a launch lists only the fronts that have
 // a real column in this panel (`list`): on the 12-agent map a level mixes 1 000-2 000 fronts of 9 .. 700 unknowns, and every one of them ran all

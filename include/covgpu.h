@@ -445,7 +445,8 @@ void covgpu_get_profile2(covgpu_context* ctx, double* out16);
  *   k_gemm_abt_q.tri       trailing update of a tile list as 64x64 quadrants (lists up to 1024 entries)
  *   k_gemm_abt.tri_grid    trailing update as the implicit triangle grid (batches without live-tile lists: dense solve)
  *   k_gemm_abt.rect        look-ahead update of the next panel's rows as full tiles
- *   k_gemm_abt_q.rect      ... as quadrants (diagonal blocks, rows h; rest rows up to 512 tiles)
+ *   k_gemm_abt_q.rect      ... as quadrants (rows h; rest rows up to 512 tiles; the next diagonal block of a one-matrix solve)
+ *   k_diag_update          look-ahead update of the next panel's diagonal block of the fronts of a tree: 32x32 sub-blocks, K in one latency
  *   bulk_one_launch        bulk updates (not a front's last) issued as one launch
  *   bulk_two_launches      ... as two: the next-but-one panel's two tile columns first
  *   last_update_whole      a batch's last trailing update issued whole on the chain's stream
