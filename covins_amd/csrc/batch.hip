@@ -1,6 +1,6 @@
 // batch.hip — host side of libcovgpu's stateless batch front end: the extern "C" entry points that take one batch of host arrays,
 // run its kernels on the context's stream and hand the results back. Nothing here touches the resident problem of the solver
-// (solver.hip): a context lends its device and its stream only. Serves DESIGN.md §4.9 (relative pose, k_relpose.hip; the landmark
+// (upload.hip, solver.hip): a context lends its device and its stream only. Serves DESIGN.md §4.9 (relative pose, k_relpose.hip; the landmark
 // re-anchoring behind a pose-graph solve), §4.10 (P3P RANSAC, k_abspose.hip), §4.11 (descriptor matching, k_match.hip), §4.12
 // (guided matching, k_guided.hip), §4.13 (bag-of-words transform, score and candidate query, k_bow.hip), §4.14 (redundant-keyframe
 // pruning, k_prune.hip), §4.15 (landmark descriptors, normals and scale ranges, k_lmrefresh.hip) and §4.17 (float descriptor matching,

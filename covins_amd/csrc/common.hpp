@@ -303,7 +303,7 @@ struct CholAux {
   TriCache tri0;                  // block-arrow batches of the pose-graph solve (k_pgo.hip)
   std::vector<TriCache> tri_lev;  // one per level of the multifrontal solve (k_front.hip), selected by DenseBatch::tri_slot
   void tri_clear();
-  // multi-GPU: sum `n` device doubles over all ranks, in place (solver.hip installs it when a shard is set; nullptr = single GPU)
+  // multi-GPU: sum `n` device doubles over all ranks, in place (shard.hip installs it when a shard is set; nullptr = single GPU)
   // (stream-ordered: the call enqueues the collective on `st`; no host synchronisation is implied)
   void (*reduce)(void* ctx, double* dev, size_t n, int op, hipStream_t st) = nullptr;
   void* reduce_ctx = nullptr;
@@ -552,7 +552,7 @@ struct NdDev {
   std::vector<int> h_top_tiles;
   // sharded solve: [top fronts | top right-hand sides | grad, hdiag of the top unknowns] is ONE contiguous range of the buffer
   size_t M_sub = 0, rhs_top = 0, gh_off = 0;   // elements of the subtree fronts | of the top levels' right-hand sides | offset of [grad | hdiag] in nd_rhs
-  // host staging of the tables (filled by nd_tables, uploaded by solver.hip)
+  // host staging of the tables (filled by nd_tables, uploaded by upload.hip)
   std::vector<int> h_vnode, h_voff, h_vord, h_vown, h_ndepth, h_nI, h_abase, h_fidx, h_own_dims, h_st_dims, h_own_g, h_st_g, h_gidx, h_cptr, h_cidx, h_cptr2,
       h_cidx2, h_inv_off, h_inv, h_rhs_node, h_ext, h_top_var, h_top_r, h_top_g, h_bb_off, h_bb;
   std::vector<long long> h_ntab;

@@ -1,5 +1,6 @@
-// host.hpp — what the host files of libcovgpu (solver.hip, batch.hip, bowdb.hip, voctrain.hip) share: the context, the error plumbing of the extern "C"
-// entry points and the per-call device scratch. Host-only: no kernel file includes it.
+// host.hpp — what the host files of libcovgpu (the solver's solver.hip, upload.hip, plan_api.hip, shard.hip, multi.hip and probe_api.hip; batch.hip,
+// bowdb.hip, voctrain.hip) share: the context, the error plumbing of the extern "C" entry points, the per-call device scratch and the declarations
+// of the solver's functions that one of its files calls in another. Host-only: no kernel file includes it.
 #pragma once
 #include <atomic>
 #include <memory>
@@ -39,6 +40,19 @@ struct PlanCache {
 
 constexpr int COVGPU_ERR_GATE_TIMEOUT = -1000;   // internal (solve_any): never returned through the C ABI
 struct covgpu_group;
+struct covgpu_nd_plan { covgpu::NdHostPlan hp; std::vector<int> pos_kf; };
+
+// sum (op 0) / max (op 1) of n device doubles over all ranks, in place, ENQUEUED on the stream. The two native forms (RCCL, the in-process group of
+// virtual ranks) are private to shard.hip.
+struct Reducer {
+  int rank = 0, world = 1;
+  size_t calls = 0, bytes = 0;
+  virtual ~Reducer() {}
+  virtual int allreduce(double* dev, size_t n, int op, hipStream_t st) = 0;
+  virtual void abort() {}                       // make every peer's pending and future collectives return
+  virtual int async_error() { return 0; }       // asynchronous error of the communicator, polled by the host while it waits for an iteration (RCCL only)
+  virtual std::string last_error() { return "all-reduce failed"; }
+};
 struct covgpu_context {
   int device = 0;
   hipStream_t st = nullptr;
@@ -63,7 +77,7 @@ struct covgpu_context {
   bool sharded = false;
   int rank = 0, world = 1;
   std::shared_ptr<covgpu::NdHostPlan> shard_plan;
-  struct Reducer* reducer = nullptr;
+  Reducer* reducer = nullptr;
   double* d_red = nullptr;     // [SC_COUNT + 2 world] scratch of the scalar all-reduce
   double cur_damp = 0.0;       // damping of the system being built (the top unknowns get theirs after the all-reduce)
   // a collective (or a scratch allocation of the linear solve) that failed while the iteration was being enqueued (broken / timed-out
@@ -126,3 +140,52 @@ struct DeviceScratch {
   hipStream_t st;
   std::vector<void*> held;
 };
+
+// device buffers of the RESIDENT problem: owned by the context (covgpu_context::allocs), freed by the next upload or with the context
+template <typename T>
+static int dev_alloc(covgpu_context* c, T** ptr, size_t count) {
+  *ptr = nullptr;
+  if (count == 0) count = 1;
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, count * sizeof(T));
+  if (e != hipSuccess) { g_err = std::string("hipMalloc: ") + hipGetErrorString(e); return COVGPU_ERR_OUT_OF_MEMORY; }
+  c->allocs.push_back(p);
+  c->alloc_bytes += count * sizeof(T);
+  *ptr = (T*)p;
+  return COVGPU_OK;
+}
+template <typename T>
+static int dev_upload(covgpu_context* c, T** ptr, const T* host, size_t count) {
+  int rc = dev_alloc(c, ptr, count);
+  if (rc) return rc;
+  if (count && host) HIPCHK(hipMemcpyAsync(*ptr, host, count * sizeof(T), hipMemcpyHostToDevice, c->st));
+  else if (count) HIPCHK(hipMemsetAsync(*ptr, 0, count * sizeof(T), c->st));
+  return COVGPU_OK;
+}
+
+// ---- the solver's functions that cross one of its files (none of them is exported)
+#define COVGPU_HIDDEN __attribute__((visibility("hidden")))
+// shard.hip
+COVGPU_HIDDEN void clear_shard(covgpu_context* c);
+COVGPU_HIDDEN void reduce_scalars(covgpu_context* c);
+// plan_api.hip
+COVGPU_HIDDEN int build_chains(const covgpu_problem* p, bool vi, std::vector<int>& perm, std::vector<int>& pos_kf, std::vector<int>& chain_ptr);
+COVGPU_HIDDEN void build_chains_pgo(const covgpu_problem* p, std::vector<int>& perm, std::vector<int>& pos_kf, std::vector<int>& chain_ptr);
+COVGPU_HIDDEN int nd_leaf_dims(int requested);
+COVGPU_HIDDEN bool plan_timing_on();   // dev aid COVGPU_PLAN_TIMING=1: where the host side of an upload and of a plan goes (stderr)
+// upload.hip
+COVGPU_HIDDEN int validate(const covgpu_problem* p, bool pgo, bool vi);
+COVGPU_HIDDEN void free_problem(covgpu_context* c);
+COVGPU_HIDDEN int upload_impl(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, bool pgo, bool allow_arrow = true);
+COVGPU_HIDDEN int upload_pair_lists(covgpu_context* c, bool second_round, std::vector<int>* host_i, std::vector<int>* host_j);
+COVGPU_HIDDEN int reset_state(covgpu_context* c);
+COVGPU_HIDDEN int download_states(covgpu_context* c, covgpu_problem* p);
+COVGPU_HIDDEN int download_impl(covgpu_context* c, covgpu_problem* p);
+// solver.hip
+COVGPU_HIDDEN int read_scalars(covgpu_context* c);
+COVGPU_HIDDEN int chol_failed(covgpu_context* c);
+COVGPU_HIDDEN void enqueue_build(covgpu_context* c, double mu);
+COVGPU_HIDDEN void enqueue_solve(covgpu_context* c, double* dst_all);
+COVGPU_HIDDEN int solve_any(covgpu_context* c, const covgpu_options* opt, covgpu_result* out);
+COVGPU_HIDDEN int gba_two_round_impl(covgpu_context* c, const covgpu_options* opt, covgpu_problem* p, const covgpu_two_round* tr, uint8_t* obs_erase,
+                                     int32_t* lm_left, int64_t* counts, covgpu_result* round1, covgpu_result* round2);

@@ -104,7 +104,7 @@ void nd_tables(const NdHostPlan& hp, const int* pos_kf, int D, int rank, NdDev& 
   if (Hs >= nlev) dev.M_sub = moff;
   dev.M_elems = moff; dev.linv_elems = loff;
   // right-hand sides: [top levels | grad, hdiag of the top unknowns | subtree levels] — with the top fronts right in front of them
-  // (solver.hip puts both in ONE allocation) the whole all-reduced region is contiguous
+  // (upload.hip puts both in ONE allocation) the whole all-reduced region is contiguous
   dev.h_rhs_node.assign(nl, 0);
   size_t roff = 0;
   auto place = [&](int l) {

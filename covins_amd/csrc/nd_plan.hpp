@@ -35,7 +35,7 @@ struct NdHostPlan {
   static int vdim(int v) { return (v & 1) ? 9 : 6; }
 };
 
-// positions are chain-major (solver.hip build_chains); pair / epair lists are keyframe pairs by position (i > j).
+// positions are chain-major (plan_api.hip build_chains); pair / epair lists are keyframe pairs by position (i > j).
 // leaf_dims: a region of at most this many scalar unknowns is not cut further. Returns false on an inconsistent input.
 bool nd_plan_build(int K, bool vi, int nchains, const int* chain_ptr, int npairs, const int* pair_i, const int* pair_j, int nepairs,
                    const int* epair_i, const int* epair_j, int leaf_dims, NdHostPlan& out, int top_mode = -1, bool allow_merge = true);

@@ -1,0 +1,195 @@
+// probe_api.hip — the test entry points of libcovgpu: each uploads a problem and reads back what ONE stage of the product path
+// computes on it (residuals, Jacobians, preintegration, the reduced system, one Gauss-Newton step, the dense solve), for the
+// parity tests against the oracle. They run the product's own upload_impl / enqueue_build / enqueue_solve (host.hpp); the
+// extern "C" wrappers at the end of the file map host exceptions to status codes (guarded) as the product entry points do.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "host.hpp"
+
+using namespace covgpu;
+
+template <typename T>
+static int fetch(covgpu_context* c, T* host, const T* dev, size_t count) {
+  if (count) HIPCHK(hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return COVGPU_OK;
+}
+
+static int residual_norms_impl(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double* norms) {
+  covgpu_options o = *opt; o.visual_only = 1;
+  RC(upload_impl(c, &o, p, false)); RC(reset_state(c));
+  double* d; RC(dev_alloc(c, &d, (size_t)c->P.O));
+  launch_obs_norms(c->P, d, c->st);
+  return fetch(c, norms, d, (size_t)c->P.O);
+}
+
+static int linearize_reprojection_impl(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double* r, double* Jp, double* Jl, double* cost) {
+  covgpu_options o = *opt; o.visual_only = 1;
+  RC(upload_impl(c, &o, p, false)); RC(reset_state(c));
+  const size_t O = c->P.O;
+  double *dr, *dJp, *dJl, *dc;
+  RC(dev_alloc(c, &dr, 2 * O)); RC(dev_alloc(c, &dJp, 12 * O)); RC(dev_alloc(c, &dJl, 6 * O)); RC(dev_alloc(c, &dc, O));
+  launch_obs_linearize(c->P, dr, dJp, dJl, dc, c->st);
+  RC(fetch(c, r, dr, 2 * O)); RC(fetch(c, Jp, dJp, 12 * O)); RC(fetch(c, Jl, dJl, 6 * O));
+  return fetch(c, cost, dc, O);
+}
+
+static int preintegrate_impl(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double* delta, double* J, double* Pm) {
+  covgpu_options o = *opt; o.visual_only = 0;
+  RC(upload_impl(c, &o, p, false)); RC(reset_state(c));
+  launch_preintegrate(c->P, c->st);
+  const size_t I = c->P.I;
+  RC(fetch(c, delta, c->P.pre_delta, 11 * I)); RC(fetch(c, J, c->P.pre_J, 225 * I));
+  return fetch(c, Pm, c->P.pre_P, 225 * I);
+}
+
+static int linearize_imu_impl(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double* r, double* J) {
+  covgpu_options o = *opt; o.visual_only = 0;
+  RC(upload_impl(c, &o, p, false)); RC(reset_state(c));
+  launch_preintegrate(c->P, c->st);
+  const size_t I = c->P.I;
+  double *dr, *dJ;
+  RC(dev_alloc(c, &dr, 15 * I)); RC(dev_alloc(c, &dJ, 450 * I));
+  launch_imu_linearize(c->P, dr, dJ, c->st);
+  RC(fetch(c, r, dr, 15 * I));
+  return fetch(c, J, dJ, 450 * I);
+}
+
+static int linearize_between_impl(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double* r, double* J, double* cost) {
+  RC(upload_impl(c, opt, p, true)); RC(reset_state(c));
+  const size_t E = c->P.E;
+  double *dr, *dJ, *dc;
+  RC(dev_alloc(c, &dr, 6 * E)); RC(dev_alloc(c, &dJ, 72 * E)); RC(dev_alloc(c, &dc, E));
+  launch_edge_linearize(c->P, dr, dJ, dc, c->st);
+  RC(fetch(c, r, dr, 6 * E)); RC(fetch(c, J, dJ, 72 * E));
+  return fetch(c, cost, dc, E);
+}
+
+static int schur_impl(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, bool pgo, double mu, double* S, double* b, double* cost) {
+  RC(upload_impl(c, opt, p, pgo, false)); RC(reset_state(c));  // dense form: the test reads C back as one matrix
+  launch_preintegrate(c->P, c->st);
+  enqueue_build(c, mu);
+  RC(read_scalars(c));
+  *cost = c->h_scal[SC_COST];
+  // assemble the reduced system in IR layout (D rows per keyframe) from its structured parts
+  const DevProblem& P = c->P;
+  const int n = P.n, npad = P.npad, K = P.K, D = P.D;
+  std::vector<double> C((size_t)npad * npad);
+  std::vector<int> perm(K), pos_kf(K), cptr(P.nchains + 1);
+  RC(fetch(c, C.data(), P.Sred, C.size()));
+  RC(fetch(c, perm.data(), P.perm, (size_t)K)); RC(fetch(c, pos_kf.data(), P.pos_kf, (size_t)K));
+  RC(fetch(c, cptr.data(), P.chain_ptr, cptr.size()));
+  std::fill(S, S + (size_t)n * n, 0.0);
+  auto Sat = [&](int r, int cc) -> double& { return S[(size_t)r * n + cc]; };
+  for (int a = 0; a < K; ++a)
+    for (int bq = 0; bq < K; ++bq) {
+      const int ra = 6 * perm[a], rb = 6 * perm[bq];
+      for (int r = 0; r < 6; ++r)
+        for (int cc = 0; cc < 6; ++cc) {
+          const int i = ra + r, j = rb + cc;
+          Sat(D * a + r, D * bq + cc) = (j <= i) ? C[(size_t)i * npad + j] : C[(size_t)j * npad + i];
+        }
+    }
+  if (P.vi) {
+    std::vector<double> Ad(81 * (size_t)K), Ae(81 * (size_t)K), Bp(54 * (size_t)K), Bs(54 * (size_t)K), Bn(54 * (size_t)K);
+    RC(fetch(c, Ad.data(), P.Ad, Ad.size())); RC(fetch(c, Ae.data(), P.Ae, Ae.size()));
+    RC(fetch(c, Bp.data(), P.Bp, Bp.size())); RC(fetch(c, Bs.data(), P.Bs, Bs.size())); RC(fetch(c, Bn.data(), P.Bn, Bn.size()));
+    std::vector<int> chain_of(K);
+    for (int ch = 0; ch < P.nchains; ++ch) for (int q = cptr[ch]; q < cptr[ch + 1]; ++q) chain_of[q] = ch;
+    for (int pos = 0; pos < K; ++pos) {
+      const int a = pos_kf[pos], ch = chain_of[pos];
+      for (int r = 0; r < 9; ++r)
+        for (int cc = 0; cc < 9; ++cc) Sat(15 * a + 6 + r, 15 * a + 6 + cc) = Ad[81 * (size_t)pos + 9 * r + cc];
+      auto put_b = [&](const std::vector<double>& B, int other_pos) {
+        const int o = pos_kf[other_pos];
+        for (int r = 0; r < 9; ++r)
+          for (int cc = 0; cc < 6; ++cc) {
+            const double v = B[54 * (size_t)pos + 6 * r + cc];
+            Sat(15 * a + 6 + r, 15 * o + cc) = v; Sat(15 * o + cc, 15 * a + 6 + r) = v;
+          }
+      };
+      put_b(Bs, pos);
+      if (pos > cptr[ch]) {
+        put_b(Bp, pos - 1);
+        const int o = pos_kf[pos - 1];
+        for (int r = 0; r < 9; ++r)
+          for (int cc = 0; cc < 9; ++cc) {
+            const double v = Ae[81 * (size_t)pos + 9 * r + cc];
+            Sat(15 * a + 6 + r, 15 * o + 6 + cc) = v; Sat(15 * o + 6 + cc, 15 * a + 6 + r) = v;
+          }
+      }
+      if (pos + 1 < cptr[ch + 1]) put_b(Bn, pos + 1);
+    }
+  }
+  return fetch(c, b, P.bred, (size_t)n);
+}
+
+// one damped Gauss-Newton step at the uploaded estimate through the PRODUCT solve path (landmark elimination, multifrontal
+// solve of the reduced camera system — sharded if a shard is set — and landmark back-substitution)
+static int gn_step_impl(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double mu, double* dx, double* dl, double* cost) {
+  RC(upload_impl(c, opt, p, false)); RC(reset_state(c));
+  launch_preintegrate(c->P, c->st);
+  enqueue_build(c, mu);
+  enqueue_solve(c, c->P.gn);
+  RC(read_scalars(c));
+  if (chol_failed(c)) { g_err = "reduced system is not positive definite"; return COVGPU_ERR_NUMERIC; }
+  if (cost) *cost = c->h_scal[SC_COST];
+  RC(fetch(c, dx, c->P.gn, (size_t)c->P.n));
+  return fetch(c, dl, c->P.gn + c->P.n, (size_t)3 * c->P.L);
+}
+
+static int solve_reduced_impl(covgpu_context* c, int32_t n, const double* S, const double* b, double* x) {
+  HIPCHK(hipSetDevice(c->device));
+  if (n <= 0) { g_err = "n <= 0"; return COVGPU_ERR_INVALID_ARG; }
+  const int npad = ((n + kTile - 1) / kTile) * kTile;
+  std::vector<double> Sp((size_t)npad * npad, 0.0), bp((size_t)2 * npad, 0.0);
+  for (int r = 0; r < npad; ++r) {
+    if (r < n) { std::memcpy(&Sp[(size_t)r * npad], S + (size_t)r * n, (size_t)(r + 1) * sizeof(double)); bp[r] = b[r]; }
+    else Sp[(size_t)r * npad + r] = 1.0;
+  }
+  int flag = 0;   // (receives a fetch: declared, like Sp and bp, before the scratch)
+  DeviceScratch U(c->st);
+  double *dS = nullptr, *db = nullptr, *dL = nullptr; int* df = nullptr;
+  HIPCHK(U.upload(&dS, Sp.data(), Sp.size())); HIPCHK(U.upload(&db, bp.data(), bp.size()));
+  HIPCHK(U.alloc(&dL, (size_t)(npad / kTile) * kTile * kTile)); HIPCHK(U.zeroed(&df, 4));
+  {
+    FormScope census(&c->chol.forms);
+    dense_cholesky_solve_raw(dS, db, dL, df, npad, c->st, c->chol);
+  }
+  HIPCHK(U.fetch(x, db, (size_t)n)); HIPCHK(U.fetch(&flag, df, 1));
+  HIPCHK(hipStreamSynchronize(c->st));
+  if (flag) { g_err = "reduced system is not positive definite"; return COVGPU_ERR_NUMERIC; }
+  return COVGPU_OK;
+}
+
+extern "C" int covgpu_reprojection_residual_norms(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double* norms) {
+  return guarded([&] { return residual_norms_impl(c, opt, p, norms); });
+}
+extern "C" int covgpu_linearize_reprojection(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double* r, double* Jp,
+                                             double* Jl, double* cost) {
+  return guarded([&] { return linearize_reprojection_impl(c, opt, p, r, Jp, Jl, cost); });
+}
+extern "C" int covgpu_preintegrate(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double* delta, double* J, double* Pm) {
+  return guarded([&] { return preintegrate_impl(c, opt, p, delta, J, Pm); });
+}
+extern "C" int covgpu_linearize_imu(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double* r, double* J) {
+  return guarded([&] { return linearize_imu_impl(c, opt, p, r, J); });
+}
+extern "C" int covgpu_linearize_between(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double* r, double* J, double* cost) {
+  return guarded([&] { return linearize_between_impl(c, opt, p, r, J, cost); });
+}
+extern "C" int covgpu_schur(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double mu, double* S, double* b, double* cost) {
+  return guarded([&] { return schur_impl(c, opt, p, false, mu, S, b, cost); });
+}
+extern "C" int covgpu_schur_pgo(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double mu, double* S, double* b, double* cost) {
+  return guarded([&] { return schur_impl(c, opt, p, true, mu, S, b, cost); });
+}
+extern "C" int covgpu_gn_step(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double mu, double* dx, double* dl, double* cost) {
+  return guarded([&] { return gn_step_impl(c, opt, p, mu, dx, dl, cost); });
+}
+extern "C" int covgpu_solve_reduced(covgpu_context* c, int32_t n, const double* S, const double* b, double* x) {
+  return guarded([&] { return solve_reduced_impl(c, n, S, b, x); });
+}

@@ -16,7 +16,7 @@ replicated. Every rank
      `opt.shard_policy = 1` (distributed top) the top fronts are instead all-reduced a 256-column panel at a time and their
      trailing updates split over the ranks (DESIGN.md §7.1);
   4. `merge_solution` assembles the optimised map from the ranks' pieces.
-No Python code sits on the data path: the collectives are issued by libcovgpu (solver.hip: RcclReducer / GroupReducer).
+No Python code sits on the data path: the collectives are issued by libcovgpu (shard.hip: RcclReducer / GroupReducer).
 """
 from __future__ import annotations
 

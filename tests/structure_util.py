@@ -1,7 +1,7 @@
 """Problems with a PRESCRIBED covisibility structure for the code between the landmark-major kernels and the linear solve: the pair lists of
 k_pairs.hip (build_pairs_device, build_kf_lists_device, round2_compact_device, k_obs_unpack), the two reductions of k_visual.hip that turn
 per-observation records into the pose system (k_kf_reduce, k_pair_blocks), the edge gathers of k_between.hip (k_edge_gather_kf, k_edge_gather_pair)
-and the host code of solver.hip that feeds them (build_chains, key_of_kf, the edge-pair lists). ONE table of points shared by the host test
+and the host code that feeds them (build_chains of plan_api.hip; key_of_kf and the edge-pair lists of upload.hip). ONE table of points shared by the host test
 (tests/test_structure_host.py: every point has the property it is named for) and the device test (tests/test_gpu_structure.py). No GPU code here.
 
 The synthetic maps list every landmark's observers in ascending keyframe order, every IMU factor from the lower to the higher index, and leave

@@ -1,6 +1,6 @@
 """Sub-map-sharded solve on VIRTUAL ranks: R contexts on the one GPU of the test box, each holding one rank's
 share of the SAME map (its subtrees of the elimination tree + the replicated top), driven in lockstep by host threads; the
-library's collectives run through its native in-process group (solver.hip GroupReducer: sums in rank order on the device).
+library's collectives run through its native in-process group (shard.hip GroupReducer: sums in rank order on the device).
 The sharded result must equal the unsharded one: one Gauss-Newton step to 1e-9 (relative) and the full 10-iteration solve
 to 1e-8 m with the identical accept sequence; three collectives per trust-region iteration (the top of the tree inside the
 linear solve, two scalar exchanges of the fused tail)."""

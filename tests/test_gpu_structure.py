@@ -1,6 +1,6 @@
 """The reduced-system assembly on PRESCRIBED covisibility structures: the pair lists of k_pairs.hip (build_pairs_device, build_kf_lists_device,
 round2_compact_device, k_obs_unpack), the reductions k_kf_reduce and k_pair_blocks of k_visual.hip, the edge gathers of k_between.hip and the host code
-of solver.hip that feeds them (build_chains, key_of_kf, the edge-pair lists), against the oracle and numpy — never against the code under test.
+that feeds them (build_chains of plan_api.hip; key_of_kf and the edge-pair lists of upload.hip), against the oracle and numpy — never against the code under test.
 
 The points are those of tests/structure_util.py (their structure is asserted on the CPU by tests/test_structure_host.py): exactly N covisible pairs of
 one common landmark each on both sides of the group, chunk and round boundaries of k_pair_blocks; pairs of 1 .. 100 common landmarks and keyframes of
