@@ -11,8 +11,7 @@
 //   * panel factorisation (default, k_panel.hip): ONE workgroup factors the whole 256x256 diagonal block (register-resident
 //     16x16 tiles, software-pipelined around a single wave that carries the serial chain), the rows below follow by block
 //     forward substitution against the sixteen 16x16 block inverses it leaves — three dependent launches per panel.
-//     COVGPU_PANEL=0 selects the earlier chain kept in this file: potrf_inv (128x128 block + explicit inverse) -> TRSM as an
-//     MFMA GEMM against L11^-1 -> rank-128 update of the panel's second tile column -> potrf_inv -> TRSM (six launches).
+//     (The earlier chain — 128x128 potrf + explicit inverse, TRSM as an MFMA GEMM against it, six launches — is retired.)
 //   * trailing update k_gemm_abt<SYRK_TRI>: C -= A_i A_j^T, one 128x128 tile per workgroup, 4 waves x (4x4)
 //     v_mfma_f64_16x16x4_f64 tiles, accumulators initialised FROM the C tile (so the epilogue is store-only),
 //     K staged through LDS in chunks of 16 with register prefetch. Workgroup ids are decoded XCD-aware: the 64
@@ -64,19 +63,15 @@ constexpr int PFQ = 2;   // quarter forms. Round 4: 4 (+2 % on a map whose trail
                          // 233.9 / 233.5 against 231.8 / 231.2 it/s
 constexpr int PFR = 2;   // the 64x64 RECT form (look-ahead of the next panel's rows; the next diagonal block of a one-matrix solve — the fronts' is k_diag_update)
 
-enum { MODE_SYRK_TRI = 0, MODE_SYRK_RECT = 1, MODE_TRSM = 2 };
+enum { MODE_SYRK_TRI = 0, MODE_SYRK_RECT = 1 };
 
 struct GemmArgs {
   double* M; size_t ld;
   int kcol0, KD;      // K range: columns kcol0 .. kcol0+KD of the panel (KD = 128 or 256)
   int ra0;            // A rows: ra0 + ti*128
   int rb0;            // B rows: rb0 + tj*128           (TRI: == ra0)
-  int cc0;            // C tile at (ra0 + ti*128, cc0 + tj*128)   (TRI: == ra0; TRSM: == kcol0, tj = 0)
+  int cc0;            // C tile at (ra0 + ti*128, cc0 + tj*128)   (TRI: == ra0)
   int nt;             // tile rows (TRI: triangle order)
-  const double* Linv; // TRSM: B = Linv (128x128, pitch 128)
-  // TRSM with a right-hand side riding along (forward substitution fused into the factorisation):
-  // rhs[rows of this workgroup] -= X[rows, :] yvec[kcol0 .. kcol0+128), X = the freshly computed L tile
-  double* rhs; const double* yvec;
   // batched form (block-arrow pose-graph solve): independent matrices of identical shape, `batch` strides apart
   size_t bsM, bsL, bsR;  // elements between consecutive matrices / Linv sets / right-hand sides (0: not batched)
   // arrow buffers of unequal blocks are padded to one shape: live[2*batch] = real interior tiles, live[2*batch+1] = real
@@ -102,8 +97,7 @@ __device__ __forceinline__ bool tile_live(const GemmArgs& g, int batch, int t) {
 }
 
 // C[i][j] (op)= sum_k A[i][k] B[j][k] on one 128x128 tile (TSA = TSB = 128), or on a quarter of it selected by
-// blockIdx.z — a 64x64 quadrant (RECT) or a 32x128 row slab (TRSM: the update is in place, X overwrites A, so a
-// workgroup must own whole rows). The quarter forms are for the few-tile launches on the serial panel chain, where
+// blockIdx.z — a 64x64 quadrant. The quarter forms are for the few-tile launches on the serial panel chain, where
 // the latency of ONE workgroup's tile is the whole cost — 4x more workgroups, each 4x shorter.
 //
 // All global addresses are a wave-uniform base (SGPRs) plus a 32-bit per-lane byte offset instead of 64-bit per-lane
@@ -121,18 +115,17 @@ COV_DEV void lds_only_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrie
 template <int MODE, int TSA, int TSB, int KC, int PF>
 COV_DEV void gemm_abt_body(const GemmArgs& g) {
   constexpr int LDT = KC + kLdsPad;
-  static_assert((TSA == kTile && TSB == kTile) || (MODE != MODE_TRSM && TSA == 64 && TSB == 64) ||
-                (MODE == MODE_TRSM && TSA == 32 && TSB == kTile), "quarter forms: RECT / TRI 64x64, TRSM 32x128");
-  constexpr int WGR = (TSA == 32) ? 1 : 2, WGC = 4 / WGR;  // wave grid
+  static_assert((TSA == kTile && TSB == kTile) || (TSA == 64 && TSB == 64), "quarter forms: RECT / TRI 64x64");
+  constexpr int WGR = 2, WGC = 2;                           // wave grid
   constexpr int WTR = TSA / WGR, WTC = TSB / WGC;           // wave tile
   constexpr int NMR = WTR / 16, NMC = WTC / 16;             // MFMA tiles per wave
   constexpr int ZQ = (TSA == kTile && TSB == kTile) ? 1 : 4;  // quarter index and batch index share blockIdx.z
-  if (ZQ == 4 && MODE != MODE_SYRK_TRI) __builtin_amdgcn_s_setprio(3);  // RECT / TRSM quarter forms run on the serial chain only, beside bulk waves: issue priority over them
+  if (ZQ == 4 && MODE != MODE_SYRK_TRI) __builtin_amdgcn_s_setprio(3);  // RECT quarter forms run on the serial chain only, beside bulk waves: issue priority over them
   int tri_entry = 0;
   if (MODE == MODE_SYRK_TRI && g.tri != nullptr) { tri_entry = g.tri[blockIdx.x]; if (tri_entry < 0) return; }
   const int zq = (int)blockIdx.z % ZQ,
             batch = (MODE == MODE_SYRK_TRI) ? (g.tri != nullptr ? (tri_entry >> 20) : (int)blockIdx.y) : (int)blockIdx.z / ZQ;
-  const int qr = (TSA == kTile) ? 0 : (TSB == kTile ? zq : (zq >> 1));
+  const int qr = (TSA == kTile) ? 0 : (zq >> 1);
   const int qc = (TSB == kTile) ? 0 : (zq & 1);
   double* const Mb = g.M + (g.btab != nullptr ? (size_t)g.btab[2 * batch] : (size_t)batch * g.bsM);
   int ti, tj;
@@ -149,25 +142,22 @@ COV_DEV void gemm_abt_body(const GemmArgs& g) {
     const int sj = s - si * (si + 1) / 2;
     ti = si * 8 + (inner >> 3); tj = sj * 8 + (inner & 7);
     if (ti >= g.nt || tj > ti) return;
-  } else if (MODE == MODE_SYRK_RECT) {
+  } else {  // RECT
     ti = blockIdx.y; tj = blockIdx.x;
     if (g.ra0 + ti * kTile < g.cc0 + tj * kTile) return;  // strictly above the diagonal
-  } else {
-    ti = blockIdx.x; tj = 0;
   }
   if (g.live != nullptr) {  // wave-uniform early exit on padding (see GemmArgs::live)
     if (!tile_live(g, batch, g.kcol0 / kTile)) return;                       // the panel itself is padding: A = B = 0
     if (!tile_live(g, batch, g.ra0 / kTile + ti)) return;                    // A rows are padding
-    if (MODE != MODE_TRSM && !tile_live(g, batch, g.rb0 / kTile + tj)) return;  // B rows are padding
+    if (!tile_live(g, batch, g.rb0 / kTile + tj)) return;                    // B rows are padding
   }
-  const int kbeg = 0;
   int kend = g.KD;
-  if (MODE != MODE_TRSM && g.own != nullptr) {
+  if (g.own != nullptr) {
     const int real = g.own[batch] - g.kcol0;
     if (real <= 0) return;   // (wave-uniform) this front has no real column in the panel: A = B = 0
     kend = min(kend, ((real + KC - 1) / KC) * KC);
   }
-  extern __shared__ __attribute__((aligned(16))) double smem[];  // [TSA][KC+1] + [TSB][KC+1] doubles
+  extern __shared__ __attribute__((aligned(16))) double smem[];  // [TSA][LDT] + [TSB][LDT] doubles
   double (*sA)[LDT] = reinterpret_cast<double (*)[LDT]>(smem);
   double (*sB)[LDT] = reinterpret_cast<double (*)[LDT]>(smem + TSA * LDT);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -175,14 +165,13 @@ COV_DEV void gemm_abt_body(const GemmArgs& g) {
   const size_t ld = g.btab != nullptr ? (size_t)g.btab[2 * batch + 1] : g.ld;
   // wave-uniform bases (the tile of a workgroup spans < 2^32 bytes: per-lane offsets are 32-bit byte offsets)
   const char* Ag = reinterpret_cast<const char*>(Mb + (size_t)(g.ra0 + ti * kTile + qr * TSA) * ld + g.kcol0);
-  const char* Bg = (MODE == MODE_TRSM) ? reinterpret_cast<const char*>(g.Linv + (size_t)batch * g.bsL)
-                                       : reinterpret_cast<const char*>(Mb + (size_t)(g.rb0 + tj * kTile + qc * TSB) * ld + g.kcol0);
-  const unsigned ldab = (unsigned)(ld * sizeof(double)), ldbb = (MODE == MODE_TRSM) ? (unsigned)(kTile * sizeof(double)) : ldab;
+  const char* Bg = reinterpret_cast<const char*>(Mb + (size_t)(g.rb0 + tj * kTile + qc * TSB) * ld + g.kcol0);
+  const unsigned ldab = (unsigned)(ld * sizeof(double));
   char* Cg = reinterpret_cast<char*>(Mb + (size_t)(g.ra0 + ti * kTile + qr * TSA) * ld + (size_t)(g.cc0 + tj * kTile + qc * TSB));
   // staging map: KC/2 lanes cover one KC-double row segment (contiguous), 512/KC rows per pass
   constexpr int LPR = KC / 2, RPP = 256 / LPR, NPA = TSA / RPP, NPB = TSB / RPP;
   const int c2 = (tid % LPR) * 2, rbase = tid / LPR;
-  const unsigned offa = (unsigned)rbase * ldab + (unsigned)c2 * 8u, offb = (unsigned)rbase * ldbb + (unsigned)c2 * 8u;
+  const unsigned offa = (unsigned)rbase * ldab + (unsigned)c2 * 8u, offb = offa;
   // PF chunks are in flight in registers (stage = chunk index mod PF: the K loop is unrolled by PF). With one chunk ahead the quarter
   // forms ran at memory latency — a chunk is 0.85 us of matrix work, a load under load 2-3 us, and a launch of ~300 workgroups leaves one
   // or two per CU: nothing else to run meanwhile.
@@ -193,10 +182,10 @@ COV_DEV void gemm_abt_body(const GemmArgs& g) {
 #pragma unroll
     for (int it = 0; it < NPA; ++it) pa[st][it] = *reinterpret_cast<const double2*>(Ak + (size_t)(RPP * it) * ldab + offa);
 #pragma unroll
-    for (int it = 0; it < NPB; ++it) pb[st][it] = *reinterpret_cast<const double2*>(Bk + (size_t)(RPP * it) * ldbb + offb);
+    for (int it = 0; it < NPB; ++it) pb[st][it] = *reinterpret_cast<const double2*>(Bk + (size_t)(RPP * it) * ldab + offb);
   };
 #pragma unroll
-  for (int u = 0; u < PF; ++u) if (kbeg + u * KC < kend) gload(kbeg + u * KC, u);
+  for (int u = 0; u < PF; ++u) if (u * KC < kend) gload(u * KC, u);
   const int fr = lane & 15, fk = lane >> 4;
   // f64 16x16x4 C/D layout: col = lane & 15, row = (lane >> 4) + 4 * reg
   const unsigned offc = (unsigned)(wr * WTR + fk) * ldab + (unsigned)(wc * WTC + fr) * 8u;  // per lane; the rest is uniform
@@ -213,12 +202,12 @@ COV_DEV void gemm_abt_body(const GemmArgs& g) {
       const unsigned rowoff = offc + (unsigned)(tm * 16 + 4 * rg) * ldab;  // one VGPR per row; tn goes into the immediate
 #pragma unroll
       for (int tn = 0; tn < NMC; ++tn) {
-        if (MODE == MODE_TRSM || fresh) acc[tm][tn][rg] = 0.0;
+        if (fresh) acc[tm][tn][rg] = 0.0;
         else acc[tm][tn][rg] = *reinterpret_cast<const double*>(Cg + rowoff + tn * 128);
       }
     }
-  const double sgn = (MODE == MODE_TRSM) ? 1.0 : -1.0;  // SYRK: acc = C - A B^T through a negated A fragment
-  for (int kc0 = kbeg; kc0 < kend; kc0 += PF * KC) {
+  const double sgn = -1.0;  // acc = C - A B^T through a negated A fragment
+  for (int kc0 = 0; kc0 < kend; kc0 += PF * KC) {
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
       const int kc = kc0 + u * KC;
@@ -244,7 +233,6 @@ COV_DEV void gemm_abt_body(const GemmArgs& g) {
       }
     }
   }
-  // (TRSM in place: every A element of this workgroup's rows was staged before the last barrier above)
 #pragma unroll
   for (int tm = 0; tm < NMR; ++tm)
 #pragma unroll
@@ -253,32 +241,6 @@ COV_DEV void gemm_abt_body(const GemmArgs& g) {
 #pragma unroll
       for (int tn = 0; tn < NMC; ++tn) *reinterpret_cast<double*>(Cg + rowoff + tn * 128) = acc[tm][tn][rg];
     }
-  if (MODE == MODE_TRSM && g.rhs != nullptr) {
-    // forward substitution riding along: rhs[row] -= sum_c X[row][c] y[c]. Lane partial over its columns, fixed
-    // butterfly over the 16 lanes that share a row, fixed-order sum over the wave columns: deterministic.
-    __syncthreads();                     // the staging buffers are free
-    double* sy = smem;                   // [128] y of this panel
-    double* sp = smem + kTile;           // [WGC][TSA] partial row sums
-    if (tid < kTile) sy[tid] = g.yvec[(size_t)batch * g.bsR + g.kcol0 + tid];
-    __syncthreads();
-#pragma unroll
-    for (int tm = 0; tm < NMR; ++tm)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        double pr = 0.0;
-#pragma unroll
-        for (int tn = 0; tn < NMC; ++tn) pr += acc[tm][tn][rg] * sy[wc * WTC + tn * 16 + fr];
-        pr += __shfl_xor(pr, 1, 64); pr += __shfl_xor(pr, 2, 64); pr += __shfl_xor(pr, 4, 64); pr += __shfl_xor(pr, 8, 64);
-        if (fr == 0) sp[wc * TSA + wr * WTR + tm * 16 + fk + 4 * rg] = pr;
-      }
-    __syncthreads();
-    if (tid < TSA) {
-      double t = 0.0;
-#pragma unroll
-      for (int w2 = 0; w2 < WGC; ++w2) t += sp[w2 * TSA + tid];
-      g.rhs[(size_t)batch * g.bsR + g.ra0 + ti * kTile + qr * TSA + tid] -= t;
-    }
-  }
 }
 
 template <int MODE>
@@ -364,6 +326,19 @@ __global__ __launch_bounds__(256, 2) void k_diag_update(GemmArgs g) {
 #pragma unroll
   for (int rg = 0; rg < 4; ++rg) *reinterpret_cast<double*>(Cg + offc + (unsigned)(4 * rg) * ldab) = acc[rg];
 }
+
+// ---- host half. Switches, read once per process:
+// trailing updates given as explicit tile lists of at most this many entries (incl. the XCD padding) run as 64x64 quadrants
+static const int kQuarterMax = env_int("COVGPU_QUARTER_MAX", 1024);
+// look-ahead update of the rows below the next panel (stream R): tiles up to which it runs as quarter tiles
+constexpr int kRectQuarterMax = 512;
+// a panel whose bulk update has at most this many tile pairs hands over through ONE event (PanelRun::chain_bound)
+static const double kChainPairs = getenv("COVGPU_CHAIN_PAIRS") ? atof(getenv("COVGPU_CHAIN_PAIRS")) : 0.0;
+// dev aid: COVGPU_TRACE_PANELS set = a mark per big panel (CholAux::mark); >= 2 = per-kernel marks as well, tag 100 (P + 1) + k
+static const bool kTracePanels = getenv("COVGPU_TRACE_PANELS") != nullptr;
+static const bool kTraceKernels = env_int("COVGPU_TRACE_PANELS", 0) >= 2;
+constexpr size_t kLdsFull = (size_t)2 * kTile * LDT * sizeof(double);                  // dynamic LDS of k_gemm_abt
+constexpr size_t kLdsQuarter = (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double);  // ... of k_gemm_abt_q
 
 // The single-workgroup potrf (133 KB LDS + 174 VGPRs x 256 threads: needs an EMPTY CU) starves for the whole duration
 // of a bulk trailing update when every CU holds two bulk workgroups: 400-800 us instead of ~100 us (profiles/r01q,
@@ -575,8 +550,7 @@ void CholAux::destroy() {
   if (aux) { (void)hipStreamDestroy(aux); aux = nullptr; }
 }
 void CholAux::mark(hipStream_t s, int tag) {
-  static const bool trace_panels = getenv("COVGPU_TRACE_PANELS") != nullptr;
-  if (!trace_panels) return;
+  if (!kTracePanels) return;
   while ((int)panel_ev.size() <= panel_n) { hipEvent_t e; (void)hipEventCreate(&e); panel_ev.push_back(e); }
   if ((int)panel_tag.size() <= panel_n) panel_tag.resize(panel_n + 1);
   (void)hipEventRecord(panel_ev[panel_n], s);
@@ -635,58 +609,62 @@ const char* const kFormNames[KF_COUNT] = {
 };
 static_assert(sizeof(kFormNames) / sizeof(kFormNames[0]) == KF_COUNT, "one name per kernel form");
 
-// trailing updates given as explicit tile lists of at most this many entries (incl. the XCD padding) run as 64x64 quadrants
-static const int kQuarterMax = env_int("COVGPU_QUARTER_MAX", 1024);
-// look-ahead update of the rows below the next panel (stream R): tiles up to which it runs as quarter tiles
-constexpr int kRectQuarterMax = 512;
-
-void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int npad, hipStream_t st, CholAux& ax, int tstop, bool solve,
-                              DenseBatch bt) {
-  const int nbt = bt.n > 0 ? bt.n : 1;
-  const int T = npad / kTile;
-  const size_t ld = (size_t)npad;
-  const size_t lds_gemm = (size_t)2 * kTile * LDT * sizeof(double);
-  static std::atomic<unsigned long long> attr_seen{0};  // (per device; several host threads may arrive at once: the attribute is idempotent)
-  if (first_use_on_device(attr_seen)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_abt<MODE_SYRK_TRI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gemm);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_abt<MODE_SYRK_RECT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gemm);
+// (profiling only) an event pair on stream s around the launches enqueued while the object lives, booked with their algorithmic flops
+struct ProfBracket {
+  std::vector<hipEvent_t>* ev = nullptr; std::vector<double>* flops; hipStream_t s; double fl;
+  ProfBracket(bool on, std::vector<hipEvent_t>& ev_, std::vector<double>& flops_, hipStream_t s_, double fl_) : flops(&flops_), s(s_), fl(fl_) {
+    if (!on) return;
+    ev = &ev_;   // (a solve may factorise several matrices — arrow blocks, then the border system: launches accumulate until collect())
+    while (ev->size() < 2 * (flops->size() + 1)) { hipEvent_t e; (void)hipEventCreate(&e); ev->push_back(e); }
+    (void)hipEventRecord((*ev)[2 * flops->size()], s);
   }
-  ax.init();
-  const int NP = (T + 1) / 2;  // big panels of two tile columns
-  // events per big panel: H rows-h done | B bulk done | C rows-r done | 1 potrf(t0) | 2 X(t0+1,t0) | 3 potrf(t0+1) | Rc next diagonal updated
-  while ((int)ax.ev.size() < 9 * (NP + 1)) { hipEvent_t e; (void)hipEventCreateWithFlags(&e, hipEventDisableTiming); ax.ev.push_back(e); }
-  // (a solve may factorise several matrices — arrow blocks, then the border system: launches accumulate until collect())
-  if (ax.profile) while (ax.prof_ev.size() < 2 * (ax.prof_flops.size() + (size_t)NP + 1)) { hipEvent_t e; (void)hipEventCreate(&e); ax.prof_ev.push_back(e); }
-  hipEvent_t* eH = ax.ev.data();
-  hipEvent_t* eB = eH + (NP + 1);
-  hipEvent_t* eC = eB + (NP + 1);
-  hipEvent_t* e1 = eC + (NP + 1);
-  hipEvent_t* e2 = e1 + (NP + 1);
-  hipEvent_t* e3 = e2 + (NP + 1);
-  hipEvent_t* eRc = e3 + (NP + 1);
-  hipEvent_t* eHp = eRc + (NP + 1);  // rows h updated with column t0 (their last TRSM then runs on the chain's own stream)
-  hipEvent_t* eA = eHp + (NP + 1);   // bulk(P) has updated the NEXT-BUT-ONE panel's two tile columns (the first of its two launches; == eB where the bulk is one launch)
+  ~ProfBracket() { if (ev != nullptr) { (void)hipEventRecord((*ev)[2 * flops->size() + 1], s); flops->push_back(fl); } }
+  ProfBracket(const ProfBracket&) = delete; ProfBracket& operator=(const ProfBracket&) = delete;
+};
 
-  // C tiles (rows [r0, r1), tile columns [tc0, tc0+ntc)) -= A[rows, K] A[tc.., K]^T, K = tiles kt0.. (KD columns); lower part only
-  auto rect = [&](int r0, int r1, int tc0, int ntc, int kt0, int KD, hipStream_t s2, bool quad) {
-    if (r1 <= r0 || ntc <= 0 || KD <= 0) return;
-    GemmArgs g{S, ld, kt0 * kTile, KD, r0 * kTile, tc0 * kTile, tc0 * kTile, r1 - r0, nullptr, nullptr, nullptr, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, nullptr, bt.tab, bt.own_dims};
-    form_hit(quad ? KF_GEMM_RECT_QUAD : KF_GEMM_RECT_FULL);
-    if (quad) hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_RECT, 64, 64>), dim3(ntc, r1 - r0, 4 * nbt), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), s2, g);
-    else hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_RECT>, dim3(ntc, r1 - r0, nbt), dim3(256), lds_gemm, s2, g);
-  };
-  // the same update of the diagonal block of tile rows / columns [u0, u0 + uw) on the chain's stream. Fronts of a tree take k_diag_update; the
-  // one-matrix solves keep the quadrant form (at three and four tiles this is their only RECT launch, and their census says so:
-  // tests/test_gpu_parity.py::test_mfma_cholesky_solve_forms). The bits are the same either way.
-  auto diag = [&](int u0, int uw, int kt0, int KD, hipStream_t s2) {
-    if (bt.tab == nullptr) { rect(u0, u0 + uw, u0, uw, kt0, KD, s2, true); return; }
-    if (uw <= 0 || KD <= 0) return;
-    GemmArgs g{S, ld, kt0 * kTile, KD, u0 * kTile, u0 * kTile, u0 * kTile, uw, nullptr, nullptr, nullptr, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, nullptr, bt.tab, bt.own_dims};
-    const int nb = uw * (kTile / kDiagSub);
-    form_hit(KF_DIAG_UPDATE);
-    hipLaunchKernelGGL(k_diag_update, dim3(nb * (nb + 1) / 2, nbt), dim3(256), 0, s2, g);
-  };
+// live tiles (i, j), j <= i, of the triangle that starts at tile tb, for the fronts whose interior reaches panel column t0;
+// part 0: all | 1: rows i < split_ta | 2: rows i >= split_ta | 3: tile columns j < 2 and rows i < split_ta | 4: the others. XCD-balanced, interleaved (position p runs on XCD p % 8).
+static std::vector<int> live_tile_list(const DenseBatch& bt, int nbt, int T, int t0, int tb, int part) {
+  std::vector<int> q[8];  // per-XCD queues; whole 8x8 supertiles of one batch go to the currently shortest queue
+  for (int a = 0; a < nbt; ++a) {
+    const int nI = bt.live_h[2 * a], nO = bt.live_h[2 * a + 1];
+    if (t0 >= nI) continue;
+    auto live = [&](int t) { return t < nI || (t >= bt.tI && t - bt.tI < nO); };
+    const int nt = T - tb, Ts = (nt + 7) / 8;
+    for (int si = 0; si < Ts; ++si)
+      for (int sj = 0; sj <= si; ++sj) {
+        std::vector<int> grp;
+        for (int i = 8 * si; i < std::min(nt, 8 * si + 8); ++i)
+          for (int j = 8 * sj; j < std::min(i + 1, 8 * sj + 8); ++j)
+            if (live(tb + i) && live(tb + j) && (part == 0 || (part <= 2 && (i < bt.split_ta) == (part == 1)) || (part >= 3 && (j < 2 || i < bt.split_ta) == (part == 3)))) grp.push_back((a << 20) | (i << 10) | j);
+        if (grp.empty()) continue;
+        int best = 0;
+        for (int x = 1; x < 8; ++x) if (q[x].size() < q[best].size()) best = x;
+        q[best].insert(q[best].end(), grp.begin(), grp.end());
+      }
+  }
+  size_t longest = 0;
+  for (int x = 0; x < 8; ++x) longest = std::max(longest, q[x].size());
+  std::vector<int> lst(8 * longest, -1);
+  for (int x = 0; x < 8; ++x) for (size_t k = 0; k < q[x].size(); ++k) lst[8 * k + x] = q[x][k];
+  return lst;
+}
+// ... as a device array (an empty list: nullptr, 0); false: out of memory
+static bool upload_list(const std::vector<int>& lst, int*& d_out, int& n_out) {
+  d_out = nullptr; n_out = 0;
+  if (lst.empty()) return true;
+  if (hipMalloc((void**)&d_out, lst.size() * sizeof(int)) != hipSuccess) { d_out = nullptr; return false; }
+  (void)hipMemcpy(d_out, lst.data(), lst.size() * sizeof(int), hipMemcpyHostToDevice);
+  n_out = (int)lst.size();
+  return true;
+}
 
+// One factorisation by dense_cholesky_solve_raw or dense_cholesky_dist: what every step needs, and the steps themselves.
+struct PanelRun {
+  double* S; double* b; double* Linv; int* flag;
+  int npad, T, NP, Pstop, nbt; size_t ld;   // T tiles, NP big panels of two tile columns, of which [0, Pstop) are eliminated
+  const DenseBatch& bt; CholAux& ax; CholAux::TriCache& tc;
+  const bool chain;   // the look-ahead driver (false: dense_cholesky_dist, which never passes beta0 and keeps the panel census to itself)
   // Four streams (timeline analysis in profiles/r01y_timeline_*.csv: once the trailing matrix is small the period of
   // the factorisation is the serial chain potrf -> trsm -> rect -> potrf ..., so nothing else may sit on it):
   //   M  (= st) the critical chain only: the panel's 2x2 diagonal tiles, and the look-ahead update of the NEXT
@@ -694,342 +672,370 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
   //   H  rows h = the next panel's two tile rows (t0+2, t0+3): their TRSMs / updates trail the chain by one kernel;
   //   R  rows r = everything below (t0+4 ..): full-tile kernels, needed one panel later;
   //   B  the bulk rank-256 trailing update (triangle from tile t0+4).
-  hipStream_t M = st, H = ax.head, R = ax.mid, B = ax.aux;
-  // ordering between the four streams: device flags (CholAux::record / wait) or, with COVGPU_GATES=0, HIP events. Waits of one stream that stand
+  // Ordering between them: device flags (CholAux::record / wait) or, with COVGPU_GATES=0, HIP events. Waits of one stream that stand
   // side by side are ONE gate launch.
-  auto wait = [&ax](hipStream_t s2, hipEvent_t e0, hipEvent_t e1 = nullptr, hipEvent_t e2 = nullptr, hipEvent_t e3 = nullptr) { ax.wait(s2, e0, e1, e2, e3); };
-  auto record = [&ax](hipEvent_t e, hipStream_t s2, int tag = 0) { ax.record(e, s2, tag); };
+  hipStream_t M, H, R, B;
+  // events per big panel (set_up_events): [NP + 1] each
+  hipEvent_t* eH = nullptr;    // rows h done
+  hipEvent_t* eB = nullptr;    // bulk done
+  hipEvent_t* eC = nullptr;    // rows r done
+  hipEvent_t* e1 = nullptr;    // potrf(t0): panel factored
+  hipEvent_t* e2 = nullptr;    // rows r carry panel P-1's update
+  hipEvent_t* e3 = nullptr;    // (potrf(t0+1) of the retired 128-column chain: unused, keeps the others' places in CholAux::ev)
+  hipEvent_t* eRc = nullptr;   // next diagonal updated
+  hipEvent_t* eHp = nullptr;   // rows h updated with column t0 (their last TRSM then runs on the chain's own stream)
+  hipEvent_t* eA = nullptr;    // bulk(P) has updated the NEXT-BUT-ONE panel's two tile columns (the first of its two launches; == eB where the bulk is one launch)
+  int Plast;
+  bool split_last = false;     // the last panel's bulk update was left running on B for the caller (DenseBatch::split_ta)
+  bool tail_on_chain = false;  // the last panel ran whole on the chain's own stream: nothing of it to join (every event packet on
+                               // the chain's stream is a few microseconds between two dependent kernels)
+
+  static CholAux::TriCache& tri_cache_of(CholAux& ax, const DenseBatch& bt) {
+    if (bt.tri_slot >= (int)ax.tri_lev.size()) ax.tri_lev.resize(bt.tri_slot + 1);
+    return bt.tri_slot >= 0 ? ax.tri_lev[bt.tri_slot] : ax.tri0;
+  }
   // Partial factorisation (tstop >= 0, even): eliminate tile columns [0, tstop) only; the trailing block then holds
   // its Schur complement (and, with the forward substitution riding along, b's trailing part the reduced right-hand
   // side). Used by the block-arrow pose-graph solve (k_pgo.hip).
-  const int Pstop = (tstop >= 0 && tstop < T) ? tstop / 2 : NP;
-  // K range of big panel Pp's rank update: its columns beyond the batch's largest real interior order are identity padding
-  // with zeros below (DenseBatch::own_max) — multiples of 32 (chunk of the quarter-tile kernels); 0: nothing to apply
-  auto kd = [&](int Pp) {
-    const int full = std::min(2, T - 2 * Pp) * kTile;
-    if (bt.own_max <= 0) return full;
-    return std::max(0, std::min(full, ((bt.own_max - 2 * Pp * kTile + 31) / 32) * 32));
-  };
-  // K range front `a` really runs in panel Pp's rank update (GemmArgs::own): for the flop count of the profiled run
-  auto kd_front = [&](int Pp, int a, int chunk) {
-    if (bt.own_dims_h == nullptr) return kd(Pp);
-    const int real = bt.own_dims_h[a] - 2 * Pp * kTile;
-    return real <= 0 ? 0 : std::min(kd(Pp), ((real + chunk - 1) / chunk) * chunk);
-  };
-  if (bt.tri_slot >= (int)ax.tri_lev.size()) ax.tri_lev.resize(bt.tri_slot + 1);
-  CholAux::TriCache& tc = bt.tri_slot >= 0 ? ax.tri_lev[bt.tri_slot] : ax.tri0;
-  // live tiles (i, j), j <= i, of the triangle that starts at tile tb, for the fronts whose interior reaches panel column t0;
-  // part 0: all | 1: rows i < split_ta | 2: rows i >= split_ta | 3: tile columns j < 2 and rows i < split_ta | 4: the others. XCD-balanced, interleaved (position p runs on XCD p % 8).
-  auto build_list = [&](int t0, int tb, int part, int*& d_out, int& n_out) {
-    d_out = nullptr; n_out = 0;
-    std::vector<int> q[8];  // per-XCD queues; whole 8x8 supertiles of one batch go to the currently shortest queue
-    for (int a = 0; a < nbt; ++a) {
-      const int nI = bt.live_h[2 * a], nO = bt.live_h[2 * a + 1];
-      if (t0 >= nI) continue;
-      auto live = [&](int t) { return t < nI || (t >= bt.tI && t - bt.tI < nO); };
-      const int nt = T - tb, Ts = (nt + 7) / 8;
-      for (int si = 0; si < Ts; ++si)
-        for (int sj = 0; sj <= si; ++sj) {
-          std::vector<int> grp;
-          for (int i = 8 * si; i < std::min(nt, 8 * si + 8); ++i)
-            for (int j = 8 * sj; j < std::min(i + 1, 8 * sj + 8); ++j)
-              if (live(tb + i) && live(tb + j) && (part == 0 || (part <= 2 && (i < bt.split_ta) == (part == 1)) || (part >= 3 && (j < 2 || i < bt.split_ta) == (part == 3)))) grp.push_back((a << 20) | (i << 10) | j);
-          if (grp.empty()) continue;
-          int best = 0;
-          for (int x = 1; x < 8; ++x) if (q[x].size() < q[best].size()) best = x;
-          q[best].insert(q[best].end(), grp.begin(), grp.end());
-        }
+  PanelRun(double* S_, double* b_, double* Linv_, int* flag_, int npad_, hipStream_t st, CholAux& ax_, int tstop, const DenseBatch& bt_, bool chain_)
+      : S(S_), b(b_), Linv(Linv_), flag(flag_), npad(npad_), T(npad_ / kTile), NP((T + 1) / 2), Pstop((tstop >= 0 && tstop < T) ? tstop / 2 : NP),
+        nbt(bt_.n > 0 ? bt_.n : 1), ld((size_t)npad_), bt(bt_), ax(ax_), tc(tri_cache_of(ax_, bt_)), chain(chain_), Plast(NP - 1) {
+    static std::atomic<unsigned long long> attr_seen{0};  // (per device; several host threads may arrive at once: the attribute is idempotent)
+    if (first_use_on_device(attr_seen)) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_abt<MODE_SYRK_TRI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsFull);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_abt<MODE_SYRK_RECT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsFull);
     }
-    size_t longest = 0;
-    for (int x = 0; x < 8; ++x) longest = std::max(longest, q[x].size());
-    if (longest == 0) return true;
-    std::vector<int> lst(8 * longest, -1);
-    for (int x = 0; x < 8; ++x) for (size_t k = 0; k < q[x].size(); ++k) lst[8 * k + x] = q[x][k];
-    if (hipMalloc((void**)&d_out, lst.size() * sizeof(int)) != hipSuccess) { d_out = nullptr; return false; }
-    (void)hipMemcpy(d_out, lst.data(), lst.size() * sizeof(int), hipMemcpyHostToDevice);
-    n_out = (int)lst.size();
-    return true;
-  };
+    ax.init();
+    M = st; H = ax.head; R = ax.mid; B = ax.aux;
+  }
+  void set_up_events() {
+    while ((int)ax.ev.size() < 9 * (NP + 1)) { hipEvent_t e; (void)hipEventCreateWithFlags(&e, hipEventDisableTiming); ax.ev.push_back(e); }
+    hipEvent_t** const roles[9] = {&eH, &eB, &eC, &e1, &e2, &e3, &eRc, &eHp, &eA};
+    for (int r = 0; r < 9; ++r) *roles[r] = ax.ev.data() + r * (NP + 1);
+  }
+  static int tag(int P, int k) { return 100 * (P + 1) + k; }   // of a record, a mark
+  void trace(hipStream_t s, int P, int k) { if (kTraceKernels) ax.mark(s, tag(P, k)); }
+  int width(int t0) const { return (T - t0 >= 2) ? 2 : 1; }
+  int row_h0(int t0) const { return std::min(t0 + 2, T); }   // rows h = [h0, h1), rows r = [h1, T)
+  int row_h1(int t0) const { return std::min(t0 + 4, T); }
+
+  // K range of big panel P's rank update: its columns beyond the batch's largest real interior order are identity padding
+  // with zeros below (DenseBatch::own_max) — multiples of 32 (chunk of the quarter-tile kernels); 0: nothing to apply
+  int kd(int P) const {
+    const int full = std::min(2, T - 2 * P) * kTile;
+    if (bt.own_max <= 0) return full;
+    return std::max(0, std::min(full, ((bt.own_max - 2 * P * kTile + 31) / 32) * 32));
+  }
+  // K range front `a` really runs in panel P's rank update (GemmArgs::own): for the flop count of the profiled run
+  int kd_front(int P, int a, int chunk) const {
+    if (bt.own_dims_h == nullptr) return kd(P);
+    const int real = bt.own_dims_h[a] - 2 * P * kTile;
+    return real <= 0 ? 0 : std::min(kd(P), ((real + chunk - 1) / chunk) * chunk);
+  }
+  // 16-column blocks of the panel at tile t0 that hold a real column of some front (-1: the whole panel)
+  int nbp(int t0, int w) const { return bt.own_max > 0 ? std::max(0, std::min(8 * w, (bt.own_max - t0 * kTile + 15) / 16)) : -1; }
+  // C tiles from (row_tile0, col_tile0), nt tile rows, -= A[rows, K] A[col_tile0.., K]^T, K = KD columns from tile kt0. `trailing`: a trailing
+  // update of the look-ahead driver — the only launches that start uncleared border tiles from zero (DenseBatch::beta0)
+  GemmArgs gemm_args(int kt0, int KD, int row_tile0, int col_tile0, int nt, bool trailing = false) const {
+    GemmArgs g{};
+    g.M = S; g.ld = ld; g.kcol0 = kt0 * kTile; g.KD = KD;
+    g.ra0 = row_tile0 * kTile; g.rb0 = g.cc0 = col_tile0 * kTile; g.nt = nt;
+    g.bsM = bt.sM; g.bsL = bt.sL; g.bsR = bt.sR; g.live = bt.live; g.tI = bt.tI; g.btab = bt.tab; g.own = bt.own_dims;
+    if (trailing && chain) { g.beta0_off = bt.beta0_off; g.beta0 = bt.beta0; }
+    return g;
+  }
+
+  // k_potrf_panel of the panel at tile t0, all fronts of the batch; profiling: an event pair around the launch and its algorithmic flops
+  // (per front n^3 / 3 for the factorisation + n^2 for the forward substitution riding along, n = the front's REAL columns in the panel)
+  void potrf(int t0, int w, hipStream_t s) {
+    const int P = t0 / 2, nb = nbp(t0, w);
+    const bool timed = chain && ax.profile && nb != 0;
+    if (chain && w == 1) form_hit(KF_PANEL_ONE_TILE);
+    if (chain && T > t0 + w) {   // K range of this panel's rank update (kd)
+      if (kd(P) == 0) form_hit(KF_KD_ZERO);
+      else if (kd(P) < w * kTile) form_hit(KF_KD_CUT);
+    }
+    double fl = 0.0;
+    for (int a = 0; timed && a < nbt; ++a) {
+      const double n = bt.own_dims_h != nullptr ? (double)std::max(0, std::min(w * kTile, bt.own_dims_h[a] - t0 * kTile)) : (double)(w * kTile);
+      fl += n * n * n / 3.0 + n * n;
+    }
+    ProfBracket prof(timed, ax.prof_ev2, ax.prof_flops2, s, fl);
+    if (bt.plist != nullptr) launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, s, bt.tab, nb, bt.own_dims, bt.plist, bt.pbig_h[P], bt.psmall_h[P]);
+    else launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, s, bt.tab, nb);
+  }
+  // block substitution of tile rows [r0, r1) against the panel at tile t0 (k_panel.hip); rhs: the right-hand side that rides along
+  void trsm(int t0, int w, int r0, int r1, hipStream_t s, bool on_chain, double* rhs) {
+    launch_trsm_sub(S, ld, t0, w, r0, r1, Linv, rhs, npad, nbt, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, s, on_chain, bt.tab, nbp(t0, w), bt.own_dims);
+  }
+  // C tiles (rows [r0, r1), tile columns [tc0, tc0+ntc)) -= A[rows, K] A[tc.., K]^T, K = tiles kt0.. (KD columns); lower part only
+  void rect(int r0, int r1, int tc0, int ntc, int kt0, int KD, hipStream_t s, bool quad) {
+    if (r1 <= r0 || ntc <= 0 || KD <= 0) return;
+    const GemmArgs g = gemm_args(kt0, KD, r0, tc0, r1 - r0);
+    form_hit(quad ? KF_GEMM_RECT_QUAD : KF_GEMM_RECT_FULL);
+    if (quad) hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_RECT, 64, 64>), dim3(ntc, r1 - r0, 4 * nbt), dim3(256), kLdsQuarter, s, g);
+    else hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_RECT>, dim3(ntc, r1 - r0, nbt), dim3(256), kLdsFull, s, g);
+  }
+  // the same update of the diagonal block of tile rows / columns [u0, u0 + uw) on the chain's stream. Fronts of a tree take k_diag_update; the
+  // one-matrix solves keep the quadrant form (at three and four tiles this is their only RECT launch, and their census says so:
+  // tests/test_gpu_parity.py::test_mfma_cholesky_solve_forms). The bits are the same either way.
+  void diag(int u0, int uw, int kt0, int KD, hipStream_t s) {
+    if (bt.tab == nullptr) { rect(u0, u0 + uw, u0, uw, kt0, KD, s, true); return; }
+    if (uw <= 0 || KD <= 0) return;
+    const int nb = uw * (kTile / kDiagSub);
+    form_hit(KF_DIAG_UPDATE);
+    hipLaunchKernelGGL(k_diag_update, dim3(nb * (nb + 1) / 2, nbt), dim3(256), 0, s, gemm_args(kt0, KD, u0, u0, uw));
+  }
+  // rank update of the triangle from tile tb with panel P: the tiles of `list` (count entries incl. the XCD padding) or, without one, the
+  // implicit triangle grid x batch. A short list runs at the LATENCY of one workgroup's K loop (16 chunks of 64 MFMAs per wave): as 64x64
+  // quadrants it is four times as many workgroups, each four times shorter.
+  void tri_update(hipStream_t s, const int* list, int count, int P, int tb) {
+    const int nt = T - tb;
+    GemmArgs g = gemm_args(2 * P, kd(P), tb, tb, nt, true);
+    g.tri = list;
+    form_hit(list == nullptr ? KF_GEMM_TRI_GRID : count <= kQuarterMax ? KF_GEMM_TRI_QUAD : KF_GEMM_TRI_FULL);
+    if (g.beta0 != nullptr && P == 0) form_hit(KF_GEMM_BETA0);
+    if (list != nullptr && count <= kQuarterMax) hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_TRI, 64, 64>), dim3(count, 1, 4), dim3(256), kLdsQuarter, s, g);
+    else if (list != nullptr) hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(count, 1), dim3(256), kLdsFull, s, g);
+    else {
+      const int Ts = (nt + 7) / 8, ns = Ts * (Ts + 1) / 2, nblk = ((ns + 7) / 8) * 8 * 64;
+      hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(nblk, nbt), dim3(256), kLdsFull, s, g);
+    }
+  }
+  // flops of that update: the tile pairs that do work, over the K range each front really runs in kernels of K chunk `chunk`;
+  // rows >= 0: of every front's first `rows` live tile rows only. (Booked by the profiled run alone: 0 otherwise.)
+  double update_flops(int P, int tb, int chunk, int rows = -1) const {
+    if (!ax.profile) return 0.0;
+    const int nt = T - tb;
+    const double per_k = 2.0 * kTile * kTile;
+    double flops = 0.0;
+    for (int a = 0; a < nbt; ++a) {
+      int nl = nt;
+      double kf = kd(P);
+      if (bt.live_h != nullptr) {
+        const int nI = bt.live_h[2 * a], nO = bt.live_h[2 * a + 1];
+        if (2 * P >= nI) continue;
+        nl = 0;
+        for (int t = tb; t < T; ++t) nl += (t < nI || (t >= bt.tI && t - bt.tI < nO)) ? 1 : 0;
+        kf = kd_front(P, a, chunk);
+      }
+      if (rows >= 0) nl = std::min(nl, rows);
+      flops += (double)nl * (nl + 1) / 2 * per_k * kf;
+    }
+    return flops;
+  }
+
+  // live-tile lists of every panel's trailing update (static per problem), cached under the batch's shape.
   // Two launches per bulk update (round 5): first the tiles of the next-but-one panel's two tile columns, then the rest. Everything on or beside the
   // chain that follows a bulk update — the next diagonal look-ahead, the look-ahead of the next panel's rows — writes those two tile columns only and
   // waits for the FIRST launch (eA). With one launch the chain of a big front waited for the whole previous bulk update every panel: on the 5-agent
   // map's root (3 726 unknowns, 15 panels, bulk 100 us) the period was bulk -> diagonal look-ahead -> bulk = 165 us instead of the chain's 128.
-  const int key = (T * 4096 + nbt) * 8 + bt.split_ta;
-  if (bt.live_h != nullptr && tc.key != key) {  // live-tile lists of every panel's bulk update (static per problem)
+  void build_tri_cache() {
+    const int key = (T * 4096 + nbt) * 8 + bt.split_ta;
+    if (bt.live_h == nullptr || tc.key == key) return;
     tc.clear();
     tc.key = key;
     tc.list.assign(NP, nullptr); tc.count.assign(NP, 0); tc.listC.assign(NP, nullptr); tc.countC.assign(NP, 0);
+    auto build = [&](int t0, int tb, int part, int*& d_out, int& n_out) { return upload_list(live_tile_list(bt, nbt, T, t0, tb, part), d_out, n_out); };
     for (int P = 0; P < NP && P < Pstop; ++P) {
       // (the LAST panel of a partial factorisation applies its whole trailing update in one launch: triangle from t0 + 2)
       const bool last = Pstop < NP && P == Pstop - 1;
       const int t0 = 2 * P, tb = last ? t0 + 2 : t0 + 4;
       if (tb >= T) break;
       bool ok = true;
-      if (last && bt.split_ta > 0) ok = build_list(t0, tb, 1, tc.listA, tc.countA) && build_list(t0, tb, 2, tc.listB, tc.countB);
-      else if (!last) ok = build_list(t0, tb, 3, tc.listC[P], tc.countC[P]) && build_list(t0, tb, 4, tc.list[P], tc.count[P]);   // (the last panel's update is ONE launch on the chain's stream)
-      else ok = build_list(t0, tb, 0, tc.list[P], tc.count[P]);
+      if (last && bt.split_ta > 0) ok = build(t0, tb, 1, tc.listA, tc.countA) && build(t0, tb, 2, tc.listB, tc.countB);
+      else if (!last) ok = build(t0, tb, 3, tc.listC[P], tc.countC[P]) && build(t0, tb, 4, tc.list[P], tc.count[P]);   // (the last panel's update is ONE launch on the chain's stream)
+      else ok = build(t0, tb, 0, tc.list[P], tc.count[P]);
       if (!ok) { tc.clear(); break; }
     }
   }
-  // k_potrf_panel of big panel P, all fronts of the batch; profiling: an event pair around the launch and its algorithmic flops
-  // (per front n^3 / 3 for the factorisation + n^2 for the forward substitution riding along, n = the front's REAL columns in the panel)
-  auto potrf = [&](int t0, int w, int nbp) {
-    const bool prof = ax.profile && nbp != 0;
-    if (w == 1) form_hit(KF_PANEL_ONE_TILE);
-    if (T > t0 + w) {   // K range of this panel's rank update (kd)
-      if (kd(t0 / 2) == 0) form_hit(KF_KD_ZERO);
-      else if (kd(t0 / 2) < w * kTile) form_hit(KF_KD_CUT);
+  bool listed(int P) const { return bt.live_h != nullptr && P < (int)tc.list.size() && tc.list[P] != nullptr; }
+
+  // ---- the steps of the panel loop, in the order dense_cholesky_solve_raw calls them
+  // H, R: look-ahead part of SYRK(P-1) (K = the 256 columns of panel P-1) on this panel's two tile columns; the
+  // 2x2 diagonal part was enqueued on M at the end of the previous iteration
+  void look_ahead_rows(int P) {
+    if (P == 0) return;
+    const int t0 = 2 * P, w = width(t0), h0 = row_h0(t0), h1 = row_h1(t0);
+    if (h1 > h0) {
+      // L rows h0.. were rest rows of panel P-1 (eC) | B operand: L rows t0, t0+1 — their last TRSM ran on the chain's stream (eH) |
+      // bulk(P-2) was the previous writer of these tiles (its first launch: these two tile columns, eA)
+      ax.wait(H, eC[P - 1], eH[P - 1], P >= 2 ? eA[P - 2] : nullptr);
+      rect(h0, h1, t0, w, t0 - 2, kd(P - 1), H, true);
+      trace(H, P, 6);   // rows h carry panel P-1
+      ax.record(eHp[P], H, tag(P, 17));
     }
-    if (prof) {
-      while (ax.prof_ev2.size() < 2 * (ax.prof_flops2.size() + 1)) { hipEvent_t e; (void)hipEventCreate(&e); ax.prof_ev2.push_back(e); }
-      (void)hipEventRecord(ax.prof_ev2[2 * ax.prof_flops2.size()], M);
+    if (T > h1) {
+      ax.wait(R, eH[P - 1], P >= 2 ? eA[P - 2] : nullptr);   // B operand: L rows t0, t0+1 (rows h of panel P-1) | previous writer
+      // (round 5: as quarter tiles while the launch is small — a full tile is one workgroup's 16-chunk K loop, 50-57 us of latency that the
+      //  rest rows' substitution and, behind it, the bulk update and the last panel's substitution wait for)
+      rect(h1, T, t0, w, t0 - 2, kd(P - 1), R, (T - h1) * w * nbt <= kRectQuarterMax);
+      trace(R, P, 7);   // rows r carry panel P-1
+      ax.record(e2[P], R, tag(P, 14));  // rows r carry panel P-1's update
     }
-    if (bt.plist != nullptr) launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, M, bt.tab, nbp, bt.own_dims, bt.plist, bt.pbig_h[t0 / 2], bt.psmall_h[t0 / 2]);
-    else launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, M, bt.tab, nbp);
-    if (prof) {
-      double fl = 0.0;
-      for (int a = 0; a < nbt; ++a) {
-        const double n = bt.own_dims_h != nullptr ? (double)std::max(0, std::min(w * kTile, bt.own_dims_h[a] - t0 * kTile)) : (double)(w * kTile);
-        fl += n * n * n / 3.0 + n * n;
-      }
-      (void)hipEventRecord(ax.prof_ev2[2 * ax.prof_flops2.size() + 1], M);
-      ax.prof_flops2.push_back(fl);
-    }
-  };
-  int Plast = NP - 1;
-  bool split_last = false;  // the last panel's bulk update was left running on B for the caller (DenseBatch::split_ta)
-  bool tail_on_chain = false;  // the last panel ran whole on the chain's own stream: nothing of it to join (every event packet on
-                               // the chain's stream is a few microseconds between two dependent kernels)
-  static const bool trace2 = env_int("COVGPU_TRACE_PANELS", 0) >= 2;   // dev aid: per-kernel marks, tag 100 (P + 1) + k
-  for (int P = 0; P < NP; ++P) {
-    const int t0 = 2 * P, w = (T - t0 >= 2) ? 2 : 1;
-    const int h0 = (t0 + 2 < T) ? t0 + 2 : T, h1 = (t0 + 4 < T) ? t0 + 4 : T;  // rows h = [h0, h1), rows r = [h1, T)
-    // ---- look-ahead part of SYRK(P-1) (K = the 256 columns of panel P-1) on this panel's two tile columns; the
-    //      2x2 diagonal part was enqueued on M at the end of the previous iteration
-    if (P > 0) {
-      if (h1 > h0) {
-        // L rows h0.. were rest rows of panel P-1 (eC) | B operand: L rows t0, t0+1 — their last TRSM ran on the chain's stream (eH) |
-        // bulk(P-2) was the previous writer of these tiles (its first launch: these two tile columns, eA)
-        wait(H, eC[P - 1], eH[P - 1], P >= 2 ? eA[P - 2] : nullptr);
-        rect(h0, h1, t0, w, t0 - 2, kd(P - 1), H, true);
-        if (trace2) ax.mark(H, 100 * (P + 1) + 6);   // rows h carry panel P-1
-        record(eHp[P], H, 100 * (P + 1) + 17);
-      }
-      if (T > h1) {
-        wait(R, eH[P - 1], P >= 2 ? eA[P - 2] : nullptr);   // B operand: L rows t0, t0+1 (rows h of panel P-1) | previous writer
-        // (round 5: as quarter tiles while the launch is small — a full tile is one workgroup's 16-chunk K loop, 50-57 us of latency that the
-        //  rest rows' substitution and, behind it, the bulk update and the last panel's substitution wait for)
-        rect(h1, T, t0, w, t0 - 2, kd(P - 1), R, (T - h1) * w * nbt <= kRectQuarterMax);
-        if (trace2) ax.mark(R, 100 * (P + 1) + 7);   // rows r carry panel P-1
-        record(e2[P], R, 100 * (P + 1) + 14);  // rows r carry panel P-1's update
-      }
-    }
-    if (P == Pstop) {  // only the look-ahead updates of the last eliminated panel; nothing of this panel is factored
-      record(eH[P], H, 100 * (P + 1) + 10);
-      record(eC[P], R, 100 * (P + 1) + 12);
-      record(eB[P], B, 100 * (P + 1) + 11);
-      record(eA[P], B, 100 * (P + 1) + 18);
-      Plast = P;
-      break;
-    }
-    // ---- M: critical chain
-    ax.mark(M, P);
-    if (Pstop < NP && P == Pstop - 1) {
-      // LAST panel of a partial factorisation (every multifrontal front, every arrow block): nothing is factored after it, so
-      // the look-ahead split of its trailing update (next panel's rows / diagonal / rest rows / bulk: four launches on three
-      // streams, ~100 us of event hops per front level) buys nothing — factor, solve ALL rows below, update the WHOLE trailing
-      // triangle, three dependent launches on the chain's own stream.
-      const int nbp = bt.own_max > 0 ? std::max(0, std::min(8 * w, (bt.own_max - t0 * kTile + 15) / 16)) : -1;
-      potrf(t0, w, nbp);
-      if (trace2) ax.mark(M, 100 * (P + 1) + 1);   // potrf done
-      if (P == 0 && bt.pre_trsm != nullptr) wait(M, bt.pre_trsm);   // rows below the first panel: second half of the caller's extend-add
-      bool split_done = false;
-      if (T > h0) {
-        const bool split = bt.split_ta > 0 && bt.live_h != nullptr && kd(P) > 0 && (tc.listA != nullptr || tc.listB != nullptr);
-        const bool waitedA = split && P >= 1;
-        // rows h / rest rows carry panel P-1 | (beside them instead of between the substitution and the update: see the multi-panel branch) bulk(P-1)'s first launch
-        if (P > 0) wait(M, h1 > h0 ? eHp[P] : nullptr, T > h1 ? e2[P] : nullptr, waitedA ? eA[P - 1] : nullptr);
-        // (measured and dropped: solving only the rows the parents' first panel receives here and the others on the bulk stream —
-        //  the bulk stream's leg (rest rows, rest of the update, second half of the extend-add) is what the next level's
-        //  substitutions wait for, and it only got longer: 3.37 vs 3.33 ms)
-        launch_trsm_sub(S, ld, t0, w, h0, T, Linv, b, npad, nbt, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, M, true, bt.tab, nbp, bt.own_dims);
-        if (split) { record(eH[P], M, 100 * (P + 1) + 10); wait(B, eH[P]); }
-        // bulk(P-1) was the previous writer of the trailing tiles. The part of this update that stays on the chain's stream (rows < split_ta: what
-        // build_list puts into the first launch beside tile columns 0, 1) only meets the FIRST launch of that bulk update — on the 5-agent map's upper levels (borders of
-        // 2 000 unknowns) the whole of it is 160 us, and the next level's first panel waited for it; the rest follows it on the bulk stream anyway
-        if (P >= 1 && !waitedA) wait(M, eB[P - 1]);
-        const int tb = h0, nt = T - tb;
-        auto syrk = [&](hipStream_t s2, const int* list, int count, double flops) {
-          GemmArgs g{S, ld, t0 * kTile, kd(P), tb * kTile, tb * kTile, tb * kTile, nt, nullptr, nullptr, nullptr, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, nullptr, bt.tab, bt.own_dims};
-          g.tri = list; g.beta0_off = bt.beta0_off; g.beta0 = bt.beta0;
-          if (ax.profile) (void)hipEventRecord(ax.prof_ev[2 * ax.prof_flops.size()], s2);
-          // a short list runs at the LATENCY of one workgroup's K loop (16 chunks of 64 MFMAs per wave): as 64x64 quadrants it is
-          // four times as many workgroups, each four times shorter
-          form_hit(list == nullptr ? KF_GEMM_TRI_GRID : count <= kQuarterMax ? KF_GEMM_TRI_QUAD : KF_GEMM_TRI_FULL);
-          if (g.beta0 != nullptr && t0 == 0) form_hit(KF_GEMM_BETA0);
-          if (list != nullptr && count <= kQuarterMax)
-            hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_TRI, 64, 64>), dim3(count, 1, 4), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), s2, g);
-          else if (list != nullptr) hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(count, 1), dim3(256), lds_gemm, s2, g);
-          else {
-            const int Ts = (nt + 7) / 8, ns = Ts * (Ts + 1) / 2, nblk = ((ns + 7) / 8) * 8 * 64;
-            hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(nblk, nbt), dim3(256), lds_gemm, s2, g);
-          }
-          if (ax.profile) {
-            (void)hipEventRecord(ax.prof_ev[2 * ax.prof_flops.size() + 1], s2);
-            ax.prof_flops.push_back(flops);
-          }
-        };
-        if (kd(P) > 0) {
-          double pairs = 0.0, pairsA = 0.0;   // flops of the whole update | of its first split_ta tile rows
-          const double per_k = 2.0 * kTile * kTile;
-          for (int a = 0; a < nbt; ++a) {
-            if (bt.live_h == nullptr) { pairs += (double)nt * (nt + 1) / 2 * per_k * kd(P); continue; }
-            const int nI = bt.live_h[2 * a], nO = bt.live_h[2 * a + 1];
-            if (t0 >= nI) continue;
-            int nl = 0;
-            for (int t = tb; t < T; ++t) nl += (t < nI || (t >= bt.tI && t - bt.tI < nO)) ? 1 : 0;
-            const double kf = kd_front(P, a, KCQ);
-            pairs += (double)nl * (nl + 1) / 2 * per_k * kf;
-            const int na = std::min(nl, bt.split_ta);
-            pairsA += (double)na * (na + 1) / 2 * per_k * kf;
-          }
-          form_hit(split ? KF_LAST_UPDATE_SPLIT : KF_LAST_UPDATE_WHOLE);
-          if (split) {
-            // look-ahead across levels: the tiles the parents' first panel receives on the chain's stream, the rest on the bulk stream
-            if (tc.countA > 0) syrk(M, tc.listA, tc.countA, pairsA);
-            if (tc.countB > 0) syrk(B, tc.listB, tc.countB, pairs - pairsA);
-            record(eB[P], B, 100 * (P + 1) + 11);
-            split_done = true;
-          } else {
-            const bool listed = bt.live_h != nullptr && P < (int)tc.list.size() && tc.list[P] != nullptr;
-            if (!listed || tc.count[P] > 0) syrk(M, listed ? tc.list[P] : nullptr, listed ? tc.count[P] : 0, pairs);
-          }
-        }
-      }
-      Plast = P; split_last = split_done; tail_on_chain = true;
-      break;
-    }
-    bool bulk_wait_rc = false;
-    {
-      // 256-column chain (k_panel.hip): one workgroup factors the whole diagonal block, rows h follow on the same stream by
-      // block substitution, rows r on theirs — three dependent launches per panel instead of six
-      const int nbp = bt.own_max > 0 ? std::max(0, std::min(8 * w, (bt.own_max - t0 * kTile + 15) / 16)) : -1;
-      const double bulk_pairs = (T - (t0 + 4) > 0) ? 0.5 * (double)(T - (t0 + 4)) * (T - (t0 + 4) + 1) * nbt : 0.0;
-      // (round 4: the threshold was 700 tile pairs — every panel of the 5-agent map's fronts. With the panel factorisation at 60 us the
-      //  period of a multi-panel front was no longer the chain but the cycle  look-ahead(P) -> rest rows(P) -> bulk(P) -> look-ahead(P+1),
-      //  all of it behind the ONE event of the chain-bound form: 140-160 us per panel. Events after every kernel: 284 -> 298 it/s, and
-      //  no loss on the one-panel fronts. COVGPU_CHAIN_PAIRS restores a threshold.)
-      static const double chain_pairs = getenv("COVGPU_CHAIN_PAIRS") ? atof(getenv("COVGPU_CHAIN_PAIRS")) : 0.0;
-      const bool chain_bound = bulk_pairs <= chain_pairs;
-      potrf(t0, w, nbp);
-      // rows below the first panel: second half of the caller's extend-add. IN FRONT of the record below — the rest rows' substitution on stream R
-      // starts from that record and inherits this wait
-      if (P == 0 && bt.pre_trsm != nullptr) wait(M, bt.pre_trsm);
-      // Every event packet on this stream sits between two dependent kernels of the chain, a few microseconds each. While the bulk
-      // update is short (the period of the factorisation is the chain: small fronts, the tail of big ones) there is ONE event per
-      // panel, eH, recorded after the look-ahead update of the next diagonal block — the rest rows (which only need the factored
-      // panel), the next panel's rows on stream H and the bulk update all start from it, two small kernels later than they could.
-      // While the bulk update is long (the period is the bulk) they start as early as possible: an event after each kernel.
-      // (Merging rows h and the rest rows into one substitution launch on this stream was measured within noise in round 5: DESIGN.md.)
-      bool waitedA = false;
-      hipEvent_t rec1 = !chain_bound ? e1[P] : nullptr;   // "panel P factored": the rest rows' substitution (stream R) starts from it
-      if (h1 > h0) {
-        // rows h carry the look-ahead update of panel P-1 (stream H, above) | bulk(P-1)'s first launch.
-        // (round 6: the record behind the factorisation and these waits are ONE launch — CholAux::sync)
-        waitedA = P >= 1 && P + 1 < NP;
-        ax.sync(M, rec1, 100 * (P + 1) + 13, nullptr, 0, P > 0 ? eHp[P] : nullptr, waitedA ? eA[P - 1] : nullptr);
-        rec1 = nullptr;
-        // (round 5: the wait of the next-diagonal update below for bulk(P-1)'s first launch — 30-40 us of slack — rides along with the one above.
-        //  Measured: no difference (231.1 / 230.5 against 231.4 / 231.2 it/s) — a wait whose event completed long ago costs nothing; the 13-14 us
-        //  between two kernels of this stream come from the RECORD behind the first when its waiter is blocked on it at that moment: DESIGN.md 4.6)
-        launch_trsm_sub(S, ld, t0, w, h0, h1, Linv, b, npad, nbt, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, M, true, bt.tab, nbp, bt.own_dims);
-        if (trace2) ax.mark(M, 100 * (P + 1) + 2);   // rows h solved
-      }
-      if (rec1 != nullptr) record(rec1, M, 100 * (P + 1) + 13);
-      // (round 6: "rows h solved" is published together with "next diagonal block updated", one launch behind that small update instead of one
-      //  launch in front of it and one behind: its waiters — the next panel's look-ahead on stream H — have ~50 us of slack)
-      const bool eh_now = !chain_bound && P + 1 == NP;
-      if (eh_now) record(eH[P], M, 100 * (P + 1) + 10);
-      // ---- M: look-ahead part of SYRK(P) on the next panel's 2x2 diagonal tiles
-      if (P + 1 < NP) {
-        const int u0 = t0 + 2, uw = (T - u0 >= 2) ? 2 : 1;
-        if (P >= 1 && !waitedA) wait(M, eA[P - 1]);          // bulk(P-1) was the previous writer of these tiles (its first launch)
-        diag(u0, uw, t0, kd(P), M);
-        if (trace2) ax.mark(M, 100 * (P + 1) + 3);   // next diagonal block updated
-      }
-      // (A bulk launched at the same instant as the next diagonal update takes every workgroup slot first and the chain waits
-      //  ~75 us for the first round of tiles to retire: the bulk starts after that small kernel in either regime.)
-      // (Both records are published by a launch of their own enqueued before any of their waiters: letting the next panel's factorisation publish
-      //  them deadlocks once two streams share a hardware queue — round 6, DESIGN.md.)
-      if (chain_bound || eh_now) record(chain_bound ? eH[P] : eRc[P], M, 100 * (P + 1) + (chain_bound ? 10 : 16));
-      else ax.sync(M, eH[P], 100 * (P + 1) + 10, eRc[P], 100 * (P + 1) + 16);
-      if (T > h1) {
-        wait(R, chain_bound ? eH[P] : e1[P]);   // (measured, round 4: waiting for rows h instead — so that the chain's substitution runs alone — 299.9 -> 297.5 it/s)
-        launch_trsm_sub(S, ld, t0, w, h1, T, Linv, b, npad, nbt, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, R, false, bt.tab, nbp, bt.own_dims);
-        if (trace2) ax.mark(R, 100 * (P + 1) + 4);   // rest rows solved
-      }
-      record(eC[P], R, 100 * (P + 1) + 12);
-      bulk_wait_rc = !chain_bound;   // (measured again in round 4 with the 60 us panel: without this wait 298.6 -> 292.7 it/s)
-    }
-    // ---- B: bulk of SYRK(P), triangle starting two tile columns further (those belong to the look-ahead)
-    const int tb = t0 + 4, nt = T - tb;
-    bool recA = false;
-    wait(B, eC[P], bulk_wait_rc ? eRc[P] : nullptr);
-    if (nt > 0 && kd(P) > 0) {
-      const int Ts = (nt + 7) / 8, ns = Ts * (Ts + 1) / 2, nblk = ((ns + 7) / 8) * 8 * 64;
-      GemmArgs g{S, ld, t0 * kTile, kd(P), tb * kTile, tb * kTile, tb * kTile, nt, nullptr, nullptr, nullptr, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, nullptr, bt.tab, bt.own_dims};
-      // arrow buffers: the live tiles of this panel's update as an explicit, XCD-balanced list (built once per problem).
-      // The implicit triangle grid x batch launched ~2.6k workgroups of which ~400 did work, with every batch's first
-      // supertile on XCD 0: 17 TFLOP/s.
-      const bool listed = bt.live_h != nullptr && P < (int)tc.list.size() && tc.list[P] != nullptr;
-      if (listed) g.tri = tc.list[P];
-      g.beta0_off = bt.beta0_off; g.beta0 = bt.beta0;
-      double flops = 0.0;  // of the tile pairs that do work, over the K range each front really runs
-      for (int a = 0; a < nbt; ++a) {
-        if (bt.live_h == nullptr) { flops += (double)nt * (nt + 1) / 2 * 2.0 * kTile * kTile * kd(P); continue; }
-        const int nI = bt.live_h[2 * a], nO = bt.live_h[2 * a + 1];
-        if (t0 >= nI) continue;
-        int nl = 0;
-        for (int t = tb; t < T; ++t) nl += (t < nI || (t >= bt.tI && t - bt.tI < nO)) ? 1 : 0;
-        flops += (double)nl * (nl + 1) / 2 * 2.0 * kTile * kTile * kd_front(P, a, KC);
-      }
-      const int cntC = (listed && P < (int)tc.listC.size() && tc.listC[P] != nullptr) ? tc.countC[P] : 0;
-      if (!listed || tc.count[P] > 0 || cntC > 0) {
-        if (ax.profile) (void)hipEventRecord(ax.prof_ev[2 * ax.prof_flops.size()], B);
-        auto tri = [&](const int* list, int count) {
-          g.tri = list;
-          form_hit(count <= kQuarterMax ? KF_GEMM_TRI_QUAD : KF_GEMM_TRI_FULL);
-          if (g.beta0 != nullptr && t0 == 0) form_hit(KF_GEMM_BETA0);
-          if (count <= kQuarterMax) hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_TRI, 64, 64>), dim3(count, 1, 4), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), B, g);
-          else hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(count, 1), dim3(256), lds_gemm, B, g);
-        };
-        form_hit(cntC > 0 && listed && tc.count[P] > 0 ? KF_BULK_TWO_LAUNCHES : KF_BULK_ONE_LAUNCH);
-        if (cntC > 0) {   // the next-but-one panel's two tile columns first: what the chain waits for
-          tri(tc.listC[P], cntC);
-          record(eA[P], B, 100 * (P + 1) + 18); recA = true;
-          if (trace2) ax.mark(B, 100 * (P + 1) + 8);   // first bulk launch done
-        }
-        if (listed) { if (tc.count[P] > 0) tri(tc.list[P], tc.count[P]); }
-        else {
-          form_hit(KF_GEMM_TRI_GRID);
-          if (g.beta0 != nullptr && t0 == 0) form_hit(KF_GEMM_BETA0);
-          hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(nblk, nbt), dim3(256), lds_gemm, B, g);
-        }
-        if (ax.profile) {
-          (void)hipEventRecord(ax.prof_ev[2 * ax.prof_flops.size() + 1], B);
-          ax.prof_flops.push_back(flops);
-        }
-      }
-    }
-    if (trace2) ax.mark(B, 100 * (P + 1) + 5);   // bulk update done
-    record(eB[P], B, 100 * (P + 1) + 11);
-    if (!recA) record(eA[P], B, 100 * (P + 1) + 18);
   }
-  wait(M, !split_last && !tail_on_chain ? eB[Plast] : nullptr, Plast >= 1 ? eB[Plast - 1] : nullptr, !tail_on_chain ? eC[Plast] : nullptr, !tail_on_chain ? eH[Plast] : nullptr);
+  // P == Pstop: only the look-ahead updates of the last eliminated panel; nothing of this panel is factored
+  void stop_panel(int P) {
+    ax.record(eH[P], H, tag(P, 10));
+    ax.record(eC[P], R, tag(P, 12));
+    ax.record(eB[P], B, tag(P, 11));
+    ax.record(eA[P], B, tag(P, 18));
+    Plast = P;
+  }
+  // LAST panel of a partial factorisation (every multifrontal front, every arrow block): nothing is factored after it, so
+  // the look-ahead split of its trailing update (next panel's rows / diagonal / rest rows / bulk: four launches on three
+  // streams, ~100 us of event hops per front level) buys nothing — factor, solve ALL rows below, update the WHOLE trailing
+  // triangle, three dependent launches on the chain's own stream.
+  void last_panel(int P) {
+    const int t0 = 2 * P, w = width(t0), h0 = row_h0(t0), h1 = row_h1(t0);
+    potrf(t0, w, M);
+    trace(M, P, 1);   // potrf done
+    if (P == 0 && bt.pre_trsm != nullptr) ax.wait(M, bt.pre_trsm);   // rows below the first panel: second half of the caller's extend-add
+    Plast = P; tail_on_chain = true;
+    if (T <= h0) return;
+    const bool split = bt.split_ta > 0 && bt.live_h != nullptr && kd(P) > 0 && (tc.listA != nullptr || tc.listB != nullptr);
+    const bool waitedA = split && P >= 1;
+    // rows h / rest rows carry panel P-1 | (beside them instead of between the substitution and the update: see chain_panel) bulk(P-1)'s first launch
+    if (P > 0) ax.wait(M, h1 > h0 ? eHp[P] : nullptr, T > h1 ? e2[P] : nullptr, waitedA ? eA[P - 1] : nullptr);
+    // (measured and dropped: solving only the rows the parents' first panel receives here and the others on the bulk stream —
+    //  the bulk stream's leg (rest rows, rest of the update, second half of the extend-add) is what the next level's
+    //  substitutions wait for, and it only got longer: 3.37 vs 3.33 ms)
+    trsm(t0, w, h0, T, M, true, b);
+    if (split) { ax.record(eH[P], M, tag(P, 10)); ax.wait(B, eH[P]); }
+    // bulk(P-1) was the previous writer of the trailing tiles. The part of this update that stays on the chain's stream (rows < split_ta: what
+    // build_tri_cache puts into the first launch beside tile columns 0, 1) only meets the FIRST launch of that bulk update — on the 5-agent map's upper levels (borders of
+    // 2 000 unknowns) the whole of it is 160 us, and the next level's first panel waited for it; the rest follows it on the bulk stream anyway
+    if (P >= 1 && !waitedA) ax.wait(M, eB[P - 1]);
+    if (kd(P) <= 0) return;
+    const int tb = h0;
+    const double pairs = update_flops(P, tb, KCQ);
+    form_hit(split ? KF_LAST_UPDATE_SPLIT : KF_LAST_UPDATE_WHOLE);
+    if (split) {
+      // look-ahead across levels: the tiles the parents' first panel receives on the chain's stream, the rest on the bulk stream
+      const double pairsA = update_flops(P, tb, KCQ, bt.split_ta);
+      if (tc.countA > 0) { ProfBracket prof(ax.profile, ax.prof_ev, ax.prof_flops, M, pairsA); tri_update(M, tc.listA, tc.countA, P, tb); }
+      if (tc.countB > 0) { ProfBracket prof(ax.profile, ax.prof_ev, ax.prof_flops, B, pairs - pairsA); tri_update(B, tc.listB, tc.countB, P, tb); }
+      ax.record(eB[P], B, tag(P, 11));
+      split_last = true;
+    } else if (!listed(P) || tc.count[P] > 0) {
+      ProfBracket prof(ax.profile, ax.prof_ev, ax.prof_flops, M, pairs);
+      tri_update(M, listed(P) ? tc.list[P] : nullptr, listed(P) ? tc.count[P] : 0, P, tb);
+    }
+  }
+  // (round 4: the threshold was 700 tile pairs — every panel of the 5-agent map's fronts. With the panel factorisation at 60 us the
+  //  period of a multi-panel front was no longer the chain but the cycle  look-ahead(P) -> rest rows(P) -> bulk(P) -> look-ahead(P+1),
+  //  all of it behind the ONE event of the chain-bound form: 140-160 us per panel. Events after every kernel: 284 -> 298 it/s, and
+  //  no loss on the one-panel fronts. COVGPU_CHAIN_PAIRS restores a threshold.)
+  bool chain_bound(int P) const {
+    const int nt = T - (2 * P + 4);
+    const double bulk_pairs = nt > 0 ? 0.5 * (double)nt * (nt + 1) * nbt : 0.0;
+    return bulk_pairs <= kChainPairs;
+  }
+  // M, R: the 256-column chain (k_panel.hip) of a panel that is not the last: one workgroup factors the whole diagonal block, rows h follow on
+  // the same stream by block substitution, rows r on theirs — three dependent launches per panel instead of six
+  void chain_panel(int P) {
+    const int t0 = 2 * P, w = width(t0), h0 = row_h0(t0), h1 = row_h1(t0);
+    const bool bound = chain_bound(P);
+    potrf(t0, w, M);
+    // rows below the first panel: second half of the caller's extend-add. IN FRONT of the record below — the rest rows' substitution on stream R
+    // starts from that record and inherits this wait
+    if (P == 0 && bt.pre_trsm != nullptr) ax.wait(M, bt.pre_trsm);
+    // Every event packet on this stream sits between two dependent kernels of the chain, a few microseconds each. While the bulk
+    // update is short (the period of the factorisation is the chain: small fronts, the tail of big ones) there is ONE event per
+    // panel, eH, recorded after the look-ahead update of the next diagonal block — the rest rows (which only need the factored
+    // panel), the next panel's rows on stream H and the bulk update all start from it, two small kernels later than they could.
+    // While the bulk update is long (the period is the bulk) they start as early as possible: an event after each kernel.
+    // (Merging rows h and the rest rows into one substitution launch on this stream was measured within noise in round 5: DESIGN.md.)
+    bool waitedA = false;
+    hipEvent_t rec1 = !bound ? e1[P] : nullptr;   // "panel P factored": the rest rows' substitution (stream R) starts from it
+    if (h1 > h0) {
+      // rows h carry the look-ahead update of panel P-1 (stream H, look_ahead_rows) | bulk(P-1)'s first launch.
+      // (round 6: the record behind the factorisation and these waits are ONE launch — CholAux::sync)
+      waitedA = P >= 1 && P + 1 < NP;
+      ax.sync(M, rec1, tag(P, 13), nullptr, 0, P > 0 ? eHp[P] : nullptr, waitedA ? eA[P - 1] : nullptr);
+      rec1 = nullptr;
+      // (round 5: the wait of the next-diagonal update below for bulk(P-1)'s first launch — 30-40 us of slack — rides along with the one above.
+      //  Measured: no difference (231.1 / 230.5 against 231.4 / 231.2 it/s) — a wait whose event completed long ago costs nothing; the 13-14 us
+      //  between two kernels of this stream come from the RECORD behind the first when its waiter is blocked on it at that moment: DESIGN.md 4.6)
+      trsm(t0, w, h0, h1, M, true, b);
+      trace(M, P, 2);   // rows h solved
+    }
+    if (rec1 != nullptr) ax.record(rec1, M, tag(P, 13));
+    // (round 6: "rows h solved" is published together with "next diagonal block updated", one launch behind that small update instead of one
+    //  launch in front of it and one behind: its waiters — the next panel's look-ahead on stream H — have ~50 us of slack)
+    const bool eh_now = !bound && P + 1 == NP;
+    if (eh_now) ax.record(eH[P], M, tag(P, 10));
+    // ---- M: look-ahead part of SYRK(P) on the next panel's 2x2 diagonal tiles
+    if (P + 1 < NP) {
+      const int u0 = t0 + 2;
+      if (P >= 1 && !waitedA) ax.wait(M, eA[P - 1]);          // bulk(P-1) was the previous writer of these tiles (its first launch)
+      diag(u0, width(u0), t0, kd(P), M);
+      trace(M, P, 3);   // next diagonal block updated
+    }
+    // (A bulk launched at the same instant as the next diagonal update takes every workgroup slot first and the chain waits
+    //  ~75 us for the first round of tiles to retire: the bulk starts after that small kernel in either regime.)
+    // (Both records are published by a launch of their own enqueued before any of their waiters: letting the next panel's factorisation publish
+    //  them deadlocks once two streams share a hardware queue — round 6, DESIGN.md.)
+    if (bound || eh_now) ax.record(bound ? eH[P] : eRc[P], M, tag(P, bound ? 10 : 16));
+    else ax.sync(M, eH[P], tag(P, 10), eRc[P], tag(P, 16));
+    if (T > h1) {
+      ax.wait(R, bound ? eH[P] : e1[P]);   // (measured, round 4: waiting for rows h instead — so that the chain's substitution runs alone — 299.9 -> 297.5 it/s)
+      trsm(t0, w, h1, T, R, false, b);
+      trace(R, P, 4);   // rest rows solved
+    }
+    ax.record(eC[P], R, tag(P, 12));
+  }
+  // B: bulk of SYRK(P), triangle starting two tile columns further (those belong to the look-ahead)
+  void bulk_update(int P) {
+    const int tb = 2 * P + 4, nt = T - tb;
+    bool recA = false;
+    // (the wait for the next diagonal update, measured again in round 4 with the 60 us panel: without it 298.6 -> 292.7 it/s)
+    ax.wait(B, eC[P], !chain_bound(P) ? eRc[P] : nullptr);
+    // arrow buffers: the live tiles of this panel's update as an explicit, XCD-balanced list (built once per problem).
+    // The implicit triangle grid x batch launched ~2.6k workgroups of which ~400 did work, with every batch's first
+    // supertile on XCD 0: 17 TFLOP/s.
+    const int cntC = (listed(P) && P < (int)tc.listC.size() && tc.listC[P] != nullptr) ? tc.countC[P] : 0;
+    if (nt > 0 && kd(P) > 0 && (!listed(P) || tc.count[P] > 0 || cntC > 0)) {
+      ProfBracket prof(ax.profile, ax.prof_ev, ax.prof_flops, B, update_flops(P, tb, KC));
+      form_hit(cntC > 0 && tc.count[P] > 0 ? KF_BULK_TWO_LAUNCHES : KF_BULK_ONE_LAUNCH);
+      if (cntC > 0) {   // the next-but-one panel's two tile columns first: what the chain waits for
+        tri_update(B, tc.listC[P], cntC, P, tb);
+        ax.record(eA[P], B, tag(P, 18)); recA = true;
+        trace(B, P, 8);   // first bulk launch done
+      }
+      if (!listed(P)) tri_update(B, nullptr, 0, P, tb);
+      else if (tc.count[P] > 0) tri_update(B, tc.list[P], tc.count[P], P, tb);
+    }
+    trace(B, P, 5);   // bulk update done
+    ax.record(eB[P], B, tag(P, 11));
+    if (!recA) ax.record(eA[P], B, tag(P, 18));
+  }
+  // M joins what the last panel left on the other streams
+  void join() {
+    ax.wait(M, !split_last && !tail_on_chain ? eB[Plast] : nullptr, Plast >= 1 ? eB[Plast - 1] : nullptr, !tail_on_chain ? eC[Plast] : nullptr,
+            !tail_on_chain ? eH[Plast] : nullptr);
+  }
+};
+
+// Right-looking blocked Cholesky of S with look-ahead on four streams (PanelRun), the forward substitution riding along, then the backward solve.
+void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int npad, hipStream_t st, CholAux& ax, int tstop, bool solve,
+                              DenseBatch bt) {
+  PanelRun run(S, b, Linv, flag, npad, st, ax, tstop, bt, true);
+  run.set_up_events();
+  run.build_tri_cache();
+  for (int P = 0; P < run.NP; ++P) {
+    run.look_ahead_rows(P);
+    if (P == run.Pstop) { run.stop_panel(P); break; }
+    ax.mark(st, P);   // M: the critical chain of panel P begins
+    if (run.Pstop < run.NP && P == run.Pstop - 1) { run.last_panel(P); break; }
+    run.chain_panel(P);
+    run.bulk_update(P);
+  }
+  run.join();
   if (!solve) return;
   // y = L^-1 b was formed along the way (potrf: y_p = L_pp^-1 b_p; every TRSM: b[rows] -= L[rows, p] y_p) and lives
   // in b[npad .. 2 npad). Remaining: L^T x = y.
-  dense_backward_solve(S, b, Linv, npad, st, T, T, bt);
+  dense_backward_solve(S, b, Linv, npad, st, run.T, run.T, bt);
 }
 
 // Distributed top fronts (shard policy 1; common.hpp: DistPanels). One stream, panel after panel: exchange -> factorisation of the panel's
@@ -1037,37 +1043,17 @@ void dense_cholesky_solve_raw(double* S, double* b, double* Linv, int* flag, int
 // their part of the sum) -> rank-256 update of the owned trailing tiles. The same kernels and the same K ranges as dense_cholesky_solve_raw.
 void dense_cholesky_dist(double* S, double* b, double* Linv, int* flag, int npad, hipStream_t st, CholAux& ax, int tstop, DenseBatch bt,
                          const DistPanels& d) {
-  const int nbt = bt.n > 0 ? bt.n : 1;
-  const int T = npad / kTile;
-  const size_t ld = (size_t)npad;
-  const size_t lds_gemm = (size_t)2 * kTile * LDT * sizeof(double);
-  static std::atomic<unsigned long long> attr_seen{0};
-  if (first_use_on_device(attr_seen)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_abt<MODE_SYRK_TRI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gemm);
-  ax.init();
-  const int NP = (T + 1) / 2;
-  const int Pstop = std::min((tstop >= 0 && tstop < T) ? tstop / 2 : NP, d.np);
-  auto kd = [&](int Pp) {
-    const int full = std::min(2, T - 2 * Pp) * kTile;
-    if (bt.own_max <= 0) return full;
-    return std::max(0, std::min(full, ((bt.own_max - 2 * Pp * kTile + 31) / 32) * 32));
-  };
+  PanelRun run(S, b, Linv, flag, npad, st, ax, tstop, bt, false);
+  const int T = run.T, Pstop = std::min(run.Pstop, d.np);
   for (int P = 0; P < Pstop; ++P) {
-    const int t0 = 2 * P, w = (T - t0 >= 2) ? 2 : 1, tb = t0 + 2;
+    const int t0 = 2 * P, w = run.width(t0), tb = t0 + 2;
     ax.mark(st, P);
     form_hit(KF_DIST_PANEL);
     if (d.exchange != nullptr) d.exchange(d.ctx, P);
-    const int nbp = bt.own_max > 0 ? std::max(0, std::min(8 * w, (bt.own_max - t0 * kTile + 15) / 16)) : -1;
-    if (bt.plist != nullptr) launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, st, bt.tab, nbp, bt.own_dims, bt.plist, bt.pbig_h[P], bt.psmall_h[P]);
-    else launch_potrf_panel(S, ld, t0, w, Linv, flag, b, npad, nbt, bt.sM, bt.sL, bt.sR, st, bt.tab, nbp);
-    if (T > tb) launch_trsm_sub(S, ld, t0, w, tb, T, Linv, d.lead ? b : nullptr, npad, nbt, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, st, true, bt.tab, nbp, bt.own_dims);
+    run.potrf(t0, w, st);
+    if (T > tb) run.trsm(t0, w, tb, T, st, true, d.lead ? b : nullptr);
     const int count = d.tri_cnt[P];
-    if (T > tb && kd(P) > 0 && count > 0 && d.tri[P] != nullptr) {
-      GemmArgs g{S, ld, t0 * kTile, kd(P), tb * kTile, tb * kTile, tb * kTile, T - tb, nullptr, nullptr, nullptr, bt.sM, bt.sL, bt.sR, bt.live, bt.tI, nullptr, bt.tab, bt.own_dims};
-      g.tri = d.tri[P];
-      form_hit(count <= kQuarterMax ? KF_GEMM_TRI_QUAD : KF_GEMM_TRI_FULL);
-      if (count <= kQuarterMax) hipLaunchKernelGGL((k_gemm_abt_q<MODE_SYRK_TRI, 64, 64>), dim3(count, 1, 4), dim3(256), (size_t)(64 + 64) * (KCQ + kLdsPad) * sizeof(double), st, g);
-      else hipLaunchKernelGGL(k_gemm_abt<MODE_SYRK_TRI>, dim3(count, 1), dim3(256), lds_gemm, st, g);
-    }
+    if (T > tb && run.kd(P) > 0 && count > 0 && d.tri[P] != nullptr) run.tri_update(st, d.tri[P], count, P, tb);
   }
 }
 

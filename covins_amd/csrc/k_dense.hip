@@ -4,12 +4,8 @@
 // Cholesky factorisation of the reduced camera system (CHOLMOD in the reference) and the two triangular
 // solves; and the vector arithmetic of Ceres' DoglegStrategy / LevenbergMarquardtStrategy.
 //
-// Factorisation = right-looking blocked Cholesky on the lower triangle, panel width kTile = 128:
-//   potrf_inv  one workgroup factors the 128x128 diagonal block in LDS and also forms L11^-1 there;
-//   gemm_abt<TRSM>   A21 <- A21 * L11^-T as an MFMA GEMM against the explicit inverse;
-//   gemm_abt<SYRK>   A22 <- A22 - A21 A21^T, one 128x128 tile per workgroup, v_mfma_f64_16x16x4_f64,
-//                    4 waves x (4x4) MFMA tiles, K staged through LDS in chunks of 32 with register prefetch.
-// Triangular solves reuse the stored L_pp^-1 blocks: one small launch per panel.
+// The factorisation itself lives elsewhere: the driver and the rank updates (k_gemm_abt) in k_chol.hip, the 256-column panel
+// factorisation, the block substitutions and the backward solve in k_panel.hip. This file keeps the vector kernels.
 #include <algorithm>
 
 #include "common.hpp"

@@ -348,7 +348,7 @@ void nd_tables(const NdHostPlan& hp, const int* pos_kf, int D, int rank, NdDev& 
         dev.dist_buf_elems = std::max(dev.dist_buf_elems, elems);
         dev.dist_solve_elems += elems;
         // owned trailing-update tiles (i, j), j <= i, relative to tile tb: tile row owner by nd_tile_owner on the front's compact rows (real interior
-        // tiles, then border tiles); XCD-balanced as k_chol.hip's build_list (whole 8x8 supertiles of a front to the shortest of 8 queues, interleaved)
+        // tiles, then border tiles); XCD-balanced as k_chol.hip's live_tile_list (whole 8x8 supertiles of a front to the shortest of 8 queues, interleaved)
         std::vector<int> q[8];
         for (int k = 0; k < L.n; ++k) {
           const int i = L.first + k, nIr = L.live_h[2 * k], nO = L.live_h[2 * k + 1], node = order[i];

@@ -21,7 +21,7 @@ int main() {
     for (int KD : {128, 256, 512}) {
       const int tb = kpan / kTile;  // triangle starts right of the panel columns
       const int Ts = (nt + 7) / 8, ns = Ts * (Ts + 1) / 2, nblk = ((ns + 7) / 8) * 8 * 64;
-      GemmArgs g{M, ld, 0, KD, tb * kTile, tb * kTile, tb * kTile, nt, nullptr, nullptr, nullptr, 0, 0, 0};
+      GemmArgs g{M, ld, 0, KD, tb * kTile, tb * kTile, tb * kTile, nt, 0, 0, 0};
       float best = 1e9f;
       for (int rep = 0; rep < 6; ++rep) {
         hipEventRecord(e0);
