@@ -151,7 +151,9 @@ __global__ __launch_bounds__(64 * kImuWaves) void k_preintegrate(DevProblem P) {
   __builtin_amdgcn_wave_barrier();
   double* Wm = P.pre_W + 225 * (size_t)f;
   if (lane == 0) {
-    bool ok = true;
+    // A factor of fewer than two samples carries no weight BY RULE: after one midpoint step C = V N V^T with the position rows of V equal to
+    // dt/2 times its velocity rows, so C is exactly singular and a pivot test would decide by rounding (+1e-24 passes, W gets entries of 1e12).
+    bool ok = ns >= 2;
     for (int c = 0; c < 15 && ok; ++c) {
       double dd = C[16 * c];
       for (int k = 0; k < c; ++k) dd -= C[15 * c + k] * C[15 * c + k];
@@ -165,7 +167,7 @@ __global__ __launch_bounds__(64 * kImuWaves) void k_preintegrate(DevProblem P) {
       }
     }
     for (int k = 0; k < 225; ++k) F[k] = 0.0;
-    if (!ok) atomicAdd(P.flag + 1, 1);  // factor carries no weight (covariance not positive definite, e.g. no samples): counted, reported in covgpu_result
+    if (!ok) atomicAdd(P.flag + 1, 1);  // factor carries no weight (fewer than two samples, or covariance not positive definite): counted, reported in covgpu_result
     if (ok)
       for (int c = 0; c < 15; ++c) {
         F[16 * c] = 1.0 / C[16 * c];

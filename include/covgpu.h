@@ -155,7 +155,9 @@ typedef struct covgpu_result {
                                 * non-positive-definite up to the largest damping. Like ceres::Solve (whose summary the reference
                                 * ignores, opt_be.cpp:567) the call still returns COVGPU_OK and the LAST ACCEPTED estimate; callers that
                                 * care check this field. COVGPU_ERR_NUMERIC is returned by covgpu_solve_reduced / covgpu_gn_step only. */
-  int32_t reserved;            /* IMU factors dropped because their preintegrated covariance was not positive definite (0 samples) */
+  int32_t reserved;            /* IMU factors that carry no weight (their whitening matrix is all zeros): every factor of FEWER THAN TWO samples,
+                                * by rule — one midpoint step leaves a covariance whose position rows are dt/2 times its velocity rows, exactly
+                                * singular, so no pivot test is asked — and every factor whose preintegrated covariance is not positive definite */
   double  initial_cost;
   double  final_cost;
   double  t_upload_s;          /* H2D incl. layout build                                    */

@@ -216,7 +216,10 @@ inline void preintegrate(const double* first6, const double* samples7, int n, co
 // whitening matrix of an IMU factor: W = chol(P)^-1 (lower). ||W r||^2 = r^T P^-1 r, i.e. the same cost,
 // gradient and Gauss-Newton matrix as the reference's chol(P^-1)^T — the two differ by an
 // orthogonal factor and the block carries no loss function (opt_be.cpp:416) — but formed without inverting P.
-inline bool imu_whitening(const Mat<15, 15>& P, Mat<15, 15>* W) {
+// A factor of fewer than two samples has no whitening by rule (false): one midpoint step leaves P = V N V^T with the
+// position rows of V equal to dt/2 times its velocity rows — exactly singular, and the Cholesky would decide by rounding.
+inline bool imu_whitening(const Mat<15, 15>& P, int num_samples, Mat<15, 15>* W) {
+  if (num_samples < 2) return false;
   Mat<15, 15> C = P;
   if (!chol_lower(C)) return false;
   *W = tri_lower_inverse(C);

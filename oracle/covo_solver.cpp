@@ -106,7 +106,7 @@ static void setup(Problem& P, const covgpu_problem* p, const covgpu_options* o, 
     const double* sbj = p->kf_speed_bias + 9 * j;
     const int s0 = p->imu_sample_ptr[f], s1 = p->imu_sample_ptr[f + 1];
     preintegrate(p->imu_first + 6 * f, p->imu_samples + 7 * s0, s1 - s0, v3(sbj + 3), v3(sbj + 6), nz, &P.pre[f]);
-    if (!imu_whitening(P.pre[f].P, &P.preW[f])) P.preW[f] = Mat<15, 15>();
+    if (!imu_whitening(P.pre[f].P, s1 - s0, &P.preW[f])) P.preW[f] = Mat<15, 15>();
   }
 }
 
@@ -904,7 +904,7 @@ void covo_imu_residual(const double* first6, const double* samples7, int n, cons
   const ImuNoise nz{noise5[0], noise5[1], noise5[2], noise5[3], noise5[4]};
   preintegrate(first6, samples7, n, v3(ba_lin), v3(bg_lin), nz, &pi);
   Mat<15, 15> W = Mat<15, 15>::Identity();
-  if (whiten) imu_whitening(pi.P, &W);
+  if (whiten && !imu_whitening(pi.P, n, &W)) W = Mat<15, 15>();
   Mat<15, 1> r; Mat<15, 30> J;
   imu_factor(pi, W, Pose(pose_i), sb_i, Pose(pose_j), sb_j, nz.g, &r, J450 ? &J : nullptr);
   for (int q = 0; q < 15; ++q) r15[q] = r[q];
