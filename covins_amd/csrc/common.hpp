@@ -76,6 +76,11 @@ struct DevProblem {
   double *pre_P;      // [I][225]
   double *pre_W;      // [I][225] whitening = chol(P)^-1 (lower)
   double *pre_bias;   // [I][6] linearisation ba, bg
+  // [I][450] whitened 15x30 Jacobian of every factor at (pose, sb), stored by k_imu_build and read by the J*v passes (k_tail_jvp, k_imu_jvp)
+  // instead of forming it again. Valid because a J*v pass is only ever enqueued behind enqueue_build of the SAME iteration
+  // (enqueue_tail_fused / enqueue_tail_legacy, !reuse branch) and the state changes only in k_tr_accept, behind both: the stored
+  // Jacobian is the one at the state the pass would linearise at. Rows of factors >= I are never read.
+  double *imu_Jw;
 
   // between factors
   int *edge_i, *edge_j;

@@ -61,11 +61,10 @@ __global__ __launch_bounds__(256) void k_tail_stats(DevProblem P) {
 
 // ---- T2: JA = |J va|^2, JB = |J vb|^2, JC = (J va).(J vb) over all residual blocks, at the current estimate. TWO == false: vb only (LM).
 //          Segments by blockIdx: [0, nb_obs) reprojection (grid-stride over the SoA stream) | [nb_obs, nb_obs + nb_imu) one wave per
-//          IMU factor | the rest: one thread per between factor.
+//          IMU factor, on the whitened Jacobian k_imu_build stored (no LDS, no second linearisation) | the rest: one thread per between factor.
 static_assert(kImuWaves == 4, "k_tail_jvp / k_tail_cost index their IMU and edge segments as 4 waves / 256 threads per workgroup");
 template <bool TWO, bool UNI>
 __global__ __launch_bounds__(64 * kImuWaves) void k_tail_jvp(DevProblem P, const double* __restrict__ va, const double* __restrict__ vb, int nb_obs, int nb_imu) {
-  __shared__ double sm[kImuWaves][kImuLds];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double ja = 0.0, jb = 0.0, jc = 0.0;
   int idx;
@@ -98,10 +97,8 @@ __global__ __launch_bounds__(64 * kImuWaves) void k_tail_jvp(DevProblem P, const
     const int bi = blockIdx.x - nb_obs;
     const int f = bi * kImuWaves + wave;
     const bool live = f < P.I;
-    double* sl = sm[wave];
-    imu_stage<true>(P, P.pose, P.sb, f, live, lane, sl);
     if (live && lane < 15) {
-      const double* Jw = sl + 450;
+      const double* Jw = P.imu_Jw + 450 * (size_t)f;   // stored by k_imu_build of this iteration, at this state (common.hpp: DevProblem::imu_Jw)
       const size_t oi = 15 * (size_t)P.imu_i[f], oj = 15 * (size_t)P.imu_j[f];
       double s2 = 0.0, t2 = 0.0;
       for (int c = 0; c < 15; ++c) {
@@ -140,22 +137,27 @@ __global__ __launch_bounds__(64 * kImuWaves) void k_tail_jvp(DevProblem P, const
   }
 }
 
-// ---- T5: cost of the candidate estimate, the same three segments
+// ---- T5: cost of the candidate estimate, the same three segments. The IMU and between-factor workgroups come FIRST in the grid (bid: the
+//          segment index the rest of the kernel works with): an IMU workgroup is one serial one-lane residual long, and behind 2048 observation
+//          workgroups it entered in the last round and the kernel ended one IMU stage after the observation sweep (27.5 -> 24.3 us on the
+//          5-agent map). The partial-sum slots depend on the segment index only, so the sums keep their bits.
 template <bool UNI>
 __global__ __launch_bounds__(64 * kImuWaves) void k_tail_cost(DevProblem P, int nb_obs, int nb_imu) {
   __shared__ double sm[kImuWaves][kImuLds];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nb_rest = (int)gridDim.x - nb_obs;
+  const int bid = (int)blockIdx.x < nb_rest ? nb_obs + (int)blockIdx.x : (int)blockIdx.x - nb_rest;
   double acc = 0.0;
   int idx;
-  if ((int)blockIdx.x < nb_obs) {
-    for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < P.O; o += nb_obs * blockDim.x) {
+  if (bid < nb_obs) {
+    for (int o = bid * blockDim.x + threadIdx.x; o < P.O; o += nb_obs * blockDim.x) {
       ObsLin e;
       eval_obs<false, UNI>(P, P.pose_c, P.lm_c, o, P.obs_kf[o], P.obs_lm[o], e);
       acc += e.cost;
     }
-    idx = blockIdx.x * 4 + wave;
-  } else if ((int)blockIdx.x < nb_obs + nb_imu) {
-    const int bi = blockIdx.x - nb_obs;
+    idx = bid * 4 + wave;
+  } else if (bid < nb_obs + nb_imu) {
+    const int bi = bid - nb_obs;
     const int f = bi * kImuWaves + wave;
     const bool live = f < P.I;
     double* sl = sm[wave];
@@ -163,7 +165,7 @@ __global__ __launch_bounds__(64 * kImuWaves) void k_tail_cost(DevProblem P, int 
     if (live && lane < 15) { const double rv = sl[1141 + lane]; acc = 0.5 * rv * rv; }
     idx = P.part_imu + bi * kImuWaves + wave;
   } else {
-    const int be = blockIdx.x - nb_obs - nb_imu;
+    const int be = bid - nb_obs - nb_imu;
     const int e = be * 256 + threadIdx.x;
     if (e < P.E) { double r[6]; acc = eval_edge<false>(P, P.pose_c, e, r, nullptr); }
     idx = P.part_edge + be * 4 + wave;

@@ -410,8 +410,14 @@ static int solve_impl_dev(covgpu_context* c, const covgpu_options* opt, covgpu_r
   c->chol.init();
   if (c->sharded) c->chol.gate_timeout_s = std::max(c->chol.gate_timeout_s, 120.0);   // (a gate may stand behind a collective that waits for a slower rank)
   RC(reset_state(c));
-  HIPCHK(hipMemsetAsync(P.flag + 1, 0, sizeof(int), c->st));
-  launch_preintegrate(P, c->st);  // R2: repropagate at the initial bias estimate (opt_be.cpp:396)
+  // R2: repropagate at the initial bias estimate (opt_be.cpp:396) — in every solve, on the side stream, behind reset_state (it reads the biases).
+  // Nothing else orders it: every reader of pre_* is either on that stream behind it (k_imu_build) or on the main stream behind the join ev_kf of
+  // the same first iteration (k_pose_finish, k_tail_jvp, k_tail_cost), so the first landmark linearisation and the pair pass run beside it and
+  // the synchronisation below does not wait for it. Its previous readers have finished: a solve returns behind its last iteration.
+  c->chol.record(c->chol.ev_zero, c->st, 1);
+  c->chol.wait(c->chol.mid, c->chol.ev_zero);
+  HIPCHK(hipMemsetAsync(P.flag + 1, 0, sizeof(int), c->chol.mid));
+  launch_preintegrate(P, c->chol.mid);
   double* h = c->h_tr;
   std::memset(h, 0, TR_COUNT * sizeof(double));
   h[TR_RADIUS] = o.initial_radius; h[TR_MU] = 1e-8; h[TR_LMDF] = 2.0; h[TR_FIRST] = 1.0; h[TR_OK] = 1.0;
@@ -440,6 +446,7 @@ static int solve_impl_dev(covgpu_context* c, const covgpu_options* opt, covgpu_r
     ++it;
     if (term == 1 || term == 4) break;
   }
+  if (it == 0) HIPCHK(hipStreamSynchronize(c->chol.mid));   // (no iteration ran: nothing has joined the preintegration yet)
   {  // IMU factors whose preintegrated covariance was not positive definite (e.g. zero samples) carry no weight: reported
     int dropped = 0;
     HIPCHK(hipMemcpy(&dropped, P.flag + 1, sizeof(int), hipMemcpyDeviceToHost));

@@ -278,6 +278,7 @@ static int up_imu(covgpu_context* c, Upload& u) {
   RC(dev_alloc(c, &P.pre_delta, (size_t)11 * P.I)); RC(dev_alloc(c, &P.pre_J, (size_t)225 * P.I));
   RC(dev_alloc(c, &P.pre_P, (size_t)225 * P.I)); RC(dev_alloc(c, &P.pre_W, (size_t)225 * P.I));
   RC(dev_alloc(c, &P.pre_bias, (size_t)6 * P.I));
+  RC(dev_alloc(c, &P.imu_Jw, (size_t)450 * P.I));   // (3.6 KB per factor: 7.9 MB on the 5-agent map, 72 MB on the 12-agent map)
   return COVGPU_OK;
 }
 
