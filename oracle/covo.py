@@ -57,6 +57,9 @@ def lib() -> C.CDLL:
         L.covo_schur_sparse.argtypes = [OP, PP, C.c_int, C.c_double, ip, ip, dp, dp, dp]
         L.covo_landmark_hessians.argtypes = [OP, PP, dp]
         L.covo_relpose.argtypes = [C.c_int, dp, dp, dp, dp, dp, dp, dp, C.c_int, dp, C.c_int, C.c_double, C.c_int, dp, C.POINTER(C.c_ubyte)]
+        L.covo_relpose_traced.argtypes = L.covo_relpose.argtypes + [dp, C.POINTER(C.c_int), dp]
+        L.covo_relpose_cost.argtypes = [dp, C.c_int, dp, dp, dp, dp, dp, dp, dp, C.c_int, dp, C.c_int, C.POINTER(C.c_ubyte)]
+        L.covo_relpose_cost.restype = C.c_double
         L.covo_relpose_residual.argtypes = [dp, dp, dp, dp, dp, C.c_double, C.c_double, dp, C.c_int, dp, C.c_int, dp, dp]
         L.covo_relpose_residual.restype = None
     return _LIB
@@ -236,15 +239,35 @@ def pgo_reanchor(pose_old, pose_new, velocity, ref_kf, lm_pos):
     return vel, lm
 
 
-def relpose(pB, pA, kpA, kpB, sigA, sigB, camA, distA, camB, distB, T_ab, th_outlier=2.0, min_inliers=12):
-    """Optimization::OptimizeRelativePose for ONE keyframe pair (optimization_be.cpp:620-831): returns (inliers, T_ab, outlier flags)."""
+# covo_relpose_traced (oracle/covo_relpose.cpp, RelTrace): the columns of a trace row and the values of its `kind` and `step` columns
+RELPOSE_TRACE_COLS = ("solve", "kind", "step", "rho", "radius", "mu", "gn_norm", "accepted", "cost", "cost_new")
+RELPOSE_KINDS = ("gauss_newton", "cauchy", "interp_c_neg", "interp_c_pos", "solve_failed", "model_not_positive", "stopped_gmax", "stopped_converged")
+
+
+def relpose(pB, pA, kpA, kpB, sigA, sigB, camA, distA, camB, distB, T_ab, th_outlier=2.0, min_inliers=12, trace=False):
+    """Optimization::OptimizeRelativePose for ONE keyframe pair (optimization_be.cpp:620-831): returns (inliers, T_ab, outlier flags).
+    trace=True: also a dict with `rows` (one per loop iteration of the two dogleg solves, columns RELPOSE_TRACE_COLS, `kind` and `step`
+    indexing RELPOSE_KINDS) and `norms` [n,2] (the residual norms that the outlier pass compared with th_outlier)."""
     f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
     pB, pA, kpA, kpB, sigA, sigB, camA, camB = map(f, (pB, pA, kpA, kpB, sigA, sigB, camA, camB))
     T = np.array(T_ab, dtype=np.float64)
     out = np.zeros(len(sigA), np.uint8)
-    n = lib().covo_relpose(len(sigA), _d(pB), _d(pA), _d(kpA), _d(kpB), _d(sigA), _d(sigB), _d(camA), int(distA), _d(camB), int(distB),
-                           float(th_outlier), int(min_inliers), _d(T), out.ctypes.data_as(C.POINTER(C.c_ubyte)))
-    return int(n), T, out.astype(bool)
+    args = (len(sigA), _d(pB), _d(pA), _d(kpA), _d(kpB), _d(sigA), _d(sigB), _d(camA), int(distA), _d(camB), int(distB),
+            float(th_outlier), int(min_inliers), _d(T), out.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    if not trace:
+        return int(lib().covo_relpose(*args)), T, out.astype(bool)
+    rows, n_rows, norms = np.full((10, len(RELPOSE_TRACE_COLS)), np.nan), C.c_int(0), np.zeros((max(len(sigA), 1), 2))
+    n = lib().covo_relpose_traced(*args, _d(rows), C.byref(n_rows), _d(norms))
+    return int(n), T, out.astype(bool), dict(rows=rows[:n_rows.value].copy(), norms=norms[:len(sigA)].copy())
+
+
+def relpose_cost(T_ab, pB, pA, kpA, kpB, sigA, sigB, camA, distA, camB, distB, outlier=None):
+    """The objective of relpose at the pose T_ab (its quaternion normalised): sum of rho/2 over the correspondences not flagged in `outlier`."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    pB, pA, kpA, kpB, sigA, sigB, camA, camB = map(f, (pB, pA, kpA, kpB, sigA, sigB, camA, camB))
+    o = None if outlier is None else np.ascontiguousarray(outlier, dtype=np.uint8)
+    return float(lib().covo_relpose_cost(_d(f(T_ab)), len(sigA), _d(pB), _d(pA), _d(kpA), _d(kpB), _d(sigA), _d(sigB), _d(camA), int(distA),
+                                         _d(camB), int(distB), None if o is None else o.ctypes.data_as(C.POINTER(C.c_ubyte))))
 
 
 def relpose_residual(T_ab, pB, pA, kpA, kpB, sigA, sigB, camA, distA, camB, distB, jac=True):

@@ -11,6 +11,7 @@
 // (:791-811); fewer than 12 left -> return 0 with T12 untouched (:813-815); else 5 more iterations (:817-822).
 #include <algorithm>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "../include/covgpu.h"
@@ -86,8 +87,31 @@ static bool chol6_solve(Mat<6, 6> A, Mat<6, 1> b, Mat<6, 1>* x) {
 
 static inline double clampd6(double h) { return std::min(std::max(std::sqrt(std::max(h, 0.0)), 1e-6), 1e32); }
 
+// What the trust-region loop decided, for the tests that must know which branches an input reaches (covo_relpose_traced): one row of
+// COVO_RELPOSE_TRACE_COLS doubles per loop iteration of each rel_dogleg call:
+//   [0] solve    0: before the outlier pass, 1: after it
+//   [1] kind     COVO_RELPOSE_* below: the step's kind, or why the iteration ended without one
+//   [2] step     the step taken (GN, CAUCHY, INTERP_NEG, INTERP_POS), also where kind says MODEL or CONVERGED; -1: no step
+//   [3] rho  [4] radius before the step  [5] mu of the solve  [6] gn_norm  [7] accepted (0/1)
+//   [8] cost  [9] cost_new                (the convergence test is |cost - cost_new| <= 1e-6 cost)
+// Entries an iteration did not compute are NaN. A null RelTrace records nothing: the loop is the same one.
+enum { COVO_RELPOSE_GN = 0, COVO_RELPOSE_CAUCHY = 1, COVO_RELPOSE_INTERP_NEG = 2 /* c <= 0 */, COVO_RELPOSE_INTERP_POS = 3 /* c > 0 */,
+       COVO_RELPOSE_SOLVE_FAILED = 4, COVO_RELPOSE_MODEL = 5 /* model not positive */, COVO_RELPOSE_GMAX = 6, COVO_RELPOSE_CONVERGED = 7 };
+enum { COVO_RELPOSE_TRACE_COLS = 10, COVO_RELPOSE_TRACE_ROWS = 10 };
+struct RelTrace {
+  double* rows;   // [COVO_RELPOSE_TRACE_ROWS][COVO_RELPOSE_TRACE_COLS]
+  int n_rows, solve;
+  double* row(int kind) {
+    double* r = rows + COVO_RELPOSE_TRACE_COLS * n_rows++;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    r[0] = solve; r[1] = kind; r[2] = -1; r[7] = 0;
+    r[3] = r[4] = r[5] = r[6] = r[8] = r[9] = nan;
+    return r;
+  }
+};
+
 // traditional dogleg on the 6-dof problem, Ceres 1.x defaults, `iters` iterations incl. rejected ones
-static void rel_dogleg(const RelProblem& P, Pose& T, int iters) {
+static void rel_dogleg(const RelProblem& P, Pose& T, int iters, RelTrace* tr) {
   double radius = 1e4, mu = 1e-8;
   Mat<6, 6> H; Mat<6, 1> g, gn, gh; double cost = 0, alpha = 0, D[6];
   bool reuse = false;
@@ -106,7 +130,7 @@ static void rel_dogleg(const RelProblem& P, Pose& T, int iters) {
   linearise();
   for (int it = 0; it < iters; ++it) {
     double gmax = 0; for (int k = 0; k < 6; ++k) gmax = std::max(gmax, std::fabs(g[k]));
-    if (gmax <= 1e-10) break;
+    if (gmax <= 1e-10) { if (tr) { double* w = tr->row(COVO_RELPOSE_GMAX); w[4] = radius; w[5] = mu; } break; }
     bool ok = true;
     if (!reuse) {
       double gg = 0; Mat<6, 1> v;
@@ -122,32 +146,43 @@ static void rel_dogleg(const RelProblem& P, Pose& T, int iters) {
         mu *= 10.0;
       }
     }
-    Mat<6, 1> step; double step_norm = 0, model = 0;
+    Mat<6, 1> step; double step_norm = 0, model = 0, gn_norm_tr = 0;
+    int kind = COVO_RELPOSE_SOLVE_FAILED;
     if (ok) {
       double gn2 = 0, g2 = 0, gdot = 0;
       for (int k = 0; k < 6; ++k) { const double a = D[k] * gn[k]; gn2 += a * a; g2 += gh[k] * gh[k]; gdot += gh[k] * a; }
       const double gn_norm = std::sqrt(gn2), g_norm = std::sqrt(g2);
       double cg, cn;
-      if (gn_norm <= radius) { cg = 0; cn = 1; step_norm = gn_norm; }
-      else if (g_norm * alpha >= radius) { cg = -radius / g_norm; cn = 0; step_norm = radius; }
+      gn_norm_tr = gn_norm;
+      if (gn_norm <= radius) { cg = 0; cn = 1; step_norm = gn_norm; kind = COVO_RELPOSE_GN; }
+      else if (g_norm * alpha >= radius) { cg = -radius / g_norm; cn = 0; step_norm = radius; kind = COVO_RELPOSE_CAUCHY; }
       else {
         const double b_dot_a = -alpha * gdot, a_sq = alpha * alpha * g2;
         const double bma = gn2 - 2 * b_dot_a + a_sq, c = b_dot_a - a_sq;
         const double dd = std::sqrt(c * c + bma * (radius * radius - a_sq));
         const double beta = (c <= 0) ? (dd - c) / bma : (radius * radius - a_sq) / (dd + c);
         cg = -alpha * (1 - beta); cn = beta; step_norm = radius;
+        kind = (c <= 0) ? COVO_RELPOSE_INTERP_NEG : COVO_RELPOSE_INTERP_POS;
       }
       for (int k = 0; k < 6; ++k) step[k] = cg * gh[k] / D[k] + cn * gn[k];
       const Mat<6, 1> Hs = H * step;
       double gs = 0, sHs = 0; for (int k = 0; k < 6; ++k) { gs += g[k] * step[k]; sHs += step[k] * Hs[k]; }
       model = -(gs + 0.5 * sHs);
     }
+    double* w = nullptr;
+    if (tr) {
+      w = tr->row(ok && !(model > 0.0) ? COVO_RELPOSE_MODEL : kind);
+      w[4] = radius; w[5] = mu; w[8] = cost;
+      if (ok) { w[2] = kind; w[6] = gn_norm_tr; }
+    }
     if (!ok || !(model > 0.0)) { mu *= 10.0; reuse = false; if (mu >= 1.0 && !ok) break; continue; }
     const Pose Tn = pose_plus(T, step.a);
     const double cost_new = rel_cost(P, Tn);
     const double rho = (cost - cost_new) / model;
+    if (w) { w[3] = rho; w[9] = cost_new; }
     if (rho > 1e-3) {
       const bool conv = std::fabs(cost - cost_new) <= 1e-6 * cost;
+      if (w) { w[7] = 1; if (conv) w[1] = COVO_RELPOSE_CONVERGED; }
       T = Tn;
       if (rho < 0.25) radius *= 0.5;
       if (rho > 0.75) radius = std::max(radius, 3.0 * step_norm);
@@ -163,24 +198,51 @@ static void rel_dogleg(const RelProblem& P, Pose& T, int iters) {
 
 using namespace covo;
 
-// One problem. Returns the number of inliers (0: fewer than `min_inliers` survived, T_ab left untouched).
-extern "C" int covo_relpose(int n, const double* pB, const double* pA, const double* kpA, const double* kpB, const double* sigA, const double* sigB,
-                            const double* camA, int distA, const double* camB, int distB, double th_outlier, int min_inliers, double* T_ab,
-                            unsigned char* outlier) {
+// One problem. Returns the number of inliers (0: fewer than `min_inliers` survived, T_ab left untouched). With `rows` (room for
+// COVO_RELPOSE_TRACE_ROWS rows of COVO_RELPOSE_TRACE_COLS, see RelTrace) the decisions of both solves are recorded and *n_rows is their
+// number; with `norms` [n][2] the two residual norms of every correspondence that the outlier pass compared with th_outlier.
+extern "C" int covo_relpose_traced(int n, const double* pB, const double* pA, const double* kpA, const double* kpB, const double* sigA,
+                                   const double* sigB, const double* camA, int distA, const double* camB, int distB, double th_outlier,
+                                   int min_inliers, double* T_ab, unsigned char* outlier, double* rows, int* n_rows, double* norms) {
   RelProblem P{n, pB, pA, kpA, kpB, sigA, sigB, camA, camB, distA, distB, std::vector<char>(n, 0)};
+  RelTrace trace{rows, 0, 0}, *tr = rows ? &trace : nullptr;
   Pose T(T_ab);
   T.q = T.q.normalized();
-  rel_dogleg(P, T, 5);
+  rel_dogleg(P, T, 5, tr);
+  if (n_rows) *n_rows = trace.n_rows;
   int bad = 0;
   for (int i = 0; i < n; ++i) {
     double r[4], c; rel_eval(P, T, i, r, nullptr, &c);
-    const bool out = std::sqrt(r[0] * r[0] + r[1] * r[1]) > th_outlier || std::sqrt(r[2] * r[2] + r[3] * r[3]) > th_outlier;
+    const double nA = std::sqrt(r[0] * r[0] + r[1] * r[1]), nB = std::sqrt(r[2] * r[2] + r[3] * r[3]);
+    if (norms) { norms[2 * i] = nA; norms[2 * i + 1] = nB; }
+    const bool out = nA > th_outlier || nB > th_outlier;
     outlier[i] = out; P.off[i] = out; bad += out;
   }
   if (n - bad < min_inliers) return 0;
-  rel_dogleg(P, T, 5);
+  trace.solve = 1;
+  rel_dogleg(P, T, 5, tr);
+  if (n_rows) *n_rows = trace.n_rows;
   T.store(T_ab);
   return n - bad;
+}
+
+extern "C" int covo_relpose(int n, const double* pB, const double* pA, const double* kpA, const double* kpB, const double* sigA, const double* sigB,
+                            const double* camA, int distA, const double* camB, int distB, double th_outlier, int min_inliers, double* T_ab,
+                            unsigned char* outlier) {
+  return covo_relpose_traced(n, pB, pA, kpA, kpB, sigA, sigB, camA, distA, camB, distB, th_outlier, min_inliers, T_ab, outlier, nullptr, nullptr,
+                             nullptr);
+}
+
+// The objective of the solve at a given pose (its quaternion normalised as covo_relpose does): the sum of the loss-corrected cost rho/2 over
+// the correspondences that `outlier` (null: none) does not flag.
+extern "C" double covo_relpose_cost(const double* T_ab, int n, const double* pB, const double* pA, const double* kpA, const double* kpB,
+                                    const double* sigA, const double* sigB, const double* camA, int distA, const double* camB, int distB,
+                                    const unsigned char* outlier) {
+  RelProblem P{n, pB, pA, kpA, kpB, sigA, sigB, camA, camB, distA, distB, std::vector<char>(n, 0)};
+  if (outlier) for (int i = 0; i < n; ++i) P.off[i] = outlier[i] != 0;
+  Pose T(T_ab);
+  T.q = T.q.normalized();
+  return rel_cost(P, T);
 }
 
 // raw residual pair + Jacobian (finite-difference test of the oracle itself)
