@@ -294,6 +294,7 @@ class Context:
         o = default_options(device=device)
         self._check(lib().covgpu_create(C.byref(o), C.byref(self._h)))
         self._keep = None
+        self._keep_pgo = False
 
     def _check(self, rc: int):
         if rc != 0:
@@ -341,6 +342,7 @@ class Context:
     # ---- split form: inputs resident in HBM before the timed region
     def upload(self, prob: FlatProblem, opt: Options, pgo: bool = False):
         self._keep = prob
+        self._keep_pgo = bool(pgo)
         s = prob.as_struct()
         fn = lib().covgpu_upload_pgo if pgo else lib().covgpu_upload
         self._check(fn(self._h, C.byref(opt), C.byref(s)))
@@ -942,6 +944,38 @@ class Context:
         s = prob.as_struct()
         self._check(lib().covgpu_gn_step(self._h, C.byref(opt), C.byref(s), float(mu), dptr(dx), dptr(dl), dptr(c)))
         return dx, dl, float(c[0])
+
+    def solve_resident_traced(self, opt: Options, capacity: int = 64):
+        """solve_resident that also returns the trust-region state at the end of every iteration, retry rounds included: (Result, trace
+        [rounds, capi.TR_COUNT], columns capi.TR)."""
+        r = Result(); tr = np.zeros((capacity, capi.TR_COUNT)); n = C.c_int32(0)
+        self._check(lib().covgpu_solve_resident_traced(self._h, C.byref(opt), C.byref(r), dptr(tr), capacity, C.byref(n)))
+        assert n.value <= capacity, (n.value, capacity)
+        return r, tr[:n.value].copy()
+
+    def fetch_tail_state(self, opt: Options) -> dict:
+        """What the last iteration of the last solve of the resident problem left on the device: grad, hdiag, gn, vtmp [N], pose_c, sb_c, lm_c."""
+        p = self._keep
+        vi = not (self._keep_pgo or opt.visual_only)
+        N = (15 if vi else 6) * p.K + (0 if self._keep_pgo else 3 * p.L)
+        out = dict(grad=np.zeros(N), hdiag=np.zeros(N), gn=np.zeros(N), vtmp=np.zeros(N), pose_c=np.zeros((p.K, 7)), sb_c=np.zeros((p.K, 9)),
+                   lm_c=np.zeros((0 if self._keep_pgo else p.L, 3)))
+        self._check(lib().covgpu_fetch_tail_state(self._h, *(dptr(out[k]) for k in ("grad", "hdiag", "gn", "vtmp", "pose_c", "sb_c", "lm_c"))))
+        return out
+
+    def tail_logic_probe(self, opt: Options, kernel: int, tr, scal, flag0: int = 0, stage: int = 1, with_logic: bool = True, fresh: bool = True,
+                         part=None):
+        """One launch of the step logic on prescribed inputs (covgpu_tail_logic_probe; kernel = capi.TAIL_LOGIC ...): (tr, scal) afterwards."""
+        tr = np.array(tr, dtype=np.float64); scal = np.array(scal, dtype=np.float64)
+        assert tr.shape == (capi.TR_COUNT,) and scal.shape == (capi.SC_COUNT,)
+        part_n = 0
+        if part is not None:
+            part = np.ascontiguousarray(part, dtype=np.float64)
+            assert part.ndim == 2 and part.shape[0] == capi.SC_COUNT
+            part_n = part.shape[1]
+        self._check(lib().covgpu_tail_logic_probe(self._h, C.byref(opt), int(kernel), int(stage), int(bool(with_logic)), int(bool(fresh)), int(flag0),
+                                                  dptr(tr), dptr(scal), dptr(part), part_n))
+        return tr, scal
 
     def solve_reduced(self, S, b):
         S = np.ascontiguousarray(S, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)

@@ -18,6 +18,15 @@ COVGPU_DOGLEG, COVGPU_LM = 0, 1
 COVGPU_DIST_RADTAN, COVGPU_DIST_EQUIDISTANT = 0, 1
 COVGPU_CAM_PINHOLE, COVGPU_CAM_UNIFIED = 0, 1   # camera projection models (values of the reference's eCamModel)
 COVGPU_MAX_TRACE = 64
+# the trust-region state of the device-side step logic (csrc/common.hpp: TR_*) and its reduced scalars (SC_*), as the test entry points
+# covgpu_solve_resident_traced / covgpu_tail_logic_probe hand them over
+TR_NAMES = ("RADIUS", "MU", "LMDF", "COST", "ALPHA", "GG", "GN2", "GDOT", "DNORM", "CG", "CN", "MODEL", "SN", "RHO", "COSTNEW", "OK", "VALID", "ACC",
+            "TERM", "FNCONV", "RETRY", "FIRST", "INITCOST", "REUSE", "JA", "JB", "JC", "VV", "VG", "NN", "XN2")
+SC_NAMES = ("COST", "JV2", "GG", "GN2", "GDOT", "GMAX", "GS", "SN2", "XN2", "VV", "VG", "NN", "JA", "JB", "JC")
+TR_COUNT, SC_COUNT = 32, 16
+TR = {k: i for i, k in enumerate(TR_NAMES)}
+SC = {k: i for i, k in enumerate(SC_NAMES)}
+TAIL_LOGIC, TAIL_FINISH, TR_AFTER_SOLVE, TR_AFTER_MODEL, TR_DECIDE = 0, 1, 2, 3, 4   # covgpu_tail_logic_probe: kernel
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -382,6 +391,9 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("pgo_partition", [C.c_int32, C.c_int32, _ip, _ip, _ip], C.c_int32)
         d("lm_group", [C.c_int64, C.c_int32], C.c_int32)
         d("gn_step", [C.c_void_p, OP, PP, C.c_double, _dp, _dp, _dp])
+        d("solve_resident_traced", [C.c_void_p, OP, RP, _dp, C.c_int32, _ip])
+        d("fetch_tail_state", [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp, _dp])
+        d("tail_logic_probe", [C.c_void_p, OP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int32])
         d("relpose_batch", [C.c_void_p, C.POINTER(RelposeBatch), C.c_double, C.c_int32])
         d("default_ransac_opts", [C.POINTER(RansacOpts)], None)
         d("abspose_ransac_batch", [C.c_void_p, C.POINTER(AbsposeBatch), C.POINTER(RansacOpts)])

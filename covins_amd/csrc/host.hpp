@@ -65,6 +65,7 @@ struct covgpu_context {
   double* h_box = nullptr;   // pinned + mapped [TR_COUNT + 1]: the last kernel of an iteration posts P.tr and a sequence number here (k_tr_accept), the host polls it
   double* d_box = nullptr;   // its device address (nullptr: not available — D2H copy + stream synchronisation)
   double box_seq = 0.0;
+  double* trace = nullptr; int trace_cap = 0, trace_n = 0;   // covgpu_solve_resident_traced: h_tr after every end_iteration (nullptr in the product path)
   int profiling = 0;
   covgpu_profile_t prof;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -165,6 +165,62 @@ static int solve_reduced_impl(covgpu_context* c, int32_t n, const double* S, con
   return COVGPU_OK;
 }
 
+// ---- the trust-region tail (k_tail.hip, k_dense.hip: k_tr_*)
+static int fetch_tail_state_impl(covgpu_context* c, double* grad, double* hdiag, double* gn, double* vtmp, double* pose_c, double* sb_c, double* lm_c) {
+  if (!c->have) { g_err = "covgpu_fetch_tail_state: no problem uploaded"; return COVGPU_ERR_INVALID_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  const DevProblem& P = c->P;
+  DeviceScratch U(c->st);   // (fetch only: skips the outputs the caller did not ask for)
+  HIPCHK(U.fetch(grad, (const double*)P.grad, (size_t)P.N)); HIPCHK(U.fetch(hdiag, (const double*)P.hdiag, (size_t)P.N));
+  HIPCHK(U.fetch(gn, (const double*)P.gn, (size_t)P.N)); HIPCHK(U.fetch(vtmp, (const double*)P.vtmp, (size_t)P.N));
+  HIPCHK(U.fetch(pose_c, (const double*)P.pose_c, (size_t)7 * P.K));
+  if (P.vi) HIPCHK(U.fetch(sb_c, (const double*)P.sb_c, (size_t)9 * P.K));
+  HIPCHK(U.fetch(lm_c, (const double*)P.lm_c, (size_t)3 * P.L));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return COVGPU_OK;
+}
+
+// the step logic on a stub problem: nothing but the trust-region state, the scalars, the flags and the partial sums exist (K = L = 0:
+// k_tr_accept behind k_tr_decide copies nothing)
+static int tail_logic_probe_impl(covgpu_context* c, const covgpu_options* o, int kernel, int stage, int with_logic, int fresh, int flag0, double* tr,
+                                 double* scal, const double* part, int part_n) {
+  auto bad = [](const char* m) -> int { g_err = std::string("covgpu_tail_logic_probe: ") + m; return COVGPU_ERR_INVALID_ARG; };
+  if (!o || !tr || !scal) return bad("NULL argument");
+  if (kernel < 0 || kernel > 4) return bad("kernel must be 0 .. 4");
+  if ((kernel == 0 || kernel == 1) && stage != 1 && stage != 2) return bad("stage must be 1 or 2");
+  if (kernel == 1 && (!part || part_n < 1)) return bad("k_tail_finish needs part[COVGPU_SC_COUNT][part_n], part_n >= 1");
+  HIPCHK(hipSetDevice(c->device));
+  DevProblem P;
+  std::memset(&P, 0, sizeof(P));
+  const int flags[4] = {flag0, 0, 0, 0};
+  DeviceScratch U(c->st);
+  HIPCHK(U.upload(&P.tr, tr, (size_t)TR_COUNT)); HIPCHK(U.upload(&P.scal, scal, (size_t)SC_COUNT)); HIPCHK(U.upload(&P.flag, flags, 4));
+  P.scal_r = P.scal; P.flag_r = P.flag;
+  if (kernel == 1) { HIPCHK(U.upload(&P.part, part, (size_t)SC_COUNT * part_n)); P.part_n = part_n; }
+  const TrConsts tc{o->strategy, o->max_radius, o->min_relative_decrease, o->function_tolerance, o->parameter_tolerance, o->gradient_tolerance};
+  switch (kernel) {
+    case 0: launch_tail_logic(P, tc, stage, fresh, c->st); break;
+    case 1: launch_tail_finish(P, tc, stage, o->strategy == COVGPU_DOGLEG, with_logic != 0, fresh, c->st); break;
+    case 2: launch_tr_after_solve(P, tc, fresh, c->st); break;
+    case 3: launch_tr_after_model(P, tc, c->st); break;
+    default: launch_tr_decide(P, tc, c->st); break;
+  }
+  HIPCHK(U.fetch(tr, (const double*)P.tr, (size_t)TR_COUNT)); HIPCHK(U.fetch(scal, (const double*)P.scal, (size_t)SC_COUNT));
+  HIPCHK(hipStreamSynchronize(c->st));
+  HIPCHK(hipGetLastError());
+  return COVGPU_OK;
+}
+
+extern "C" int covgpu_fetch_tail_state(covgpu_context* c, double* grad, double* hdiag, double* gn, double* vtmp, double* pose_c, double* sb_c, double* lm_c) {
+  if (!c) { g_err = "covgpu_fetch_tail_state: NULL context"; return COVGPU_ERR_INVALID_ARG; }
+  return guarded([&] { return fetch_tail_state_impl(c, grad, hdiag, gn, vtmp, pose_c, sb_c, lm_c); });
+}
+extern "C" int covgpu_tail_logic_probe(covgpu_context* c, const covgpu_options* opt, int32_t kernel, int32_t stage, int32_t with_logic, int32_t fresh,
+                                       int32_t flag0, double* tr, double* scal, const double* part, int32_t part_n) {
+  if (!c) { g_err = "covgpu_tail_logic_probe: NULL context"; return COVGPU_ERR_INVALID_ARG; }
+  return guarded([&] { return tail_logic_probe_impl(c, opt, kernel, stage, with_logic, fresh, flag0, tr, scal, part, part_n); });
+}
+
 extern "C" int covgpu_reprojection_residual_norms(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, double* norms) {
   return guarded([&] { return residual_norms_impl(c, opt, p, norms); });
 }

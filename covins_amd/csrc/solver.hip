@@ -409,6 +409,7 @@ static int solve_impl_dev(covgpu_context* c, const covgpu_options* opt, covgpu_r
   const auto t_begin = std::chrono::steady_clock::now();
   c->chol.init();
   if (c->sharded) c->chol.gate_timeout_s = std::max(c->chol.gate_timeout_s, 120.0);   // (a gate may stand behind a collective that waits for a slower rank)
+  c->trace_n = 0;
   RC(reset_state(c));
   // R2: repropagate at the initial bias estimate (opt_be.cpp:396) — in every solve, on the side stream, behind reset_state (it reads the biases).
   // Nothing else orders it: every reader of pre_* is either on that stream behind it (k_imu_build) or on the main stream behind the join ev_kf of
@@ -433,6 +434,10 @@ static int solve_impl_dev(covgpu_context* c, const covgpu_options* opt, covgpu_r
     const double damp = (o.strategy == COVGPU_LM) ? 1.0 / h[TR_RADIUS] : h[TR_MU];   // (of the system a rebuild forms)
     const bool use_box = fused_tail ? enqueue_tail_fused(c, tc, reuse, damp) : enqueue_tail_legacy(c, tc, reuse, damp);
     RC(end_iteration(c, use_box));
+    if (c->trace != nullptr) {   // (test hook: covgpu_solve_resident_traced)
+      if (c->trace_n < c->trace_cap) std::memcpy(c->trace + (size_t)TR_COUNT * c->trace_n, h, TR_COUNT * sizeof(double));
+      ++c->trace_n;
+    }
     collect_profile(c, !reuse, !reuse);
     if (!got_initial) { res->initial_cost = h[TR_INITCOST]; got_initial = true; }
     if (h[TR_RETRY] != 0.0) { reuse = false; continue; }  // factorisation failed: same iteration again with the raised damping
@@ -479,6 +484,16 @@ int solve_any(covgpu_context* c, const covgpu_options* opt, covgpu_result* out) 
   return rc;
 }
 extern "C" int covgpu_solve_resident(covgpu_context* c, const covgpu_options* opt, covgpu_result* out) { return guarded([&] { return solve_any(c, opt, out); }); }
+static_assert(COVGPU_TR_COUNT == TR_COUNT && COVGPU_SC_COUNT == SC_COUNT, "include/covgpu.h states the sizes of the test entry points' buffers");
+extern "C" int covgpu_solve_resident_traced(covgpu_context* c, const covgpu_options* opt, covgpu_result* out, double* trace, int32_t capacity, int32_t* count) {
+  if (!c) { g_err = "covgpu_solve_resident_traced: NULL context"; return COVGPU_ERR_INVALID_ARG; }
+  if (!opt || !out || !trace || !count || capacity < 0) { g_err = "covgpu_solve_resident_traced: NULL argument"; return COVGPU_ERR_INVALID_ARG; }
+  c->trace = trace; c->trace_cap = capacity;
+  const int rc = guarded([&] { return solve_any(c, opt, out); });
+  *count = c->trace_n;
+  c->trace = nullptr; c->trace_cap = 0;
+  return rc;
+}
 
 static int full_solve(covgpu_context* c, const covgpu_options* opt, covgpu_problem* p, covgpu_result* out, bool pgo) {
   covgpu_result local;

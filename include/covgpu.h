@@ -325,6 +325,27 @@ int covgpu_solve_reduced(covgpu_context* ctx, int32_t n, const double* S, const 
 
 int32_t covgpu_reduced_dim(const covgpu_options* opt, const covgpu_problem* p);
 
+/* ---- test entry points of the trust-region tail (k_tail.hip and its COVGPU_TAIL=0 predecessor in k_dense.hip) ----
+ * covgpu_solve_resident that also copies the trust-region state the host reads at the end of EVERY iteration (COVGPU_TR_COUNT doubles, the
+ * TR_* slots of csrc/common.hpp; rounds repeated with a raised damping included) into trace[k][COVGPU_TR_COUNT], k < capacity. *count = rounds
+ * the solve ran (it may exceed capacity: the rounds beyond it are not stored). */
+#define COVGPU_TR_COUNT 32
+#define COVGPU_SC_COUNT 16
+int covgpu_solve_resident_traced(covgpu_context* ctx, const covgpu_options* opt, covgpu_result* out, double* trace, int32_t capacity,
+                                 int32_t* count);
+/* What the last iteration of the last solve left on the device: gradient, diag(J^T J), the Gauss-Newton (LM) step and the scaled gradient
+ * c = g / d^2 (fused tail and dogleg only), each [N = dim_per_kf K + 3 L], and the candidate estimate. NULL outputs are skipped. */
+int covgpu_fetch_tail_state(covgpu_context* ctx, double* grad, double* hdiag, double* gn, double* vtmp, double* pose_c /* [K][7] */,
+                            double* sb_c /* [K][9] */, double* lm_c /* [L][3] */);
+/* One launch of the step logic on prescribed inputs; needs no uploaded problem. tr[COVGPU_TR_COUNT] and scal[COVGPU_SC_COUNT] are read and
+ * written back; flag0 is the factorisation's failure flag; the options give strategy, max_radius and the tolerances. kernel:
+ *   0 k_tail_logic(stage, fresh)
+ *   1 k_tail_finish(stage, with_logic, fresh) on part[COVGPU_SC_COUNT][part_n]: fixed-order sums of the stage's slots into scal, and, with_logic
+ *     != 0, stage A (stage 1) or B (stage 2) of the step logic in the workgroup that finishes last
+ *   2 k_tr_after_solve(fresh)   3 k_tr_after_model   4 k_tr_decide     (the COVGPU_TAIL=0 form) */
+int covgpu_tail_logic_probe(covgpu_context* ctx, const covgpu_options* opt, int32_t kernel, int32_t stage, int32_t with_logic, int32_t fresh,
+                            int32_t flag0, double* tr, double* scal, const double* part, int32_t part_n);
+
 /* Host-only: lanes per landmark (4 | 8 | 16) of the landmark-major kernels k_lm_lin, k_lm_backsub and k_lm_outliers for a problem of
  * num_obs observations on num_lm landmarks — the rule covgpu_upload applies: mean track length O/L <= 5 -> 4, <= 8 -> 8, else 16
  * (no landmarks: 4). DESIGN.md 4.1. */

@@ -56,6 +56,9 @@ def lib() -> C.CDLL:
         ip = capi._ip
         L.covo_schur_sparse.argtypes = [OP, PP, C.c_int, C.c_double, ip, ip, dp, dp, dp]
         L.covo_landmark_hessians.argtypes = [OP, PP, dp]
+        L.covo_set_preintegration_bias.argtypes = [dp]
+        L.covo_set_preintegration_bias.restype = None
+        L.covo_tail_ref.argtypes = [OP, PP, C.c_int, dp, dp, dp, dp, dp]
         L.covo_relpose.argtypes = [C.c_int, dp, dp, dp, dp, dp, dp, dp, C.c_int, dp, C.c_int, C.c_double, C.c_int, dp, C.POINTER(C.c_ubyte)]
         L.covo_relpose_traced.argtypes = L.covo_relpose.argtypes + [dp, C.POINTER(C.c_int), dp]
         L.covo_relpose_cost.argtypes = [dp, C.c_int, dp, dp, dp, dp, dp, dp, dp, C.c_int, dp, C.c_int, C.POINTER(C.c_ubyte)]
@@ -116,6 +119,22 @@ def use_sparse_solver(min_n: int = 3000, enable: bool = True, kind: str = "super
     else:
         lib().covo_set_sparse_solver(C.cast(None, _SOLVER_FN), 0)
         _solver_keepalive = None
+
+
+class preintegrated_at:
+    """For the length of a `with`: every oracle call preintegrates the IMU factors at the biases of `prob0` — the problem a solve STARTED from —
+    whatever estimate the problem it is handed holds (a solve preintegrates once and corrects to first order afterwards; a problem that holds a
+    later estimate would otherwise be preintegrated again at that estimate's biases)."""
+
+    def __init__(self, prob0):
+        self.sb = np.ascontiguousarray(prob0.kf_speed_bias, dtype=np.float64).copy()
+
+    def __enter__(self):
+        lib().covo_set_preintegration_bias(_d(self.sb))
+        return self
+
+    def __exit__(self, *a):
+        lib().covo_set_preintegration_bias(None)
 
 
 def default_options(**kw) -> capi.Options:
@@ -220,6 +239,22 @@ def solve_reduced(S, b):
 def cost(prob, opt, pgo=False):
     s = prob.as_struct()
     return lib().covo_cost(C.byref(opt), C.byref(s), int(pgo))
+
+
+TAIL_REF_KEYS = ("cost", "xnorm", "gmax", "aHa", "bHb", "aHb", "g_a", "g_b", "a_a", "a_b", "b_b")   # covo_tail_ref: out[.][0..10]
+
+
+def tail_ref(prob, opt, va, vb, pgo=False):
+    """What the trust-region step logic reads at the state held in `prob` for two vectors va, vb [N] (covo_tail_ref): (g[N], clamped d[N],
+    dict of the sums in double, dict of the same sums with long double accumulation)."""
+    D = 6 if (pgo or opt.visual_only) else 15
+    N = D * prob.K + (0 if pgo else 3 * prob.L)
+    va = np.ascontiguousarray(va, dtype=np.float64); vb = np.ascontiguousarray(vb, dtype=np.float64)
+    assert va.shape == (N,) and vb.shape == (N,), (va.shape, vb.shape, N)
+    g, d, out = np.zeros(N), np.zeros(N), np.zeros((2, len(TAIL_REF_KEYS)))
+    s = prob.as_struct()
+    assert lib().covo_tail_ref(C.byref(opt), C.byref(s), int(pgo), _d(va), _d(vb), _d(g), _d(d), _d(out)) == 0
+    return g, d, dict(zip(TAIL_REF_KEYS, out[0].tolist())), dict(zip(TAIL_REF_KEYS, out[1].tolist()))
 
 
 def residual_norms(prob, opt):

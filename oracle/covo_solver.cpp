@@ -63,6 +63,9 @@ struct Problem {
 // this repository). Returns 0 on success, non-zero if the matrix is not positive definite.
 typedef int (*covo_sparse_solver_fn)(int n, int D, int K, const int* ptr, const int* col, const double* blocks, const double* rhs, double* x);
 static covo_sparse_solver_fn g_sparse_solver = nullptr;
+// Linearisation biases of the preintegration when a problem holds a LATER estimate of a solve (covo_set_preintegration_bias): a solve
+// preintegrates once, at the biases it starts from, and corrects to first order from there on. nullptr: the problem's own speed-bias rows.
+static const double* g_preint_sb = nullptr;
 static int g_sparse_min_n = 0;
 
 static void setup(Problem& P, const covgpu_problem* p, const covgpu_options* o, bool pgo) {
@@ -103,7 +106,7 @@ static void setup(Problem& P, const covgpu_problem* p, const covgpu_options* o, 
     const ImuNoise nz = q ? ImuNoise{q[0], q[1], q[2], q[3], q[4]} : ImuNoise{o->sigma_a, o->sigma_g, o->sigma_aw, o->sigma_gw, o->gravity};
     P.grav[f] = nz.g;
     const int j = p->imu_kf_j[f];
-    const double* sbj = p->kf_speed_bias + 9 * j;
+    const double* sbj = (g_preint_sb ? g_preint_sb : p->kf_speed_bias) + 9 * j;
     const int s0 = p->imu_sample_ptr[f], s1 = p->imu_sample_ptr[f + 1];
     preintegrate(p->imu_first + 6 * f, p->imu_samples + 7 * s0, s1 - s0, v3(sbj + 3), v3(sbj + 6), nz, &P.pre[f]);
     if (!imu_whitening(P.pre[f].P, s1 - s0, &P.preW[f])) P.preW[f] = Mat<15, 15>();
@@ -500,6 +503,67 @@ static double x_norm(const Problem& P, const State& s) {
   return std::sqrt(q);
 }
 
+// u^T H v over the full undamped Gauss-Newton matrix (quad_form's sum for two vectors), every sum accumulated in T
+template <typename T>
+static T bilinear_form(const Problem& P, const Lin& lin, const double* u, const double* v) {
+  const int D = P.D, n = P.n;
+  std::vector<T> qi(P.K, T(0)), ql(P.L, T(0));
+#pragma omp parallel for schedule(static)
+  for (int i = 0; i < P.K; ++i) {
+    T acc = 0;
+    for (int q = P.pat.ptr[i]; q < P.pat.ptr[i + 1]; ++q) {
+      const int j = P.pat.col[q];
+      const double* blk = &lin.H[(size_t)q * D * D];
+      for (int r = 0; r < D; ++r) {
+        T s = 0;
+        for (int c = 0; c < D; ++c) s += (T)blk[r * D + c] * (T)v[D * j + c];
+        acc += (T)u[D * i + r] * s;
+      }
+    }
+    qi[i] = acc;
+  }
+#pragma omp parallel for schedule(static)
+  for (int l = 0; l < P.L; ++l) {
+    T q2 = 0;
+    const double* H = &lin.Hll[(size_t)l * 9];
+    const double* ul = u + n + (size_t)l * 3;
+    const double* vl = v + n + (size_t)l * 3;
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) q2 += (T)ul[r] * (T)H[r * 3 + c] * (T)vl[c];
+    for (int k = P.p->lm_obs_ptr[l]; k < P.p->lm_obs_ptr[l + 1]; ++k) {
+      const int i = P.p->obs_kf[k];
+      const double* W = &lin.W[(size_t)k * 18];
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 3; ++c) q2 += (T)W[r * 3 + c] * ((T)u[D * i + r] * (T)vl[c] + (T)v[D * i + r] * (T)ul[c]);
+    }
+    ql[l] = q2;
+  }
+  T q = 0;
+  for (T x : qi) q += x;
+  for (T x : ql) q += x;
+  return q;
+}
+template <typename T>
+static T dot_as(const double* a, const double* b, size_t n) {
+  T s = 0;
+  for (size_t q = 0; q < n; ++q) s += (T)a[q] * (T)b[q];
+  return s;
+}
+template <typename T>
+static void tail_sums(const Problem& P, const State& x, const Lin& lin, const double* g, const double* va, const double* vb, double* out) {
+  const size_t N = (size_t)P.n + 3 * (size_t)P.L;
+  T xn = 0;
+  for (int i = 0; i < P.K; ++i) {
+    if (!P.p->kf_fixed[i]) for (int c = 0; c < 7; ++c) xn += (T)x.pose[7 * i + c] * (T)x.pose[7 * i + c];
+    if (P.vi) for (int c = 0; c < 9; ++c) xn += (T)x.sb[9 * i + c] * (T)x.sb[9 * i + c];
+  }
+  for (double v : x.lm) xn += (T)v * (T)v;
+  out[1] = (double)std::sqrt(xn);
+  out[3] = (double)bilinear_form<T>(P, lin, va, va); out[4] = (double)bilinear_form<T>(P, lin, vb, vb); out[5] = (double)bilinear_form<T>(P, lin, va, vb);
+  out[6] = (double)dot_as<T>(g, va, N); out[7] = (double)dot_as<T>(g, vb, N);
+  out[8] = (double)dot_as<T>(va, va, N); out[9] = (double)dot_as<T>(va, vb, N); out[10] = (double)dot_as<T>(vb, vb, N);
+}
+
 // ------------------------------------------------------------------ trust-region loop (A.6)
 static int solve(Problem& P, State& x, covgpu_result* res) {
   const covgpu_options& o = P.o;
@@ -729,6 +793,9 @@ int covo_linearize_between(const covgpu_options* opt, const covgpu_problem* p, d
   return COVGPU_OK;
 }
 
+// Every later call preintegrates at these speed-bias rows [K][9] (the caller keeps them alive) instead of the problem's own; NULL ends that.
+void covo_set_preintegration_bias(const double* speed_bias) { g_preint_sb = speed_bias; }
+
 // Install (fn != NULL) or remove the sparse linear solver used for reduced systems with >= min_n unknowns.
 void covo_set_sparse_solver(covo_sparse_solver_fn fn, int min_n) { g_sparse_solver = fn; g_sparse_min_n = min_n; }
 
@@ -855,6 +922,37 @@ double covo_cost(const covgpu_options* opt, const covgpu_problem* p, int pgo) {
   setup(P, p, opt, pgo != 0);
   State x = initial_state(P);
   return evaluate_cost(P, x);
+}
+
+// What the trust-region step logic reads at the state held in `p`, for two vectors va, vb [N = D K + 3 L] (pose part first): g[N], the clamped
+// d[N], and out[2][COVO_TAIL_COUNT = 11] = { cost, |x|, max|g|, va^T H va, vb^T H vb, va^T H vb, g.va, g.vb, |va|^2, va.vb, |vb|^2 } over the undamped
+// Gauss-Newton matrix H — row 0 summed in double as the solver's loop does (quad_form, x_norm), row 1 with long double accumulation of the same
+// terms: the difference of the two is the rounding scale of a double evaluation.
+int covo_tail_ref(const covgpu_options* opt, const covgpu_problem* p, int pgo, const double* va, const double* vb, double* g, double* d, double* out) {
+  Problem P;
+  setup(P, p, opt, pgo != 0);
+  State x = initial_state(P);
+  Lin lin;
+  linearize(P, x, lin);
+  const int n = P.n;
+  const size_t N = (size_t)n + 3 * (size_t)P.L;
+  std::copy(lin.g.begin(), lin.g.end(), g);
+  std::copy(lin.gl.begin(), lin.gl.end(), g + n);
+  for (int q = 0; q < n; ++q) d[q] = clampd(lin.dp2[q]);
+  for (size_t q = 0; q < 3 * (size_t)P.L; ++q) d[n + q] = clampd(lin.Hll[(q / 3) * 9 + (q % 3) * 4]);
+  double gmax = 0;
+  for (size_t q = 0; q < N; ++q) gmax = std::max(gmax, std::fabs(g[q]));
+  long double cost_l = 0;
+  {
+    for (int k = 0; k < P.O; ++k) { ObsLin ol; eval_obs(P, x, k, false, &ol); cost_l += ol.cost; }
+    for (int f = 0; f < P.I; ++f) { Mat<15, 1> r; eval_imu(P, x, f, false, &r, nullptr); long double s = 0; for (int q = 0; q < 15; ++q) s += (long double)r[q] * r[q]; cost_l += 0.5L * s; }
+    for (int e = 0; e < P.E; ++e) { Vec6 r; double c; eval_edge(P, x, e, false, &r, nullptr, nullptr, &c); cost_l += c; }
+  }
+  out[0] = evaluate_cost(P, x); out[11] = (double)cost_l;
+  out[2] = out[13] = gmax;
+  tail_sums<double>(P, x, lin, g, va, vb, out);
+  tail_sums<long double>(P, x, lin, g, va, vb, out + 11);
+  return COVGPU_OK;
 }
 
 // PGO tail (opt_be.cpp:1046-1047, 1066-1081)

@@ -184,6 +184,10 @@ def test_every_batch_entry_point_rejects_a_null_context_by_name():
         "covgpu_bow_transform_batch": (None, None),
         "covgpu_bow_score_pairs": (0, None, None, None, 0, None, None, None),
         "covgpu_detect_candidates_batch": (None, None),
+        # the test entry points of the trust-region tail (probe_api.hip) keep the same contract
+        "covgpu_solve_resident_traced": (None, None, None, 0, None),
+        "covgpu_fetch_tail_state": (None,) * 7,
+        "covgpu_tail_logic_probe": (None, 0, 1, 0, 0, 0, None, None, None, 0),
     }
     for name, args in calls.items():
         assert getattr(lib, name)(None, *args) == 1, name               # COVGPU_ERR_INVALID_ARG
