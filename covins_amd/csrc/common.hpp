@@ -13,6 +13,7 @@
 //     length N = n + 3 L with the pose part first, so norms and combinations are single flat kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <stdint.h>
@@ -500,7 +501,7 @@ struct Round2Lists {
 bool round2_compact_device(int L, int O, int K, const unsigned char* d_erase, const int* d_left, const int* d_obs_kf, const int* d_obs_lm, const double* d_u,
                            const double* d_v, const double* d_sigma, const double* d_lm0, hipStream_t st, Round2Lists& out);
 
-// ---- multifrontal solve of the whole reduced camera system (k_front.hip)
+// ---- multifrontal solve of the whole reduced camera system (k_front.hip: kernels and launchers; nd_tables.hip: the host tables)
 struct NdHostPlan;
 constexpr int kExtRec = 144;   // ints per extend-add record: 8 header | 8 child | 64 + 64 row maps (576 bytes)
 struct NdLevel {
@@ -513,7 +514,7 @@ struct NdLevel {
   // k_potrf_panel's front lists (round 6): the level's fronts (index in the batch) by DEcreasing interior order; per 256-column panel P the first
   // pbig[P] of them have more than 128 real columns in that panel (sixteen-wave form), the next psmall[P] have 1 .. 128 (four-wave form), the rest none
   int* plist = nullptr; std::vector<int> plist_h, pbig, psmall;
-  int ext_first = 0, ext_count = 0;       // extend-add work list (NdDev::ext) for the SUBTREE children of this level's fronts
+  int ext_first = 0, ext_count = 0;       // extend-add work list (tiles of NdDev::extw / extr) for the SUBTREE children of this level's fronts
   int ext_countA = 0;                     // ... of which the first ext_countA tiles lie in the fronts' first 256 rows (first panel)
   int split_ta = 0;                       // border tiles (128) of this level's fronts that reach their parents' first 256 columns (max)
   int ext2_first = 0, ext2_count = 0, ext2_countA = 0;   // ... for their TOP children (top levels of a sharded solve only)
@@ -521,6 +522,10 @@ struct NdLevel {
   // right-hand-side segments of 256 rows) and the trailing-update tiles this rank owns in NdDev::dist_tri (first, count incl. the XCD padding)
   std::vector<int> dx_first, dx_nt, dx_nr, dt_first, dt_cnt;
   std::vector<const int*> dt_dev;                // device addresses of the owned-tile lists (set at upload)
+  // shapes the backward substitution's launchers, its scratch and nd_tables' grouping of levels must agree on
+  int interior_tiles() const { return std::min(nI / kTile, (own_max + kTile - 1) / kTile); }            // tiles that hold a real interior column of some front
+  int pipe_chunks() const { return (ntot - nI + kPipeChunk - 1) / kPipeChunk; }                         // helper workgroups over the widest border (k_bwd_pipe)
+  size_t pipe_scratch_elems() const { return (size_t)n * interior_tiles() * (pipe_chunks() + 1) * kTile; }   // [fronts][interior tiles][chunks + 1][128]
 };
 struct NdDev {
   bool active = false;
@@ -534,22 +539,20 @@ struct NdDev {
   // fronts' own unknowns (filled with the hand-over's "empty" word at the start of a solve)
   int tree_levels = 0; int* tree_fill = nullptr; std::vector<int> h_tree_fill;
   int tree_top0 = 0;                       // ... and the TOP levels [tree_top0, levels) as one launch of the 64x64-inverse form (== levels: none)
-  int *cptr = nullptr, *cidx = nullptr;    // [nodes + 1], children that are subtree nodes (all children on a single GPU)
-  int *cptr2 = nullptr, *cidx2 = nullptr;  // [nodes + 1], children that are top nodes
   int *inv_off = nullptr, *inv = nullptr;  // [nodes] offset of the node's map parent front row -> own front row (-1: none)
   int *rhs_node = nullptr;                 // [nodes] element offset of the node's right-hand side in nd_rhs
-  int *ext = nullptr;                      // extend-add work lists: (node, tile row, tile column) of 64x64 tiles
-  // the same lists FLATTENED for the kernel (round 5): per tile 8 ints {front offset lo, hi | leading dimension | right-hand side offset | tile row |
+  // extend-add work lists — the 64x64 tiles of the fronts that receive something from a child, per level and kind of child (subtree children: all
+  // children on a single GPU | top children) — FLATTENED for the kernel (round 5): per tile 8 ints {front offset lo, hi | leading dimension | right-hand side offset | tile row |
   // tile column | first, last+1 child entry}, per child entry 6 ints {front offset lo, hi | leading dimension | right-hand side offset | offset of its
-  // row map | 0} — a workgroup reaches a child's entries through three dependent loads (tile, child, row map) instead of six (tile, cptr, cidx,
-  // inv_off / ntab, row map)
+  // row map | 0}, extc for the subtree children and extc2 for the top children — a workgroup reaches a child's entries through three dependent loads
+  // (tile, child, row map)
   int *extw = nullptr, *extc = nullptr, *extc2 = nullptr;
-  std::vector<int> h_extw, h_extc, h_extc2, h_ext_kind;
+  std::vector<int> h_extw, h_extc, h_extc2;
   // ... and as records of kExtRec ints (k_nd_extend_rec): [tiles] first records, then the overflow records of tiles with several contributing children
   int* extr = nullptr; size_t ext_over = 0; std::vector<int> h_extr;
   int *bb_off = nullptr, *bb = nullptr;    // per node: offset of its lower-triangular map over BORDER 128-tiles in bb (1: a child contributes to the tile; see DenseBatch::beta0)
   int *top_var = nullptr, *top_r = nullptr, *top_g = nullptr;  // per scalar unknown of the top nodes: variable | component | solution index
-  int ntop = 0;
+  int ntop = 0;                            // (set by nd_tables, as n_top_tiles below)
   // sharded solve: what the ranks exchange of the top fronts = their LIVE LOWER-TRIANGULAR 128x128 tiles, packed (the fronts are stored
   // as full squares: the upper triangle and the dead tiles are never read). top_tiles: (node, tile row, tile column) triples;
   // top_pack: [n_top_tiles][128][128 tiles | top right-hand sides | grad, hdiag of the top unknowns] — one all-reduce
@@ -557,9 +560,9 @@ struct NdDev {
   std::vector<int> h_top_tiles;
   // sharded solve: [top fronts | top right-hand sides | grad, hdiag of the top unknowns] is ONE contiguous range of the buffer
   size_t M_sub = 0, rhs_top = 0, gh_off = 0;   // elements of the subtree fronts | of the top levels' right-hand sides | offset of [grad | hdiag] in nd_rhs
-  // host staging of the tables (filled by nd_tables, uploaded by upload.hip)
-  std::vector<int> h_vnode, h_voff, h_vord, h_vown, h_ndepth, h_nI, h_abase, h_fidx, h_own_dims, h_st_dims, h_own_g, h_st_g, h_gidx, h_cptr, h_cidx, h_cptr2,
-      h_cidx2, h_inv_off, h_inv, h_rhs_node, h_ext, h_top_var, h_top_r, h_top_g, h_bb_off, h_bb;
+  // host staging of the tables (filled by nd_tables: nd_tables.hip; uploaded by upload.hip)
+  std::vector<int> h_vnode, h_voff, h_vord, h_vown, h_ndepth, h_nI, h_abase, h_fidx, h_own_dims, h_st_dims, h_own_g, h_st_g, h_gidx, h_inv_off, h_inv, h_rhs_node,
+      h_top_var, h_top_r, h_top_g, h_bb_off, h_bb;
   std::vector<long long> h_ntab;
   // shard policy 1 (distributed top): exchange entries {front, tile row | first row, tile column | rows, 0 tile | 1 right-hand side} per panel, the
   // owned trailing-update tiles per panel, the reduce buffer (largest panel), what one linear solve all-reduces, and whether this rank leads
@@ -571,7 +574,7 @@ struct NdDev {
   size_t M_elems = 0, rhs_elems = 0, linv_elems = 0;
   double plan_flops = 0;                   // flops of one factorisation of the plan's fronts (NdHostPlan::flops: dense count on the real sizes)
 };
-void nd_tables(const NdHostPlan& hp, const int* pos_kf, int D, int rank, NdDev& dev);  // host tables + level shapes from the plan
+void nd_tables(const NdHostPlan& hp, const int* pos_kf, int D, int rank, NdDev& dev);  // nd_tables.hip: host tables + level shapes from the plan, NdDev complete but for the device addresses
 void launch_nd_init(const DevProblem& P, const NdDev& nd, hipStream_t st);    // once per upload: identity block inverses for the padding columns
 void launch_nd_zero(const DevProblem& P, const NdDev& nd, hipStream_t st);    // per iteration: clear the live tiles, identity on interior padding
 bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hipStream_t st, CholAux& ax);  // false: scratch allocation failed, nothing enqueued. damped system in the fronts + bred -> dst (IR layout)

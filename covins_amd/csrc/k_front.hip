@@ -13,374 +13,14 @@
 // then top-down one backward substitution per level with the ancestors' unknowns given. Same arithmetic as a dense Cholesky
 // of the 15K-order system up to the elimination order. Replaces round 2's IMU-chain elimination + per-agent dense blocks:
 // 5-agent map 1.2e11 -> 2.7e10 flops, single-agent maps no longer factor a dense 6K system.
+// This file: the kernels and their launchers; launch_nd_solve is the sequence of the steps of struct FrontRun. The host tables the kernels and
+// the launchers read (NdDev, NdLevel) are built by nd_tables.hip.
 #include <algorithm>
 
 #include "common.hpp"
 #include "dev_math.hpp"
-#include "nd_plan.hpp"
 
 namespace covgpu {
-
-// ------------------------------------------------------------------------------------------------ host tables
-// rank: this context's rank in an agent-sharded solve (hp.node_rank non-empty); fronts exist for the rank's own subtrees and for
-// the TOP nodes (replicated). Batches = levels: subtree nodes by height, then the top nodes by their height inside the top.
-void nd_tables(const NdHostPlan& hp, const int* pos_kf, int D, int rank, NdDev& dev) {
-  dev = NdDev();
-  const int nn = hp.nnodes, K = hp.K;
-  const bool sh = !hp.node_rank.empty();
-  auto is_top = [&](int n) { return sh && hp.node_rank[n] < 0; };
-  auto is_local = [&](int n) { return !sh || hp.node_rank[n] < 0 || hp.node_rank[n] == rank; };
-  int Hs = 0;
-  for (int n = 0; n < nn; ++n) if (!is_top(n)) Hs = std::max(Hs, hp.level[n] + 1);
-  std::vector<int> lev(nn), toph(nn, 0);
-  for (int n = nn - 1; n >= 0; --n) if (is_top(n)) for (int c : hp.child[n]) if (is_top(c)) toph[n] = std::max(toph[n], toph[c] + 1);
-  int nlev = Hs;
-  for (int n = 0; n < nn; ++n) { lev[n] = is_top(n) ? Hs + toph[n] : hp.level[n]; nlev = std::max(nlev, lev[n] + 1); }
-  std::vector<std::vector<int>> lnodes(nlev);
-  for (int n = 0; n < nn; ++n) if (is_local(n)) lnodes[lev[n]].push_back(n);
-  // local nodes renumbered in level order: a level's slice of nd_ntab is its batch table; foreign nodes have no id
-  std::vector<int> order, newid(nn, -1);
-  for (int l = 0; l < nlev; ++l) for (int n : lnodes[l]) { newid[n] = (int)order.size(); order.push_back(n); }
-  const int nl = (int)order.size();
-  dev.nnodes = nl; dev.top_lev0 = Hs; dev.plan_flops = hp.flops;
-  dev.h_vnode.assign(2 * (size_t)K, -1); dev.h_voff.assign(2 * (size_t)K, 0); dev.h_vord.assign(2 * (size_t)K, 0); dev.h_vown.assign(2 * (size_t)K, 0);
-  for (int v = 0; v < 2 * K; ++v)
-    if (hp.vnode[v] >= 0) {
-      const int n = hp.vnode[v];
-      dev.h_vnode[v] = newid[n]; dev.h_voff[v] = hp.voff[v]; dev.h_vord[v] = hp.vord[v];
-      dev.h_vown[v] = !is_local(n) ? 0 : (is_top(n) ? 2 : 1);
-    }
-  dev.h_ndepth.resize(nl); dev.h_nI.resize(nl); dev.h_ntab.resize(2 * (size_t)nl);
-  dev.h_own_dims.resize(nl); dev.h_st_dims.resize(nl); dev.h_own_g.resize(nl); dev.h_st_g.resize(nl);
-  dev.lev.resize(nlev);
-  auto gidx_of = [&](int v, int r) { return D * pos_kf[v >> 1] + ((v & 1) ? 6 + r : r); };
-  std::vector<int> ld(nl);
-  size_t moff = 0, loff = 0;
-  for (int l = 0, i = 0; l < nlev; ++l) {
-    NdLevel& L = dev.lev[l];
-    L.n = (int)lnodes[l].size(); L.first = i; L.nI = 256; L.own_max = 0;
-    for (int n : lnodes[l]) L.own_max = std::max(L.own_max, hp.own_dims[n]);
-    L.nI = std::max(256, ((L.own_max + 255) / 256) * 256);
-    L.ntot = L.nI;
-    if (l == Hs) dev.M_sub = moff;
-    for (int n : lnodes[l]) {
-      const int nO = ((hp.st_dims[n] + kTile - 1) / kTile) * kTile;
-      ld[i] = L.nI + nO;
-      L.ntot = std::max(L.ntot, ld[i]);
-      dev.h_ndepth[i] = hp.depth[n]; dev.h_nI[i] = L.nI;
-      dev.h_ntab[2 * (size_t)i] = (long long)moff; dev.h_ntab[2 * (size_t)i + 1] = ld[i];
-      moff += (size_t)ld[i] * ld[i];
-      dev.h_own_dims[i] = hp.own_dims[n]; dev.h_st_dims[i] = hp.st_dims[n];
-      dev.h_own_g[i] = (int)dev.h_gidx.size();
-      for (int v : hp.own[n]) for (int r = 0; r < NdHostPlan::vdim(v); ++r) dev.h_gidx.push_back(gidx_of(v, r));
-      dev.h_st_g[i] = (int)dev.h_gidx.size();
-      for (int v : hp.strct[n]) for (int r = 0; r < NdHostPlan::vdim(v); ++r) dev.h_gidx.push_back(gidx_of(v, r));
-      L.live_h.push_back((hp.own_dims[n] + kTile - 1) / kTile);
-      L.live_h.push_back(nO / kTile);
-      if (is_top(n)) {   // live lower-triangular tiles of a replicated front: what a sharded solve exchanges (same liveness as k_nd_zero)
-        const int nIt = L.nI / kTile, lo2 = 2 * ((hp.own_dims[n] + 2 * kTile - 1) / (2 * kTile)), lb = (hp.st_dims[n] + kTile - 1) / kTile;
-        auto live = [&](int t) { return t < lo2 || (t >= nIt && t - nIt < lb); };
-        const int Tn = ld[i] / kTile;
-        for (int tr = 0; tr < Tn; ++tr) for (int tc = 0; tc <= tr; ++tc) if (live(tr) && live(tc)) { dev.h_top_tiles.push_back(i); dev.h_top_tiles.push_back(tr); dev.h_top_tiles.push_back(tc); }
-      }
-      if (is_top(n))
-        for (int v : hp.own[n]) for (int r = 0; r < NdHostPlan::vdim(v); ++r) { dev.h_top_var.push_back(v); dev.h_top_r.push_back(r); dev.h_top_g.push_back(gidx_of(v, r)); }
-      ++i;
-    }
-    L.linv_off = loff; loff += (size_t)L.n * L.nI * kTile;
-    {  // front lists of the panel factorisation (NdLevel::plist)
-      L.plist_h.resize(L.n);
-      for (int k = 0; k < L.n; ++k) L.plist_h[k] = k;
-      std::stable_sort(L.plist_h.begin(), L.plist_h.end(), [&](int a, int b) { return dev.h_own_dims[L.first + a] > dev.h_own_dims[L.first + b]; });
-      const int np = L.nI / 256;
-      L.pbig.assign(np, 0); L.psmall.assign(np, 0);
-      for (int k = 0; k < L.n; ++k)
-        for (int P = 0; P < np; ++P) {
-          const int real = dev.h_own_dims[L.first + k] - 256 * P;
-          if (real > 128) ++L.pbig[P]; else if (real > 0) ++L.psmall[P];
-        }
-    }
-  }
-  if (Hs >= nlev) dev.M_sub = moff;
-  dev.M_elems = moff; dev.linv_elems = loff;
-  // right-hand sides: [top levels | grad, hdiag of the top unknowns | subtree levels] — with the top fronts right in front of them
-  // (upload.hip puts both in ONE allocation) the whole all-reduced region is contiguous
-  dev.h_rhs_node.assign(nl, 0);
-  size_t roff = 0;
-  auto place = [&](int l) {
-    NdLevel& L = dev.lev[l];
-    L.rhs_off = roff;
-    for (int k = 0; k < L.n; ++k) dev.h_rhs_node[L.first + k] = (int)(roff + (size_t)k * 2 * L.ntot);
-    roff += (size_t)L.n * 2 * L.ntot;
-  };
-  for (int l = Hs; l < nlev; ++l) place(l);
-  dev.rhs_top = roff; dev.gh_off = roff; roff += 2 * dev.h_top_g.size();
-  for (int l = 0; l < Hs; ++l) place(l);
-  dev.rhs_elems = roff;
-  // front row of every ancestor variable a node's subtree couples to: nd_fidx[nd_abase[node][depth of the ancestor] + ordinal]
-  dev.h_abase.assign((size_t)nl * hp.maxdepth, -1);
-  for (int i = 0; i < nl; ++i) {
-    const int n = order[i];
-    for (int a = hp.parent[n]; a >= 0; a = hp.parent[a]) {
-      dev.h_abase[(size_t)i * hp.maxdepth + hp.depth[a]] = (int)dev.h_fidx.size();
-      dev.h_fidx.resize(dev.h_fidx.size() + hp.own[a].size(), -1);
-    }
-    int row = dev.h_nI[i];
-    for (int v : hp.strct[n]) {
-      const int a = hp.vnode[v];
-      dev.h_fidx[dev.h_abase[(size_t)i * hp.maxdepth + hp.depth[a]] + hp.vord[v]] = row;
-      row += NdHostPlan::vdim(v);
-    }
-  }
-  // children (subtree children | top children, see NdDev) + the map (parent front row -> child front row) the extend-add gathers through
-  dev.h_cptr.assign(nl + 1, 0); dev.h_cptr2.assign(nl + 1, 0); dev.h_inv_off.assign(nl, -1);
-  for (int i = 0; i < nl; ++i) {
-    const int n = order[i];
-    dev.h_cptr[i + 1] = dev.h_cptr[i]; dev.h_cptr2[i + 1] = dev.h_cptr2[i];
-    for (int c : hp.child[n]) {
-      if (!is_local(c)) continue;   // another rank's subtree: its contribution arrives through the all-reduce of the top fronts
-      if (is_top(c)) { dev.h_cidx2.push_back(newid[c]); ++dev.h_cptr2[i + 1]; }
-      else { dev.h_cidx.push_back(newid[c]); ++dev.h_cptr[i + 1]; }
-    }
-    const int p = hp.parent[n];
-    if (p < 0) continue;
-    const int ip = newid[p];   // (a local node's parent is local: own subtree or top)
-    dev.h_inv_off[i] = (int)dev.h_inv.size();
-    dev.h_inv.resize(dev.h_inv.size() + ld[ip], -1);
-    int* inv = dev.h_inv.data() + dev.h_inv_off[i];
-    int row = dev.h_nI[i];
-    for (int v : hp.strct[n]) {
-      // the variable's row in the parent's front: own column there, or one of the parent's border rows
-      const int prow = hp.vnode[v] == p ? hp.voff[v] : dev.h_fidx[dev.h_abase[(size_t)ip * hp.maxdepth + hp.depth[hp.vnode[v]]] + hp.vord[v]];
-      for (int r = 0; r < NdHostPlan::vdim(v); ++r) inv[prow + r] = row + r;
-      row += NdHostPlan::vdim(v);
-    }
-  }
-  // extend-add work lists: per level the 64x64 tiles of the parents' fronts that receive something from a child of either kind
-  auto worklist = [&](int l, const std::vector<int>& cptr, const std::vector<int>& cidx, int& first, int& count, int& countA) {
-    NdLevel& L = dev.lev[l];
-    first = (int)dev.h_ext.size() / 3;
-    std::vector<int> tiles;
-    for (int k = 0; k < L.n; ++k) {
-      const int i = L.first + k;
-      const int T = (ld[i] + 63) / 64;
-      std::vector<char> mark((size_t)T * T, 0);
-      for (int q = cptr[i]; q < cptr[i + 1]; ++q) {
-        const int* inv = dev.h_inv.data() + dev.h_inv_off[cidx[q]];
-        std::vector<int> rows;
-        for (int t = 0; t < T; ++t) {
-          bool any = false;
-          for (int r = 64 * t; r < std::min(ld[i], 64 * t + 64) && !any; ++r) any = inv[r] >= 0;
-          if (any) rows.push_back(t);
-        }
-        for (int a : rows) for (int b : rows) if (b <= a) mark[(size_t)a * T + b] = 1;
-      }
-      // Round 6: the border x border part of a front is never cleared (k_nd_zero) — the extend-add STORES every entry of the 64-tiles it visits there
-      // (children's sum, or zero), so it must visit every lower 64-tile of each 128-tile some child reaches (NdDev::bb marks those for the first
-      // trailing update, which reads them; the others it starts from zero itself)
-      if (&cptr == &dev.h_cptr && !is_top(order[i])) {
-        const int t0 = dev.h_nI[i] / 64;
-        for (int A = t0; A < T; A += 2)
-          for (int B = t0; B <= A; B += 2) {
-            bool any = false;
-            for (int a = A; a < std::min(T, A + 2); ++a) for (int b = B; b < std::min(T, B + 2); ++b) if (b <= a && mark[(size_t)a * T + b]) any = true;
-            if (any) for (int a = A; a < std::min(T, A + 2); ++a) for (int b = B; b < std::min(T, B + 2); ++b) if (b <= a) mark[(size_t)a * T + b] = 1;
-          }
-      }
-      for (int a = 0; a < T; ++a) for (int b = 0; b <= a; ++b) if (mark[(size_t)a * T + b]) { tiles.push_back(i); tiles.push_back(a); tiles.push_back(b); }
-    }
-    // tiles of the fronts' first 256 rows (what the first panel's factorisation needs) first: NdLevel::ext_countA
-    countA = 0;
-    for (int pass = 0; pass < 2; ++pass)
-      for (size_t q = 0; q < tiles.size(); q += 3)
-        if ((tiles[q + 1] < 4) == (pass == 0)) {
-          dev.h_ext.insert(dev.h_ext.end(), tiles.begin() + q, tiles.begin() + q + 3); countA += pass == 0 ? 1 : 0;
-          dev.h_ext_kind.push_back(&cptr == &dev.h_cptr2 ? 1 : 0);
-        }
-    count = (int)dev.h_ext.size() / 3 - first;
-  };
-  for (int l = 0; l < nlev; ++l) {
-    worklist(l, dev.h_cptr, dev.h_cidx, dev.lev[l].ext_first, dev.lev[l].ext_count, dev.lev[l].ext_countA);
-    worklist(l, dev.h_cptr2, dev.h_cidx2, dev.lev[l].ext2_first, dev.lev[l].ext2_count, dev.lev[l].ext2_countA);
-    // border tiles of this level's fronts that carry unknowns of the parents' first 256 columns (a front's border lists its
-    // parent's unknowns first, in the parent's own order)
-    NdLevel& L = dev.lev[l];
-    L.split_ta = 0;
-    for (int k = 0; k < L.n; ++k) {
-      const int n = order[L.first + k], p = hp.parent[n];
-      if (p < 0) continue;
-      int d = 0;
-      for (int v : hp.strct[n]) if (hp.vnode[v] == p && hp.voff[v] < 256) d += NdHostPlan::vdim(v);
-      L.split_ta = std::max(L.split_ta, (d + kTile - 1) / kTile);
-    }
-  }
-  // flattened work / child lists of the extend-add kernel (NdDev::extw / extc / extc2)
-  {
-    auto flat = [&](const std::vector<int>& cidx, std::vector<int>& out) {
-      for (int ch : cidx) {
-        const unsigned long long mo = (unsigned long long)dev.h_ntab[2 * (size_t)ch];
-        out.push_back((int)(unsigned)(mo & 0xffffffffull)); out.push_back((int)(unsigned)(mo >> 32));
-        out.push_back((int)dev.h_ntab[2 * (size_t)ch + 1]); out.push_back(dev.h_rhs_node[ch]); out.push_back(dev.h_inv_off[ch]); out.push_back(0);
-      }
-    };
-    flat(dev.h_cidx, dev.h_extc); flat(dev.h_cidx2, dev.h_extc2);
-    const size_t nt = dev.h_ext.size() / 3;
-    dev.h_extw.resize(8 * nt);
-    for (size_t q = 0; q < nt; ++q) {
-      const int node = dev.h_ext[3 * q];
-      const std::vector<int>& cp = dev.h_ext_kind[q] ? dev.h_cptr2 : dev.h_cptr;
-      const unsigned long long fo = (unsigned long long)dev.h_ntab[2 * (size_t)node];
-      int* w = dev.h_extw.data() + 8 * q;
-      w[0] = (int)(unsigned)(fo & 0xffffffffull); w[1] = (int)(unsigned)(fo >> 32); w[2] = (int)dev.h_ntab[2 * (size_t)node + 1]; w[3] = dev.h_rhs_node[node];
-      w[4] = dev.h_ext[3 * q + 1]; w[5] = dev.h_ext[3 * q + 2]; w[6] = cp[node]; w[7] = cp[node + 1];
-    }
-    // Round 6, the same lists as RECORDS of kExtRec ints (k_nd_extend_rec): per tile ONE record {header | first contributing child | that child's row
-    // maps for the tile's 64 rows and 64 columns}, found by the tile's index alone, and one overflow record per further contributing child. The kernel's
-    // chain of dependent loads is record -> values instead of tile -> child entries -> row maps -> values; children that reach neither the tile's rows
-    // nor its columns are not visited at all (their terms were zero: same sums, same order).
-    dev.h_extr.assign((size_t)kExtRec * nt, -1);
-    dev.ext_over = nt;
-    for (size_t q = 0; q < nt; ++q) {
-      const int node = dev.h_ext[3 * q], a = dev.h_ext[3 * q + 1], b = dev.h_ext[3 * q + 2];
-      const std::vector<int>& cp = dev.h_ext_kind[q] ? dev.h_cptr2 : dev.h_cptr;
-      const std::vector<int>& ci = dev.h_ext_kind[q] ? dev.h_cidx2 : dev.h_cidx;
-      int nrec = 0;
-      const size_t next = dev.h_extr.size() / kExtRec - nt;
-      for (int k = cp[node]; k < cp[node + 1]; ++k) {
-        const int ch = ci[k];
-        const int* inv = dev.h_inv.data() + dev.h_inv_off[ch];
-        int maps[128];
-        bool anyr = false, anyc = false;
-        for (int e = 0; e < 64; ++e) {
-          const int r = 64 * a + e, c = 64 * b + e;
-          maps[e] = r < ld[node] ? inv[r] : -1; maps[64 + e] = c < ld[node] ? inv[c] : -1;
-          anyr = anyr || maps[e] >= 0; anyc = anyc || maps[64 + e] >= 0;
-        }
-        if (!anyr || !anyc) continue;
-        if (nrec > 0) dev.h_extr.resize(dev.h_extr.size() + kExtRec, -1);
-        int* r = nrec == 0 ? dev.h_extr.data() + (size_t)kExtRec * q : dev.h_extr.data() + dev.h_extr.size() - kExtRec;
-        const unsigned long long mo = (unsigned long long)dev.h_ntab[2 * (size_t)ch];
-        r[8] = (int)(unsigned)(mo & 0xffffffffull); r[9] = (int)(unsigned)(mo >> 32); r[10] = (int)dev.h_ntab[2 * (size_t)ch + 1]; r[11] = dev.h_rhs_node[ch];
-        for (int e = 0; e < 128; ++e) r[16 + e] = maps[e];
-        ++nrec;
-      }
-      int* w = dev.h_extr.data() + (size_t)kExtRec * q;
-      for (int e = 0; e < 6; ++e) w[e] = dev.h_extw[8 * q + e];
-      w[6] = nrec; w[7] = (int)next;
-    }
-  }
-  // border x border 128-tiles that receive something from a child (NdDev::bb): only those are cleared per iteration and read by the first
-  // panel's trailing update. A top front of a sharded solve is summed over the ranks as it stands: all its tiles count as contributed to.
-  dev.h_bb_off.assign(nl, 0); dev.h_bb.clear();
-  for (int i = 0; i < nl; ++i) {
-    const int nI = dev.h_nI[i], lb = (ld[i] - nI + kTile - 1) / kTile;
-    dev.h_bb_off[i] = (int)dev.h_bb.size();
-    dev.h_bb.resize(dev.h_bb.size() + (size_t)lb * (lb + 1) / 2, is_top(order[i]) ? 1 : 0);
-    if (is_top(order[i]) || lb == 0) continue;
-    int* bb = dev.h_bb.data() + dev.h_bb_off[i];
-    auto children = [&](const std::vector<int>& cptr, const std::vector<int>& cidx) {
-      for (int q = cptr[i]; q < cptr[i + 1]; ++q) {
-        const int* inv = dev.h_inv.data() + dev.h_inv_off[cidx[q]];
-        std::vector<int> rows;
-        for (int t = 0; t < lb; ++t) {
-          bool any = false;
-          for (int r = nI + kTile * t; r < std::min(ld[i], nI + kTile * t + kTile) && !any; ++r) any = inv[r] >= 0;
-          if (any) rows.push_back(t);
-        }
-        for (int a : rows) for (int b : rows) if (b <= a) bb[a * (a + 1) / 2 + b] = 1;
-      }
-    };
-    children(dev.h_cptr, dev.h_cidx);
-    children(dev.h_cptr2, dev.h_cidx2);
-  }
-  {  // bottom levels whose backward substitution runs as one launch (k_panel.hip: k_bwd_tree): while a level's fronts hold at most two interior tiles
-    int ls = 0;
-    const int lmax = std::min(std::min(nlev, Hs), kBwdTreeMax);
-    while (ls < lmax && dev.lev[ls].n > 0 && dev.lev[ls].n <= 65535 && (dev.lev[ls].own_max + kTile - 1) / kTile <= 2) ++ls;
-    dev.tree_levels = ls >= 2 ? ls : 0;
-    // the top levels, from the root down while the tile workgroups stay within 128 (k_bwd_tree64: a workgroup takes a whole CU) and every front has two
-    // interior tiles or more somewhere in the level
-    int lt = nlev, wgs = 0;
-    while (lt > dev.tree_levels && nlev - lt < kBwdTreeMax) {
-      const NdLevel& L = dev.lev[lt - 1];
-      const int T = std::min(L.nI / kTile, (L.own_max + kTile - 1) / kTile);
-      if (L.n <= 0 || T < 2 || wgs + L.n * T > 128) break;
-      wgs += L.n * T; --lt;
-    }
-    dev.tree_top0 = nlev - lt >= 2 ? lt : nlev;
-    dev.h_tree_fill.clear();
-    for (int l = 0; l < nlev; ++l)
-      if (l < dev.tree_levels || l >= dev.tree_top0)
-        for (int i = dev.lev[l].first; i < dev.lev[l].first + dev.lev[l].n; ++i)
-          for (int q = 0; q < dev.h_own_dims[i]; ++q) dev.h_tree_fill.push_back(dev.h_gidx[dev.h_own_g[i] + q]);
-  }
-  // ---- shard policy 1 (distributed top): per panel of every top level, what is exchanged and which trailing-update tiles this rank applies
-  dev.dist = sh && hp.shard_policy == 1;
-  dev.dist_lead = rank == 0;
-  dev.h_dist_ent.clear(); dev.h_dist_tri.clear(); dev.dist_buf_elems = 0; dev.dist_solve_elems = 0;
-  if (dev.dist) {
-    const int world = std::max(hp.world, 1);
-    for (int l = Hs; l < nlev; ++l) {
-      NdLevel& L = dev.lev[l];
-      const int np = L.nI / 256, T = L.ntot / kTile, tI = L.nI / kTile;
-      L.dx_first.assign(np, 0); L.dx_nt.assign(np, 0); L.dx_nr.assign(np, 0); L.dt_first.assign(np, 0); L.dt_cnt.assign(np, 0);
-      for (int P = 0; P < np; ++P) {
-        const int t0 = 2 * P, tb = t0 + 2;
-        // exchange: the live tiles of the panel's real tile columns, from the diagonal down, then 256 right-hand-side rows, of every front whose
-        // interior reaches the panel (the others hold identity padding there, the same on every rank)
-        L.dx_first[P] = (int)dev.h_dist_ent.size() / 4;
-        for (int pass = 0; pass < 2; ++pass)
-          for (int k = 0; k < L.n; ++k) {
-            const int i = L.first + k, nIr = L.live_h[2 * k], nO = L.live_h[2 * k + 1], Tn = ld[i] / kTile;
-            if (t0 >= nIr) continue;
-            auto live = [&](int t) { return t < nIr || (t >= tI && t - tI < nO); };
-            if (pass == 1) {
-              const int rows = std::min(256, ld[i] - t0 * kTile);
-              dev.h_dist_ent.insert(dev.h_dist_ent.end(), {i, t0 * kTile, rows, 1});
-              ++L.dx_nr[P];
-              continue;
-            }
-            for (int c = t0; c < std::min(t0 + 2, nIr); ++c)
-              for (int t = c; t < Tn; ++t)
-                if (live(t)) { dev.h_dist_ent.insert(dev.h_dist_ent.end(), {i, t, c, 0}); ++L.dx_nt[P]; }
-          }
-        const size_t elems = (size_t)L.dx_nt[P] * kTile * kTile + (size_t)L.dx_nr[P] * 256;
-        dev.dist_buf_elems = std::max(dev.dist_buf_elems, elems);
-        dev.dist_solve_elems += elems;
-        // owned trailing-update tiles (i, j), j <= i, relative to tile tb: tile row owner by nd_tile_owner on the front's compact rows (real interior
-        // tiles, then border tiles); XCD-balanced as k_chol.hip's live_tile_list (whole 8x8 supertiles of a front to the shortest of 8 queues, interleaved)
-        std::vector<int> q[8];
-        for (int k = 0; k < L.n; ++k) {
-          const int i = L.first + k, nIr = L.live_h[2 * k], nO = L.live_h[2 * k + 1], node = order[i];
-          if (t0 >= nIr) continue;
-          auto live = [&](int t) { return t < nIr || (t >= tI && t - tI < nO); };
-          auto mine = [&](int t) { return nd_tile_owner(node, t < tI ? t : nIr + (t - tI), world) == rank; };
-          const int nt = T - tb, Ts = (nt + 7) / 8;
-          for (int si = 0; si < Ts; ++si)
-            for (int sj = 0; sj <= si; ++sj) {
-              std::vector<int> grp;
-              for (int a = 8 * si; a < std::min(nt, 8 * si + 8); ++a) {
-                if (!live(tb + a) || !mine(tb + a)) continue;
-                for (int b = 8 * sj; b < std::min(a + 1, 8 * sj + 8); ++b) if (live(tb + b)) grp.push_back((k << 20) | (a << 10) | b);
-              }
-              if (grp.empty()) continue;
-              int best = 0;
-              for (int x = 1; x < 8; ++x) if (q[x].size() < q[best].size()) best = x;
-              q[best].insert(q[best].end(), grp.begin(), grp.end());
-            }
-        }
-        size_t longest = 0;
-        for (int x = 0; x < 8; ++x) longest = std::max(longest, q[x].size());
-        L.dt_first[P] = (int)dev.h_dist_tri.size();
-        L.dt_cnt[P] = (int)(8 * longest);
-        dev.h_dist_tri.resize(dev.h_dist_tri.size() + 8 * longest, -1);
-        for (int x = 0; x < 8; ++x) for (size_t e = 0; e < q[x].size(); ++e) dev.h_dist_tri[L.dt_first[P] + 8 * e + x] = q[x][e];
-      }
-    }
-    dev.dist_solve_elems += 2 * dev.h_top_g.size();   // gradient and diag(J^T J) of the top unknowns
-  }
-  dev.active = true;
-}
 
 // ------------------------------------------------------------------------------------------------ device kernels
 struct NdLevArgs {
@@ -396,12 +36,6 @@ struct NdLevArgs {
 // (ONE launch over the tiles of all levels — a level per launch was seven dependent host enqueues at the head of every linearisation,
 //  with the chip idle behind them: blocks [blk0[l], blk0[l + 1]) belong to level l, tile (tr, tc) of its front number `fz`)
 struct NdZeroArgs { int nlev; int first[24], n[24], nI[24], T[24]; long long blk0[25]; const int *own_dims, *st_dims, *bb_off, *bb; int first_top; };
-// COVGPU_BETA0 (on unless 0): the first rank update of a border x border tile no child adds into starts it from zero (GemmArgs::beta0), and the
-// extend-add stores the tiles a child does add into whole — k_nd_zero clears neither. Off: k_nd_zero clears every border tile (round 5's form).
-static bool nd_beta0() {
-  static const bool v = env_int("COVGPU_BETA0", 1) != 0;
-  return v;
-}
 __global__ __launch_bounds__(256) void k_nd_zero(DevProblem P, NdZeroArgs z) {
   int l = 0;
   while (l + 1 < z.nlev && (long long)blockIdx.x >= z.blk0[l + 1]) ++l;
@@ -684,6 +318,15 @@ __global__ __launch_bounds__(256) void k_nd_panel_xfer(DevProblem P, const int4*
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
+// the switches of the driver, read once when the library loads
+static const bool kLookahead = env_int("COVGPU_ND_LOOKAHEAD", 1) != 0;   // look-ahead across the levels of the tree (FrontRun::run_levels)
+static const bool kFusedBwd = env_int("COVGPU_ND_BWD_FUSED", 1) != 0;    // backward substitution as one launch per level (0: one per tile)
+static const bool kBwdTree = env_int("COVGPU_BWD_TREE", 1) != 0;         // ... and as one launch per group of levels (0: a launch per level)
+static const bool kExtRecords = env_int("COVGPU_EXT_RECORDS", 1) != 0;   // extend-add from records (0: through the round-5 tables, k_nd_extend)
+// COVGPU_BETA0 (on unless 0): the first rank update of a border x border tile no child adds into starts it from zero (GemmArgs::beta0), and the
+// extend-add stores the tiles a child does add into whole — k_nd_zero clears neither. Off: k_nd_zero clears every border tile (round 5's form).
+static const bool kBeta0 = env_int("COVGPU_BETA0", 1) != 0;
+
 static NdLevArgs lev_args(const DevProblem& P, const NdDev& nd, int l) {
   const NdLevel& L = nd.lev[l];
   return NdLevArgs{L.first, L.n, L.nI, L.ntot, P.nd_rhs + L.rhs_off, nd.own_dims, nd.st_dims, nd.own_g, nd.st_g, nd.gidx, nd.inv_off, nd.inv};
@@ -695,9 +338,9 @@ void launch_nd_init(const DevProblem& P, const NdDev& nd, hipStream_t st) {
 
 void launch_nd_zero(const DevProblem& P, const NdDev& nd, hipStream_t st) {
   NdZeroArgs z;
-  z.nlev = 0; z.blk0[0] = 0; z.own_dims = nd.own_dims; z.st_dims = nd.st_dims; z.bb_off = nd.bb_off; z.bb = nd_beta0() ? nd.bb : nullptr;
+  z.nlev = 0; z.blk0[0] = 0; z.own_dims = nd.own_dims; z.st_dims = nd.st_dims; z.bb_off = nd.bb_off; z.bb = kBeta0 ? nd.bb : nullptr;
   // nodes are numbered in level order: the first node of the first top level (sharded solve) — below it the extend-add stores the border tiles
-  z.first_top = !nd_beta0() ? 0 : (nd.top_lev0 < (int)nd.lev.size() ? nd.lev[nd.top_lev0].first : nd.nnodes);
+  z.first_top = !kBeta0 ? 0 : (nd.top_lev0 < (int)nd.lev.size() ? nd.lev[nd.top_lev0].first : nd.nnodes);
   auto flush = [&] {
     if (z.nlev > 0 && z.blk0[z.nlev] > 0) hipLaunchKernelGGL(k_nd_zero, dim3((unsigned)z.blk0[z.nlev]), dim3(256), 0, st, P, z);
     z.nlev = 0; z.blk0[0] = 0;
@@ -715,89 +358,100 @@ void launch_nd_zero(const DevProblem& P, const NdDev& nd, hipStream_t st) {
   flush();
 }
 
-bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hipStream_t st, CholAux& ax) {
-  const int nlev = (int)nd.lev.size(), ltop = nd.top_lev0;
-  static const bool lookahead = env_int("COVGPU_ND_LOOKAHEAD", 1) != 0;
-  ax.init();
-  {  // scratch of the one-launch backward substitution (k_bwd_front): [fronts][interior tiles <= 4][256-row chunks of the border][128]
-    size_t need = 0;
-    for (const NdLevel& L : nd.lev)
-      need = std::max(need, (size_t)L.n * std::min(kBwdFrontMaxTiles, (L.own_max + kTile - 1) / kTile) * std::max(1, (L.ntot - L.nI + 255) / 256) * kTile);
-    if (need > ax.bwd_scr_elems) {
-      if (ax.bwd_scr) (void)hipFree(ax.bwd_scr);
-      ax.bwd_scr = nullptr; ax.bwd_scr_elems = 0;
-      if (hipMalloc((void**)&ax.bwd_scr, need * sizeof(double)) != hipSuccess) { ax.bwd_scr = nullptr; return false; }   // (nothing enqueued yet)
-      ax.bwd_scr_elems = need;
+// One linear solve as steps: what launch_nd_solve's arguments and the steps share. Every enqueue of the solve is made by one of the members; the order
+// of the members in launch_nd_solve is the order on the stream.
+struct FrontRun {
+  const DevProblem& P; NdDev& nd; double* dst; const double mu; hipStream_t st; CholAux& ax;
+  const int nlev, ltop;   // levels | first top level (== nlev: none)
+  bool tree_on = false, tree_top_on = false;   // the bottom | top levels' backward substitution as one launch (set by ensure_scratch)
+  FrontRun(const DevProblem& P_, NdDev& nd_, double* dst_, double mu_, hipStream_t st_, CholAux& ax_)
+      : P(P_), nd(nd_), dst(dst_), mu(mu_), st(st_), ax(ax_), nlev((int)nd_.lev.size()), ltop(nd_.top_lev0) {}
+  // leaves both scratches of the backward substitution large enough for this tree, and tree_on / tree_top_on. false: allocation failed, nothing enqueued
+  bool ensure_scratch() {
+    {  // scratch of the one-launch backward substitution (k_bwd_front): [fronts][interior tiles <= 4][256-row chunks of the border][128]
+      size_t need = 0;
+      for (const NdLevel& L : nd.lev)
+        need = std::max(need, (size_t)L.n * std::min(kBwdFrontMaxTiles, (L.own_max + kTile - 1) / kTile) * std::max(1, (L.ntot - L.nI + 255) / 256) * kTile);
+      if (need > ax.bwd_scr_elems) {
+        if (ax.bwd_scr) (void)hipFree(ax.bwd_scr);
+        ax.bwd_scr = nullptr; ax.bwd_scr_elems = 0;
+        if (hipMalloc((void**)&ax.bwd_scr, need * sizeof(double)) != hipSuccess) { ax.bwd_scr = nullptr; return false; }   // (nothing enqueued yet)
+        ax.bwd_scr_elems = need;
+      }
     }
-  }
-  if (!ax.pipe_broken && ax.gate_dead != nullptr && ax.gate_dead_h != nullptr) {  // scratch of the pipelined backward substitution (k_bwd_pipe): [fronts][interior tiles][chunks + 1][128], filled once
-    size_t need = 0;
-    for (const NdLevel& L : nd.lev) {
-      const int T = std::min(L.nI / kTile, (L.own_max + kTile - 1) / kTile);
-      if (L.n > 0 && bwd_pipe_on() && T >= kBwdPipeMinTiles) need = std::max(need, (size_t)L.n * T * ((L.ntot - L.nI + kPipeChunk - 1) / kPipeChunk + 1) * kTile);
-    }
-    {
-      size_t tree = 0, tree2 = 0;
-      for (int l = 0; l < (int)nd.lev.size(); ++l) {
+    if (!ax.pipe_broken && ax.gate_dead != nullptr && ax.gate_dead_h != nullptr) {  // scratch of the pipelined backward substitution (k_bwd_pipe): [fronts][interior tiles][chunks + 1][128], filled once
+      size_t need = 0, tree = 0, tree2 = 0;   // a level of its own | the bottom | the top levels in one launch
+      for (int l = 0; l < nlev; ++l) {
         const NdLevel& L = nd.lev[l];
-        const size_t e = (size_t)L.n * std::min(L.nI / kTile, (L.own_max + kTile - 1) / kTile) * ((L.ntot - L.nI + kPipeChunk - 1) / kPipeChunk + 1) * kTile;
-        if (l < nd.tree_levels) tree += e;
-        if (l >= nd.tree_top0) tree2 += e;
+        if (L.n > 0 && bwd_pipe_on() && L.interior_tiles() >= kBwdPipeMinTiles) need = std::max(need, L.pipe_scratch_elems());
+        if (l < nd.tree_levels) tree += L.pipe_scratch_elems();
+        if (l >= nd.tree_top0) tree2 += L.pipe_scratch_elems();
       }
       need = std::max(need, std::max(tree, tree2));
+      if (need > ax.bwd_pipe_elems) {
+        if (ax.bwd_pipe) { (void)hipDeviceSynchronize(); (void)hipFree(ax.bwd_pipe); }
+        ax.bwd_pipe = nullptr; ax.bwd_pipe_elems = 0;
+        if (hipMalloc((void**)&ax.bwd_pipe, need * sizeof(double)) == hipSuccess) {
+          ax.bwd_pipe_elems = need;
+          launch_pipe_fill(ax.bwd_pipe, need, st);   // (stream-ordered before the first use)
+        } else ax.bwd_pipe = nullptr;                // (launch per tile)
+      }
     }
-    if (need > ax.bwd_pipe_elems) {
-      if (ax.bwd_pipe) { (void)hipDeviceSynchronize(); (void)hipFree(ax.bwd_pipe); }
-      ax.bwd_pipe = nullptr; ax.bwd_pipe_elems = 0;
-      if (hipMalloc((void**)&ax.bwd_pipe, need * sizeof(double)) == hipSuccess) {
-        ax.bwd_pipe_elems = need;
-        launch_pipe_fill(ax.bwd_pipe, need, st);   // (stream-ordered before the first use)
-      } else ax.bwd_pipe = nullptr;                // (launch per tile)
-    }
+    // the bottom levels' backward substitution as one launch (k_bwd_tree): needs the pipeline (not COVGPU_BWD_PIPE=0), its scratch and the give-up word
+    const bool tree_ok = kBwdTree && kFusedBwd && nd.tree_fill != nullptr && !ax.pipe_broken && ax.bwd_pipe != nullptr && ax.gate_dead != nullptr && bwd_pipe_on();
+    tree_on = tree_ok && nd.tree_levels >= 2;
+    tree_top_on = tree_ok && nd.tree_top0 < nlev;
+    return true;
   }
-  static const bool fused_bwd = env_int("COVGPU_ND_BWD_FUSED", 1) != 0;
-  static const bool tree_env = env_int("COVGPU_BWD_TREE", 1) != 0;
-  // the bottom levels' backward substitution as one launch (k_bwd_tree): needs the pipeline (not COVGPU_BWD_PIPE=0), its scratch and the give-up word
-  const bool tree_ok = tree_env && fused_bwd && nd.tree_fill != nullptr && !ax.pipe_broken && ax.bwd_pipe != nullptr && ax.gate_dead != nullptr && bwd_pipe_on();
-  const bool tree_on = tree_ok && nd.tree_levels >= 2;
-  const bool tree_top_on = tree_ok && nd.tree_top0 < (int)nd.lev.size();
-  ax.mark(st, -1);
+  // leaves the speed-bias part of the system and the right-hand side in the fronts, and the one-launch levels' entries of dst "empty"
   // (the right-hand sides were cleared on the head stream of the build, beside the fronts: solver.hip enqueue_build)
-  {
+  void assemble() {
+    ax.mark(st, -1);
     const int nfill = (tree_on || tree_top_on) ? (int)nd.h_tree_fill.size() : 0;
     const int cnt = std::max(std::max(P.vi ? 324 * P.K : 0, P.n), nfill);
     hipLaunchKernelGGL(k_nd_assemble, dim3((cnt + 255) / 256), dim3(256), 0, st, P, (const int*)nd.rhs_node, dst, (const int*)nd.tree_fill, nfill, pipe_empty_word());
+    ax.mark(st, -2);
   }
-  ax.mark(st, -2);
-  auto batch = [&](int l) {
+  // level l's fronts as a batch of the dense factorisation
+  DenseBatch batch(int l) const {
     const NdLevel& L = nd.lev[l];
     DenseBatch bt;
     bt.n = L.n; bt.sM = 0; bt.sL = (size_t)L.nI * kTile; bt.sR = (size_t)2 * L.ntot;
     bt.live = L.live; bt.tI = L.nI / kTile; bt.live_h = L.live_h.data();
-    if (nd_beta0() && nd.bb != nullptr) { bt.beta0_off = nd.bb_off + L.first; bt.beta0 = nd.bb; }
+    if (kBeta0 && nd.bb != nullptr) { bt.beta0_off = nd.bb_off + L.first; bt.beta0 = nd.bb; }
     if (L.plist != nullptr) { bt.plist = L.plist; bt.pbig_h = L.pbig.data(); bt.psmall_h = L.psmall.data(); }
     bt.tab = P.nd_ntab + 2 * (size_t)L.first; bt.tri_slot = l; bt.own_max = L.own_max; bt.own_dims = nd.own_dims + L.first; bt.own_dims_h = nd.h_own_dims.data() + L.first;
     return bt;
-  };
-  // part: 0 all tiles | 1 the tiles of the fronts' first 256 rows | 2 the others
-  auto extend = [&](int l, bool top_children, int part, hipStream_t s2, DevSignal sig = DevSignal()) -> bool {
+  }
+  // fronts <-> solution vector for a batch whose first front is `first`: the ancestors' unknowns are read from dst by the first launch of a
+  // level's backward substitution, the fronts' own unknowns are written there by its last
+  BwdXfer xfer(int first) const {
+    BwdXfer xf;
+    xf.gidx = nd.gidx; xf.own_g = nd.own_g; xf.st_g = nd.st_g; xf.own_dims = nd.own_dims; xf.st_dims = nd.st_dims; xf.x = dst; xf.first = first;
+    return xf;
+  }
+  // extend-add into level l's fronts from their children of one kind, on stream s2. part: 0 all tiles | 1 the tiles of the fronts' first 256 rows |
+  // 2 the others. true: something was enqueued
+  bool extend(int l, bool top_children, int part, hipStream_t s2, DevSignal sig = DevSignal()) {
     const NdLevel& L = nd.lev[l];
     int first = top_children ? L.ext2_first : L.ext_first, count = top_children ? L.ext2_count : L.ext_count;
     const int countA = top_children ? L.ext2_countA : L.ext_countA;
     if (part == 1) count = countA;
     if (part == 2) { first += countA; count -= countA; }
-    static const bool records = env_int("COVGPU_EXT_RECORDS", 1) != 0;
-    if (count > 0) { form_hit(records && nd.extr != nullptr ? KF_ND_EXTEND_REC : KF_ND_EXTEND); if (part != 0) form_hit(KF_ND_EXTEND_SPLIT); }
-    if (count > 0 && records && nd.extr != nullptr)
+    const bool records = kExtRecords && nd.extr != nullptr;
+    const int store_border = (!top_children && l < ltop && kBeta0) ? 1 : 0;
+    if (count > 0) { form_hit(records ? KF_ND_EXTEND_REC : KF_ND_EXTEND); if (part != 0) form_hit(KF_ND_EXTEND_SPLIT); }
+    if (count > 0 && records)
       hipLaunchKernelGGL(k_nd_extend_rec, dim3(count), dim3(256), 0, s2, P, lev_args(P, nd, l), (const int*)(nd.extr + (size_t)kExtRec * first),
-                         (const int*)(nd.extr + (size_t)kExtRec * nd.ext_over), top_children ? 1 : 0, (!top_children && l < ltop && nd_beta0()) ? 1 : 0, sig);
+                         (const int*)(nd.extr + (size_t)kExtRec * nd.ext_over), top_children ? 1 : 0, store_border, sig);
     else if (count > 0)
       hipLaunchKernelGGL(k_nd_extend, dim3(count), dim3(256), 0, s2, P, lev_args(P, nd, l), (const int*)(nd.extw + 8 * (size_t)first),
-                         (const int*)(top_children ? nd.extc2 : nd.extc), top_children ? 1 : 0, (!top_children && l < ltop && nd_beta0()) ? 1 : 0, sig);
+                         (const int*)(top_children ? nd.extc2 : nd.extc), top_children ? 1 : 0, store_border, sig);
     return count > 0;
-  };
-  // split: the trailing update of this level's last panel is split for the look-ahead into the next level (DenseBatch::split_ta)
-  auto factor = [&](int l, bool split, hipEvent_t pre_trsm) {
+  }
+  // partial factorisation of level l's fronts. split: the trailing update of this level's last panel is split for the look-ahead into the next
+  // level (DenseBatch::split_ta)
+  void factor(int l, bool split, hipEvent_t pre_trsm) {
     const NdLevel& L = nd.lev[l];
     ax.mark(st, -3);
     if (L.n > 0) {
@@ -806,11 +460,11 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
       dense_cholesky_solve_raw(P.nd_M, P.nd_rhs + L.rhs_off, P.nd_Linv + L.linv_off, P.flag, L.ntot, st, ax, L.nI / kTile, false, bt);
     }
     ax.mark(st, -4);
-  };
+  }
   // Levels [l0, l1) one after the other, with a look-ahead across the level boundary: of level l's last trailing update only the
   // tiles its parents' first panel receives run on the chain's stream, followed by that part of the extend-add and the parents'
   // first panel; the rest of the update and of the extend-add run beside it on the bulk stream (ax.aux).
-  auto run_levels = [&](int l0, int l1, bool top_children) {
+  void run_levels(int l0, int l1, bool top_children) {
     bool prev_split = false;
     for (int l = l0; l < l1; ++l) {
       hipEvent_t pre = nullptr;
@@ -827,77 +481,69 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
         pre = ax.ev_xb;
       } else extend(l, top_children, 0, st);
       const NdLevel& L = nd.lev[l];
-      const bool split = lookahead && l + 1 < l1 && L.n > 0 && nd.lev[l + 1].n > 0 && L.split_ta > 0;
+      const bool split = kLookahead && l + 1 < l1 && L.n > 0 && nd.lev[l + 1].n > 0 && L.split_ta > 0;
       factor(l, split, pre);
       prev_split = split;
     }
-  };
-  // ---- the subtrees of this rank (single GPU: the whole tree), level by level
-  run_levels(0, ltop, false);
-  if (ltop < nlev && !nd.dist) {
-    // ---- agent-sharded solve: the top fronts so far hold THIS rank's residuals and subtrees only. One
-    //      all-reduce over [top fronts | their right-hand sides | grad, hdiag of the top unknowns] (contiguous), then the
-    //      damping of the top unknowns; from here on every rank runs the top of the tree redundantly, with no further exchange.
-    for (int l = ltop; l < nlev; ++l) extend(l, false, 0, st);
+  }
+  // sharded solve, either policy: gradient and diag(J^T J) of the top unknowns summed over the ranks — packed behind the top right-hand sides, the
+  // policy's all-reduce, unpacked — then the damping of the top unknowns (lead: this rank's copy takes it; the replicated top: every rank's)
+  void top_gh_damp(bool lead) {
     double* gh = P.nd_rhs + nd.gh_off;
+    const unsigned nb = (unsigned)((nd.ntop + 255) / 256);
     if (nd.ntop > 0) { form_hit(KF_ND_GH, 2); form_hit(KF_ND_TOP_DAMP); }
-    if (ax.reduce != nullptr && nd.n_top_tiles > 0) form_hit(KF_ND_TOP_PACK, 2);
-    if (nd.ntop > 0) hipLaunchKernelGGL(k_nd_gh, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 0);
-    if (ax.reduce != nullptr) {
-      // ONE all-reduce of [live lower tiles of the top fronts, packed | top right-hand sides | grad, hdiag of the top unknowns]: the
-      // fronts are stored as full squares, of which the exchange needs half (33.6 -> 17.9 MB for the 5-agent map's root)
-      const size_t ntile = (size_t)nd.n_top_tiles * kTile * kTile, nvec = nd.rhs_top + 2 * (size_t)nd.ntop;
-      if (nd.n_top_tiles > 0) hipLaunchKernelGGL(k_nd_top_pack, dim3(nd.n_top_tiles), dim3(256), 0, st, P, (const int*)nd.top_tiles, nd.top_pack, 0);
-      if (nvec > 0) (void)hipMemcpyAsync(nd.top_pack + ntile, P.nd_rhs, nvec * sizeof(double), hipMemcpyDeviceToDevice, st);
-      ax.reduce(ax.reduce_ctx, nd.top_pack, ntile + nvec, 0, st);
-      if (nd.n_top_tiles > 0) hipLaunchKernelGGL(k_nd_top_pack, dim3(nd.n_top_tiles), dim3(256), 0, st, P, (const int*)nd.top_tiles, nd.top_pack, 1);
-      if (nvec > 0) (void)hipMemcpyAsync(P.nd_rhs, nd.top_pack + ntile, nvec * sizeof(double), hipMemcpyDeviceToDevice, st);
-    }
+    if (nd.ntop > 0) hipLaunchKernelGGL(k_nd_gh, dim3(nb), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 0);
+    if (!nd.dist) reduce_top_replicated();
+    else if (nd.ntop > 0 && ax.reduce != nullptr) ax.reduce(ax.reduce_ctx, gh, 2 * (size_t)nd.ntop, 0, st);
     if (nd.ntop > 0) {
-      hipLaunchKernelGGL(k_nd_gh, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 1);
-      hipLaunchKernelGGL(k_nd_top_damp, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_var, (const int*)nd.top_r, (const int*)nd.top_g, nd.ntop,
-                         (const int*)nd.rhs_node, mu, 1);
+      hipLaunchKernelGGL(k_nd_gh, dim3(nb), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 1);
+      hipLaunchKernelGGL(k_nd_top_damp, dim3(nb), dim3(256), 0, st, P, (const int*)nd.top_var, (const int*)nd.top_r, (const int*)nd.top_g, nd.ntop,
+                         (const int*)nd.rhs_node, mu, lead ? 1 : 0);
     }
-    run_levels(ltop, nlev, true);
-  } else if (ltop < nlev) {
-    // ---- distributed top (shard policy 1): the top fronts stay SUMS over the ranks' copies. One all-reduce of gradient and
-    //      diag(J^T J) of the top unknowns, the damping on the lead rank's copy; then per top level the extend-add of the top children (partial
-    //      sums added to partial sums) and the panels one at a time — each panel's column block and right-hand-side rows all-reduced when it
-    //      becomes the panel (dense_cholesky_dist). Everything of the top runs on this one stream: the subtree levels above joined it, so no
-    //      gate on another stream waits for anything enqueued behind an all-reduce.
-    for (int l = ltop; l < nlev; ++l) extend(l, false, 0, st);
-    double* gh = P.nd_rhs + nd.gh_off;
-    if (nd.ntop > 0) {
-      form_hit(KF_ND_GH, 2); form_hit(KF_ND_TOP_DAMP);
-      hipLaunchKernelGGL(k_nd_gh, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 0);
-      if (ax.reduce != nullptr) ax.reduce(ax.reduce_ctx, gh, 2 * (size_t)nd.ntop, 0, st);
-      hipLaunchKernelGGL(k_nd_gh, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_g, nd.ntop, gh, 1);
-      hipLaunchKernelGGL(k_nd_top_damp, dim3((nd.ntop + 255) / 256), dim3(256), 0, st, P, (const int*)nd.top_var, (const int*)nd.top_r, (const int*)nd.top_g, nd.ntop,
-                         (const int*)nd.rhs_node, mu, nd.dist_lead ? 1 : 0);
-    }
-    struct XCtx { const DevProblem* P; NdDev* nd; const NdLevel* L; CholAux* ax; hipStream_t st; };
-    auto xchg = [](void* vc, int Pp) {
-      XCtx& x = *static_cast<XCtx*>(vc);
-      const NdLevel& L = *x.L;
-      const int nt = L.dx_nt[Pp], ne = nt + L.dx_nr[Pp];
-      if (ne == 0 || x.ax->reduce == nullptr) return;
-      const int4* ent = reinterpret_cast<const int4*>(x.nd->dist_ent) + L.dx_first[Pp];
-      const size_t n = (size_t)nt * kTile * kTile + (size_t)L.dx_nr[Pp] * 256;
-      form_hit(KF_ND_PANEL_XFER, 2);
-      hipLaunchKernelGGL(k_nd_panel_xfer, dim3(ne), dim3(256), 0, x.st, *x.P, ent, nt, x.nd->dist_buf, (const int*)x.nd->rhs_node, (const int*)x.nd->own_dims, 0,
-                         x.nd->dist_lead ? 1 : 0);
-      x.ax->reduce(x.ax->reduce_ctx, x.nd->dist_buf, n, 0, x.st);
-      hipLaunchKernelGGL(k_nd_panel_xfer, dim3(ne), dim3(256), 0, x.st, *x.P, ent, nt, x.nd->dist_buf, (const int*)x.nd->rhs_node, (const int*)x.nd->own_dims, 1,
-                         x.nd->dist_lead ? 1 : 0);
-    };
+  }
+  // Agent-sharded solve: the top fronts so far hold THIS rank's residuals and subtrees only. ONE all-reduce of [live lower tiles
+  // of the top fronts, packed | top right-hand sides | grad, hdiag of the top unknowns] (the last two contiguous in nd_rhs): the fronts are stored
+  // as full squares, of which the exchange needs half (33.6 -> 17.9 MB for the 5-agent map's root). From here on every rank runs the top of the
+  // tree redundantly, with no further exchange.
+  void reduce_top_replicated() {
+    if (ax.reduce == nullptr) return;
+    if (nd.n_top_tiles > 0) form_hit(KF_ND_TOP_PACK, 2);
+    const size_t ntile = (size_t)nd.n_top_tiles * kTile * kTile, nvec = nd.rhs_top + 2 * (size_t)nd.ntop;
+    if (nd.n_top_tiles > 0) hipLaunchKernelGGL(k_nd_top_pack, dim3(nd.n_top_tiles), dim3(256), 0, st, P, (const int*)nd.top_tiles, nd.top_pack, 0);
+    if (nvec > 0) (void)hipMemcpyAsync(nd.top_pack + ntile, P.nd_rhs, nvec * sizeof(double), hipMemcpyDeviceToDevice, st);
+    ax.reduce(ax.reduce_ctx, nd.top_pack, ntile + nvec, 0, st);
+    if (nd.n_top_tiles > 0) hipLaunchKernelGGL(k_nd_top_pack, dim3(nd.n_top_tiles), dim3(256), 0, st, P, (const int*)nd.top_tiles, nd.top_pack, 1);
+    if (nvec > 0) (void)hipMemcpyAsync(P.nd_rhs, nd.top_pack + ntile, nvec * sizeof(double), hipMemcpyDeviceToDevice, st);
+  }
+  // distributed top: panel Pp of level x.L becomes the panel — its column block and right-hand-side rows all-reduced (DistPanels::exchange)
+  struct XCtx { FrontRun* run; const NdLevel* L; };
+  static void exchange_panel(void* vc, int Pp) {
+    const XCtx& x = *static_cast<XCtx*>(vc);
+    const FrontRun& r = *x.run;
+    const NdLevel& L = *x.L;
+    const int nt = L.dx_nt[Pp], ne = nt + L.dx_nr[Pp];
+    if (ne == 0 || r.ax.reduce == nullptr) return;
+    const int4* ent = reinterpret_cast<const int4*>(r.nd.dist_ent) + L.dx_first[Pp];
+    const size_t n = (size_t)nt * kTile * kTile + (size_t)L.dx_nr[Pp] * 256;
+    const int lead = r.nd.dist_lead ? 1 : 0;
+    form_hit(KF_ND_PANEL_XFER, 2);
+    hipLaunchKernelGGL(k_nd_panel_xfer, dim3(ne), dim3(256), 0, r.st, r.P, ent, nt, r.nd.dist_buf, (const int*)r.nd.rhs_node, (const int*)r.nd.own_dims, 0, lead);
+    r.ax.reduce(r.ax.reduce_ctx, r.nd.dist_buf, n, 0, r.st);
+    hipLaunchKernelGGL(k_nd_panel_xfer, dim3(ne), dim3(256), 0, r.st, r.P, ent, nt, r.nd.dist_buf, (const int*)r.nd.rhs_node, (const int*)r.nd.own_dims, 1, lead);
+  }
+  // Distributed top (shard policy 1): the top fronts stay SUMS over the ranks' copies. Per top level the extend-add of the top
+  // children (partial sums added to partial sums) and the panels one at a time — each panel's column block and right-hand-side rows all-reduced
+  // when it becomes the panel (dense_cholesky_dist). Everything of the top runs on this one stream: the subtree levels above joined it, so no
+  // gate on another stream waits for anything enqueued behind an all-reduce.
+  void dist_levels() {
     for (int l = ltop; l < nlev; ++l) {
       extend(l, true, 0, st);
       const NdLevel& L = nd.lev[l];
       ax.mark(st, -3);
       if (L.n > 0) {
-        XCtx xc{&P, &nd, &L, &ax, st};
+        XCtx xc{this, &L};
         DistPanels d;
-        d.np = (int)L.dx_nt.size(); d.tri = L.dt_dev.data(); d.tri_cnt = L.dt_cnt.data(); d.lead = nd.dist_lead; d.exchange = xchg; d.ctx = &xc;
+        d.np = (int)L.dx_nt.size(); d.tri = L.dt_dev.data(); d.tri_cnt = L.dt_cnt.data(); d.lead = nd.dist_lead; d.exchange = exchange_panel; d.ctx = &xc;
         DenseBatch bt = batch(l);
         bt.beta0 = nullptr; bt.beta0_off = nullptr;   // (top fronts: every border tile is cleared and read)
         dense_cholesky_dist(P.nd_M, P.nd_rhs + L.rhs_off, P.nd_Linv + L.linv_off, P.flag, L.ntot, st, ax, L.nI / kTile, bt, d);
@@ -905,37 +551,50 @@ bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hip
       ax.mark(st, -4);
     }
   }
-  auto tree_launch = [&](int l_hi, int l_lo, bool form64) {   // levels l_hi .. l_lo (downwards) in one launch
+  // backward substitution of levels l_hi .. l_lo (downwards) in one launch
+  void tree_launch(int l_hi, int l_lo, bool form64) {
     BwdTreeLevel tl[kBwdTreeMax];
     int nq = 0;
     for (int l = l_hi; l >= l_lo; --l) {
       const NdLevel& L = nd.lev[l];
       BwdTreeLevel& t = tl[nq++];
-      t.nbt = L.n; t.T = std::min(L.nI / kTile, (L.own_max + kTile - 1) / kTile); t.nchunk = (L.ntot - L.nI + kPipeChunk - 1) / kPipeChunk; t.tI = L.nI / kTile; t.first = L.first;
+      t.nbt = L.n; t.T = L.interior_tiles(); t.nchunk = L.pipe_chunks(); t.tI = L.nI / kTile; t.first = L.first;
       t.y = P.nd_rhs + L.rhs_off + L.ntot; t.bsR = (size_t)2 * L.ntot; t.Dinv = P.nd_Linv + L.linv_off; t.bsL = (size_t)L.nI * kTile;
       t.btab = P.nd_ntab + 2 * (size_t)L.first; t.live = L.live; t.scr_off = t.xpub_off = 0;
     }
-    BwdXfer xf;
-    xf.gidx = nd.gidx; xf.own_g = nd.own_g; xf.st_g = nd.st_g; xf.own_dims = nd.own_dims; xf.st_dims = nd.st_dims; xf.x = dst; xf.first = 0;
-    launch_bwd_tree(P.nd_M, tl, nq, xf, ax.bwd_pipe, ax.gate_dead, ax.gate_dead_h, ax.gate_timeout_s, st, form64);
-    ax.mark(st, -5);
-  };
-  if (tree_top_on) tree_launch(nlev - 1, nd.tree_top0, true);
-  for (int l = (tree_top_on ? nd.tree_top0 : nlev) - 1; l >= (tree_on ? nd.tree_levels : 0); --l) {
-    // top-down: the ancestors' unknowns are read from `dst` by the first launch of the level, the fronts' own unknowns are
-    // written there by its last (BwdXfer)
-    const NdLevel& L = nd.lev[l];
-    if (L.n == 0) continue;
-    DenseBatch bt = batch(l);
-    bt.xfer.gidx = nd.gidx; bt.xfer.own_g = nd.own_g; bt.xfer.st_g = nd.st_g; bt.xfer.own_dims = nd.own_dims; bt.xfer.st_dims = nd.st_dims;
-    bt.xfer.x = dst; bt.xfer.first = L.first;
-    bt.bwd_cnt = fused_bwd ? ax.bwd_cnt : nullptr; bt.bwd_scr = ax.bwd_scr;
-    if (fused_bwd && !ax.pipe_broken && ax.bwd_pipe != nullptr) { bt.bwd_pipe = ax.bwd_pipe; bt.pipe_dead = ax.gate_dead; bt.pipe_dead_h = ax.gate_dead_h; bt.pipe_timeout_s = ax.gate_timeout_s; }
-    dense_backward_solve(P.nd_M, P.nd_rhs + L.rhs_off, P.nd_Linv + L.linv_off, L.ntot, st, L.nI / kTile, L.ntot / kTile, bt);
+    launch_bwd_tree(P.nd_M, tl, nq, xfer(0), ax.bwd_pipe, ax.gate_dead, ax.gate_dead_h, ax.gate_timeout_s, st, form64);
     ax.mark(st, -5);
   }
-  if (tree_on) tree_launch(nd.tree_levels - 1, 0, false);   // levels tree_levels - 1 .. 0 in one launch
-  ax.mark(st, -6);
+  // backward substitution, top-down: the top group in one launch, the levels between the groups one by one, the bottom group in one launch
+  void backward() {
+    if (tree_top_on) tree_launch(nlev - 1, nd.tree_top0, true);
+    for (int l = (tree_top_on ? nd.tree_top0 : nlev) - 1; l >= (tree_on ? nd.tree_levels : 0); --l) {
+      const NdLevel& L = nd.lev[l];
+      if (L.n == 0) continue;
+      DenseBatch bt = batch(l);
+      bt.xfer = xfer(L.first);
+      bt.bwd_cnt = kFusedBwd ? ax.bwd_cnt : nullptr; bt.bwd_scr = ax.bwd_scr;
+      if (kFusedBwd && !ax.pipe_broken && ax.bwd_pipe != nullptr) { bt.bwd_pipe = ax.bwd_pipe; bt.pipe_dead = ax.gate_dead; bt.pipe_dead_h = ax.gate_dead_h; bt.pipe_timeout_s = ax.gate_timeout_s; }
+      dense_backward_solve(P.nd_M, P.nd_rhs + L.rhs_off, P.nd_Linv + L.linv_off, L.ntot, st, L.nI / kTile, L.ntot / kTile, bt);
+      ax.mark(st, -5);
+    }
+    if (tree_on) tree_launch(nd.tree_levels - 1, 0, false);   // levels tree_levels - 1 .. 0 in one launch
+    ax.mark(st, -6);
+  }
+};
+
+bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hipStream_t st, CholAux& ax) {
+  FrontRun r(P, nd, dst, mu, st, ax);
+  ax.init();
+  if (!r.ensure_scratch()) return false;
+  r.assemble();
+  r.run_levels(0, r.ltop, false);   // the subtrees of this rank (single GPU: the whole tree), level by level
+  if (r.ltop < r.nlev) {            // sharded solve: the top fronts take their subtree children, then the exchange of the shard policy
+    for (int l = r.ltop; l < r.nlev; ++l) r.extend(l, false, 0, st);
+    r.top_gh_damp(nd.dist ? nd.dist_lead : true);
+    if (nd.dist) r.dist_levels(); else r.run_levels(r.ltop, r.nlev, true);
+  }
+  r.backward();
   return true;
 }
 

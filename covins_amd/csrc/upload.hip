@@ -429,7 +429,6 @@ static int up_fronts(covgpu_context* c, Upload& u) {
   nd_tables(nhp, u.pos_kf.data(), P.D, c->rank, nd);
   tm(u, "front tables");
   P.nd = 1; P.nd_nnodes = nd.nnodes; P.nd_nlev = (int)nd.lev.size(); P.nd_maxd = nhp.maxdepth;
-  nd.ntop = (int)nd.h_top_g.size();
   RC(dev_upload(c, &P.nd_vnode, nd.h_vnode.data(), nd.h_vnode.size())); RC(dev_upload(c, &P.nd_voff, nd.h_voff.data(), nd.h_voff.size()));
   RC(dev_upload(c, &P.nd_vord, nd.h_vord.data(), nd.h_vord.size()));
   if (c->sharded) RC(dev_upload(c, &P.nd_vown, nd.h_vown.data(), nd.h_vown.size()));
@@ -440,11 +439,8 @@ static int up_fronts(covgpu_context* c, Upload& u) {
   RC(dev_upload(c, &nd.own_g, nd.h_own_g.data(), nd.h_own_g.size())); RC(dev_upload(c, &nd.st_g, nd.h_st_g.data(), nd.h_st_g.size()));
   RC(dev_upload(c, &nd.gidx, nd.h_gidx.data(), nd.h_gidx.size()));
   RC(dev_upload(c, &nd.tree_fill, nd.h_tree_fill.empty() ? (const int*)nullptr : nd.h_tree_fill.data(), std::max<size_t>(nd.h_tree_fill.size(), 1)));
-  RC(dev_upload(c, &nd.cptr, nd.h_cptr.data(), nd.h_cptr.size())); RC(dev_upload(c, &nd.cidx, nd.h_cidx.data(), nd.h_cidx.size()));
-  RC(dev_upload(c, &nd.cptr2, nd.h_cptr2.data(), nd.h_cptr2.size())); RC(dev_upload(c, &nd.cidx2, nd.h_cidx2.data(), nd.h_cidx2.size()));
   RC(dev_upload(c, &nd.inv_off, nd.h_inv_off.data(), nd.h_inv_off.size())); RC(dev_upload(c, &nd.inv, nd.h_inv.data(), nd.h_inv.size()));
   RC(dev_upload(c, &nd.rhs_node, nd.h_rhs_node.data(), nd.h_rhs_node.size()));
-  RC(dev_upload(c, &nd.ext, nd.h_ext.data(), nd.h_ext.size()));
   RC(up_or_zero(c, &nd.extw, nd.h_extw, 8)); RC(up_or_zero(c, &nd.extc, nd.h_extc, 6)); RC(up_or_zero(c, &nd.extc2, nd.h_extc2, 6));
   RC(up_or_zero(c, &nd.extr, nd.h_extr, kExtRec));
   RC(dev_upload(c, &nd.bb_off, nd.h_bb_off.data(), nd.h_bb_off.size()));
@@ -481,7 +477,6 @@ static int up_sharded_top(covgpu_context* c, Upload& u) {
   }
   RC(dev_upload(c, &P.vw, vw.data(), vw.size()));
   RC(dev_alloc(c, &c->d_red, (size_t)SC_COUNT + 2 * (size_t)c->world));
-  nd.n_top_tiles = (int)(nd.h_top_tiles.size() / 3);
   if (nd.dist) {   // distributed top (shard policy 1): per-panel exchange entries, owned trailing-update tiles, one reduce buffer for the largest panel
     RC(up_or_zero(c, &nd.dist_ent, nd.h_dist_ent, 4)); RC(up_or_zero(c, &nd.dist_tri, nd.h_dist_tri, 1));
     RC(dev_alloc(c, &nd.dist_buf, std::max<size_t>(nd.dist_buf_elems, 1)));

@@ -104,7 +104,7 @@ def host_plan(pt):
 
 
 def plan_shape(pt, plan=None):
-    """Shape figures of a point's host plan, from the plan arrays alone (k_front.hip nd_tables / k_chol.hip read the same quantities):
+    """Shape figures of a point's host plan, from the plan arrays alone (nd_tables.hip front_layout / k_chol.hip read the same quantities):
     own / border order per front, per level the padded interior order (multiple of 256 = two tiles) and, per 256-column panel, the number of
     fronts with 1 .. 128 real columns in it (NdLevel::psmall: what selects k_potrf_panel4)."""
     info, parent, level, own, st = plan if plan is not None else host_plan(pt)

@@ -60,8 +60,8 @@ EXCEPTIONS = {
     "panel_one_tile": "a front's interior is padded to whole 256-column panels; only the dense solve has an odd tile count to factor",
     "k_bwd_step_sub": "launch-per-tile substitution: the dense solve, COVGPU_BWD_PIPE=0",
 }
-# Named in the header, reachable by no plan: a level's padded interior order is the round-up of its largest REAL interior order (nd_tables,
-# k_front.hip), so no panel of a level is all padding. Asserted to stay at zero: if one comes alive, the sweep has to reach it.
+# Named in the header, reachable by no plan: a level's padded interior order is the round-up of its largest REAL interior order (front_layout,
+# nd_tables.hip), so no panel of a level is all padding. Asserted to stay at zero: if one comes alive, the sweep has to reach it.
 DEAD = {"potrf_skipped": "no all-padding panel exists in a level", "kd_zero": "no all-padding panel exists in a level"}
 
 
