@@ -25,6 +25,50 @@ class CovGpuError(RuntimeError):
     pass
 
 
+# ---- what the batch wrappers share: coercion to the C ABI's array types, option structs, output offsets
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _u8(a):
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _opt(coerce, a):
+    """coerce(a), or None for an array the caller left out."""
+    return None if a is None else coerce(a)
+
+
+def _bp(a):
+    return None if a is None else a.ctypes.data_as(capi._bp)
+
+
+def _set_opts(o, allowed, opts, what, convert=None):
+    """Sets the fields `opts` of the option struct `o` (already at its defaults); a name outside `allowed` is a TypeError."""
+    for k, v in opts.items():
+        if k not in allowed:
+            raise TypeError(f"unknown {what} option {k}")
+        setattr(o, k, v if convert is None else convert(k, v))
+    return o
+
+
+def _job_offsets(ptr, sets, ok):
+    """[J+1] int64: the first output row of every job, job j writing one row per row of set sets[j] (zeros unless the indices are ok)."""
+    off = np.zeros(len(sets) + 1, np.int64)
+    if ok and len(sets):
+        off[1:] = np.cumsum(np.maximum(ptr[sets + 1] - ptr[sets], 0))
+    return off
+
+
+_MATCH_MODES = {"dense": capi.MATCH_DENSE, "knn2": capi.MATCH_KNN2}
+_DETECT_MODES = {"covins": capi.DETECT_COVINS, "covins_g": capi.DETECT_COVINS_G}
+_DETECT_OPTS = ("min_score_factor", "min_loop_dist", "exclude_kfs_with_id_less_than", "inter_map_matches_only", "scratch_kib")
+
+
 def build(force: bool = False) -> str:
     """Compiles the HIP sources for gfx950 (hipcc cross-compiles without a GPU)."""
     args = ["make", "-C", os.path.join(_HERE, "csrc"), "-j8"]
@@ -150,16 +194,12 @@ class BowDb:
 
     def __init__(self, ctx: "Context", voc: Optional[dict] = None, mode="covins", **opts):
         self._ctx, self._h = ctx, C.c_void_p()
-        m = {"covins": capi.DETECT_COVINS, "covins_g": capi.DETECT_COVINS_G}.get(mode, mode)
         o = capi.BowDbOpts()
-        lib().covgpu_default_bowdb_opts(C.byref(o), int(m))
-        for k, v in opts.items():
-            if k in ("min_score_factor", "min_loop_dist", "exclude_kfs_with_id_less_than", "inter_map_matches_only", "scratch_kib"):
-                setattr(o.detect, k, v)
-            elif k in ("levelsup", "tail_limit", "reserve_kf", "reserve_words", "num_words"):
-                setattr(o, k, int(v))
-            else:
-                raise TypeError(f"unknown bowdb option {k}")
+        lib().covgpu_default_bowdb_opts(C.byref(o), int(_DETECT_MODES.get(mode, mode)))
+        detect = {k: v for k, v in opts.items() if k in _DETECT_OPTS}
+        _set_opts(o.detect, _DETECT_OPTS, detect, "bowdb")
+        _set_opts(o, ("levelsup", "tail_limit", "reserve_kf", "reserve_words", "num_words"), {k: v for k, v in opts.items() if k not in detect},
+                  "bowdb", lambda k, v: int(v))
         self.levelsup = int(o.levelsup)
         keep = []
         v = None if voc is None else C.byref(Context._bow_vocab(voc, keep))
@@ -181,7 +221,7 @@ class BowDb:
 
     @staticmethod
     def _i32(a):
-        return np.ascontiguousarray(a, dtype=np.int32).ravel()
+        return _i32(a).ravel()
 
     def _meta(self, slot, id, client):
         s, i, c = self._i32(slot), self._i32(id), self._i32(client)
@@ -193,7 +233,7 @@ class BowDb:
         """Stores vectors computed elsewhere: a bow CSR with one row per slot (covgpu_bowdb_put)."""
         s, i, c = self._meta(slot, id, client)
         ptr, w = self._i32(bow_ptr), self._i32(word)
-        v = np.ascontiguousarray(value, dtype=np.float64).ravel()
+        v = _f64(value).ravel()
         if len(ptr) != len(s) + 1 or len(v) != len(w) or (len(s) and int(ptr[-1]) > len(w)):
             raise ValueError("bow arrays do not fit the slots")
         self._check(lib().covgpu_bowdb_put(self._h, len(s), iptr(s), iptr(i), iptr(c), iptr(ptr), iptr(w), dptr(v)))
@@ -203,11 +243,11 @@ class BowDb:
         round trip (covgpu_bowdb_put_descriptors). want: also download them; returns what Context.bow_transform_batch returns."""
         s, i, c = self._meta(slot, id, client)
         ptr = self._i32(sets["row_ptr"])
-        desc = np.ascontiguousarray(sets["desc"], dtype=np.uint8).reshape(-1, 32)
+        desc = _u8(sets["desc"]).reshape(-1, 32)
         S, rows = len(ptr) - 1, len(desc)
         if S != len(s) or (S > 0 and int(ptr[-1]) > rows):
             raise ValueError("descriptor sets do not fit the slots")
-        bt = capi.BowTransformBatch(S, iptr(ptr), desc.ctypes.data_as(capi._bp), self.levelsup, 0, None, None, None, None, None, None)
+        bt = capi.BowTransformBatch(S, iptr(ptr), _bp(desc), self.levelsup, 0, None, None, None, None, None, None)
         if want:
             bptr = np.zeros(S + 1, np.int32); word = np.zeros(max(rows, 1), np.int32); value = np.zeros(max(rows, 1))
             rw = np.full(max(rows, 1), -1, np.int32); rn = np.zeros(max(rows, 1), np.int32); tot = C.c_int64(0)
@@ -229,10 +269,10 @@ class BowDb:
         self._check(lib().covgpu_bowdb_set_neighbours(self._h, len(s), iptr(s), iptr(ptr), iptr(nb)))
 
     def set_invalid(self, slot, flag):
-        s = self._i32(slot); f = np.ascontiguousarray(flag, dtype=np.uint8).ravel()
+        s = self._i32(slot); f = _u8(flag).ravel()
         if len(f) != len(s):
             raise ValueError("one flag per slot")
-        self._check(lib().covgpu_bowdb_set_invalid(self._h, len(s), iptr(s), f.ctypes.data_as(capi._bp)))
+        self._check(lib().covgpu_bowdb_set_invalid(self._h, len(s), iptr(s), _bp(f)))
 
     def add(self, slot):
         """AddKeyframe: the slots join the insertion order at its end."""
@@ -254,7 +294,7 @@ class BowDb:
             raise ValueError("one connected list per query")
         cptr = np.zeros(Q + 1, np.int32); cptr[1:] = np.cumsum([len(x) for x in connected])
         con = self._i32(np.concatenate([self._i32(x) for x in connected] + [np.zeros(0, np.int32)]))
-        ms = None if min_score is None else np.ascontiguousarray(min_score, dtype=np.float64).ravel()
+        ms = _opt(lambda a: _f64(a).ravel(), min_score)
         if ms is not None and len(ms) != Q:
             raise ValueError("min_score does not fit the queries")
         cap = self.stats()["live"] if cap is None else int(cap)
@@ -403,20 +443,19 @@ class Context:
         """Batched Optimization::OptimizeRelativePose (covgpu_relpose_batch). `bt`: dict with ptr, pA, pB, kpA, kpB, sigA, sigB,
         camA, camB, distA, distB, T0 (see include/covgpu.h), optionally modelA, modelB, xiA, xiB (COVGPU_CAM_* and xi per pair and side;
         absent = pinhole). Returns (T_ab [B,7], outlier flags [C], inliers [B])."""
-        f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        i = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        f, i = _f64, _i32
         keep = dict(ptr=i(bt["ptr"]), pB=f(bt["pB"]), pA=f(bt["pA"]), kA=f(bt["kpA"]), kB=f(bt["kpB"]), sA=f(bt["sigA"]), sB=f(bt["sigB"]),
                     cA=f(bt["camA"]), cB=f(bt["camB"]), dA=i(bt["distA"]), dB=i(bt["distB"]), T=np.array(bt["T0"], dtype=np.float64, order="C"))
         for k in ("modelA", "modelB"):
-            keep[k] = i(bt[k]) if bt.get(k) is not None else None
+            keep[k] = _opt(i, bt.get(k))
         for k in ("xiA", "xiB"):
-            keep[k] = f(bt[k]) if bt.get(k) is not None else None
+            keep[k] = _opt(f, bt.get(k))
         B = len(keep["ptr"]) - 1
         out = np.zeros(max(int(keep["ptr"][-1]), 1), np.uint8); inl = np.zeros(max(B, 1), np.int32)
-        ip = lambda a: None if a is None else iptr(a)
+        ip = lambda a: _opt(iptr, a)
         s = capi.RelposeBatch(B, iptr(keep["ptr"]), dptr(keep["pB"]), dptr(keep["pA"]), dptr(keep["kA"]), dptr(keep["kB"]), dptr(keep["sA"]),
                               dptr(keep["sB"]), dptr(keep["cA"]), dptr(keep["cB"]), iptr(keep["dA"]), iptr(keep["dB"]), dptr(keep["T"]),
-                              out.ctypes.data_as(capi._bp), iptr(inl), ip(keep["modelA"]), ip(keep["modelB"]), dptr(keep["xiA"]), dptr(keep["xiB"]))
+                              _bp(out), iptr(inl), ip(keep["modelA"]), ip(keep["modelB"]), dptr(keep["xiA"]), dptr(keep["xiB"]))
         self._check(lib().covgpu_relpose_batch(self._h, C.byref(s), float(th_outlier), int(min_inliers)))
         return keep["T"], out[:int(keep["ptr"][-1])].astype(bool), inl[:B]
 
@@ -427,22 +466,19 @@ class Context:
         inlier [C] bool, inliers [num], iterations [num], best_draw [num])."""
         o = capi.RansacOpts()
         lib().covgpu_default_ransac_opts(C.byref(o))
-        for k, v in opts.items():
-            if not hasattr(o, k):
-                raise TypeError(f"unknown RANSAC option {k}")
-            setattr(o, k, v)
-        ptr = np.ascontiguousarray(bt["ptr"], dtype=np.int32)
+        _set_opts(o, [name for name, _ in capi.RansacOpts._fields_], opts, "RANSAC")
+        ptr = _i32(bt["ptr"])
         B = len(ptr) - 1
         Cn = int(ptr[-1]) if B >= 0 and len(ptr) else 0
-        f = np.ascontiguousarray(bt["bearing"], dtype=np.float64).reshape(-1, 3)
-        P = np.ascontiguousarray(bt["point_w"], dtype=np.float64).reshape(-1, 3)
-        sg = np.ascontiguousarray(bt["sigma_angle"], dtype=np.float64)
-        seed = None if bt.get("seed") is None else np.ascontiguousarray(bt["seed"], dtype=np.uint64)
+        f = _f64(bt["bearing"]).reshape(-1, 3)
+        P = _f64(bt["point_w"]).reshape(-1, 3)
+        sg = _f64(bt["sigma_angle"])
+        seed = _opt(lambda a: np.ascontiguousarray(a, dtype=np.uint64), bt.get("seed"))
         T = np.array(bt["T0"], dtype=np.float64, order="C").reshape(-1, 7) if bt.get("T0") is not None else np.zeros((max(B, 1), 7))
         mask = np.zeros(max(Cn, 1), np.uint8)
         inl, its, bd = (np.zeros(max(B, 1), np.int32) for _ in range(3))
         s = capi.AbsposeBatch(B, iptr(ptr), dptr(f), dptr(P), dptr(sg), None if seed is None else seed.ctypes.data_as(C.POINTER(C.c_uint64)),
-                              dptr(T), mask.ctypes.data_as(capi._bp), iptr(inl), iptr(its), iptr(bd))
+                              dptr(T), _bp(mask), iptr(inl), iptr(its), iptr(bd))
         self._check(lib().covgpu_abspose_ransac_batch(self._h, C.byref(s), C.byref(o)))
         return dict(T_wc=T[:max(B, 0)], inlier=mask[:Cn].astype(bool), inliers=inl[:max(B, 0)], iterations=its[:max(B, 0)], best_draw=bd[:max(B, 0)])
 
@@ -452,29 +488,22 @@ class Context:
         set_b[j]. mode "dense" (LandmarkMatchingAlgorithm + DenseMatcher) or "knn2" (BFMatcher knnMatch k=2 + distance and ratio tests).
         `opts`: dist_threshold, ratio (defaults: covgpu_default_match_opts). Returns dict(match [sumA] local B row or -1, dist [sumA],
         nmatches [num_jobs], offset [num_jobs+1] the output rows of job j are offset[j]:offset[j+1])."""
-        m = {"dense": capi.MATCH_DENSE, "knn2": capi.MATCH_KNN2}.get(mode, mode)
+        m = _MATCH_MODES.get(mode, mode)
         o = capi.MatchOpts()
         lib().covgpu_default_match_opts(C.byref(o), int(m) if isinstance(m, int) else -1)
-        for k, v in opts.items():
-            if k not in ("dist_threshold", "ratio"):
-                raise TypeError(f"unknown match option {k}")
-            setattr(o, k, v)
-        ptr = np.ascontiguousarray(sets["row_ptr"], dtype=np.int32)
+        _set_opts(o, ("dist_threshold", "ratio"), opts, "match")
+        ptr = _i32(sets["row_ptr"])
         S = len(ptr) - 1
-        desc = np.ascontiguousarray(sets["desc"], dtype=np.uint8).reshape(-1, 32)
-        skip = None if sets.get("skip") is None else np.ascontiguousarray(sets["skip"], dtype=np.uint8)
-        sa = np.ascontiguousarray(set_a, dtype=np.int32).ravel()
-        sb = np.ascontiguousarray(set_b, dtype=np.int32).ravel()
+        desc = _u8(sets["desc"]).reshape(-1, 32)
+        skip = _opt(_u8, sets.get("skip"))
+        sa, sb = _i32(set_a).ravel(), _i32(set_b).ravel()
         J = len(sa)
         if len(sb) != J:
             raise ValueError("set_a and set_b differ in length")
-        ok = S >= 0 and np.all((sa >= 0) & (sa < S))
-        nA = (ptr[sa + 1] - ptr[sa]) if ok and J else np.zeros(J, np.int32)
-        off = np.zeros(J + 1, np.int64); off[1:] = np.cumsum(np.maximum(nA, 0))
+        off = _job_offsets(ptr, sa, S >= 0 and np.all((sa >= 0) & (sa < S)))
         tot = int(off[-1])
         match = np.full(max(tot, 1), -1, np.int32); dist = np.full(max(tot, 1), -1, np.int32); nm = np.zeros(max(J, 1), np.int32)
-        s = capi.MatchBatch(S, iptr(ptr), desc.ctypes.data_as(capi._bp), None if skip is None else skip.ctypes.data_as(capi._bp), J,
-                            iptr(sa), iptr(sb), iptr(match), iptr(dist), iptr(nm))
+        s = capi.MatchBatch(S, iptr(ptr), _bp(desc), _bp(skip), J, iptr(sa), iptr(sb), iptr(match), iptr(dist), iptr(nm))
         self._check(lib().covgpu_match_batch(self._h, C.byref(s), C.byref(o)))
         return dict(match=match[:tot], dist=dist[:tot], nmatches=nm[:J], offset=off)
 
@@ -485,24 +514,18 @@ class Context:
         `opts`: dist_threshold, ratio, mode (defaults: covgpu_default_match_float_opts). Returns the dict of match_batch, dist in float32."""
         o = capi.MatchOpts()
         lib().covgpu_default_match_float_opts(C.byref(o))
-        for k, v in opts.items():
-            if k not in ("dist_threshold", "ratio", "mode"):
-                raise TypeError(f"unknown match option {k}")
-            setattr(o, k, {"dense": capi.MATCH_DENSE, "knn2": capi.MATCH_KNN2}.get(v, v) if k == "mode" else v)
-        ptr = np.ascontiguousarray(sets["row_ptr"], dtype=np.int32)
+        _set_opts(o, ("dist_threshold", "ratio", "mode"), opts, "match", lambda k, v: _MATCH_MODES.get(v, v) if k == "mode" else v)
+        ptr = _i32(sets["row_ptr"])
         S = len(ptr) - 1
         desc = np.ascontiguousarray(sets["desc"], dtype=np.float32)
         dim = int(sets["dim"]) if sets.get("dim") is not None else (int(desc.shape[-1]) if desc.ndim == 2 else 0)
-        sa = np.ascontiguousarray(set_a, dtype=np.int32).ravel()
-        sb = np.ascontiguousarray(set_b, dtype=np.int32).ravel()
+        sa, sb = _i32(set_a).ravel(), _i32(set_b).ravel()
         J = len(sa)
         if len(sb) != J:
             raise ValueError("set_a and set_b differ in length")
         if dim > 0 and S >= 0 and desc.size != int(ptr[-1]) * dim:
             raise ValueError("desc does not hold row_ptr[-1] rows of dim floats")
-        ok = S >= 0 and np.all((sa >= 0) & (sa < S))
-        nA = (ptr[sa + 1] - ptr[sa]) if ok and J else np.zeros(J, np.int32)
-        off = np.zeros(J + 1, np.int64); off[1:] = np.cumsum(np.maximum(nA, 0))
+        off = _job_offsets(ptr, sa, S >= 0 and np.all((sa >= 0) & (sa < S)))
         tot = int(off[-1])
         match = np.full(max(tot, 1), -1, np.int32); dist = np.full(max(tot, 1), -1, np.float32); nm = np.zeros(max(J, 1), np.int32)
         dbuf = desc if desc.size else np.zeros(1, np.float32)
@@ -515,28 +538,24 @@ class Context:
     def _guided_opts(mode, opts):
         o = capi.GuidedOpts()
         lib().covgpu_default_guided_opts(C.byref(o), mode)
-        for k, v in opts.items():
-            if k not in ("th_low", "radius", "scale_factor", "num_octaves", "agreement"):
-                raise TypeError(f"unknown guided-matching option {k}")
-            setattr(o, k, v)
-        return o
+        return _set_opts(o, ("th_low", "radius", "scale_factor", "num_octaves", "agreement"), opts, "guided-matching")
 
     @staticmethod
     def _keypoint_sets(sets: dict, keep: list):
         """covgpu_keypoint_sets_t of `sets` (row_ptr, kp [rows,2], level, desc [rows,32], bounds [S,4], optional grid_inv [S,2]); the
         arrays it points into are appended to `keep`."""
-        ptr = np.ascontiguousarray(sets["row_ptr"], dtype=np.int32).ravel()
+        ptr = _i32(sets["row_ptr"]).ravel()
         S = len(ptr) - 1
         kp = np.ascontiguousarray(sets["kp"], dtype=np.float32).reshape(-1, 2)
-        level = np.ascontiguousarray(sets["level"], dtype=np.int32).ravel()
-        desc = np.ascontiguousarray(sets["desc"], dtype=np.uint8).reshape(-1, 32)
-        bounds = np.ascontiguousarray(sets["bounds"], dtype=np.float64).reshape(-1, 4)
-        grid = None if sets.get("grid_inv") is None else np.ascontiguousarray(sets["grid_inv"], dtype=np.float64).reshape(-1, 2)
+        level = _i32(sets["level"]).ravel()
+        desc = _u8(sets["desc"]).reshape(-1, 32)
+        bounds = _f64(sets["bounds"]).reshape(-1, 4)
+        grid = _opt(lambda a: _f64(a).reshape(-1, 2), sets.get("grid_inv"))
         rows = int(ptr[-1]) if S > 0 else 0
         if len(kp) != rows or len(level) != rows or len(desc) != rows or len(bounds) != S or (grid is not None and len(grid) != S):
             raise ValueError("keypoint set arrays do not fit row_ptr")
         keep += [ptr, kp, level, desc, bounds, grid]
-        return capi.KeypointSets(S, iptr(ptr), kp.ctypes.data_as(capi._fp), iptr(level), desc.ctypes.data_as(capi._bp), dptr(bounds),
+        return capi.KeypointSets(S, iptr(ptr), kp.ctypes.data_as(capi._fp), iptr(level), _bp(desc), dptr(bounds),
                                  dptr(grid)), ptr, S, rows
 
     def search_se3_batch(self, sets: dict, set_1, set_2, T12, **opts):
@@ -548,27 +567,22 @@ class Context:
         o = self._guided_opts(capi.GUIDED_SE3, opts)
         keep = []
         ks, ptr, S, rows = self._keypoint_sets(sets, keep)
-        f64 = lambda k, w: np.ascontiguousarray(sets[k], dtype=np.float64).reshape((-1,) + w)
-        K, pos, maxd = f64("K", (4,)), f64("lm_pos", (3,)), f64("lm_max_distance", ())
-        ldesc = np.ascontiguousarray(sets["lm_desc"], dtype=np.uint8).reshape(-1, 32)
-        free = np.ascontiguousarray(sets["lm_free"], dtype=np.uint8).ravel()
+        K, pos, maxd = _f64(sets["K"]).reshape(-1, 4), _f64(sets["lm_pos"]).reshape(-1, 3), _f64(sets["lm_max_distance"]).reshape(-1)
+        ldesc = _u8(sets["lm_desc"]).reshape(-1, 32)
+        free = _u8(sets["lm_free"]).ravel()
         if len(K) != S or len(pos) != rows or len(maxd) != rows or len(ldesc) != rows or len(free) != rows:
             raise ValueError("landmark arrays do not fit row_ptr")
-        s1 = np.ascontiguousarray(set_1, dtype=np.int32).ravel()
-        s2 = np.ascontiguousarray(set_2, dtype=np.int32).ravel()
-        T = np.ascontiguousarray(T12, dtype=np.float64).reshape(-1, 7)
+        s1, s2 = _i32(set_1).ravel(), _i32(set_2).ravel()
+        T = _f64(T12).reshape(-1, 7)
         J = len(s1)
         if len(s2) != J or len(T) != J:
             raise ValueError("set_1, set_2 and T12 differ in length")
         ok = J > 0 and np.all((s1 >= 0) & (s1 < S) & (s2 >= 0) & (s2 < S))
-        off1 = np.zeros(J + 1, np.int64); off2 = np.zeros(J + 1, np.int64)
-        if ok:
-            off1[1:] = np.cumsum(np.maximum(ptr[s1 + 1] - ptr[s1], 0)); off2[1:] = np.cumsum(np.maximum(ptr[s2 + 1] - ptr[s2], 0))
+        off1, off2 = _job_offsets(ptr, s1, ok), _job_offsets(ptr, s2, ok)
         t1, t2 = int(off1[-1]), int(off2[-1])
         match = np.full(max(t1, 1), -1, np.int32); m1 = np.full(max(t1, 1), -1, np.int32); m2 = np.full(max(t2, 1), -1, np.int32)
         nf = np.zeros(max(J, 1), np.int32)
-        bp = lambda a: a.ctypes.data_as(capi._bp)
-        s = capi.SearchSe3Batch(ks, dptr(K), dptr(pos), dptr(maxd), bp(ldesc), bp(free), J, iptr(s1), iptr(s2), dptr(T), iptr(match),
+        s = capi.SearchSe3Batch(ks, dptr(K), dptr(pos), dptr(maxd), _bp(ldesc), _bp(free), J, iptr(s1), iptr(s2), dptr(T), iptr(match),
                                 iptr(m1), iptr(m2), iptr(nf))
         self._check(lib().covgpu_search_se3_batch(self._h, C.byref(s), C.byref(o)))
         return dict(match=match[:t1], match1=m1[:t1], match2=m2[:t2], nfound=nf[:J], offset=off1, offset2=off2)
@@ -581,31 +595,31 @@ class Context:
         o = self._guided_opts(capi.GUIDED_PROJECTION, opts)
         keep = []
         ks, ptr, S, rows = self._keypoint_sets(sets, keep)
-        bp = lambda a: None if a is None else a.ctypes.data_as(capi._bp)
-        u8 = lambda d, k: None if d.get(k) is None else np.ascontiguousarray(d[k], dtype=np.uint8).ravel()
-        i32 = lambda d, k: None if d.get(k) is None else np.ascontiguousarray(d[k], dtype=np.int32).ravel()
-        cam = np.ascontiguousarray(sets["cam"], dtype=np.float64).reshape(-1, 8)
+        bp = _bp
+        u8 = lambda d, k: _opt(lambda a: _u8(a).ravel(), d.get(k))
+        i32 = lambda d, k: _opt(lambda a: _i32(a).ravel(), d.get(k))
+        cam = _f64(sets["cam"]).reshape(-1, 8)
         dt, cm, taken = i32(sets, "dist_type"), i32(sets, "cam_model"), u8(sets, "taken")
-        xi = None if sets.get("xi") is None else np.ascontiguousarray(sets["xi"], dtype=np.float64).ravel()
+        xi = _opt(lambda a: _f64(a).ravel(), sets.get("xi"))
         if len(cam) != S or len(dt) != S or (cm is not None and len(cm) != S) or (xi is not None and len(xi) != S) \
                 or (taken is not None and len(taken) != rows):
             raise ValueError("camera or taken arrays do not fit row_ptr")
         st = i32(jobs, "set")
         J = len(st)
-        T = np.ascontiguousarray(jobs["T_cw"], dtype=np.float64).reshape(-1, 7)
+        T = _f64(jobs["T_cw"]).reshape(-1, 7)
         pp = i32(jobs, "point_ptr")
-        f64 = lambda k, w: np.ascontiguousarray(jobs[k], dtype=np.float64).reshape((-1,) + w)
+        f64 = lambda k, w: _f64(jobs[k]).reshape((-1,) + w)
         pw, nrm, mind, maxd = f64("p_w", (3,)), f64("normal", (3,)), f64("min_distance", ()), f64("max_distance", ())
-        pdesc = np.ascontiguousarray(jobs["desc"], dtype=np.uint8).reshape(-1, 32)
+        pdesc = _u8(jobs["desc"]).reshape(-1, 32)
         skip, ex = u8(jobs, "skip"), i32(jobs, "existing_idx")
         P = len(pw)
         if len(T) != J or len(pp) != J + 1 or int(pp[-1]) != P or any(a is not None and len(a) != P for a in (nrm, mind, maxd, pdesc, skip, ex)):
             raise ValueError("job or point arrays differ in length")
         claimed = np.full(max(P, 1), -1, np.int32); remap = np.full(max(P, 1), -1, np.int32); bd = np.full(max(P, 1), -1, np.int32)
         nm = np.zeros(max(J, 1), np.int32)
-        s = capi.SearchProjectionBatch(ks, bp(taken), dptr(cam), iptr(dt), None if cm is None else iptr(cm), dptr(xi), J, iptr(st), dptr(T),
+        s = capi.SearchProjectionBatch(ks, bp(taken), dptr(cam), iptr(dt), _opt(iptr, cm), dptr(xi), J, iptr(st), dptr(T),
                                        iptr(pp), dptr(pw), dptr(nrm), dptr(mind), dptr(maxd), bp(pdesc), bp(skip),
-                                       None if ex is None else iptr(ex), iptr(claimed), iptr(remap), iptr(bd), iptr(nm))
+                                       _opt(iptr, ex), iptr(claimed), iptr(remap), iptr(bd), iptr(nm))
         self._check(lib().covgpu_search_projection_batch(self._h, C.byref(s), C.byref(o)))
         return dict(claimed=claimed[:P], remap_to=remap[:P], best_dist=bd[:P], nmatches=nm[:J])
 
@@ -618,16 +632,15 @@ class Context:
     @staticmethod
     def _bow_vocab(voc: dict, keep: list):
         """covgpu_bow_vocab_t over the flat form of covins_amd/vocio.py (`keep` holds the arrays alive)."""
-        i32 = lambda k: np.ascontiguousarray(voc[k], dtype=np.int32).ravel()
-        parent, cptr, child, wid = i32("parent"), i32("child_ptr"), i32("child"), i32("word_id")
-        desc = np.ascontiguousarray(voc["desc"], dtype=np.uint8).reshape(-1, 32)
-        weight = np.ascontiguousarray(voc["weight"], dtype=np.float64).ravel()
+        parent, cptr, child, wid = (_i32(voc[k]).ravel() for k in ("parent", "child_ptr", "child", "word_id"))
+        desc = _u8(voc["desc"]).reshape(-1, 32)
+        weight = _f64(voc["weight"]).ravel()
         N = len(parent)
         if len(cptr) != N + 1 or len(child) != max(N - 1, 0) or len(desc) != N or len(wid) != N or len(weight) != N:
             raise ValueError("vocabulary arrays differ in length")
         keep += [parent, cptr, child, wid, desc, weight]
         return capi.BowVocab(N, int(voc["num_words"]), int(voc["k"]), int(voc["L"]), int(voc["scoring"]), int(voc["weighting"]),
-                             iptr(parent), iptr(cptr), iptr(child), desc.ctypes.data_as(capi._bp), iptr(wid), dptr(weight))
+                             iptr(parent), iptr(cptr), iptr(child), _bp(desc), iptr(wid), dptr(weight))
 
     def bow_transform_batch(self, voc: dict, sets: dict, levelsup: int = 4, capacity: Optional[int] = None):
         """DBoW2's transform(features, bow_vec, feat_vec, levelsup) of every descriptor set (covgpu_bow_transform_batch, DESIGN.md
@@ -637,14 +650,14 @@ class Context:
         the entries written; bow_ptr and total stay exact."""
         keep = []
         v = self._bow_vocab(voc, keep)
-        ptr = np.ascontiguousarray(sets["row_ptr"], dtype=np.int32)
+        ptr = _i32(sets["row_ptr"])
         S = len(ptr) - 1
-        desc = np.ascontiguousarray(sets["desc"], dtype=np.uint8).reshape(-1, 32)
+        desc = _u8(sets["desc"]).reshape(-1, 32)
         rows = len(desc)
         cap = rows if capacity is None else int(capacity)
         bptr = np.zeros(S + 1, np.int32); word = np.zeros(max(cap, 1), np.int32); value = np.zeros(max(cap, 1))
         rw = np.full(max(rows, 1), -1, np.int32); rn = np.zeros(max(rows, 1), np.int32); tot = C.c_int64(0)
-        s = capi.BowTransformBatch(S, iptr(ptr), desc.ctypes.data_as(capi._bp), int(levelsup), cap, iptr(bptr), iptr(word), dptr(value),
+        s = capi.BowTransformBatch(S, iptr(ptr), _bp(desc), int(levelsup), cap, iptr(bptr), iptr(word), dptr(value),
                                    C.pointer(tot), iptr(rw), iptr(rn))
         self._check(lib().covgpu_bow_transform_batch(self._h, C.byref(v), C.byref(s)))
         n = min(cap, int(tot.value))
@@ -652,9 +665,8 @@ class Context:
 
     def bow_score_pairs(self, bow_ptr, word, value, a, b):
         """L1Scoring::score of the pairs (a[i], b[i]) of the rows of a bow CSR (covgpu_bow_score_pairs). Returns float64 [len(a)]."""
-        ptr = np.ascontiguousarray(bow_ptr, dtype=np.int32); w = np.ascontiguousarray(word, dtype=np.int32)
-        v = np.ascontiguousarray(value, dtype=np.float64)
-        pa = np.ascontiguousarray(a, dtype=np.int32).ravel(); pb = np.ascontiguousarray(b, dtype=np.int32).ravel()
+        ptr, w, v = _i32(bow_ptr), _i32(word), _f64(value)
+        pa, pb = _i32(a).ravel(), _i32(b).ravel()
         if len(pa) != len(pb):
             raise ValueError("a and b differ in length")
         out = np.zeros(max(len(pa), 1))
@@ -670,17 +682,13 @@ class Context:
         covgpu_default_detect_opts(mode)). `cap` (default: len(db_order)) bounds the candidates kept per query. Returns
         dict(candidates: list of arrays of table indices in the reference's order, acc_score: list of float32 arrays,
         num_candidates, min_score, num_sharing, max_common_words, num_scored [Q])."""
-        m = {"covins": capi.DETECT_COVINS, "covins_g": capi.DETECT_COVINS_G}.get(mode, mode)
         o = capi.DetectOpts()
-        lib().covgpu_default_detect_opts(C.byref(o), int(m))
-        for k, v in opts.items():
-            if k not in ("min_score_factor", "min_loop_dist", "exclude_kfs_with_id_less_than", "inter_map_matches_only", "scratch_kib"):
-                raise TypeError(f"unknown detect option {k}")
-            setattr(o, k, v)
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ravel()
+        lib().covgpu_default_detect_opts(C.byref(o), int(_DETECT_MODES.get(mode, mode)))
+        _set_opts(o, _DETECT_OPTS, opts, "detect")
+        i32 = lambda a: _i32(a).ravel()
         kid, client, bptr, word, nptr, nb = (i32(table[k]) for k in ("id", "client", "bow_ptr", "word", "nb_ptr", "nb"))
-        value = np.ascontiguousarray(table["value"], dtype=np.float64).ravel()
-        inv = None if table.get("invalid") is None else np.ascontiguousarray(table["invalid"], dtype=np.uint8).ravel()
+        value = _f64(table["value"]).ravel()
+        inv = _opt(lambda a: _u8(a).ravel(), table.get("invalid"))
         N = len(kid)
         if len(client) != N or len(bptr) != N + 1 or len(nptr) != N + 1 or len(value) != len(word) or (inv is not None and len(inv) != N):
             raise ValueError("table arrays differ in length")
@@ -688,7 +696,7 @@ class Context:
         Q = len(qk)
         if len(vis) != Q:
             raise ValueError("query_kf and db_visible differ in length")
-        ms = None if min_score is None else np.ascontiguousarray(min_score, dtype=np.float64).ravel()
+        ms = _opt(lambda a: _f64(a).ravel(), min_score)
         if ms is not None and len(ms) != Q:
             raise ValueError("min_score does not fit the queries")
         cap = len(db) if cap is None else int(cap)
@@ -696,7 +704,7 @@ class Context:
         nc = np.zeros(n, np.int32); cand = np.full((n, max(cap, 1)), -1, np.int32); acc = np.zeros((n, max(cap, 1)), np.float32)
         mso = np.zeros(n); nsh = np.zeros(n, np.int32); mcw = np.zeros(n, np.int32); nsc = np.zeros(n, np.int32)
         s = capi.DetectBatch(N, iptr(kid), iptr(client), iptr(bptr), iptr(word), dptr(value), iptr(nptr), iptr(nb),
-                             None if inv is None else inv.ctypes.data_as(capi._bp), len(db), iptr(db), Q, iptr(qk), iptr(vis), dptr(ms), cap,
+                             _bp(inv), len(db), iptr(db), Q, iptr(qk), iptr(vis), dptr(ms), cap,
                              iptr(nc), iptr(cand), acc.ctypes.data_as(capi._fp), dptr(mso), iptr(nsh), iptr(mcw), iptr(nsc))
         self._check(lib().covgpu_detect_candidates_batch(self._h, C.byref(s), C.byref(o)))
         kept = np.minimum(nc[:Q], cap)
@@ -707,10 +715,10 @@ class Context:
     def _prune_batch(lm_obs_ptr, obs_kf, kf_pred, kf_succ, kf_time, lm_invalid, kf_invalid, kf_first, kf_loop, kf_not_erase, capacity,
                      opts, want_loop_ms=False):
         """(PruneBatch, PruneOpts, outputs, keep-alive list) of one covgpu_prune_redundant call."""
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ravel()
-        flag = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint8).ravel()
+        i32 = lambda a: _i32(a).ravel()
+        flag = lambda a: _opt(lambda x: _u8(x).ravel(), a)
         ptr, okf, pred, succ = i32(lm_obs_ptr), i32(obs_kf), i32(kf_pred), i32(kf_succ)
-        time = np.ascontiguousarray(kf_time, dtype=np.float64).ravel()
+        time = _f64(kf_time).ravel()
         K, L = len(pred), len(ptr) - 1
         flags = [flag(a) for a in (lm_invalid, kf_invalid, kf_first, kf_loop, kf_not_erase)]
         if L < 0 or len(succ) != K or len(time) != K or any(f is not None and len(f) != n for f, n in zip(flags, (L, K, K, K, K))):
@@ -719,18 +727,14 @@ class Context:
             raise ValueError("lm_obs_ptr runs past obs_kf")
         o = capi.PruneOpts()
         lib().covgpu_default_prune_opts(C.byref(o))
-        for k, v in opts.items():
-            if k not in ("th_red", "max_time_dist", "max_kfs", "max_rounds"):
-                raise TypeError(f"unknown prune option {k}")
-            setattr(o, k, -1 if k == "max_kfs" and v is None else v)
+        _set_opts(o, ("th_red", "max_time_dist", "max_kfs", "max_rounds"), opts, "prune", lambda k, v: -1 if k == "max_kfs" and v is None else v)
         cap = K if capacity is None else int(capacity)
         out = dict(round_kf=np.full(max(cap, 1), -1, np.int32), round_action=np.full(max(cap, 1), -1, np.int32),
                    scal=np.zeros(3, np.int32), kf_pred=np.zeros(max(K, 1), np.int32), kf_succ=np.zeros(max(K, 1), np.int32),
                    lm_nobs=np.zeros(max(L, 1), np.int32), red_num=np.zeros(max(K, 1), np.int32), red_den=np.zeros(max(K, 1), np.int32),
                    loop_ms=np.zeros(1))
-        bp = lambda a: None if a is None else a.ctypes.data_as(capi._bp)
         sc = out["scal"]
-        s = capi.PruneBatch(K, L, iptr(ptr), iptr(okf), *(bp(f) for f in flags), iptr(pred), iptr(succ), dptr(time), cap,
+        s = capi.PruneBatch(K, L, iptr(ptr), iptr(okf), *(_bp(f) for f in flags), iptr(pred), iptr(succ), dptr(time), cap,
                             iptr(out["round_kf"]), iptr(out["round_action"]), iptr(sc[0:1]), iptr(sc[1:2]), iptr(sc[2:3]),
                             iptr(out["kf_pred"]), iptr(out["kf_succ"]), iptr(out["lm_nobs"]), iptr(out["red_num"]), iptr(out["red_den"]),
                             dptr(out["loop_ms"]) if want_loop_ms else None)
@@ -761,12 +765,11 @@ class Context:
     def _refresh_batch(lm_obs_ptr, obs_kf, obs_desc, obs_octave, lm_ref_obs, lm_pos, kf_center, kf_invalid, lm_invalid, opts,
                        want_kernel_ms=False):
         """(LandmarkRefresh, LandmarkRefreshOpts, outputs, keep-alive list) of one covgpu_landmark_refresh call."""
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ravel()
-        flag = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint8).ravel()
+        i32 = lambda a: _i32(a).ravel()
+        flag = lambda a: _opt(lambda x: _u8(x).ravel(), a)
         ptr, okf, ooc, ref = i32(lm_obs_ptr), i32(obs_kf), i32(obs_octave), i32(lm_ref_obs)
-        pos = np.ascontiguousarray(lm_pos, dtype=np.float64).reshape(-1, 3)
-        cen = np.ascontiguousarray(kf_center, dtype=np.float64).reshape(-1, 3)
-        desc = None if obs_desc is None else np.ascontiguousarray(obs_desc, dtype=np.uint8).reshape(-1, 32)
+        pos, cen = _f64(lm_pos).reshape(-1, 3), _f64(kf_center).reshape(-1, 3)
+        desc = _opt(lambda a: _u8(a).reshape(-1, 32), obs_desc)
         kinv, linv = flag(kf_invalid), flag(lm_invalid)
         K, L = len(cen), len(ptr) - 1
         if L < 0 or len(ref) != L or len(pos) != L or len(ooc) != len(okf) or (desc is not None and len(desc) != len(okf)) or \
@@ -776,15 +779,12 @@ class Context:
             raise ValueError("lm_obs_ptr runs past obs_kf")
         o = capi.LandmarkRefreshOpts()
         lib().covgpu_default_landmark_refresh_opts(C.byref(o))
-        for k, v in opts.items():
-            if k not in ("scale_factor", "num_octaves"):
-                raise TypeError(f"unknown landmark-refresh option {k}")
-            setattr(o, k, v)
+        _set_opts(o, ("scale_factor", "num_octaves"), opts, "landmark-refresh")
         n = max(L, 1)
         out = dict(lm_desc_obs=np.full(n, -1, np.int32), lm_desc=np.zeros((n, 32), np.uint8), lm_normal=np.zeros((n, 3)),
                    lm_min_distance=np.zeros(n), lm_max_distance=np.zeros(n), lm_status=np.zeros(n, np.int32),
                    form_count=np.zeros(capi.LMR_FORMS, np.int32), kernel_ms=np.zeros(1))
-        bp = lambda a: None if a is None else a.ctypes.data_as(capi._bp)
+        bp = _bp
         s = capi.LandmarkRefresh(K, L, iptr(ptr), iptr(okf), bp(desc), iptr(ooc), iptr(ref), dptr(pos), dptr(cen), bp(kinv), bp(linv),
                                  iptr(out["lm_desc_obs"]), bp(out["lm_desc"]), dptr(out["lm_normal"]), dptr(out["lm_min_distance"]),
                                  dptr(out["lm_max_distance"]), iptr(out["lm_status"]), iptr(out["form_count"]),
@@ -814,17 +814,14 @@ class Context:
     @staticmethod
     def _voc_train_batch(row_ptr, desc, k, L, weighting, seed, opts, node_capacity=None, want_row_word=False):
         """(VocTrain, VocTrainOpts, outputs, keep-alive list) of one covgpu_voc_train call."""
-        ptr = np.ascontiguousarray(row_ptr, dtype=np.int32).ravel()
-        d = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        ptr = _i32(row_ptr).ravel()
+        d = _u8(desc).reshape(-1, 32)
         if len(ptr) < 1 or (len(ptr) > 1 and int(ptr[-1]) > len(d)):
             raise ValueError("row_ptr runs past desc")
         o = capi.VocTrainOpts()
         lib().covgpu_default_voc_train_opts(C.byref(o))
         o.k, o.L, o.weighting, o.seed = int(k), int(L), int(weighting), int(seed) & ((1 << 64) - 1)
-        for name, v in opts.items():
-            if name not in ("scoring", "max_iterations", "scratch_kib"):
-                raise TypeError(f"unknown vocabulary-training option {name}")
-            setattr(o, name, int(v))
+        _set_opts(o, ("scoring", "max_iterations", "scratch_kib"), opts, "vocabulary-training", lambda k, v: int(v))
         rows = len(d)
         if node_capacity is None:                                  # every node the k-ary tree of depth L can have, or what the rows can fill
             full = sum(int(k) ** i for i in range(int(L) + 1)) if 2 <= int(k) <= 32 and 1 <= int(L) <= 20 else 1
@@ -833,9 +830,9 @@ class Context:
         out = dict(num_nodes=np.zeros(1, np.int32), num_words=np.zeros(1, np.int32), parent=np.full(n, -2, np.int32),
                    desc=np.zeros((n, 32), np.uint8), word_id=np.full(n, -2, np.int32), weight=np.full(n, -1.0),
                    row_word=np.full(max(rows, 1), -2, np.int32) if want_row_word else None, stats=np.zeros(8, np.int64))
-        s = capi.VocTrain(len(ptr) - 1, iptr(ptr), d.ctypes.data_as(capi._bp), int(node_capacity), iptr(out["num_nodes"]),
-                          iptr(out["num_words"]), iptr(out["parent"]), out["desc"].ctypes.data_as(capi._bp), iptr(out["word_id"]),
-                          dptr(out["weight"]), None if out["row_word"] is None else iptr(out["row_word"]),
+        s = capi.VocTrain(len(ptr) - 1, iptr(ptr), _bp(d), int(node_capacity), iptr(out["num_nodes"]),
+                          iptr(out["num_words"]), iptr(out["parent"]), _bp(out["desc"]), iptr(out["word_id"]),
+                          dptr(out["weight"]), _opt(iptr, out["row_word"]),
                           out["stats"].ctypes.data_as(capi._lp))
         return s, o, out, [ptr, d]
 
@@ -864,8 +861,7 @@ class Context:
 
     def p3p_batch(self, f, P):
         """covgpu_p3p_batch: f, P [n,4,3] -> (T [n,4,7] every solution, qx qy qz qw x y z, ascending v = s3/s1; nsol [n]; chosen [n], -1: none)."""
-        f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 4, 3)
-        P = np.ascontiguousarray(P, dtype=np.float64).reshape(-1, 4, 3)
+        f, P = _f64(f).reshape(-1, 4, 3), _f64(P).reshape(-1, 4, 3)
         n = f.shape[0]
         T = np.zeros((max(n, 1), 4, 7)); ns = np.zeros(max(n, 1), np.int32); ch = np.zeros(max(n, 1), np.int32)
         self._check(lib().covgpu_p3p_batch(self._h, n, dptr(f), dptr(P), dptr(T), iptr(ns), iptr(ch)))

@@ -5,8 +5,9 @@
 // (guided matching, k_guided.hip), §4.13 (bag-of-words transform, score and candidate query, k_bow.hip), §4.14 (redundant-keyframe
 // pruning, k_prune.hip), §4.15 (landmark descriptors, normals and scale ranges, k_lmrefresh.hip) and §4.17 (float descriptor matching,
 // k_matchf.hip).
-// Every entry point checks all its arguments before its first device call, holds its device buffers in one DeviceScratch
-// (host.hpp) and synchronises its stream once, at the end.
+// Every entry point reads: check (batch_check.hpp: a pure function that also fills the call's plan), hipSetDevice, uploads into one
+// DeviceScratch (host.hpp), launch, fetches and one synchronisation of its stream, at the end. The prologue (batch_entry) and the body of
+// the covgpu_*_check exports (check_export) are in host.hpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -17,44 +18,12 @@
 
 using namespace covgpu;
 
-// The prologue of every device entry point of this file: a NULL context is an argument error, and no C++ exception leaves the call.
-// `bad` is the body's argument-error return: "<function>: <message>".
-template <typename F>
-static int batch_entry(const char* fn, covgpu_context* c, F&& body) {
-  auto bad = [fn](const char* m) -> int { g_err = std::string(fn) + ": " + m; return COVGPU_ERR_INVALID_ARG; };
-  if (!c) return bad("NULL context");
-  return guarded([&] { return body(bad); });
-}
-
 extern "C" int covgpu_relpose_batch(covgpu_context* c, const covgpu_relpose_batch_t* bt, double th_outlier, int32_t min_inliers) {
   return batch_entry("covgpu_relpose_batch", c, [&](auto bad) -> int {
-    if (!bt || bt->num_pairs < 0 || (bt->num_pairs > 0 && (!bt->corr_ptr || !bt->T_ab || !bt->inliers || !bt->cam_a || !bt->cam_b || !bt->dist_type_a || !bt->dist_type_b)))
-      return bad("NULL array");
-    const size_t B = (size_t)bt->num_pairs;
+    RelposePlan P;
+    if (const char* m = relpose_check(bt, P)) return bad(m);
+    const size_t B = (size_t)bt->num_pairs, C = P.corr;
     if (B == 0) return COVGPU_OK;
-    for (size_t b = 0; b < B; ++b) if (bt->corr_ptr[b + 1] < bt->corr_ptr[b]) return bad("corr_ptr not monotone");
-    for (const int32_t* m : {bt->cam_model_a, bt->cam_model_b}) if (m) for (size_t b = 0; b < B; ++b) {
-      if (m[b] != COVGPU_CAM_PINHOLE && m[b] != COVGPU_CAM_UNIFIED) return bad("unknown camera model");
-    }
-    // per side: model and xi of every pair (xi 0 for pinhole rows); uploaded only if some camera of the batch is unified
-    std::vector<int32_t> hmA(B, COVGPU_CAM_PINHOLE), hmB(B, COVGPU_CAM_PINHOLE);
-    std::vector<double> hxA(B, 0.0), hxB(B, 0.0);
-    bool uni = false;
-    for (int side = 0; side < 2; ++side) {
-      const int32_t* m = side ? bt->cam_model_b : bt->cam_model_a;
-      const double* x = side ? bt->xi_b : bt->xi_a;
-      std::vector<int32_t>& hm = side ? hmB : hmA;
-      std::vector<double>& hx = side ? hxB : hxA;
-      if (!m) continue;
-      for (size_t b = 0; b < B; ++b) {
-        if (m[b] != COVGPU_CAM_UNIFIED) continue;
-        if (!x) return bad("unified camera without xi");
-        if (!std::isfinite(x[b]) || x[b] < 0.0) return bad("xi of a unified camera is negative or not finite");
-        hm[b] = COVGPU_CAM_UNIFIED; hx[b] = x[b]; uni = true;
-      }
-    }
-    const size_t C = (size_t)bt->corr_ptr[B];
-    if (C > 0 && (!bt->p_a || !bt->p_b || !bt->kp_a || !bt->kp_b || !bt->sigma_a || !bt->sigma_b || !bt->outlier)) return bad("NULL correspondence array");
     HIPCHK(hipSetDevice(c->device));
     DeviceScratch U(c->st);
     int *dptr_ = nullptr, *dda = nullptr, *ddb = nullptr, *din = nullptr, *dmA = nullptr, *dmB = nullptr;
@@ -68,9 +37,9 @@ extern "C" int covgpu_relpose_batch(covgpu_context* c, const covgpu_relpose_batc
     HIPCHK(U.upload(&dcA, bt->cam_a, 8 * B)); HIPCHK(U.upload(&dcB, bt->cam_b, 8 * B));
     HIPCHK(U.upload(&dda, bt->dist_type_a, B)); HIPCHK(U.upload(&ddb, bt->dist_type_b, B));
     HIPCHK(U.upload(&dT, bt->T_ab, 7 * B));
-    if (uni) {
-      HIPCHK(U.upload(&dmA, hmA.data(), B)); HIPCHK(U.upload(&dmB, hmB.data(), B));
-      HIPCHK(U.upload(&dxA, hxA.data(), B)); HIPCHK(U.upload(&dxB, hxB.data(), B));
+    if (P.unified) {
+      HIPCHK(U.upload(&dmA, P.model_a.data(), B)); HIPCHK(U.upload(&dmB, P.model_b.data(), B));
+      HIPCHK(U.upload(&dxA, P.xi_a.data(), B)); HIPCHK(U.upload(&dxB, P.xi_b.data(), B));
     }
     HIPCHK(U.alloc(&din, B)); HIPCHK(U.alloc(&dout, C));
     launch_relpose((int)B, dptr_, dpB, dpA, dkA, dkB, dsA, dsB, dcA, dda, dcB, ddb, th_outlier, min_inliers, dT, dout, din, c->st, dmA, dxA, dmB, dxB);
@@ -87,27 +56,10 @@ extern "C" void covgpu_default_ransac_opts(covgpu_ransac_opts* o) {
 
 extern "C" int covgpu_abspose_ransac_batch(covgpu_context* c, const covgpu_abspose_batch_t* bt, const covgpu_ransac_opts* opts) {
   return batch_entry("covgpu_abspose_ransac_batch", c, [&](auto bad) -> int {
-    if (!bt || !opts) return bad("NULL batch or options");
-    if (bt->num < 0) return bad("num < 0");
-    if (opts->max_iterations <= 0) return bad("max_iterations <= 0");
-    if (opts->max_iterations > 100000) return bad("max_iterations > 100000 (a candidate makes up to 11 max_iterations draws in one launch)");
-    if (!(opts->probability > 0.0 && opts->probability < 1.0)) return bad("probability outside (0, 1)");
-    if (!std::isfinite(opts->threshold) || !(opts->threshold > 0.0)) return bad("threshold not finite or not positive");
-    const size_t B = (size_t)bt->num;
+    AbsposePlan P;
+    if (const char* m = abspose_check(bt, opts, P)) return bad(m);
+    const size_t B = (size_t)bt->num, C = P.corr;
     if (B == 0) return COVGPU_OK;
-    if (!bt->corr_ptr || !bt->T_wc || !bt->inliers) return bad("NULL array");
-    if (bt->corr_ptr[0] != 0) return bad("corr_ptr[0] != 0");
-    int max_n = 0;
-    for (size_t b = 0; b < B; ++b) {
-      if (bt->corr_ptr[b + 1] < bt->corr_ptr[b]) return bad("corr_ptr not monotone");
-      max_n = std::max(max_n, bt->corr_ptr[b + 1] - bt->corr_ptr[b]);
-    }
-    const size_t C = (size_t)bt->corr_ptr[B];
-    if (C > 0 && (!bt->bearing || !bt->point_w || !bt->sigma_angle || !bt->inlier)) return bad("NULL correspondence array");
-    for (size_t i = 0; i < 3 * C; ++i)
-      if (!std::isfinite(bt->bearing[i]) || !std::isfinite(bt->point_w[i])) return bad("non-finite bearing or point");
-    std::vector<unsigned long long> seeds(B);   // (the kernel's type for the 64-bit seeds)
-    for (size_t b = 0; b < B; ++b) seeds[b] = bt->seed ? bt->seed[b] : opts->seed + (uint64_t)b;
     HIPCHK(hipSetDevice(c->device));
     DeviceScratch U(c->st);
     int *dptr_ = nullptr, *din = nullptr, *dit = nullptr, *dbd = nullptr;
@@ -116,11 +68,11 @@ extern "C" int covgpu_abspose_ransac_batch(covgpu_context* c, const covgpu_abspo
     unsigned char* dmask = nullptr;
     HIPCHK(U.upload(&dptr_, bt->corr_ptr, B + 1));
     HIPCHK(U.upload(&df, bt->bearing, 3 * C)); HIPCHK(U.upload(&dP, bt->point_w, 3 * C)); HIPCHK(U.upload(&ds, bt->sigma_angle, C));
-    HIPCHK(U.upload(&dseed, seeds.data(), B));
+    HIPCHK(U.upload(&dseed, P.seeds.data(), B));
     HIPCHK(U.upload(&dT, bt->T_wc, 7 * B));   // untouched rows come back as they went
     HIPCHK(U.alloc(&dmask, C)); HIPCHK(U.alloc(&din, B)); HIPCHK(U.alloc(&dit, B)); HIPCHK(U.alloc(&dbd, B));
     launch_abspose((int)B, dptr_, df, dP, ds, dseed, dT, dmask, din, dit, dbd, opts->min_inliers, opts->max_iterations, opts->probability, opts->threshold,
-                   max_n, c->st);
+                   P.max_n, c->st);
     HIPCHK(hipGetLastError());
     HIPCHK(U.fetch(bt->T_wc, dT, 7 * B)); HIPCHK(U.fetch(bt->inliers, din, B));
     HIPCHK(U.fetch(bt->iterations, dit, B)); HIPCHK(U.fetch(bt->best_draw, dbd, B));
@@ -132,12 +84,9 @@ extern "C" int covgpu_abspose_ransac_batch(covgpu_context* c, const covgpu_abspo
 
 extern "C" int covgpu_p3p_batch(covgpu_context* c, int32_t n, const double* f, const double* P, double* T, int32_t* nsol, int32_t* chosen) {
   return batch_entry("covgpu_p3p_batch", c, [&](auto bad) -> int {
-    if (n < 0) return bad("n < 0");
+    if (const char* m = p3p_check(n, f, P, T, nsol, chosen)) return bad(m);
     if (n == 0) return COVGPU_OK;
-    if (!f || !P || !T || !nsol || !chosen) return bad("NULL array");
     const size_t N = (size_t)n;
-    for (size_t i = 0; i < 12 * N; ++i)
-      if (!std::isfinite(f[i]) || !std::isfinite(P[i])) return bad("non-finite bearing or point");
     HIPCHK(hipSetDevice(c->device));
     DeviceScratch U(c->st);
     double *df, *dP, *dT; int *dn, *dc;
@@ -160,39 +109,12 @@ extern "C" void covgpu_default_match_opts(covgpu_match_opts* o, int32_t mode) {
 
 extern "C" int covgpu_match_batch(covgpu_context* c, const covgpu_match_batch_t* bt, const covgpu_match_opts* opts) {
   return batch_entry("covgpu_match_batch", c, [&](auto bad) -> int {
-    if (!bt || !opts) return bad("NULL batch or options");
-    if (opts->mode != COVGPU_MATCH_DENSE && opts->mode != COVGPU_MATCH_KNN2) return bad("unknown mode");
-    if (!std::isfinite(opts->dist_threshold) || !(opts->dist_threshold > 0.0f)) return bad("dist_threshold not finite or not positive");
-    if (!std::isfinite(opts->ratio) || !(opts->ratio > 0.0f)) return bad("ratio not finite or not positive");
-    const bool dense = opts->mode == COVGPU_MATCH_DENSE;
-    if (bt->num_sets < 0 || bt->num_jobs < 0) return bad("num_sets or num_jobs < 0");
-    if (!dense && bt->skip) return bad("skip must be NULL in KNN2");
-    if (bt->num_sets > 0 && !bt->row_ptr) return bad("NULL row_ptr");
-    if (bt->num_sets > 0 && bt->row_ptr[0] != 0) return bad("row_ptr[0] != 0");
-    for (int s = 0; s < bt->num_sets; ++s) {
-      if (bt->row_ptr[s + 1] < bt->row_ptr[s]) return bad("row_ptr not monotone");
-      if (bt->row_ptr[s + 1] - bt->row_ptr[s] > COVGPU_MATCH_MAX_ROWS) return bad("a set holds more than COVGPU_MATCH_MAX_ROWS rows");
-    }
-    const size_t R = bt->num_sets > 0 ? (size_t)bt->row_ptr[bt->num_sets] : 0;
-    if (R > 0 && !bt->desc) return bad("NULL desc");
+    MatchPlan P;
+    if (const char* m = match_check(bt, opts, P)) return bad(m);
     const int J = bt->num_jobs;
-    if (J > 0 && (!bt->set_a || !bt->set_b || !bt->nmatches)) return bad("NULL job array");
-    std::vector<int32_t> off(J > 0 ? J : 1, 0);
-    size_t totalA = 0;
-    int maxA = 0, maxB = 0;
-    for (int j = 0; j < J; ++j) {
-      if (bt->set_a[j] < 0 || bt->set_a[j] >= bt->num_sets || bt->set_b[j] < 0 || bt->set_b[j] >= bt->num_sets) return bad("set index out of range");
-      const int nA = bt->row_ptr[bt->set_a[j] + 1] - bt->row_ptr[bt->set_a[j]];
-      off[j] = (int32_t)totalA;
-      totalA += (size_t)nA;
-      if (totalA > (size_t)INT32_MAX) return bad("more than 2^31 - 1 output rows");
-      maxA = std::max(maxA, nA);
-      maxB = std::max(maxB, bt->row_ptr[bt->set_b[j] + 1] - bt->row_ptr[bt->set_b[j]]);
-    }
-    if (totalA > 0 && !bt->match) return bad("NULL match");
     if (J == 0) return COVGPU_OK;
-    const int tiles = (maxA + kMatchScanRows - 1) / kMatchScanRows;  // scan workgroups per job (launch_match): one 1-D grid of J * tiles
-    if ((int64_t)J * tiles > (int64_t)INT32_MAX) return bad("num_jobs * ceil(max query rows / 256) exceeds 2^31 - 1 workgroups");
+    const bool dense = opts->mode == COVGPU_MATCH_DENSE;
+    const size_t R = P.rows, totalA = P.total_a;
     HIPCHK(hipSetDevice(c->device));
     int dcut = 0;                                                    // (float)d < dist_threshold  <=>  d < dcut, for d in 0..256
     while (dcut <= 256 && (float)dcut < opts->dist_threshold) ++dcut;
@@ -202,10 +124,10 @@ extern "C" int covgpu_match_batch(covgpu_context* c, const covgpu_match_batch_t*
     HIPCHK(U.upload(&ddesc, bt->desc, 32 * R));
     if (dense && bt->skip) HIPCHK(U.upload(&dskip, bt->skip, R));
     HIPCHK(U.upload(&dptr_, bt->row_ptr, (size_t)bt->num_sets + 1));
-    HIPCHK(U.upload(&dsa, bt->set_a, (size_t)J)); HIPCHK(U.upload(&dsb, bt->set_b, (size_t)J)); HIPCHK(U.upload(&doff, off.data(), (size_t)J));
+    HIPCHK(U.upload(&dsa, bt->set_a, (size_t)J)); HIPCHK(U.upload(&dsb, bt->set_b, (size_t)J)); HIPCHK(U.upload(&doff, P.off.data(), (size_t)J));
     if (dense) HIPCHK(U.alloc(&dlist, 4 * totalA));                  // the 4 best of every query row
     HIPCHK(U.alloc(&dmatch, totalA)); HIPCHK(U.alloc(&ddist, totalA)); HIPCHK(U.zeroed(&dn, (size_t)J));
-    launch_match(opts->mode, J, maxA, maxB, ddesc, dskip, dptr_, dsa, dsb, doff, dlist, dmatch, ddist, dn, dcut, opts->dist_threshold, opts->ratio,
+    launch_match(opts->mode, J, P.max_a, P.max_b, ddesc, dskip, dptr_, dsa, dsb, doff, dlist, dmatch, ddist, dn, dcut, opts->dist_threshold, opts->ratio,
                  c->st);
     HIPCHK(hipGetLastError());
     HIPCHK(U.fetch(bt->match, dmatch, totalA)); HIPCHK(U.fetch(bt->dist, ddist, totalA)); HIPCHK(U.fetch(bt->nmatches, dn, (size_t)J));
@@ -226,60 +148,13 @@ extern "C" void covgpu_match_float_limits(int32_t out[4]) {
   out[0] = COVGPU_MATCH_MAX_ROWS; out[1] = kMatchFloatMaxDim; out[2] = kMatchFloatTileRows; out[3] = kMatchFloatChunkRows;
 }
 
-namespace {
-
-// What covgpu_match_float_batch derives from its arguments while it checks them.
-struct MatchFloatPlan { size_t rows = 0, total_a = 0; int max_a = 0; std::vector<int32_t> off; };
-
-// All checks of covgpu_match_float_batch; the message of the first violation, or nullptr.
-const char* match_float_check(const covgpu_match_float_batch_t* bt, const covgpu_match_opts* opts, MatchFloatPlan& P) {
-  if (!bt || !opts) return "NULL batch or options";
-  if (opts->mode != COVGPU_MATCH_KNN2) return "mode must be COVGPU_MATCH_KNN2";
-  if (!std::isfinite(opts->dist_threshold) || !(opts->dist_threshold > 0.0f)) return "dist_threshold not finite or not positive";
-  if (!std::isfinite(opts->ratio) || !(opts->ratio > 0.0f)) return "ratio not finite or not positive";
-  if (bt->dim <= 0 || bt->dim % 4 != 0 || bt->dim > kMatchFloatMaxDim) return "dim must be a positive multiple of 4 up to 256";
-  if (bt->num_sets < 0 || bt->num_jobs < 0) return "num_sets or num_jobs < 0";
-  if (bt->num_sets > 0 && !bt->row_ptr) return "NULL row_ptr";
-  if (bt->num_sets > 0 && bt->row_ptr[0] != 0) return "row_ptr[0] != 0";
-  for (int s = 0; s < bt->num_sets; ++s) {
-    if (bt->row_ptr[s + 1] < bt->row_ptr[s]) return "row_ptr not monotone";
-    if (bt->row_ptr[s + 1] - bt->row_ptr[s] > COVGPU_MATCH_MAX_ROWS) return "a set holds more than COVGPU_MATCH_MAX_ROWS rows";
-  }
-  P.rows = bt->num_sets > 0 ? (size_t)bt->row_ptr[bt->num_sets] : 0;
-  if (P.rows > 0 && !bt->desc) return "NULL desc";
-  const int J = bt->num_jobs;
-  if (J > 0 && (!bt->set_a || !bt->set_b || !bt->nmatches)) return "NULL job array";
-  P.off.assign(J > 0 ? J : 1, 0);
-  for (int j = 0; j < J; ++j) {
-    if (bt->set_a[j] < 0 || bt->set_a[j] >= bt->num_sets || bt->set_b[j] < 0 || bt->set_b[j] >= bt->num_sets) return "set index out of range";
-    const int nA = bt->row_ptr[bt->set_a[j] + 1] - bt->row_ptr[bt->set_a[j]];
-    P.off[j] = (int32_t)P.total_a;
-    P.total_a += (size_t)nA;
-    if (P.total_a > (size_t)INT32_MAX) return "more than 2^31 - 1 output rows";
-    P.max_a = std::max(P.max_a, nA);
-  }
-  if (P.total_a > 0 && !bt->match) return "NULL match";
-  const int tiles = (P.max_a + kMatchFloatTileRows - 1) / kMatchFloatTileRows;   // scan workgroups per job (launch_matchf)
-  if ((int64_t)J * tiles > (int64_t)INT32_MAX) return "num_jobs * ceil(max query rows / 128) exceeds 2^31 - 1 workgroups";
-  // a NaN would leave the order by (distance, index) undefined, and |x|^2 has to stay finite in float32
-  for (size_t i = 0; i < P.rows * (size_t)bt->dim; ++i)
-    if (!(std::fabs(bt->desc[i]) <= kMatchFloatMaxAbs)) return "descriptor value not finite or above 1e18 in magnitude";
-  return nullptr;
-}
-
-}  // namespace
-
 extern "C" int covgpu_match_float_check(const covgpu_match_float_batch_t* bt, const covgpu_match_opts* opts) {
-  return guarded([&]() -> int {
-    MatchFloatPlan P;
-    if (const char* m = match_float_check(bt, opts, P)) { g_err = std::string("covgpu_match_float_check: ") + m; return COVGPU_ERR_INVALID_ARG; }
-    return COVGPU_OK;
-  });
+  return check_export("covgpu_match_float_check", [&] { MatchPlan P; return match_float_check(bt, opts, P); });
 }
 
 extern "C" int covgpu_match_float_batch(covgpu_context* c, const covgpu_match_float_batch_t* bt, const covgpu_match_opts* opts) {
   return batch_entry("covgpu_match_float_batch", c, [&](auto bad) -> int {
-    MatchFloatPlan P;
+    MatchPlan P;
     if (const char* m = match_float_check(bt, opts, P)) return bad(m);
     const int J = bt->num_jobs;
     if (J == 0) return COVGPU_OK;
@@ -311,26 +186,6 @@ extern "C" void covgpu_default_guided_opts(covgpu_guided_opts* o, int32_t mode) 
 }
 
 namespace {
-
-// Checks shared by the two guided entry points; the message of the first violation, or nullptr.
-const char* guided_check(const covgpu_keypoint_sets_t& s, const covgpu_guided_opts* o) {
-  if (!o) return "NULL options";
-  if (o->th_low < 0 || o->th_low > 255) return "th_low outside [0, 255]";
-  if (!std::isfinite(o->radius) || !(o->radius > 0.0)) return "radius not finite or not positive";
-  if (o->num_octaves < 1) return "num_octaves < 1";
-  if (o->num_octaves > 1 && (!std::isfinite(o->scale_factor) || !(o->scale_factor > 1.0))) return "scale_factor not finite or not above 1";
-  if (o->agreement != 0 && o->agreement != 1) return "agreement is neither 0 nor 1";
-  if (s.num_sets < 0) return "num_sets < 0";
-  if (s.num_sets > 0 && !s.row_ptr) return "NULL row_ptr";
-  if (s.num_sets > 0 && s.row_ptr[0] != 0) return "row_ptr[0] != 0";
-  for (int i = 0; i < s.num_sets; ++i) {
-    if (s.row_ptr[i + 1] < s.row_ptr[i]) return "row_ptr not monotone";
-    if (s.row_ptr[i + 1] - s.row_ptr[i] > COVGPU_MATCH_MAX_ROWS) return "a set holds more than COVGPU_MATCH_MAX_ROWS rows";
-  }
-  if (s.num_sets > 0 && !s.bounds) return "NULL bounds";
-  if (s.num_sets > 0 && s.row_ptr[s.num_sets] > 0 && (!s.kp || !s.level || !s.desc)) return "NULL keypoint array";
-  return nullptr;
-}
 
 // Device records of the keypoints: {x, y, level, visiting rank}. Grid order is ascending (cell_x, cell_y, index) with the cell of
 // AssignFeaturesToGrid (keyframe_base.cpp:134-139) clamped to the 64 x 48 grid; index order when the set has no grid. A taken keypoint
@@ -365,55 +220,53 @@ std::vector<int4> guided_records(const covgpu_keypoint_sets_t& s, const uint8_t*
   return rec;
 }
 
+// The keypoint sets of a guided call on the device (the 32-byte descriptors go up as the kernels read them: two uint4 a row). `rec`
+// stages the records: the caller declares it before the scratch, so that it outlives the copy.
+int upload_guided_sets(DeviceScratch& U, const covgpu_keypoint_sets_t& s, const uint8_t* taken, std::vector<int4>& rec, GuidedSets& D) {
+  const size_t R = s.num_sets > 0 ? (size_t)s.row_ptr[s.num_sets] : 0, S = (size_t)s.num_sets;
+  rec = guided_records(s, taken);
+  HIPCHK(U.upload(&D.kpr, rec.data(), R)); HIPCHK(U.upload(&D.kdesc, (const uint4*)s.desc, 2 * R));
+  HIPCHK(U.upload(&D.row_ptr, s.row_ptr, S + 1)); HIPCHK(U.upload(&D.bounds, s.bounds, 4 * S));
+  return COVGPU_OK;
+}
+
+// The scan tiles of a guided call on the device: the kernels read a GuidedTile as an int4 {job, direction, first point, points}.
+static_assert(sizeof(GuidedTile) == sizeof(int4) && offsetof(GuidedTile, job) == offsetof(int4, x) && offsetof(GuidedTile, dir) == offsetof(int4, y) &&
+              offsetof(GuidedTile, first) == offsetof(int4, z) && offsetof(GuidedTile, count) == offsetof(int4, w), "a GuidedTile is uploaded as an int4");
+int upload_guided_tiles(DeviceScratch& U, const std::vector<GuidedTile>& tiles, const int4** d) {
+  HIPCHK(U.upload(d, reinterpret_cast<const int4*>(tiles.data()), tiles.size()));
+  return COVGPU_OK;
+}
+
+GuidedOptsDev guided_opts_dev(const covgpu_guided_opts* o) {
+  return GuidedOptsDev{o->th_low, o->radius, o->scale_factor, std::log(o->scale_factor), o->num_octaves, o->agreement};
+}
+
 }  // namespace
-// (the 32-byte descriptors below go up as the kernels read them: two uint4 a row)
 
 extern "C" int covgpu_search_se3_batch(covgpu_context* c, const covgpu_search_se3_batch_t* bt, const covgpu_guided_opts* opts) {
   return batch_entry("covgpu_search_se3_batch", c, [&](auto bad) -> int {
-    if (!bt) return bad("NULL batch");
-    if (const char* m = guided_check(bt->sets, opts)) return bad(m);
-    const covgpu_keypoint_sets_t& s = bt->sets;
-    const int S = s.num_sets, J = bt->num_jobs;
-    const size_t R = S > 0 ? (size_t)s.row_ptr[S] : 0;
-    if (J < 0) return bad("num_jobs < 0");
-    if (S > 0 && !bt->K) return bad("NULL K");
-    if (R > 0 && (!bt->lm_pos || !bt->lm_max_distance || !bt->lm_desc || !bt->lm_free)) return bad("NULL landmark array");
-    if (J > 0 && (!bt->set_1 || !bt->set_2 || !bt->T12 || !bt->nfound)) return bad("NULL job array");
-    std::vector<int32_t> off1(J > 0 ? J : 1, 0), off2(J > 0 ? J : 1, 0);
-    std::vector<int4> tiles;
-    size_t tot1 = 0, tot2 = 0;
-    for (int j = 0; j < J; ++j) {
-      if (bt->set_1[j] < 0 || bt->set_1[j] >= S || bt->set_2[j] < 0 || bt->set_2[j] >= S) return bad("set index out of range");
-      for (int k = 0; k < 7; ++k) if (!std::isfinite(bt->T12[7 * (size_t)j + k])) return bad("non-finite T12");
-      const int n1 = s.row_ptr[bt->set_1[j] + 1] - s.row_ptr[bt->set_1[j]], n2 = s.row_ptr[bt->set_2[j] + 1] - s.row_ptr[bt->set_2[j]];
-      off1[j] = (int32_t)tot1; off2[j] = (int32_t)tot2;
-      tot1 += (size_t)n1; tot2 += (size_t)n2;
-      if (tot1 > (size_t)INT32_MAX || tot2 > (size_t)INT32_MAX) return bad("more than 2^31 - 1 output rows");
-      for (int dir = 0; dir < 2; ++dir)
-        for (int f = 0, n = dir ? n2 : n1; f < n; f += kGuidedScanPoints) tiles.push_back(make_int4(j, dir, f, std::min(kGuidedScanPoints, n - f)));
-      if (tiles.size() > (size_t)INT32_MAX) return bad("more than 2^31 - 1 scan workgroups");
-    }
-    if (tot1 > 0 && !bt->match) return bad("NULL match");
+    GuidedPlan P;
+    if (const char* m = search_se3_check(bt, opts, P)) return bad(m);
+    const int J = bt->num_jobs;
     if (J == 0) return COVGPU_OK;
+    const size_t Ss = (size_t)bt->sets.num_sets, Js = (size_t)J, R = P.rows, tot1 = P.tot1, tot2 = P.tot2;
     HIPCHK(hipSetDevice(c->device));
-    const std::vector<int4> rec = guided_records(s, nullptr);
-    const size_t Ss = (size_t)S, Js = (size_t)J;
+    std::vector<int4> rec;
     DeviceScratch U(c->st);
     GuidedSe3Args A{};
-    HIPCHK(U.upload(&A.S.kpr, rec.data(), R)); HIPCHK(U.upload(&A.S.kdesc, (const uint4*)s.desc, 2 * R));
-    HIPCHK(U.upload(&A.S.row_ptr, s.row_ptr, Ss + 1)); HIPCHK(U.upload(&A.S.bounds, s.bounds, 4 * Ss));
+    RC(upload_guided_sets(U, bt->sets, nullptr, rec, A.S));
     HIPCHK(U.upload(&A.K, bt->K, 4 * Ss)); HIPCHK(U.upload(&A.lm_pos, bt->lm_pos, 3 * R));
     HIPCHK(U.upload(&A.lm_maxd, bt->lm_max_distance, R)); HIPCHK(U.upload(&A.lm_desc, (const uint4*)bt->lm_desc, 2 * R));
     HIPCHK(U.upload(&A.lm_free, bt->lm_free, R));
     HIPCHK(U.upload(&A.set_1, bt->set_1, Js)); HIPCHK(U.upload(&A.set_2, bt->set_2, Js));
     HIPCHK(U.upload(&A.T12, bt->T12, 7 * Js));
-    HIPCHK(U.upload(&A.off1, off1.data(), Js)); HIPCHK(U.upload(&A.off2, off2.data(), Js));
+    HIPCHK(U.upload(&A.off1, P.off1.data(), Js)); HIPCHK(U.upload(&A.off2, P.off2.data(), Js));
     const int4* dtiles = nullptr;
-    HIPCHK(U.upload(&dtiles, tiles.data(), tiles.size()));
+    RC(upload_guided_tiles(U, P.tiles, &dtiles));
     HIPCHK(U.alloc(&A.m1, tot1)); HIPCHK(U.alloc(&A.m2, tot2)); HIPCHK(U.alloc(&A.match, tot1));
     HIPCHK(U.zeroed(&A.nfound, Js));
-    const GuidedOptsDev O{opts->th_low, opts->radius, opts->scale_factor, std::log(opts->scale_factor), opts->num_octaves, opts->agreement};
-    launch_guided_se3(A, O, J, dtiles, (int)tiles.size(), c->st);
+    launch_guided_se3(A, guided_opts_dev(opts), J, dtiles, (int)P.tiles.size(), c->st);
     HIPCHK(hipGetLastError());
     HIPCHK(U.fetch(bt->match, A.match, tot1)); HIPCHK(U.fetch(bt->match1, A.m1, tot1)); HIPCHK(U.fetch(bt->match2, A.m2, tot2));
     HIPCHK(U.fetch(bt->nfound, A.nfound, Js));
@@ -424,53 +277,18 @@ extern "C" int covgpu_search_se3_batch(covgpu_context* c, const covgpu_search_se
 
 extern "C" int covgpu_search_projection_batch(covgpu_context* c, const covgpu_search_projection_batch_t* bt, const covgpu_guided_opts* opts) {
   return batch_entry("covgpu_search_projection_batch", c, [&](auto bad) -> int {
-    if (!bt) return bad("NULL batch");
-    if (const char* m = guided_check(bt->sets, opts)) return bad(m);
-    const covgpu_keypoint_sets_t& s = bt->sets;
-    const int S = s.num_sets, J = bt->num_jobs;
-    const size_t R = S > 0 ? (size_t)s.row_ptr[S] : 0;
-    if (J < 0) return bad("num_jobs < 0");
-    if (S > 0 && (!bt->cam || !bt->dist_type)) return bad("NULL camera array");
-    for (int i = 0; i < S; ++i) {
-      if (bt->dist_type[i] != COVGPU_DIST_RADTAN && bt->dist_type[i] != COVGPU_DIST_EQUIDISTANT) return bad("unknown distortion type");
-      if (!bt->cam_model || bt->cam_model[i] == COVGPU_CAM_PINHOLE) continue;
-      if (bt->cam_model[i] != COVGPU_CAM_UNIFIED) return bad("unknown camera model");
-      if (!bt->xi) return bad("unified camera without xi");
-      if (!std::isfinite(bt->xi[i]) || bt->xi[i] < 0.0) return bad("xi of a unified camera is negative or not finite");
-    }
-    if (J > 0 && (!bt->set || !bt->T_cw || !bt->point_ptr || !bt->nmatches)) return bad("NULL job array");
-    if (J > 0 && bt->point_ptr[0] != 0) return bad("point_ptr[0] != 0");
-    std::vector<int4> tiles;
-    for (int j = 0; j < J; ++j) {
-      if (bt->set[j] < 0 || bt->set[j] >= S) return bad("set index out of range");
-      if (bt->point_ptr[j + 1] < bt->point_ptr[j]) return bad("point_ptr not monotone");
-      for (int k = 0; k < 7; ++k) if (!std::isfinite(bt->T_cw[7 * (size_t)j + k])) return bad("non-finite T_cw");
-      for (int f = 0, n = bt->point_ptr[j + 1] - bt->point_ptr[j]; f < n; f += kGuidedScanPoints)
-        tiles.push_back(make_int4(j, 0, f, std::min(kGuidedScanPoints, n - f)));
-    }
-    const size_t P = J > 0 ? (size_t)bt->point_ptr[J] : 0;
-    if (P > 0 && (!bt->p_w || !bt->normal || !bt->min_distance || !bt->max_distance || !bt->p_desc || !bt->claimed || !bt->remap_to))
-      return bad("NULL point array");
-    if (bt->existing_idx)
-      for (int j = 0; j < J; ++j) {
-        const int n = s.row_ptr[bt->set[j] + 1] - s.row_ptr[bt->set[j]];
-        for (int p = bt->point_ptr[j]; p < bt->point_ptr[j + 1]; ++p)
-          if (bt->existing_idx[p] < -1 || bt->existing_idx[p] >= n) return bad("existing_idx out of range");
-      }
+    GuidedPlan G;
+    if (const char* m = search_projection_check(bt, opts, G)) return bad(m);
+    const int J = bt->num_jobs;
     if (J == 0) return COVGPU_OK;
+    const size_t Ss = (size_t)bt->sets.num_sets, Js = (size_t)J, P = G.points;
     HIPCHK(hipSetDevice(c->device));
-    const std::vector<int4> rec = guided_records(s, bt->taken);
-    const size_t Ss = (size_t)S, Js = (size_t)J;
+    std::vector<int4> rec;
     DeviceScratch U(c->st);
     GuidedProjArgs A{};
-    HIPCHK(U.upload(&A.S.kpr, rec.data(), R)); HIPCHK(U.upload(&A.S.kdesc, (const uint4*)s.desc, 2 * R));
-    HIPCHK(U.upload(&A.S.row_ptr, s.row_ptr, Ss + 1)); HIPCHK(U.upload(&A.S.bounds, s.bounds, 4 * Ss));
+    RC(upload_guided_sets(U, bt->sets, bt->taken, rec, A.S));
     HIPCHK(U.upload(&A.cam, bt->cam, 8 * Ss)); HIPCHK(U.upload(&A.dist_type, bt->dist_type, Ss));
-    std::vector<double> xi(S, 0.0);                                    // 0 for the pinhole rows, whose xi is not read
-    if (bt->cam_model) {
-      for (int i = 0; i < S; ++i) if (bt->cam_model[i] == COVGPU_CAM_UNIFIED) xi[i] = bt->xi[i];
-      HIPCHK(U.upload(&A.cam_model, bt->cam_model, Ss)); HIPCHK(U.upload(&A.xi, xi.data(), Ss));
-    }
+    if (bt->cam_model) { HIPCHK(U.upload(&A.cam_model, bt->cam_model, Ss)); HIPCHK(U.upload(&A.xi, G.xi.data(), Ss)); }
     HIPCHK(U.upload(&A.set, bt->set, Js)); HIPCHK(U.upload(&A.T_cw, bt->T_cw, 7 * Js));
     HIPCHK(U.upload(&A.point_ptr, bt->point_ptr, Js + 1));
     HIPCHK(U.upload(&A.p_w, bt->p_w, 3 * P)); HIPCHK(U.upload(&A.normal, bt->normal, 3 * P));
@@ -479,13 +297,12 @@ extern "C" int covgpu_search_projection_batch(covgpu_context* c, const covgpu_se
     if (bt->skip) HIPCHK(U.upload(&A.skip, bt->skip, P));
     if (bt->existing_idx) HIPCHK(U.upload(&A.existing, bt->existing_idx, P));
     const int4* dtiles = nullptr;
-    HIPCHK(U.upload(&dtiles, tiles.data(), tiles.size()));
+    RC(upload_guided_tiles(U, G.tiles, &dtiles));
     HIPCHK(U.alloc(&A.lists, kGuidedListCap * P)); HIPCHK(U.alloc(&A.cnt, P)); HIPCHK(U.alloc(&A.target, 2 * P));
     HIPCHK(U.alloc(&A.rad, P)); HIPCHK(U.alloc(&A.lvl, P)); HIPCHK(U.alloc(&A.dold, P));
     HIPCHK(U.alloc(&A.claimed, P)); HIPCHK(U.alloc(&A.remap_to, P)); HIPCHK(U.alloc(&A.best_dist, P));
     HIPCHK(U.alloc(&A.nmatches, Js));
-    const GuidedOptsDev O{opts->th_low, opts->radius, opts->scale_factor, std::log(opts->scale_factor), opts->num_octaves, opts->agreement};
-    launch_guided_projection(A, O, J, dtiles, (int)tiles.size(), c->st);
+    launch_guided_projection(A, guided_opts_dev(opts), J, dtiles, (int)G.tiles.size(), c->st);
     HIPCHK(hipGetLastError());
     HIPCHK(U.fetch(bt->claimed, A.claimed, P)); HIPCHK(U.fetch(bt->remap_to, A.remap_to, P)); HIPCHK(U.fetch(bt->best_dist, A.best_dist, P));
     HIPCHK(U.fetch(bt->nmatches, A.nmatches, Js));
@@ -497,8 +314,7 @@ extern "C" int covgpu_search_projection_batch(covgpu_context* c, const covgpu_se
 extern "C" int covgpu_pgo_reanchor(covgpu_context* c, int32_t K, const double* pose_old, const double* pose_new, double* velocity, int32_t L,
                                    const int32_t* ref_kf, double* lm_pos) {
   return batch_entry("covgpu_pgo_reanchor", c, [&](auto bad) -> int {
-    if (K < 0 || L < 0 || (K > 0 && (!pose_old || !pose_new)) || (L > 0 && (!ref_kf || !lm_pos))) return bad("NULL array");
-    for (int l = 0; l < L; ++l) if (ref_kf[l] >= K) return bad("ref_kf out of range");
+    if (const char* m = reanchor_check(K, pose_old, pose_new, L, ref_kf, lm_pos)) return bad(m);
     HIPCHK(hipSetDevice(c->device));
     const size_t Ks = (size_t)K, Ls = (size_t)L;
     DeviceScratch U(c->st);
@@ -514,76 +330,13 @@ extern "C" int covgpu_pgo_reanchor(covgpu_context* c, int32_t K, const double* p
 }
 
 // ---- bag-of-words retrieval (k_bow.hip) ----
-// (the two checks are shared with bowdb.hip: declared in host.hpp)
-
-// The first violation of a bow CSR over `rows` rows (word ids ascending and duplicate-free, values finite), or nullptr.
-const char* bow_csr_check(int rows, const int32_t* ptr, const int32_t* word, const double* value) {
-  if (rows < 0) return "negative row count";
-  if (rows == 0) return nullptr;
-  if (!ptr) return "NULL bow_ptr";
-  if (ptr[0] != 0) return "bow_ptr[0] != 0";
-  for (int r = 0; r < rows; ++r) if (ptr[r + 1] < ptr[r]) return "bow_ptr not monotone";
-  if (ptr[rows] > 0 && (!word || !value)) return "NULL word or value";
-  for (int r = 0; r < rows; ++r)
-    for (int i = ptr[r]; i < ptr[r + 1]; ++i) {
-      if (word[i] < 0) return "negative word id";
-      if (i > ptr[r] && word[i] <= word[i - 1]) return "word ids of a bow row not ascending and duplicate-free";
-      if (!std::isfinite(value[i])) return "non-finite bow value";
-    }
-  return nullptr;
-}
-
-// The first violation of the vocabulary's tree shape, or nullptr.
-const char* bow_vocab_check(const covgpu_bow_vocab_t* v) {
-  if (!v) return "NULL vocabulary";
-  if (v->scoring != COVGPU_BOW_L1_NORM) return "only L1_NORM scoring is supported";
-  if (v->weighting < COVGPU_BOW_TF_IDF || v->weighting > COVGPU_BOW_BINARY) return "unknown weighting";
-  const int N = v->num_nodes, W = v->num_words;
-  if (N < 2) return "the vocabulary has no node below the root";
-  if (W < 1 || W > COVGPU_BOW_MAX_WORDS) return "num_words is not in 1..COVGPU_BOW_MAX_WORDS";
-  if (v->k < 1 || v->L < 0) return "k < 1 or L < 0";
-  if (!v->parent || !v->child_ptr || !v->child || !v->desc || !v->word_id || !v->weight) return "NULL vocabulary array";
-  if (v->parent[0] != -1) return "parent[0] != -1";
-  for (int n = 1; n < N; ++n) if (v->parent[n] < 0 || v->parent[n] >= n) return "parent[n] is not in 0..n-1";
-  if (v->child_ptr[0] != 0) return "child_ptr[0] != 0";
-  for (int n = 0; n < N; ++n) if (v->child_ptr[n + 1] < v->child_ptr[n]) return "child_ptr not monotone";
-  if (v->child_ptr[N] != N - 1) return "child_ptr[num_nodes] != num_nodes - 1";
-  std::vector<uint8_t> seen(W, 0);
-  for (int n = 0; n < N; ++n) {
-    for (int i = v->child_ptr[n]; i < v->child_ptr[n + 1]; ++i) {
-      const int c = v->child[i];
-      if (c <= 0 || c >= N) return "child index out of range";
-      if (v->parent[c] != n) return "child lists inconsistent with parent";
-      if (i > v->child_ptr[n] && c <= v->child[i - 1]) return "children not in ascending (line) order";
-    }
-    const bool leaf = v->child_ptr[n + 1] == v->child_ptr[n];
-    if (leaf != (v->word_id[n] >= 0)) return "leaves are not exactly the nodes with a word id";
-    if (leaf) {
-      if (v->word_id[n] >= W) return "word id out of range";
-      if (seen[v->word_id[n]]) return "word ids are not a permutation of 0..num_words-1";
-      seen[v->word_id[n]] = 1;
-    }
-    if (!std::isfinite(v->weight[n])) return "non-finite weight";
-  }
-  for (int w = 0; w < W; ++w) if (!seen[w]) return "word ids are not a permutation of 0..num_words-1";
-  return nullptr;
-}
+// (the vocabulary and bow CSR checks are shared with bowdb.hip: batch_check.hpp)
 
 extern "C" int covgpu_bow_transform_batch(covgpu_context* c, const covgpu_bow_vocab_t* v, const covgpu_bow_transform_batch_t* bt) {
   return batch_entry("covgpu_bow_transform_batch", c, [&](auto bad) -> int {
-    if (!bt) return bad("NULL batch");
-    if (const char* m = bow_vocab_check(v)) return bad(m);
+    size_t R = 0;
+    if (const char* m = bow_transform_check(v, bt, R)) return bad(m);
     const int S = bt->num_sets;
-    if (S < 0 || bt->capacity < 0) return bad("num_sets or capacity < 0");
-    if (S > 0 && (!bt->row_ptr || !bt->bow_ptr)) return bad("NULL row_ptr or bow_ptr");
-    if (S > 0 && bt->row_ptr[0] != 0) return bad("row_ptr[0] != 0");
-    for (int s = 0; s < S; ++s) {
-      if (bt->row_ptr[s + 1] < bt->row_ptr[s]) return bad("row_ptr not monotone");
-      if (bt->row_ptr[s + 1] - bt->row_ptr[s] > COVGPU_MATCH_MAX_ROWS) return bad("a set holds more than COVGPU_MATCH_MAX_ROWS rows");
-    }
-    const size_t R = S > 0 ? (size_t)bt->row_ptr[S] : 0;
-    if (R > 0 && !bt->desc) return bad("NULL desc");
-    if (bt->capacity > 0 && (!bt->word || !bt->value)) return bad("NULL word or value");
     if (bt->total) *bt->total = 0;
     if (S == 0) return COVGPU_OK;
     const size_t N = (size_t)v->num_nodes, W = (size_t)v->num_words, Ss = (size_t)S;
@@ -631,11 +384,7 @@ extern "C" int covgpu_bow_transform_batch(covgpu_context* c, const covgpu_bow_vo
 extern "C" int covgpu_bow_score_pairs(covgpu_context* c, int32_t num_vec, const int32_t* bow_ptr, const int32_t* word, const double* value,
                                       int32_t num_pairs, const int32_t* a, const int32_t* b, double* score) {
   return batch_entry("covgpu_bow_score_pairs", c, [&](auto bad) -> int {
-    if (const char* m = bow_csr_check(num_vec, bow_ptr, word, value)) return bad(m);
-    if (num_pairs < 0) return bad("num_pairs < 0");
-    if (num_pairs > 0 && (!a || !b || !score)) return bad("NULL pair array");
-    for (int i = 0; i < num_pairs; ++i)
-      if (a[i] < 0 || a[i] >= num_vec || b[i] < 0 || b[i] >= num_vec) return bad("pair index out of range");
+    if (const char* m = bow_score_pairs_check(num_vec, bow_ptr, word, value, num_pairs, a, b, score)) return bad(m);
     if (num_pairs == 0) return COVGPU_OK;
     HIPCHK(hipSetDevice(c->device));
     const size_t nnz = (size_t)bow_ptr[num_vec], P = (size_t)num_pairs;
@@ -663,87 +412,24 @@ extern "C" void covgpu_default_detect_opts(covgpu_detect_opts* o, int32_t mode) 
 
 extern "C" int covgpu_detect_candidates_batch(covgpu_context* c, const covgpu_detect_batch_t* bt, const covgpu_detect_opts* opts) {
   return batch_entry("covgpu_detect_candidates_batch", c, [&](auto bad) -> int {
-    if (!bt || !opts) return bad("NULL batch or options");
-    if (!std::isfinite(opts->min_score_factor)) return bad("non-finite min_score_factor");
-    if (opts->scratch_kib < 0) return bad("scratch_kib < 0");
+    DetectPlan P;
+    if (const char* m = detect_check(bt, opts, P)) return bad(m);
     const int N = bt->num_kf, M = bt->num_db, Q = bt->num_queries, cap = bt->cap;
-    if (N < 0 || M < 0 || Q < 0 || cap < 0) return bad("negative count");
-    if (N > 0 && (!bt->id || !bt->client || !bt->nb_ptr)) return bad("NULL keyframe array");
-    for (int k = 0; k < N; ++k) if (bt->id[k] < 0) return bad("negative keyframe id");
-    if (const char* m = bow_csr_check(N, bt->bow_ptr, bt->word, bt->value)) return bad(m);
-    if (N > 0 && bt->nb_ptr[0] != 0) return bad("nb_ptr[0] != 0");
-    for (int k = 0; k < N; ++k) if (bt->nb_ptr[k + 1] < bt->nb_ptr[k]) return bad("nb_ptr not monotone");
-    const size_t NB = N > 0 ? (size_t)bt->nb_ptr[N] : 0;
-    if (NB > 0 && !bt->nb) return bad("NULL nb");
-    for (size_t i = 0; i < NB; ++i) if (bt->nb[i] < 0 || bt->nb[i] >= N) return bad("neighbour index out of range");
-    if (M > 0 && !bt->db_order) return bad("NULL db_order");
-    std::vector<int32_t> pos_of(N > 0 ? N : 1, -1);
-    for (int p = 0; p < M; ++p) {
-      const int k = bt->db_order[p];
-      if (k < 0 || k >= N) return bad("db_order index out of range");
-      if (pos_of[k] >= 0) return bad("db_order repeats a keyframe");
-      pos_of[k] = p;
-    }
-    if (Q > 0 && (!bt->query_kf || !bt->db_visible || !bt->num_candidates)) return bad("NULL query array");
-    if (Q > 0 && cap > 0 && !bt->candidates) return bad("NULL candidates");
-    int max_words = 0;
-    size_t num_pairs = 0;
-    for (int q = 0; q < Q; ++q) {
-      const int k = bt->query_kf[q];
-      if (k < 0 || k >= N) return bad("query_kf out of range");
-      if (bt->db_visible[q] < 0 || bt->db_visible[q] > M) return bad("db_visible is not in 0..num_db");
-      if (bt->min_score_in && std::isnan(bt->min_score_in[q])) return bad("min_score_in is NaN");
-      max_words = std::max(max_words, bt->bow_ptr[k + 1] - bt->bow_ptr[k]);
-      num_pairs += (size_t)(bt->nb_ptr[k + 1] - bt->nb_ptr[k]);
-    }
-    if (num_pairs > (size_t)INT32_MAX) return bad("more than 2^31 - 1 query neighbours");
     if (Q == 0) return COVGPU_OK;
-    // host side of the call: the reference-score pairs and the inverted index of the database (posting lists in insertion order)
-    std::vector<int32_t> pa, pb, poff(Q + 1, 0);
-    if (!bt->min_score_in) {
-      pa.reserve(num_pairs); pb.reserve(num_pairs);
-      for (int q = 0; q < Q; ++q) {
-        const int k = bt->query_kf[q];
-        for (int i = bt->nb_ptr[k]; i < bt->nb_ptr[k + 1]; ++i) {
-          if (bt->invalid && bt->invalid[bt->nb[i]]) continue;
-          pa.push_back(k); pb.push_back(bt->nb[i]);
-        }
-        poff[q + 1] = (int32_t)pa.size();
-      }
-    }
-    int inv_words = 0;
-    for (int p = 0; p < M; ++p) {
-      const int k = bt->db_order[p];
-      if (bt->bow_ptr[k + 1] > bt->bow_ptr[k]) inv_words = std::max(inv_words, bt->word[bt->bow_ptr[k + 1] - 1] + 1);
-    }
-    std::vector<int32_t> inv_ptr((size_t)inv_words + 1, 0);
-    for (int p = 0; p < M; ++p) {
-      const int k = bt->db_order[p];
-      for (int i = bt->bow_ptr[k]; i < bt->bow_ptr[k + 1]; ++i) ++inv_ptr[bt->word[i] + 1];
-    }
-    for (int w = 0; w < inv_words; ++w) {
-      if ((int64_t)inv_ptr[w + 1] + inv_ptr[w] > (int64_t)INT32_MAX) return bad("more than 2^31 - 1 database words");
-      inv_ptr[w + 1] += inv_ptr[w];
-    }
-    std::vector<int32_t> inv_pos((size_t)inv_ptr[inv_words]), fill(inv_ptr.begin(), inv_ptr.end() - 1);
-    for (int p = 0; p < M; ++p) {
-      const int k = bt->db_order[p];
-      for (int i = bt->bow_ptr[k]; i < bt->bow_ptr[k + 1]; ++i) inv_pos[fill[bt->word[i]]++] = p;
-    }
     HIPCHK(hipSetDevice(c->device));
     DeviceScratch U(c->st);
     DetectDev D{};
-    D.M = M; D.inv_words = inv_words;
+    D.M = M; D.inv_words = P.inv_words;
     const size_t nnz = N > 0 ? (size_t)bt->bow_ptr[N] : 0, Ns = (size_t)N, Qs = (size_t)Q, caps = (size_t)cap;
     HIPCHK(U.upload(&D.id, bt->id, Ns)); HIPCHK(U.upload(&D.client, bt->client, Ns));
     HIPCHK(U.upload(&D.vec_beg, bt->bow_ptr, Ns + 1)); HIPCHK(U.upload(&D.word, bt->word, nnz));
     HIPCHK(U.upload(&D.value, bt->value, nnz)); HIPCHK(U.upload(&D.nb_beg, bt->nb_ptr, Ns + 1));
-    HIPCHK(U.upload(&D.nb, bt->nb, NB));
+    HIPCHK(U.upload(&D.nb, bt->nb, P.num_nb));
     D.vec_end = D.vec_beg + 1; D.nb_end = D.nb_beg + 1;                // a CSR pointer array as (begin, end)
     D.con_beg = D.nb_beg; D.con_end = D.nb_end; D.con = D.nb;          // a query's connected list is its row of the table
     HIPCHK(U.upload(&D.db_order, bt->db_order, (size_t)M));
-    HIPCHK(U.upload(&D.pos_of, pos_of.data(), Ns)); HIPCHK(U.upload(&D.inv_ptr, inv_ptr.data(), inv_ptr.size()));
-    HIPCHK(U.upload(&D.inv_pos, inv_pos.data(), inv_pos.size())); HIPCHK(U.upload(&D.query_kf, bt->query_kf, Qs));
+    HIPCHK(U.upload(&D.pos_of, P.pos_of.data(), Ns)); HIPCHK(U.upload(&D.inv_ptr, P.inv_ptr.data(), P.inv_ptr.size()));
+    HIPCHK(U.upload(&D.inv_pos, P.inv_pos.data(), P.inv_pos.size())); HIPCHK(U.upload(&D.query_kf, bt->query_kf, Qs));
     HIPCHK(U.upload(&D.db_visible, bt->db_visible, Qs));
     if (bt->min_score_in) HIPCHK(U.upload(&D.min_score, bt->min_score_in, Qs)); else HIPCHK(U.alloc(&D.min_score, Qs));
     int* counters = nullptr;                                           // max_common, num_sharing, num_scored, num_candidates
@@ -754,16 +440,16 @@ extern "C" int covgpu_detect_candidates_batch(covgpu_context* c, const covgpu_de
     if (!bt->min_score_in) {
       int *dpa = nullptr, *dpb = nullptr, *dpo = nullptr;
       double* dps = nullptr;
-      HIPCHK(U.upload(&dpa, pa.data(), pa.size())); HIPCHK(U.upload(&dpb, pb.data(), pb.size()));
-      HIPCHK(U.upload(&dpo, poff.data(), poff.size())); HIPCHK(U.alloc(&dps, pa.size()));
-      launch_bow_score_pairs(D.vec_beg, D.vec_end, D.word, D.value, (int)pa.size(), dpa, dpb, dps, c->st);
+      HIPCHK(U.upload(&dpa, P.pair_a.data(), P.pair_a.size())); HIPCHK(U.upload(&dpb, P.pair_b.data(), P.pair_b.size()));
+      HIPCHK(U.upload(&dpo, P.pair_off.data(), P.pair_off.size())); HIPCHK(U.alloc(&dps, P.pair_a.size()));
+      launch_bow_score_pairs(D.vec_beg, D.vec_end, D.word, D.value, (int)P.pair_a.size(), dpa, dpb, dps, c->st);
       launch_bow_min_score(D, Q, dpo, dps, opts->min_score_factor, c->st);
     }
     // per-query scratch is 28 B per database entry; queries run in chunks that keep it within the budget
     const size_t budget = (size_t)(opts->scratch_kib > 0 ? opts->scratch_kib : 65536) << 10;
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(Qs, budget / (28 * std::max<size_t>(1, (size_t)M))));
     const size_t cm = (size_t)chunk * (size_t)M;
-    const int hist_stride = max_words + 1;
+    const int hist_stride = P.max_words + 1;
     int *common = nullptr, *first = nullptr, *best = nullptr, *order = nullptr, *hist = nullptr;
     double* score = nullptr;
     float* acc = nullptr;
@@ -790,41 +476,8 @@ extern "C" void covgpu_default_prune_opts(covgpu_prune_opts* o) {
   o->max_kfs = -1; o->max_rounds = 0;
 }
 
-namespace {
-
-// The first violation of a prune call's arguments, or nullptr.
-const char* prune_check(const covgpu_prune_t* p, const covgpu_prune_opts* o) {
-  if (!p || !o) return "NULL problem or options";
-  if (!std::isfinite(o->th_red) || !std::isfinite(o->max_time_dist)) return "non-finite th_red or max_time_dist";
-  const int K = p->num_kf, L = p->num_lm;
-  if (K < 0 || L < 0 || p->capacity < 0) return "negative count";
-  if (!p->lm_obs_ptr) return "NULL lm_obs_ptr";
-  if (p->lm_obs_ptr[0] != 0) return "lm_obs_ptr[0] != 0";
-  for (int l = 0; l < L; ++l) if (p->lm_obs_ptr[l + 1] < p->lm_obs_ptr[l]) return "lm_obs_ptr not monotone";
-  const int O = p->lm_obs_ptr[L];
-  if (O > 0 && !p->obs_kf) return "NULL obs_kf";
-  for (int i = 0; i < O; ++i) if (p->obs_kf[i] < 0 || p->obs_kf[i] >= K) return "obs_kf out of range";
-  if (K > 0 && (!p->kf_pred || !p->kf_succ || !p->kf_time)) return "NULL keyframe array";
-  if (p->capacity > 0 && (!p->round_kf || !p->round_action)) return "NULL round array";
-  for (int k = 0; k < K; ++k) {
-    if (!std::isfinite(p->kf_time[k])) return "non-finite kf_time";
-    if (p->kf_pred[k] < -1 || p->kf_pred[k] >= K || p->kf_succ[k] < -1 || p->kf_succ[k] >= K) return "kf_pred or kf_succ out of range";
-  }
-  for (int k = 0; k < K; ++k) {
-    const int pr = p->kf_pred[k], su = p->kf_succ[k];
-    if ((pr >= 0 && p->kf_succ[pr] >= 0 && p->kf_succ[pr] != k) || (su >= 0 && p->kf_pred[su] >= 0 && p->kf_pred[su] != k))
-      return "kf_pred and kf_succ are not mutual";
-  }
-  return nullptr;
-}
-
-}  // namespace
-
 extern "C" int covgpu_prune_check(const covgpu_prune_t* p, const covgpu_prune_opts* o) {
-  return guarded([&]() -> int {
-    if (const char* m = prune_check(p, o)) { g_err = std::string("covgpu_prune_check: ") + m; return COVGPU_ERR_INVALID_ARG; }
-    return COVGPU_OK;
-  });
+  return check_export("covgpu_prune_check", [&] { return prune_check(p, o); });
 }
 
 extern "C" int covgpu_prune_redundant(covgpu_context* c, const covgpu_prune_t* p, const covgpu_prune_opts* o) {
@@ -844,10 +497,7 @@ extern "C" int covgpu_prune_redundant(covgpu_context* c, const covgpu_prune_t* p
     }
     int32_t res[3] = {0, 0, 0};
     HIPCHK(hipSetDevice(c->device));
-    struct Events {   // around the greedy loop, only when the caller asks for its time
-      hipEvent_t a = nullptr, b = nullptr;
-      ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
+    EventPair ev;   // around the greedy loop, only when the caller asks for its time
     DeviceScratch U(c->st);
     PruneDev D{};
     D.K = K; D.L = L;
@@ -902,40 +552,8 @@ extern "C" void covgpu_landmark_refresh_limits(int32_t out[4]) {
 static_assert(kLmrGroupMax == COVGPU_LMR_GROUP_MAX && kLmrLongThreads == COVGPU_LMR_LONG_THREADS && kLmrStage == COVGPU_LMR_STAGE &&
               kLmrForms == COVGPU_LMR_FORMS && COVGPU_LMR_WAVE == 64, "covgpu.h names the limits of k_lmrefresh.hip");
 
-namespace {
-
-// The first violation of a landmark-refresh call's arguments, or nullptr.
-const char* lm_refresh_check(const covgpu_landmark_refresh_t* p, const covgpu_landmark_refresh_opts* o) {
-  if (!p || !o) return "NULL problem or options";
-  if (!std::isfinite(o->scale_factor) || !(o->scale_factor > 0.0)) return "scale_factor not finite or not positive";
-  if (o->num_octaves < 1 || o->num_octaves > 64) return "num_octaves outside [1, 64]";
-  const int K = p->num_kf, L = p->num_lm;
-  if (K < 0 || L < 0) return "negative count";
-  if (!p->lm_obs_ptr) return "NULL lm_obs_ptr";
-  if (p->lm_obs_ptr[0] != 0) return "lm_obs_ptr[0] != 0";
-  for (int l = 0; l < L; ++l) if (p->lm_obs_ptr[l + 1] < p->lm_obs_ptr[l]) return "lm_obs_ptr not monotone";
-  const int O = p->lm_obs_ptr[L];
-  if (O > 0 && (!p->obs_kf || !p->obs_octave)) return "NULL obs_kf or obs_octave";
-  if (L > 0 && (!p->lm_ref_obs || !p->lm_pos)) return "NULL lm_ref_obs or lm_pos";
-  if (K > 0 && !p->kf_center) return "NULL kf_center";
-  for (int i = 0; i < O; ++i) if (p->obs_kf[i] < 0 || p->obs_kf[i] >= K) return "obs_kf out of range";
-  for (int l = 0; l < L; ++l) {
-    const int r = p->lm_ref_obs[l], m = p->lm_obs_ptr[l + 1] - p->lm_obs_ptr[l];
-    if (r < -1 || r >= m) return "lm_ref_obs outside its landmark's list";
-    if (r >= 0) { const int oc = p->obs_octave[p->lm_obs_ptr[l] + r]; if (oc < 0 || oc >= 64) return "octave of a reference observation outside [0, 64)"; }
-  }
-  for (size_t i = 0; i < 3 * (size_t)L; ++i) if (!std::isfinite(p->lm_pos[i])) return "non-finite lm_pos";
-  for (size_t i = 0; i < 3 * (size_t)K; ++i) if (!std::isfinite(p->kf_center[i])) return "non-finite kf_center";
-  return nullptr;
-}
-
-}  // namespace
-
 extern "C" int covgpu_landmark_refresh_check(const covgpu_landmark_refresh_t* p, const covgpu_landmark_refresh_opts* o) {
-  return guarded([&]() -> int {
-    if (const char* m = lm_refresh_check(p, o)) { g_err = std::string("covgpu_landmark_refresh_check: ") + m; return COVGPU_ERR_INVALID_ARG; }
-    return COVGPU_OK;
-  });
+  return check_export("covgpu_landmark_refresh_check", [&] { return lm_refresh_check(p, o); });
 }
 
 extern "C" int covgpu_landmark_refresh(covgpu_context* c, const covgpu_landmark_refresh_t* p, const covgpu_landmark_refresh_opts* o) {
@@ -960,10 +578,7 @@ extern "C" int covgpu_landmark_refresh(covgpu_context* c, const covgpu_landmark_
     double scale[64];
     for (int l = 0; l < 64; ++l) scale[l] = std::pow(o->scale_factor, l);   // the device never calls pow
     HIPCHK(hipSetDevice(c->device));
-    struct Events {   // around the kernels, only when the caller asks for their time
-      hipEvent_t a = nullptr, b = nullptr;
-      ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
+    EventPair ev;   // around the kernels, only when the caller asks for their time
     DeviceScratch U(c->st);
     LmRefreshDev D{};
     int* dlist = nullptr;

@@ -313,12 +313,11 @@ extern "C" int covgpu_bowdb_put_descriptors(covgpu_bowdb* db, const int32_t* slo
     if (bt->total) *bt->total = 0;
     if (S == 0) return COVGPU_OK;
     if (!id || !client || !bt->row_ptr) return bad("NULL id, client or row_ptr");
-    if (bt->row_ptr[0] != 0) return bad("row_ptr[0] != 0");
+    if (bt->row_ptr[0] != 0) return bad(kRowPtr.first);
     for (int s = 0; s < S; ++s) {
       if (id[s] < 0) return bad("negative keyframe id");
       if ((size_t)slot[s] < db->live.size() && db->live[slot[s]]) return bad("the slot is in the index: erase it before it gets another vector");
-      if (bt->row_ptr[s + 1] < bt->row_ptr[s]) return bad("row_ptr not monotone");
-      if (bt->row_ptr[s + 1] - bt->row_ptr[s] > COVGPU_MATCH_MAX_ROWS) return bad("a set holds more than COVGPU_MATCH_MAX_ROWS rows");
+      if (const char* m = csr_row_check(bt->row_ptr, s, kRowPtr, COVGPU_MATCH_MAX_ROWS)) return bad(m);
     }
     const size_t R = (size_t)bt->row_ptr[S], Ss = (size_t)S;
     if (R > 0 && !bt->desc) return bad("NULL desc");
@@ -379,8 +378,7 @@ extern "C" int covgpu_bowdb_set_neighbours(covgpu_bowdb* db, int32_t n, const in
     if (const char* m = slots_check(n, slot, &seen)) return bad(m);
     if (n == 0) return COVGPU_OK;
     if (!nb_ptr) return bad("NULL nb_ptr");
-    if (nb_ptr[0] != 0) return bad("nb_ptr[0] != 0");
-    for (int i = 0; i < n; ++i) if (nb_ptr[i + 1] < nb_ptr[i]) return bad("nb_ptr not monotone");
+    if (const char* m = csr_check(nb_ptr, n, kNbPtr)) return bad(m);
     if (nb_ptr[n] > 0 && !nb) return bad("NULL nb");
     const size_t ns = (size_t)n;
     std::vector<int32_t> rows(ns * kBowDbNeighbours, 0), cnt(ns);

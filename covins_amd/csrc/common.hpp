@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/covgpu.h"
+#include "batch_limits.hpp"
 
 namespace covgpu {
 
@@ -610,24 +611,18 @@ void launch_abspose(int num, const int* ptr, const double* f, const double* P, c
                     double threshold, int max_n, hipStream_t st);
 void launch_p3p(int num, const double* F, const double* P, double* T, int* nsol, int* chosen, hipStream_t st);
 // k_match.hip: batched ORB descriptor matching of loop candidates (DENSE: scan + assignbest replay; KNN2: scan only)
-constexpr int kMatchScanRows = 256;   // query rows per scan workgroup (grid = num_jobs * ceil(max query rows / 256))
 size_t match_assign_lds_bytes(int maxA, int maxB);
 void launch_match(int mode, int num_jobs, int maxA, int maxB, const unsigned char* desc, const unsigned char* skip, const int* row_ptr,
                   const int* set_a, const int* set_b, const int* out_off, int* lists, int* match, int* dist, int* nmatches, int dcut,
                   float thr, float ratio, hipStream_t st);
 // k_matchf.hip: batched L2 matching of float (SIFT) descriptors of loop candidates (row norms; MFMA scan with the top-2 and the tests fused)
-constexpr int kMatchFloatTileRows = 128;    // query rows per scan workgroup (grid = num_jobs * ceil(max query rows / 128))
-constexpr int kMatchFloatChunkRows = 64;    // train rows staged in LDS per chunk
-constexpr int kMatchFloatMaxDim = 256;      // dim: a positive multiple of 4 up to this
-constexpr float kMatchFloatMaxAbs = 1e18f;  // |value| bound of a descriptor entry: |x|^2 of 256 such entries stays finite in float32
 size_t matchf_lds_bytes(int kp);
 void launch_matchf_norms(int rows, int dim, const float* desc, float* norm, hipStream_t st);
 void launch_matchf(int num_jobs, int maxA, int dim, const float* desc, const float* norm, const int* row_ptr, const int* set_a,
                    const int* set_b, const int* out_off, int* match, float* dist, int* nmatches, float thr, float ratio, hipStream_t st);
 // k_guided.hip: batched guided matching of loop candidates (SearchBySE3: two-direction scan + agreement; SearchByProjection: scan with
-// per-point lists + the sequential claim replay). Device arrays; a tile is {job, direction, first point, points} of at most 256 points.
-constexpr int kGuidedScanPoints = 256;
-constexpr int kGuidedListCap = 8;      // PROJECTION: entries a point keeps for the replay (more: the replay rescans)
+// per-point lists + the sequential claim replay). Device arrays; a tile is {job, direction, first point, points} of at most 256 points
+// (kGuidedScanPoints; the sizes of the three matching files are in batch_limits.hpp).
 struct GuidedSets {
   const int4* kpr;                     // [rows] {bits of float x, bits of float y, level (INT_MIN: taken), visiting rank within the set}
   const uint4* kdesc;                  // [rows][2]

@@ -1,6 +1,7 @@
 // host.hpp — what the host files of libcovgpu (the solver's solver.hip, upload.hip, plan_api.hip, shard.hip, multi.hip and probe_api.hip; batch.hip,
-// bowdb.hip, voctrain.hip) share: the context, the error plumbing of the extern "C" entry points, the per-call device scratch and the declarations
-// of the solver's functions that one of its files calls in another. Host-only: no kernel file includes it.
+// bowdb.hip, voctrain.hip) share: the context, the error plumbing of the extern "C" entry points (guarded, batch_entry, check_export), the
+// per-call device scratch and event pair, and the declarations of the solver's functions that one of its files calls in another. The
+// argument checks themselves are plain C++ in batch_check.hpp, which this header includes. Host-only: no kernel file includes it.
 #pragma once
 #include <atomic>
 #include <memory>
@@ -8,6 +9,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "batch_check.hpp"
 #include "common.hpp"
 #include "nd_plan.hpp"
 
@@ -94,10 +96,6 @@ struct covgpu_context {
   std::vector<covgpu_bowdb*> bowdbs;       // resident keyframe databases of this context (bowdb.hip): destroyed with it
 };
 
-// argument checks of the bag-of-words entry points (batch.hip), shared with the resident database (bowdb.hip): the first violation, or nullptr
-__attribute__((visibility("hidden"))) const char* bow_csr_check(int rows, const int32_t* ptr, const int32_t* word, const double* value);
-__attribute__((visibility("hidden"))) const char* bow_vocab_check(const covgpu_bow_vocab_t* v);
-
 #define RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 // no C++ exception may cross the extern "C" boundary (std::bad_alloc from the host staging vectors, std::system_error from
 // std::thread): map them to status codes
@@ -107,6 +105,33 @@ static int guarded(F&& body) {
   catch (const std::bad_alloc&) { g_err = "host allocation failed"; return COVGPU_ERR_OUT_OF_MEMORY; }
   catch (const std::exception& e) { g_err = std::string("host exception: ") + e.what(); return COVGPU_ERR_INVALID_ARG; }
 }
+
+// The prologue of every stateless device entry point (batch.hip, voctrain.hip): a NULL context is an argument error, and no C++
+// exception leaves the call. `bad` is the body's argument-error return: "<function>: <message>".
+template <typename F>
+static int batch_entry(const char* fn, covgpu_context* c, F&& body) {
+  auto bad = [fn](const std::string& m) -> int { g_err = std::string(fn) + ": " + m; return COVGPU_ERR_INVALID_ARG; };
+  if (!c) return bad("NULL context");
+  return guarded([&] { return body(bad); });
+}
+
+// A covgpu_*_check export: the entry point's own check without a context or a device. `check` returns the first violation or nullptr.
+template <typename F>
+static int check_export(const char* fn, F&& check) {
+  return guarded([&]() -> int {
+    if (const char* m = check()) { g_err = std::string(fn) + ": " + m; return COVGPU_ERR_INVALID_ARG; }
+    return COVGPU_OK;
+  });
+}
+
+// Two events around the kernels of a call whose caller asks for their device time; destroyed however the call returns.
+struct EventPair {
+  hipEvent_t a = nullptr, b = nullptr;
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+  ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
 
 // Every device buffer of one call: freed when the call returns, however it returns. Counts are in elements of T; an empty buffer is
 // still a valid pointer (16 B, which no kernel reads). Declare the host vectors that receive a fetch() BEFORE the scratch object:

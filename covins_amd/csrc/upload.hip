@@ -40,12 +40,7 @@ int validate(const covgpu_problem* p, bool pgo, bool vi) {
     if (p->num_cam <= 0 || !p->cam_extr || !p->cam_intr || !p->cam_dist || !p->cam_dist_type) return bad("NULL camera array");
     for (int k = 0; k < K; ++k) if (p->kf_cam[k] < 0 || p->kf_cam[k] >= p->num_cam) return bad("kf_cam out of range");
     for (int a = 0; a < p->num_cam; ++a) if (p->cam_dist_type[a] != COVGPU_DIST_RADTAN && p->cam_dist_type[a] != COVGPU_DIST_EQUIDISTANT) return bad("unknown distortion type");
-    if (p->cam_model) for (int a = 0; a < p->num_cam; ++a) {
-      if (p->cam_model[a] != COVGPU_CAM_PINHOLE && p->cam_model[a] != COVGPU_CAM_UNIFIED) return bad("unknown camera model");
-      if (p->cam_model[a] != COVGPU_CAM_UNIFIED) continue;
-      if (!p->cam_xi) return bad("unified camera without cam_xi");
-      if (!std::isfinite(p->cam_xi[a]) || p->cam_xi[a] < 0.0) return bad("xi of a unified camera is negative or not finite");
-    }
+    for (int a = 0; a < p->num_cam; ++a) if (const char* m = cam_check(p->cam_model, p->cam_xi, (size_t)a, kNoCamXi)) return bad(m);
     if (vi && p->num_imu > 0 && (!p->imu_kf_i || !p->imu_kf_j || !p->imu_sample_ptr || !p->imu_first)) return bad("NULL IMU array");
     if (vi && p->num_imu > 0 && p->imu_sample_ptr[p->num_imu] > 0 && !p->imu_samples) return bad("NULL IMU sample array");
     if (vi && p->num_imu > 0 && (p->imu_sample_ptr[0] != 0 || p->imu_sample_ptr[p->num_imu] != p->num_imu_samples)) return bad("imu_sample_ptr does not span the IMU samples");

@@ -2,7 +2,8 @@
 // grows level by level: the host keeps the nodes, builds each level's segment and tile tables, drives the seeding rounds and the
 // k-means iterations of k_voctrain.hip (one word read back per iteration: did any association change), reads the level's centres and
 // group sizes, and renumbers the nodes depth first at the end. The weights come from k_bow.hip's tree descent over the training rows
-// and a per-set unique word count. A stateless batch call: the context lends its device and its stream only.
+// and a per-set unique word count. A stateless batch call: the context lends its device and its stream only; its argument check
+// (voc_train_check) is in batch_check.hpp.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -38,39 +39,6 @@ uint64_t mix64(uint64_t x) {                      // splitmix64
   return z ^ (z >> 31);
 }
 
-// k^L, or 0 if it exceeds COVGPU_BOW_MAX_WORDS
-int64_t full_words(int k, int L) {
-  int64_t w = 1;
-  for (int l = 0; l < L; ++l) { w *= k; if (w > COVGPU_BOW_MAX_WORDS) return 0; }
-  return w;
-}
-
-// The first violation of a training call's arguments, or nullptr.
-const char* voc_train_check(const covgpu_voc_train_t* p, const covgpu_voc_train_opts* o) {
-  if (!p || !o) return "NULL problem or options";
-  if (o->k < 2) return "k < 2";
-  if (o->k > COVGPU_VOCTRAIN_MAX_K) return "k > COVGPU_VOCTRAIN_MAX_K";
-  if (o->L < 1) return "L < 1";
-  const int64_t full = full_words(o->k, o->L);
-  if (!full) return "k^L > COVGPU_BOW_MAX_WORDS";
-  if (o->weighting < COVGPU_BOW_TF_IDF || o->weighting > COVGPU_BOW_BINARY) return "unknown weighting";
-  if (o->scoring != COVGPU_BOW_L1_NORM) return "only L1_NORM scoring is supported";
-  if (o->max_iterations < 1) return "max_iterations < 1";
-  if ((int64_t)o->scratch_kib * 8192 < full) return "scratch_kib below one set's word bitmap, ceil(k^L / 8192)";
-  const int S = p->num_sets;
-  if (S < 0 || p->node_capacity < 0) return "num_sets or node_capacity < 0";
-  if (S == 0) return "no descriptor rows";
-  if (!p->row_ptr) return "NULL row_ptr";
-  if (p->row_ptr[0] != 0) return "row_ptr[0] != 0";
-  for (int s = 0; s < S; ++s) if (p->row_ptr[s + 1] < p->row_ptr[s]) return "row_ptr not monotone";
-  if (p->row_ptr[S] == 0) return "no descriptor rows";
-  if (p->row_ptr[S] > INT32_MAX - COVGPU_VOCTRAIN_TILE) return "more than 2^31 - 1 - COVGPU_VOCTRAIN_TILE rows";   // a tile's position loop steps past its end
-  if (!p->desc) return "NULL desc";
-  if (!p->num_nodes || !p->num_words) return "NULL num_nodes or num_words";
-  if (p->node_capacity > 0 && (!p->parent || !p->desc_out || !p->word_id || !p->weight)) return "NULL output array";
-  return nullptr;
-}
-
 struct HostNode {
   int parent, level, beg, n;                      // rows: positions [beg, beg + n) of the level that made the node
   int child0 = -1, nchild = 0;                    // children are consecutive in creation (breadth-first) order
@@ -81,16 +49,11 @@ struct HostNode {
 }  // namespace
 
 extern "C" int covgpu_voc_train_check(const covgpu_voc_train_t* p, const covgpu_voc_train_opts* o) {
-  return guarded([&]() -> int {
-    if (const char* m = voc_train_check(p, o)) { g_err = std::string("covgpu_voc_train_check: ") + m; return COVGPU_ERR_INVALID_ARG; }
-    return COVGPU_OK;
-  });
+  return check_export("covgpu_voc_train_check", [&] { return voc_train_check(p, o); });
 }
 
 extern "C" int covgpu_voc_train(covgpu_context* c, const covgpu_voc_train_t* p, const covgpu_voc_train_opts* o) {
-  auto bad = [](const std::string& m) -> int { g_err = "covgpu_voc_train: " + m; return COVGPU_ERR_INVALID_ARG; };
-  if (!c) return bad("NULL context");
-  return guarded([&]() -> int {
+  return batch_entry("covgpu_voc_train", c, [&](auto bad) -> int {
     if (const char* m = voc_train_check(p, o)) return bad(m);
     const int S = p->num_sets, k = o->k, L = o->L;
     const size_t R = (size_t)p->row_ptr[S], ks = (size_t)k;

@@ -99,7 +99,7 @@ def test_header_capi_and_limits_agree():
     max_rows, max_dim, tile, chunk = list(lim)
     assert max_rows == capi.MATCH_MAX_ROWS == 4096 and max_dim >= 256 and max_dim % 4 == 0
     assert tile > 0 and tile % 32 == 0 and chunk > 0 and chunk % 32 == 0
-    src = open(os.path.join(ROOT, "covins_amd", "csrc", "common.hpp")).read()
+    src = open(os.path.join(ROOT, "covins_amd", "csrc", "batch_limits.hpp")).read()
     assert int(re.search(r"kMatchFloatTileRows = (\d+);", src).group(1)) == tile
     assert int(re.search(r"kMatchFloatChunkRows = (\d+);", src).group(1)) == chunk
     assert int(re.search(r"kMatchFloatMaxDim = (\d+);", src).group(1)) == max_dim
