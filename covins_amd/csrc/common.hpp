@@ -265,6 +265,7 @@ enum KernelForm {
   KF_ND_EXTEND_REC, KF_ND_EXTEND, KF_ND_EXTEND_SPLIT,
   KF_ND_TOP_PACK, KF_ND_GH, KF_ND_TOP_DAMP, KF_ND_PANEL_XFER, KF_DIST_PANEL,
   KF_PGO_ARROW, KF_PGO_DENSE,
+  KF_POTRF_LEAF,
   KF_COUNT
 };
 extern const char* const kFormNames[KF_COUNT];
@@ -291,6 +292,7 @@ struct CholAux {
   hipEvent_t ev_xa = nullptr;    // ... the chain's stream has enqueued the level below completely
   hipEvent_t ev_zero = nullptr;  // per-iteration buffers cleared (main stream): the side stream's inertial kernels follow
   hipEvent_t ev_lin = nullptr, ev_kf = nullptr;  // landmark linearisation done (main stream) | per-keyframe reduction done (side stream): launch_lm_build
+  hipEvent_t ev_sb = nullptr, ev_leaf = nullptr; // speed-bias part of the system final (side stream) | the leaf fronts factored beside the landmark pass (head stream): enqueue_build
   std::vector<hipEvent_t> ev, prof_ev, panel_ev;  // panel_ev: start of every big panel on the main stream (COVGPU_TRACE_PANELS=1)
   std::vector<double> prof_flops;
   // (profiling only) the same for every k_potrf_panel launch — the serial chain, the kernel with the largest share of GPU time
@@ -437,6 +439,9 @@ void dense_backward_solve(double* S, double* b, double* Linv, int npad, hipStrea
 void launch_potrf_panel(double* S, size_t ld, int t0, int w, double* Linv, int* flag, double* b, int npad, int nbt, size_t sM, size_t sL, size_t sR,
                         hipStream_t st, const long long* btab = nullptr, int nb = -1, const int* own = nullptr, const int* list = nullptr, int n_big = 0,
                         int n_small = 0);   // nb: 16-column blocks to factor (-1: the whole panel); own / list / n_big / n_small: k_panel.hip (round 6)
+// a level of leaf fronts whole in one launch (k_panel.hip: k_potrf_leaf; NdLevel::leaf_one): own / stdim = the fronts' own / border orders (device)
+void launch_potrf_leaf(double* S, double* Linv, int* flag, double* b, int npad, int nbt, size_t sL, size_t sR, hipStream_t st, const long long* btab,
+                       const int* own, const int* stdim, int nI);
 void launch_bwd_given(const double* S, size_t ld, int r0, int r1, double* y, double* x, int ncol, int nbt, size_t sM, size_t sR, hipStream_t st,
                       const long long* btab, const int* live, int tI, BwdXfer xf = BwdXfer());
 void launch_bwd_front(const double* S, int tI, int ntiles, int nchunk, double* y, const double* Linv, int nbt, size_t sL, size_t sR, hipStream_t st,
@@ -512,6 +517,7 @@ struct NdLevel {
   int* live = nullptr;                    // [n][2] device: real interior tiles | real border tiles (GemmArgs::live)
   std::vector<int> live_h;
   int own_max = 0;                        // largest real interior order of the batch (DenseBatch::own_max)
+  bool leaf_one = false;                  // level 0 of an unsharded tree whose fronts the one-launch leaf form takes (leaf_front.hpp: leaf_level_eligible)
   // k_potrf_panel's front lists (round 6): the level's fronts (index in the batch) by DEcreasing interior order; per 256-column panel P the first
   // pbig[P] of them have more than 128 real columns in that panel (sixteen-wave form), the next psmall[P] have 1 .. 128 (four-wave form), the rest none
   int* plist = nullptr; std::vector<int> plist_h, pbig, psmall;
@@ -531,6 +537,7 @@ struct NdLevel {
 struct NdDev {
   bool active = false;
   int nnodes = 0;                          // local fronts
+  bool leaves_done = false;                // the bottom level of THIS system was assembled and factored by launch_nd_leaves (consumed by launch_nd_solve)
   int top_lev0 = 0;                        // first top level (== lev.size(): none — single GPU)
   std::vector<NdLevel> lev;
   // device tables of the assembly kernels (owned by the context's allocation list)
@@ -578,6 +585,8 @@ struct NdDev {
 void nd_tables(const NdHostPlan& hp, const int* pos_kf, int D, int rank, NdDev& dev);  // nd_tables.hip: host tables + level shapes from the plan, NdDev complete but for the device addresses
 void launch_nd_init(const DevProblem& P, const NdDev& nd, hipStream_t st);    // once per upload: identity block inverses for the padding columns
 void launch_nd_zero(const DevProblem& P, const NdDev& nd, hipStream_t st);    // per iteration: clear the live tiles, identity on interior padding
+bool nd_leaves_beside_pass(const NdDev& nd);   // this tree's bottom level is factored early, beside the landmark pass (launch_nd_leaves)
+bool launch_nd_leaves(const DevProblem& P, NdDev& nd, hipStream_t s, CholAux& ax);   // the bottom level of leaf fronts, early on stream s (k_front.hip); false: nothing enqueued
 bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hipStream_t st, CholAux& ax);  // false: scratch allocation failed, nothing enqueued. damped system in the fronts + bred -> dst (IR layout)
 
 // fused trust-region tail (k_tail.hip): T1 stats, T2 J*v of (c, n) over all residual families, T3 / T6 finish (+ step logic in the

@@ -370,6 +370,8 @@ void CholAux::init() {
   if (!ev_fill) (void)hipEventCreateWithFlags(&ev_fill, hipEventDisableTiming);
   if (!ev_xb) (void)hipEventCreateWithFlags(&ev_xb, hipEventDisableTiming);
   if (!ev_xa) (void)hipEventCreateWithFlags(&ev_xa, hipEventDisableTiming);
+  if (!ev_sb) (void)hipEventCreateWithFlags(&ev_sb, hipEventDisableTiming);
+  if (!ev_leaf) (void)hipEventCreateWithFlags(&ev_leaf, hipEventDisableTiming);
   if (!bwd_cnt && hipMalloc((void**)&bwd_cnt, 65536 * sizeof(int)) == hipSuccess) (void)hipMemset(bwd_cnt, 0, 65536 * sizeof(int));
   // (the "gave up" word and its host mirror serve the gates and the pipelined backward substitution alike)
   if (!gate_dead && hipMalloc((void**)&gate_dead, sizeof(int)) == hipSuccess) (void)hipMemset(gate_dead, 0, sizeof(int));
@@ -539,6 +541,8 @@ void CholAux::destroy() {
   if (ev_fill) { (void)hipEventDestroy(ev_fill); ev_fill = nullptr; }
   if (ev_xb) { (void)hipEventDestroy(ev_xb); ev_xb = nullptr; }
   if (ev_xa) { (void)hipEventDestroy(ev_xa); ev_xa = nullptr; }
+  if (ev_sb) { (void)hipEventDestroy(ev_sb); ev_sb = nullptr; }
+  if (ev_leaf) { (void)hipEventDestroy(ev_leaf); ev_leaf = nullptr; }
   if (bwd_cnt) { (void)hipFree(bwd_cnt); bwd_cnt = nullptr; }
   if (gate_flags) { (void)hipFree(gate_flags); gate_flags = nullptr; }
   if (gate_dead) { (void)hipFree(gate_dead); gate_dead = nullptr; }
@@ -606,6 +610,7 @@ const char* const kFormNames[KF_COUNT] = {
   "k_nd_extend_rec", "k_nd_extend", "nd_extend_split",
   "k_nd_top_pack", "k_nd_gh", "k_nd_top_damp", "k_nd_panel_xfer", "dist_panel",
   "pgo_arrow", "pgo_dense",
+  "k_potrf_leaf",
 };
 static_assert(sizeof(kFormNames) / sizeof(kFormNames[0]) == KF_COUNT, "one name per kernel form");
 

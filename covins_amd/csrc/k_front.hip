@@ -71,12 +71,16 @@ __global__ __launch_bounds__(256) void k_nd_zero(DevProblem P, NdZeroArgs z) {
 
 // speed-bias part of the system (block-tridiagonal rows Ad / Ae and their couplings Bp / Bs / Bn to the poses, filled by the
 // inertial kernels and damped by k_finalize_diag) and the right-hand side -> fronts. One thread per entry.
+// part: 0 everything | 1 what is final as soon as the speed-bias part of the system is — every matrix entry (Ad .. Bn are the inertial kernels' alone)
+// and the right-hand side of the bottom level's fronts (nodes < nleaf in level order: speed-bias rows only) —, written early, beside the landmark pass,
+// where that level is factored there (launch_nd_leaves) | 2 the rest: the "empty" words and the other fronts' right-hand sides. Every entry belongs to
+// one part.
 __global__ __launch_bounds__(256) void k_nd_assemble(DevProblem P, const int* __restrict__ rhs_off, double* __restrict__ x, const int* __restrict__ fill, int nfill,
-                                                      unsigned long long empty) {
+                                                      unsigned long long empty, int part, int nleaf) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   // (the solution vector's entries of the levels whose backward substitution is ONE launch start a solve "empty": k_panel.hip, k_bwd_tree)
   if (t < nfill) reinterpret_cast<unsigned long long*>(x)[fill[t]] = empty;
-  if (P.vi) {
+  if (P.vi && part != 2) {
     const int pos = t / 324, e = t - 324 * pos;
     if (pos < P.K) {
       const int vs = 2 * pos + 1;
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(256) void k_nd_assemble(DevProblem P, const int* __
     const int kf = t / P.D, r = t - kf * P.D, pos = P.perm[kf];
     const int v = r < 6 ? 2 * pos : 2 * pos + 1, rr = r < 6 ? r : r - 6;
     const int node = P.nd_vnode[v];
-    if (node >= 0) P.nd_rhs[rhs_off[node] + P.nd_voff[v] + rr] = P.bred[t];  // (node < 0: an unknown of another rank's subtree)
+    if (node >= 0 && (part == 0 || (node < nleaf) == (part == 1))) P.nd_rhs[rhs_off[node] + P.nd_voff[v] + rr] = P.bred[t];  // (node < 0: an unknown of another rank's subtree)
   }
 }
 
@@ -326,6 +330,11 @@ static const bool kExtRecords = env_int("COVGPU_EXT_RECORDS", 1) != 0;   // exte
 // COVGPU_BETA0 (on unless 0): the first rank update of a border x border tile no child adds into starts it from zero (GemmArgs::beta0), and the
 // extend-add stores the tiles a child does add into whole — k_nd_zero clears neither. Off: k_nd_zero clears every border tile (round 5's form).
 static const bool kBeta0 = env_int("COVGPU_BETA0", 1) != 0;
+// COVGPU_LEAF_ONE (on unless 0): a bottom level of speed-bias leaf fronts is factored whole in one launch (k_potrf_leaf). Off: the panel route
+// (k_potrf_panel, k_trsm_sub4 and the trailing update through their gates) — kept for the A/B of the two and for the test that compares them.
+// 2: the one-launch form, left on the chain at the level's old place instead of beside the landmark pass (the other half of the A/B).
+static int env_leaf_one() { static const int v = env_int("COVGPU_LEAF_ONE", 1); return v; }
+static const bool kLeafOne = env_leaf_one() != 0;
 
 static NdLevArgs lev_args(const DevProblem& P, const NdDev& nd, int l) {
   const NdLevel& L = nd.lev[l];
@@ -405,12 +414,19 @@ struct FrontRun {
   }
   // leaves the speed-bias part of the system and the right-hand side in the fronts, and the one-launch levels' entries of dst "empty"
   // (the right-hand sides were cleared on the head stream of the build, beside the fronts: solver.hip enqueue_build)
-  void assemble() {
+  // leaves_early: the speed-bias system and the bottom level's right-hand sides are in place already (launch_nd_leaves) — the rest
+  void assemble(bool leaves_early) {
     ax.mark(st, -1);
     const int nfill = (tree_on || tree_top_on) ? (int)nd.h_tree_fill.size() : 0;
-    const int cnt = std::max(std::max(P.vi ? 324 * P.K : 0, P.n), nfill);
-    hipLaunchKernelGGL(k_nd_assemble, dim3((cnt + 255) / 256), dim3(256), 0, st, P, (const int*)nd.rhs_node, dst, (const int*)nd.tree_fill, nfill, pipe_empty_word());
+    const int cnt = std::max(std::max(P.vi && !leaves_early ? 324 * P.K : 0, P.n), nfill);
+    hipLaunchKernelGGL(k_nd_assemble, dim3((cnt + 255) / 256), dim3(256), 0, st, P, (const int*)nd.rhs_node, dst, (const int*)nd.tree_fill, nfill, pipe_empty_word(),
+                       leaves_early ? 2 : 0, leaves_early ? nd.lev[0].n : 0);
     ax.mark(st, -2);
+  }
+  // the early share of the assembly on stream s: the speed-bias system (all of it) and the right-hand sides of the bottom level's fronts
+  void assemble_leaves(hipStream_t s) {
+    const int cnt = std::max(P.vi ? 324 * P.K : 0, P.n);
+    hipLaunchKernelGGL(k_nd_assemble, dim3((cnt + 255) / 256), dim3(256), 0, s, P, (const int*)nd.rhs_node, (double*)nullptr, (const int*)nullptr, 0, 0ull, 1, nd.lev[0].n);
   }
   // level l's fronts as a batch of the dense factorisation
   DenseBatch batch(int l) const {
@@ -449,12 +465,21 @@ struct FrontRun {
                          (const int*)(top_children ? nd.extc2 : nd.extc), top_children ? 1 : 0, store_border, sig);
     return count > 0;
   }
+  // level l is the bottom level of speed-bias leaf fronts that the one-launch form takes (NdLevel::leaf_one; COVGPU_LEAF_ONE=0: the panel route)
+  bool leaf_one(int l) const { return kLeafOne && l == 0 && nd.lev[0].leaf_one && nd.lev[0].n > 0; }
+  // the bottom level whole on stream s: one launch, no gate inside (k_panel.hip: k_potrf_leaf)
+  void leaf_launch(hipStream_t s) {
+    const NdLevel& L = nd.lev[0];
+    launch_potrf_leaf(P.nd_M, P.nd_Linv + L.linv_off, P.flag, P.nd_rhs + L.rhs_off, L.ntot, L.n, (size_t)L.nI * kTile, (size_t)2 * L.ntot, s,
+                      P.nd_ntab + 2 * (size_t)L.first, nd.own_dims + L.first, nd.st_dims + L.first, L.nI);
+  }
   // partial factorisation of level l's fronts. split: the trailing update of this level's last panel is split for the look-ahead into the next
   // level (DenseBatch::split_ta)
   void factor(int l, bool split, hipEvent_t pre_trsm) {
     const NdLevel& L = nd.lev[l];
     ax.mark(st, -3);
-    if (L.n > 0) {
+    if (leaf_one(l)) leaf_launch(st);
+    else if (L.n > 0) {
       DenseBatch bt = batch(l);
       bt.split_ta = split ? L.split_ta : 0; bt.pre_trsm = pre_trsm;
       dense_cholesky_solve_raw(P.nd_M, P.nd_rhs + L.rhs_off, P.nd_Linv + L.linv_off, P.flag, L.ntot, st, ax, L.nI / kTile, false, bt);
@@ -464,9 +489,12 @@ struct FrontRun {
   // Levels [l0, l1) one after the other, with a look-ahead across the level boundary: of level l's last trailing update only the
   // tiles its parents' first panel receives run on the chain's stream, followed by that part of the extend-add and the parents'
   // first panel; the rest of the update and of the extend-add run beside it on the bulk stream (ax.aux).
-  void run_levels(int l0, int l1, bool top_children) {
+  // leaves_early: level l0 = 0 was factored beside the landmark pass (launch_nd_leaves; the chain's stream has waited for it: enqueue_build) — the
+  // chain starts at level 1, whose extend-add keeps its two halves as behind a split update
+  void run_levels(int l0, int l1, bool top_children, bool leaves_early = false) {
     bool prev_split = false;
     for (int l = l0; l < l1; ++l) {
+      if (leaves_early && l == 0) { prev_split = kLookahead && l + 1 < l1 && nd.lev[1].n > 0 && nd.lev[0].split_ta > 0; continue; }
       hipEvent_t pre = nullptr;
       if (prev_split) {
         // (the bulk stream already follows the level below through its own update; this also covers a batch that declined the split. Round 6: the
@@ -583,12 +611,27 @@ struct FrontRun {
   }
 };
 
+// The bottom level of speed-bias leaf fronts, assembled and factored on stream s as soon as the speed-bias part of the system is final and the fronts
+// are cleared — beside the landmark pass (solver.hip: enqueue_build), one launch each and no gate inside. false: this tree has no such level (or
+// COVGPU_LEAF_ONE is 0, or 2: the one-launch form at the level's old place on the chain) and nothing was enqueued; the solve then runs level 0 itself.
+bool nd_leaves_beside_pass(const NdDev& nd) { return kLeafOne && env_leaf_one() != 2 && !nd.lev.empty() && nd.lev[0].leaf_one && nd.lev[0].n > 0 && nd.top_lev0 == (int)nd.lev.size(); }
+bool launch_nd_leaves(const DevProblem& P, NdDev& nd, hipStream_t s, CholAux& ax) {
+  if (!nd_leaves_beside_pass(nd)) return false;
+  FrontRun r(P, nd, nullptr, 0.0, s, ax);
+  r.assemble_leaves(s);
+  r.leaf_launch(s);
+  nd.leaves_done = true;
+  return true;
+}
+
 bool launch_nd_solve(const DevProblem& P, NdDev& nd, double* dst, double mu, hipStream_t st, CholAux& ax) {
   FrontRun r(P, nd, dst, mu, st, ax);
   ax.init();
   if (!r.ensure_scratch()) return false;
-  r.assemble();
-  r.run_levels(0, r.ltop, false);   // the subtrees of this rank (single GPU: the whole tree), level by level
+  const bool leaves_early = nd.leaves_done;   // (of THIS system: enqueue_build's launch_nd_leaves)
+  nd.leaves_done = false;
+  r.assemble(leaves_early);
+  r.run_levels(0, r.ltop, false, leaves_early);   // the subtrees of this rank (single GPU: the whole tree), level by level
   if (r.ltop < r.nlev) {            // sharded solve: the top fronts take their subtree children, then the exchange of the shard policy
     for (int l = r.ltop; l < r.nlev; ++l) r.extend(l, false, 0, st);
     r.top_gh_damp(nd.dist ? nd.dist_lead : true);

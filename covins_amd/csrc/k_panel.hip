@@ -30,6 +30,7 @@
 
 #include "common.hpp"
 #include "dev_math.hpp"
+#include "leaf_front.hpp"
 
 namespace covgpu {
 
@@ -163,11 +164,14 @@ __constant__ PanelTileTab8 kPanelTile8 = make_panel_tiles8();
 
 // Panel j (LDS, complete: block column j of the factor from row o = 16 j on, raw diagonal block + its column factors `rs`) leaves for
 // memory, and the right-hand side below it takes y_j (in sRhs[o ..)): thread u of NT, half rows of 64 bytes.
-template <int NT>
-COV_DEV void panel_out(const double* pan, double* sRhs, const double* rs, double* Mg, size_t ld, int o, int n, int u, double* yo) {
+// LEAF (the one-launch leaf form, potrf_panel_body): logical rows from `nown` on are the front's border rows, `bshift` rows further down in
+// memory; bo != nullptr (the last step): their right-hand side, now complete, leaves for bo[physical row].
+template <int NT, bool LEAF = false>
+COV_DEV void panel_out(const double* pan, double* sRhs, const double* rs, double* Mg, size_t ld, int o, int n, int u, double* yo, int nown = 0, int bshift = 0,
+                       double* bo = nullptr) {
   for (int row = o + PB + (u >> 1); row < n; row += NT / 2) {
     const double2* src = reinterpret_cast<const double2*>(pan + row * PP + 8 * (u & 1));
-    double2* dst = reinterpret_cast<double2*>(Mg + (size_t)row * ld + o + 8 * (u & 1));
+    double2* dst = reinterpret_cast<double2*>(Mg + (size_t)(LEAF ? leaf_phys_row(row, nown, bshift) : row) * ld + o + 8 * (u & 1));
     const double2 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3];
     dst[0] = v0; dst[1] = v1; dst[2] = v2; dst[3] = v3;
   }
@@ -182,7 +186,9 @@ COV_DEV void panel_out(const double* pan, double* sRhs, const double* rs, double
       t0 += sRhs[o + c] * pan[row * PP + c]; t1 += sRhs[o + c + 1] * pan[row * PP + c + 1];
       t2 += sRhs[o + c + 2] * pan[row * PP + c + 2]; t3 += sRhs[o + c + 3] * pan[row * PP + c + 3];
     }
-    sRhs[row] -= (t0 + t1) + (t2 + t3);
+    const double bv = sRhs[row] - ((t0 + t1) + (t2 + t3));
+    sRhs[row] = bv;
+    if (LEAF && bo != nullptr && row >= nown) bo[row + bshift] = bv;
   }
   if (yo != nullptr && u < PB) yo[o + u] = sRhs[o + u];
 }
@@ -215,10 +221,20 @@ COV_DEV void panel_out(const double* pan, double* sRhs, const double* rs, double
 // THREE tile waves (27 trailing tiles of an 8-block panel, 128 panel rows, 42 KB of LDS) for fronts of at most 128 real columns in the panel — the
 // speed-bias segments and the small pose fronts, thousands per level: three workgroups per CU instead of one. The arithmetic of a front is the
 // same in both forms (same tile updates in the same order).
-template <int NWV>
+// The one-launch LEAF form (LEAF, sixteen waves; leaf_front.hpp says which fronts take it): the working set is a WHOLE front of at most 256 rows, its
+// own blocks 0 .. nbo-1 followed at once by its border blocks (in memory the border starts at row nI: leaf_phys_row), and the step loop stops
+// behind the own blocks. The border rows of the panels are then L21, the right-hand side that rides along is y on the own rows and the updated
+// right-hand side on the border rows, and the tiles left in the registers are the front's Schur complement: no substitution kernel, no update kernel
+// and no round trip of L21 through memory between them. The border x border tiles are never cleared between iterations (k_nd_zero skips them, the
+// first trailing update of the other route starts them from zero: GemmArgs::beta0) — their accumulators START FROM ZERO here and are never loaded.
+// The complement leaves as the lower 16x16 tiles of the border x border block (diagonal tiles whole, both triangles, as the quadrant kernel leaves
+// them): the extend-add reads max(row, column), min(row, column) only.
+template <int NWV, bool LEAF = false>
 COV_DEV void potrf_panel_body(double* __restrict__ M, size_t ld, int k0, int nb, double* __restrict__ Dinv_out, int* flag,
                               const double* __restrict__ rhs, double* __restrict__ yout, size_t bsM, size_t bsL, size_t bsR,
-                              const long long* __restrict__ btab, const int* __restrict__ own, const int* __restrict__ list) {
+                              const long long* __restrict__ btab, const int* __restrict__ own, const int* __restrict__ list,
+                              const int* __restrict__ stdim = nullptr, int nI = 0) {
+  static_assert(!LEAF || NWV == 16, "the leaf form is a sixteen-wave form");
   constexpr int PROWS = (NWV == 16) ? 256 : PROWS4;   // (shadows the 16-wave constant)
   constexpr int NTW = (NWV == 16) ? 12 : 3;           // tile waves
   const int front = list != nullptr ? list[blockIdx.x] : (int)blockIdx.x;
@@ -226,6 +242,13 @@ COV_DEV void potrf_panel_body(double* __restrict__ M, size_t ld, int k0, int nb,
     const int real = __builtin_amdgcn_readfirstlane(own[front]) - k0;
     nb = min(nb, (real + PB - 1) / PB);
     if (nb <= 0) return;   // (workgroup-uniform) no real column of this front in the panel
+  }
+  // block columns to factor | LEAF: logical rows from nown on are border rows, bshift rows further down in memory; nb becomes ALL blocks of the front
+  const int nsteps = nb;
+  int nown = 0, bshift = 0;
+  if constexpr (LEAF) {
+    nown = PB * nsteps; bshift = leaf_border_shift(nsteps, nI);
+    nb = min(nsteps + leaf_blocks(__builtin_amdgcn_readfirstlane(stdim[front])), PROWS / PB);
   }
   if (btab != nullptr) { M += (size_t)btab[2 * front]; ld = (size_t)btab[2 * front + 1]; }  // fronts of unequal order (GemmArgs::btab)
   else M += (size_t)front * bsM;
@@ -251,16 +274,17 @@ COV_DEV void potrf_panel_body(double* __restrict__ M, size_t ld, int k0, int nb,
 #pragma unroll
     for (int c = 0; c < PB; ++c) fv[c] = 0.0;
     if (fid < n) {
+      const int prow = LEAF ? leaf_phys_row(fid, nown, bshift) : fid;
       if (fid >= PB) {
 #pragma unroll
-        for (int c = 0; c < PB; c += 2) { const double2 v = *reinterpret_cast<const double2*>(Mg + (size_t)fid * ld + c); fv[c] = v.x; fv[c + 1] = v.y; }
+        for (int c = 0; c < PB; c += 2) { const double2 v = *reinterpret_cast<const double2*>(Mg + (size_t)prow * ld + c); fv[c] = v.x; fv[c + 1] = v.y; }
       } else {
 #pragma unroll
         for (int c = 0; c < PB; ++c) fv[c] = Mg[(size_t)(c > fid ? c : fid) * ld + (c > fid ? fid : c)];
       }
-      if (rhs != nullptr) frhs = rhs[k0 + fid];
+      if (rhs != nullptr) frhs = rhs[k0 + prow];
     }
-    if (nb > 1) {  // diagonal tile (1,1): wave 0 takes it over at step 0 (see below)
+    if (nb > 1 && (!LEAF || nsteps > 1)) {  // diagonal tile (1,1): wave 0 takes it over at step 0 (see below). LEAF, one own block: a border tile, from zero
       const int rr = fid >> 4, cc = fid & 15;
       fdg = Mg[(size_t)(PB + (cc <= rr ? rr : cc)) * ld + PB + (cc <= rr ? cc : rr)];
     }
@@ -280,7 +304,7 @@ COV_DEV void potrf_panel_body(double* __restrict__ M, size_t ld, int k0, int nb,
     fill_lds();
     PPROBE_ACC(4, tp0);
     __builtin_amdgcn_s_setprio(3);
-    for (int j = 0; j < nb; ++j) {
+    for (int j = 0; j < nsteps; ++j) {
       double* cur = sP + (j & 1) * PROWS * PP;          // block column j, rows 16 j .. n
       double* oth = sP + ((j + 1) & 1) * PROWS * PP;    // block column j+1 (being assembled)
       double* dv = sDv;
@@ -356,6 +380,11 @@ COV_DEV void potrf_panel_body(double* __restrict__ M, size_t ld, int k0, int nb,
         for (int s2 = 0; s2 < 4; ++s2) cur[(o + PB + r) * PP + g + 4 * s2] = xt[s2];
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) oth[(o + PB + g + 4 * rg) * PP + r] = dg[rg];
+        if (LEAF && j + 1 == nsteps) {   // the first border tile of the Schur complement is this wave's: it leaves from here
+          double* sc = Mg + (size_t)(nI + g) * ld + nI + r;
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg) sc[(size_t)(4 * rg) * ld] = dg[rg];
+        }
       }
       lds_barrier();  // ---- Y(j): panel j complete in `cur`, the next diagonal tile in `oth`
       PPROBE_ACC(2, tq1);
@@ -366,13 +395,16 @@ COV_DEV void potrf_panel_body(double* __restrict__ M, size_t ld, int k0, int nb,
     return;
   }
 
-  const int jsplit = (NWV == 16 && nb > 8) ? nb - 8 : 0;   // steps before it are bound by the matrix pipes (the chain wave waits), the last eight by the chain
+  // steps before it are bound by the matrix pipes (the chain wave waits), the last eight by the chain. LEAF: the loop ends after at most eight steps
+  // with the border x border tiles still in the registers — every step is the matrix pipes', and the tile waves have the epilogue to run: all of SIMD 0's
+  const int jsplit = LEAF ? nsteps : (NWV == 16 && nb > 8) ? nb - 8 : 0;
+  double* const bout = LEAF ? const_cast<double*>(rhs) : nullptr;   // LEAF: the border rows' right-hand side goes back in place
   if (NWV == 16 && (wave & 3) == 0) {
     // ================================================================ SIMD 0's other waves: y_j, and the way out of panel j while the steps
     // are bound by the matrix pipes (the chain wave, which takes every issue slot of this SIMD during its sweep, then waits for the tiles)
     fill_lds();
     const int lq = tid0 & 63;
-    for (int j = 0; j < nb; ++j) {
+    for (int j = 0; j < nsteps; ++j) {
       const double* cur = sP + (j & 1) * PROWS * PP;
       const int o = PB * j;
       PARR(j, tp0);
@@ -387,7 +419,9 @@ COV_DEV void potrf_panel_body(double* __restrict__ M, size_t ld, int k0, int nb,
         sRhs[o + lq] = (y0 + y1) + (y2 + y3);
       }
       lds_barrier();  // ---- Y(j)
-      if (j < jsplit) panel_out<192>(cur, sRhs, sdd + PB * (j & 1), Mg, ld, o, n, 64 * ((wave >> 2) - 1) + lq, yout != nullptr ? yout + k0 : nullptr);
+      if (j < jsplit)
+        panel_out<192, LEAF>(cur, sRhs, sdd + PB * (j & 1), Mg, ld, o, n, 64 * ((wave >> 2) - 1) + lq, yout != nullptr ? yout + k0 : nullptr, nown, bshift,
+                             j + 1 == nsteps ? bout : nullptr);
       if (wave == PPROBE_WAVE) PSTEP(3, j, tp0);
     }
     return;
@@ -424,14 +458,19 @@ COV_DEV void potrf_panel_body(double* __restrict__ M, size_t ld, int k0, int nb,
   for (int s = 0; s < NSLOT; ++s) {
     const bool on = (tik[s] >> 8) != 99;
     const int ii = on ? (tik[s] & 255) : 1, kk = on ? (tik[s] >> 8) : 1;
-    const double* base = Mg + (size_t)(PB * ii) * ld + PB * kk;
+    if (LEAF && (!on || kk >= nsteps)) {   // (wave-uniform) a border x border tile: never cleared, never read — the complement starts from zero
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) acc[s][rg] = 0.0;
+      continue;
+    }
+    const double* base = Mg + (size_t)(LEAF ? leaf_phys_row(PB * ii, nown, bshift) : PB * ii) * ld + PB * kk;   // (LEAF: kk is an own block here)
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg) acc[s][rg] = base[ii == kk ? offm[rg] : offn[rg]];
   }
   // (The first step is as long as the tile loads take to issue, ~5 us: 244 KB into ONE CU at ~50 GB/s. Measured and dropped: half of them
   //  behind barrier X(0) — the conditional load inside the step loop costs 38 spilled registers —; 16-byte loads by lane pairs with a DPP
   //  swap behind X(0): half the instructions, the same time.)
-  for (int j = 0; j < nb; ++j) {
+  for (int j = 0; j < nsteps; ++j) {
     double* cur = sP + (j & 1) * PROWS * PP;
     double* oth = sP + ((j + 1) & 1) * PROWS * PP;
     const double* dv = sDv;
@@ -488,6 +527,21 @@ COV_DEV void potrf_panel_body(double* __restrict__ M, size_t ld, int k0, int nb,
     if (j >= jsplit) panel_out<64 * NTW>(cur, sRhs, sdd + PB * (j & 1), Mg, ld, PB * j, n, 64 * tw + lq, yout != nullptr ? yout + k0 : nullptr);   // (the tile waves have the time now)
     PPROBE_ACC(7, tq3);
   }
+  if constexpr (LEAF) {
+    // ---- the Schur complement leaves: every tile of this wave with both blocks in the border, every panel applied. Tile (nsteps, nsteps) is wave 0's.
+    const int lq = hw_lane_id();
+    const int fr = lq & 15, fk = lq >> 4;
+    double* const sc = Mg + (size_t)(bshift + fk) * ld + bshift + fr;
+#pragma unroll
+    for (int s = 0; s < NSLOT; ++s) {
+      const int i = tik[s] & 255, k = tik[s] >> 8;
+      if (k != 99 && k >= nsteps && !(i == k && k == nsteps)) {
+        double* dstp = sc + (size_t)(PB * i) * ld + PB * k;
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) dstp[(size_t)(4 * rg) * ld] = acc[s][rg];
+      }
+    }
+  }
   PPROBE_FLUSH();
 }
 
@@ -501,6 +555,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                                                          const double* __restrict__ rhs, double* __restrict__ yout, size_t bsM, size_t bsL, size_t bsR,
                                                          const long long* __restrict__ btab, const int* __restrict__ own, const int* __restrict__ list) {
   potrf_panel_body<4>(M, ld, k0, nb, Dinv_out, flag, rhs, yout, bsM, bsL, bsR, btab, own, list);
+}
+// the one-launch leaf form: workgroup = front of the batch, whole (own: up to eight blocks | stdim: the border's order | nI: where the border starts)
+__global__ __launch_bounds__(64 * NW) void k_potrf_leaf(double* __restrict__ M, double* __restrict__ Dinv_out, int* flag, double* __restrict__ rhs,
+                                                        double* __restrict__ yout, size_t bsL, size_t bsR, const long long* __restrict__ btab,
+                                                        const int* __restrict__ own, const int* __restrict__ stdim, int nI) {
+  potrf_panel_body<16, true>(M, 0, 0, PROWS / 2 / PB, Dinv_out, flag, rhs, yout, 0, bsL, bsR, btab, own, nullptr, stdim, nI);
 }
 
 struct TrsmSubArgs {
@@ -1448,6 +1508,16 @@ void launch_potrf_panel(double* S, size_t ld, int t0, int w, double* Linv, int* 
   if (n_small > 0)
     hipLaunchKernelGGL(k_potrf_panel4, dim3(n_small), dim3(256), kPanelLds4, st, S, ld, t0 * kTile, std::min(nb, 8), Lp, flag, (const double*)b, (double*)yb, sM, sL, sR, btab, own,
                        list + n_big);
+}
+
+// a level of leaf fronts (leaf_front.hpp: leaf_level_eligible) factored whole in one launch: L, the block inverses, y, the border rows' right-hand
+// side and the Schur complements are all in place behind it. Counted as k_potrf_panel's: it is that kernel's sixteen-wave form
+void launch_potrf_leaf(double* S, double* Linv, int* flag, double* b, int npad, int nbt, size_t sL, size_t sR, hipStream_t st, const long long* btab,
+                       const int* own, const int* stdim, int nI) {
+  static std::atomic<unsigned long long> seen{0};
+  if (first_use_on_device(seen)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_potrf_leaf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPanelLds);
+  form_hit(KF_POTRF_PANEL); form_hit(KF_POTRF_PANEL_FRONTS, nbt); form_hit(KF_POTRF_LEAF, nbt);
+  hipLaunchKernelGGL(k_potrf_leaf, dim3(nbt), dim3(64 * NW), kPanelLds, st, S, Linv, flag, b, b + npad, sL, sR, btab, own, stdim, nI);
 }
 
 void launch_trsm_sub(double* S, size_t ld, int t0, int w, int r0, int r1, const double* Linv, double* b, int npad, int nbt, size_t sM, size_t sL,

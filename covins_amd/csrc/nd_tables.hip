@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "leaf_front.hpp"
 #include "nd_plan.hpp"
 
 namespace covgpu {
@@ -104,6 +105,18 @@ struct FrontTables {
         if (real > 128) ++L.pbig[P]; else if (real > 0) ++L.psmall[P];
       }
   }
+  // whether the one-launch leaf form takes the bottom level `nodes` (NdLevel::leaf_one): a level below other levels of an unsharded tree (a sharded
+  // solve keeps the panel route: its ranks' bottom levels differ, and its schedule is not this one's) that leaf_level_eligible accepts
+  bool leaf_one_level(const std::vector<int>& nodes) const {
+    if (sh || nlev < 2) return false;
+    std::vector<int> od, sd, ptr{0}, var;
+    for (int n : nodes) {
+      od.push_back(hp.own_dims[n]); sd.push_back(hp.st_dims[n]);
+      var.insert(var.end(), hp.own[n].begin(), hp.own[n].end());
+      ptr.push_back((int)var.size());
+    }
+    return leaf_level_eligible((int)nodes.size(), od.data(), sd.data(), ptr.data(), var.data());
+  }
   // leaves the level shapes (dev.lev: n, first, nI, ntot, own_max, linv_off, live counts, panel lists), the fronts laid out one behind the other
   // (ld, h_ntab, the per-node tables of lay_front) and the totals M_sub / M_elems / linv_elems / ntop / n_top_tiles
   void front_layout() {
@@ -122,6 +135,7 @@ struct FrontTables {
       for (int n : lnodes[l]) lay_front(L, n, i++, moff);
       L.linv_off = loff; loff += (size_t)L.n * L.nI * kTile;
       panel_lists(L);
+      if (l == 0) L.leaf_one = leaf_one_level(lnodes[l]);
     }
     if (Hs >= nlev) dev.M_sub = moff;
     dev.M_elems = moff; dev.linv_elems = loff;

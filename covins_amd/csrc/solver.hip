@@ -196,6 +196,20 @@ void enqueue_build(covgpu_context* c, double mu) {
     launch_imu_gather(P, 1, side);
     launch_finalize_diag(P, mu, 1, side);
   }
+  // The bottom level of the elimination tree, where it consists of speed-bias leaf fronts only (NdLevel::leaf_one): everything those fronts hold is
+  // final here, long before the pose system is. They are assembled and factored whole — one launch each, no gate inside (k_panel.hip: k_potrf_leaf) —
+  // on the head stream, which has just cleared them and is idle during the landmark pass; the serial chain of the solve then starts at level 1.
+  // One dependency in (the record below), one out (ev_leaf, which the main stream takes with its join of the side stream further down). In the
+  // first iteration of a solve the side stream carries the preintegration: the leaves then finish late, and the join waits for them as it waits
+  // for the side stream itself.
+  bool leaves_early = false;
+  if (P.nd && P.vi && nd_leaves_beside_pass(c->nd)) {
+    c->chol.record(c->chol.ev_sb, side, 7);
+    c->chol.wait(c->chol.head, c->chol.ev_sb);
+    FormScope census(&c->chol.forms);
+    leaves_early = launch_nd_leaves(P, c->nd, c->chol.head, c->chol);
+    c->chol.record(c->chol.ev_leaf, c->chol.head, 8);
+  }
   // Between the pair pass and the first factorisation every launch is a link of the chain (~6 us each): the loop edges are linearised
   // on the side stream beside the landmark pass (they depend on the estimate only), and the cost partials are summed there too — behind
   // the last kernel that writes one (the landmark pass's own finisher runs on the side stream when the pass forks).
@@ -203,7 +217,7 @@ void enqueue_build(covgpu_context* c, double mu) {
   launch_lm_build(P, mu, c->st, c->chol.ev_fill, side, c->chol.ev_lin, c->chol.ev_kf, &c->chol);
   if (forked) launch_part_finish(P, SC_COST, 1, side);
   c->chol.record(c->chol.ev_kf, side, 4);
-  c->chol.wait(c->st, c->chol.ev_kf);
+  c->chol.wait(c->st, c->chol.ev_kf, leaves_early ? c->chol.ev_leaf : nullptr);
   // pose-dimension part: adds onto the blocks k_kf_reduce assigned (fixed order: visual, inertial, loop), then the damping. Visual-inertial: one launch
   // (k_pose_finish: every entry gets the same operands in the same order from ONE thread). Not where a loop edge joins two neighbouring chain positions:
   // that pair block can be an IMU factor's cross block as well, and the two additions onto it are ordered by the launches only. Visual-only problems and

@@ -495,6 +495,7 @@ void covgpu_get_profile2(covgpu_context* ctx, double* out16);
  *   dist_panel             sharded solve, distributed top: panels factored by dense_cholesky_dist
  *   pgo_arrow              pose-graph solves by the block-arrow elimination
  *   pgo_dense              pose-graph solves by one dense factorisation
+ *   k_potrf_leaf           FRONTS of a bottom level of speed-bias leaf fronts factored whole, one launch per solve (also under k_potrf_panel / .fronts)
  *   FORMS-END */
 int  covgpu_get_kernel_forms(covgpu_context* ctx, int64_t* out, int32_t n);
 const char* covgpu_kernel_form_name(int32_t i);
