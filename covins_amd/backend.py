@@ -122,6 +122,46 @@ def lm_group(num_obs: int, num_lm: int) -> int:
     return int(lib().covgpu_lm_group(int(num_obs), int(num_lm)))
 
 
+def marginal_limits():
+    """Host-only: {max_kf, max_cols, mfma_cols, panel_rows} of Context.marginal_covariance as the library was built (covgpu_marginal_limits)."""
+    out = (C.c_int32 * 4)()
+    lib().covgpu_marginal_limits(out)
+    return dict(zip(("max_kf", "max_cols", "mfma_cols", "panel_rows"), (int(v) for v in out)))
+
+
+def _quat_rot(q):
+    x, y, z, w = (float(v) for v in q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def between_jacobian(pose_i, pose_j):
+    """Host-only: the 6x12 Jacobian [d/d(dtheta_i, dp_i) | d/d(dtheta_j, dp_j)] of the SE3 between residual (R7: rotation rows first) at zero
+    residual — the measurement is the relative pose of the two estimates itself — with unit weight and no loss, in A.1's tangent
+    (q <- q * exp(dtheta), p <- p + dp). Poses are [qx, qy, qz, qw, px, py, pz] = T_w_s."""
+    pi, pj = np.asarray(pose_i, np.float64), np.asarray(pose_j, np.float64)
+    Ri, Rj = _quat_rot(pi[:4]), _quat_rot(pj[:4])
+    t = Ri.T @ (pj[4:] - pi[4:])
+    sk = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+    J = np.zeros((6, 12))
+    J[:3, 0:3] = -(Rj.T @ Ri); J[:3, 6:9] = np.eye(3)
+    J[3:, 0:3] = sk; J[3:, 3:6] = -Ri.T; J[3:, 9:12] = Ri.T
+    return J
+
+
+def relative_pose_covariance(cov12, pose_i, pose_j):
+    """Host-only: covariance J cov12 J^T (6x6, rotation first, translation second: the order of LoopConstraint::cov_mat) of the relative pose
+    T_si_sj of two keyframes from their joint pose covariance cov12 (12x12, Context.marginal_covariance(.., [i, j], block="pose")), J =
+    between_jacobian(pose_i, pose_j)."""
+    S = np.asarray(cov12, np.float64)
+    if S.shape != (12, 12):
+        raise ValueError("cov12 must be 12x12: the joint pose covariance of two keyframes")
+    J = between_jacobian(pose_i, pose_j)
+    out = J @ S @ J.T
+    return 0.5 * (out + out.T)
+
+
 def kernel_form_names():
     """Names of the kernel forms Context.kernel_forms() counts, in the library's order."""
     n = lib().covgpu_get_kernel_forms(None, None, 0)
@@ -940,6 +980,37 @@ class Context:
         s = prob.as_struct()
         self._check(lib().covgpu_gn_step(self._h, C.byref(opt), C.byref(s), float(mu), dptr(dx), dptr(dl), dptr(c)))
         return dx, dl, float(c[0])
+
+    @staticmethod
+    def _marginal(kfs, block, mu, D):
+        """(Marginal, cov, stats, keep-alive) of one marginal-covariance call; D = unknowns per keyframe of the problem."""
+        if block not in ("pose", "full"):
+            raise ValueError('block must be "pose" or "full"')
+        kf = np.ascontiguousarray(kfs, np.int32).reshape(-1)
+        m = len(kf) * (D if block == "full" else 6)
+        cov = np.zeros((m, m)); stats = np.zeros(8, np.int64)
+        s = capi.Marginal()
+        s.num_kf = len(kf); s.kf = iptr(kf); s.block = 1 if block == "full" else 0; s.mu = float(mu)
+        s.cov = dptr(cov); s.stats = stats.ctypes.data_as(capi._lp)
+        return s, cov, stats, kf
+
+    def marginal_covariance(self, prob, opt, kfs, block="pose", mu=0.0, pgo=False):
+        """Joint marginal covariance of the keyframes `kfs` (problem indices, any order) at the estimate in `prob`: the rows and columns of
+        the inverse of the reduced camera system at damping mu (covgpu_marginal_covariance). block "pose": 6 rows per
+        keyframe (dtheta, dp); "full": all 15 of a visual-inertial problem. Returns (cov [m, m] in the order of kfs, stats dict)."""
+        D = 6 if (pgo or opt.visual_only) else 15
+        s, cov, stats, keep = self._marginal(kfs, block, mu, D)
+        ps = prob.as_struct()
+        self._keep = prob; self._keep_pgo = bool(pgo)
+        self._check(lib().covgpu_marginal_covariance(self._h, C.byref(opt), C.byref(ps), 1 if pgo else 0, C.byref(s)))
+        return cov, dict(zip(capi.MARGINAL_STATS, (int(v) for v in stats)))
+
+    def marginal_covariance_resident(self, opt, kfs, block="pose", mu=0.0):
+        """The same at the estimate the context holds (what download() returns), after upload() or a finished solve_resident()."""
+        D = 6 if (self._keep_pgo or opt.visual_only) else 15
+        s, cov, stats, keep = self._marginal(kfs, block, mu, D)
+        self._check(lib().covgpu_marginal_resident(self._h, C.byref(opt), C.byref(s)))
+        return cov, dict(zip(capi.MARGINAL_STATS, (int(v) for v in stats)))
 
     def solve_resident_traced(self, opt: Options, capacity: int = 64):
         """solve_resident that also returns the trust-region state at the end of every iteration, retry rounds included: (Result, trace

@@ -355,6 +355,14 @@ VOCTRAIN_STATS = ("iterations", "max_node_iterations", "nodes_at_cap", "emptied_
                   "d2h_bytes")                                                                   # covgpu_voc_train_t::stats[0..7]
 
 
+class Marginal(C.Structure):
+    """covgpu_marginal_t (include/covgpu.h): marginal covariances of selected keyframes, DESIGN.md §4.19."""
+    _fields_ = [("num_kf", C.c_int32), ("kf", _ip), ("block", C.c_int32), ("mu", C.c_double), ("cov", _dp), ("stats", _lp)]
+
+
+MARGINAL_STATS = ("columns", "fronts", "launches", "mfma_launches", "vector_launches", "scratch_bytes", "reserved6", "reserved7")
+
+
 PRUNE_ERASED, PRUNE_TIME_GATE, PRUNE_LOOP_KF, PRUNE_NOT_ERASE = 0, 1, 2, 3                       # round_action
 PRUNE_STOP_NO_CANDIDATES, PRUNE_STOP_THRESHOLD, PRUNE_STOP_MAX_KFS, PRUNE_STOP_MAX_ROUNDS = 0, 1, 2, 3   # stop_reason
 
@@ -435,6 +443,10 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("voc_train_limits", [_ip], None)
         d("voc_train_check", [C.POINTER(VocTrain), C.POINTER(VocTrainOpts)])
         d("voc_train", [C.c_void_p, C.POINTER(VocTrain), C.POINTER(VocTrainOpts)])
+        d("marginal_limits", [_ip], None)
+        d("marginal_check", [PP, OP, C.POINTER(Marginal)])
+        d("marginal_covariance", [C.c_void_p, OP, PP, C.c_int32, C.POINTER(Marginal)])
+        d("marginal_resident", [C.c_void_p, OP, C.POINTER(Marginal)])
         d("outlier_pass", [C.c_void_p, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])
         d("covisibility", [C.c_void_p, C.c_int32, C.c_int64, _ip, _ip, _ip, C.POINTER(C.c_int64)])
         d("gba_solve_multi", [OP, PP, RP, C.c_int32, _ip, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])

@@ -60,6 +60,7 @@ struct covgpu_context {
   hipStream_t st = nullptr;
   covgpu::DevProblem P;
   bool have = false, pgo = false;
+  bool state_set = false;    // the working estimate (P.pose, P.sb, P.lm) holds the uploaded one or a solve's result (reset_state; cleared by an upload)
   std::vector<void*> allocs;
   size_t alloc_bytes = 0;  // device bytes behind `allocs` (the footprint covgpu_get_layout reports)
   double* h_scal = nullptr;  // pinned mirror of P.scal + flag

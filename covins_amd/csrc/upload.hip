@@ -60,7 +60,7 @@ void free_problem(covgpu_context* c) {
   c->allocs.clear();
   c->alloc_bytes = 0;
   c->chol.tri_clear();
-  c->have = false;
+  c->have = false; c->state_set = false;
   c->pgo_plan.active = false;  // its device buffers were in `allocs`
   c->d_pairkey = nullptr;
   c->nd = NdDev();
@@ -581,6 +581,7 @@ int reset_state(covgpu_context* c) {
   HIPCHK(hipMemcpyAsync(P.pose, P.pose0, (size_t)7 * P.K * sizeof(double), hipMemcpyDeviceToDevice, c->st));
   HIPCHK(hipMemcpyAsync(P.sb, P.sb0, (size_t)9 * P.K * sizeof(double), hipMemcpyDeviceToDevice, c->st));
   if (P.L) HIPCHK(hipMemcpyAsync(P.lm, P.lm0, (size_t)3 * P.L * sizeof(double), hipMemcpyDeviceToDevice, c->st));
+  c->state_set = true;
   return COVGPU_OK;
 }
 

@@ -1022,6 +1022,45 @@ void covgpu_voc_train_limits(int32_t out[4]);
 int covgpu_voc_train_check(const covgpu_voc_train_t*, const covgpu_voc_train_opts*);
 int covgpu_voc_train(covgpu_context*, const covgpu_voc_train_t*, const covgpu_voc_train_opts*);
 
+/* ---- Marginal covariances of selected keyframes from the multifrontal factor ----
+ *
+ * The joint covariance of the chosen keyframes' unknowns after the landmarks (and every other keyframe) are marginalised: the rows and
+ * columns `kf` of the inverse of exactly the matrix covgpu_schur / covgpu_schur_pgo return at the same mu (whitened, loss-corrected
+ * residuals; A.1's right-perturbation tangent; no further scaling: the fronts hold that matrix entry for entry). With S = L L^T the
+ * block is (L^-1 E)^T (L^-1 E) over the unit columns E of the chosen unknowns: forward substitutions along the paths from the fronts
+ * that own them to the root, then one Gram product, every sum in a fixed order (k_marginal.hip). `cov` is symmetric bit for bit: a
+ * pair is computed once and stored twice.
+ * Refused with COVGPU_ERR_INVALID_ARG: num_kf outside [1, COVGPU_MARGINAL_MAX_KF], an index out of range, a duplicate, a keyframe
+ * whose pose is constant (kf_fixed: its rows of the system are identity rows, it has no covariance), block outside {0, 1}, mu
+ * negative or not finite, a NULL cov; a sharded context; a context whose pose graph is off the elimination tree (COVGPU_PGO_ND=0).
+ * A factorisation that meets a non-positive pivot is COVGPU_ERR_NUMERIC, as in covgpu_gn_step.
+ * Scratch: per call, freed when it returns: 8 bytes x (columns rounded up to 16) x (own unknowns of the fronts on the chosen paths,
+ * each front's rounded up to 16) for the working right-hand sides, 8 m^2 for the result and the index tables. The rows are at most
+ * n + 15 per front, so at the limits (32 keyframes, block 1: 480 columns) on the 12-agent map (n = 36 000) a call stays below
+ * 8 x 480 x 40 000 = 154 MB. */
+#define COVGPU_MARGINAL_MAX_KF 32                /* keyframes of one call */
+#define COVGPU_MARGINAL_MAX_COLS 480             /* its columns: 32 x 15 */
+#define COVGPU_MARGINAL_MFMA_COLS 16             /* a front with this many active columns or more takes the matrix-core form */
+typedef struct covgpu_marginal_t {
+  int32_t num_kf;        /* q: 1 .. COVGPU_MARGINAL_MAX_KF */
+  const int32_t* kf;     /* [q] keyframe indices of the problem, distinct, any order */
+  int32_t block;         /* 0: pose rows only (d = 6); 1: all D rows of the keyframe (15 visual-inertial, 6 visual-only / pose graph) */
+  double mu;             /* damping of the factored system, >= 0; 0 = the covariance proper */
+  double* cov;           /* out [m][m], m = q*d, row-major, in the order of `kf`, rows of a keyframe in IR order (A.1: dtheta, dp, then dv, db_a, db_g) */
+  int64_t* stats;        /* out [8], may be NULL: columns, fronts visited, launches, launches of the matrix-core form, of the vector form,
+                          * bytes of scratch, 0, 0 */
+} covgpu_marginal_t;
+/* {COVGPU_MARGINAL_MAX_KF, COVGPU_MARGINAL_MAX_COLS, COVGPU_MARGINAL_MFMA_COLS, rows of a panel step (128)} as the library was built */
+void covgpu_marginal_limits(int32_t out[4]);
+/* The argument checks of covgpu_marginal_covariance alone (no context, no device): COVGPU_OK or COVGPU_ERR_INVALID_ARG with the message.
+ * The two refusals that depend on the context (sharded; pose graph off the tree) are made by the calls themselves. */
+int covgpu_marginal_check(const covgpu_problem*, const covgpu_options*, const covgpu_marginal_t*);
+/* Uploads `p` as covgpu_gn_step does (pgo != 0: as covgpu_upload_pgo), linearises at its estimate, builds and factors at mu, sweeps. */
+int covgpu_marginal_covariance(covgpu_context*, const covgpu_options*, const covgpu_problem*, int32_t pgo, const covgpu_marginal_t*);
+/* The same at the estimate the context holds (what covgpu_download returns) after an upload or a finished solve. A following
+ * covgpu_solve_resident returns the bits it would have returned without this call: every solve restarts from the uploaded estimate. */
+int covgpu_marginal_resident(covgpu_context*, const covgpu_options*, const covgpu_marginal_t*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@
 #include <unordered_map>
 #include <memory>
 #include <set>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <utility>
@@ -668,6 +669,59 @@ class OptimizationT {
     if (covgpu_gba_solve(ctx, &o, &p, &r) != COVGPU_OK) detail::fatal(covgpu_last_error());
     // problem.Evaluate + threshold (:270-289) on the device at the estimate the solve left resident: flags come back
     if (erase && covgpu_outlier_pass(ctx, prm.th_gba_outlier_global, erase->data(), lm_left->data(), counts) != COVGPU_OK) detail::fatal(covgpu_last_error());
+  }
+
+  // ---- marginal covariances from the factor of the reduced camera system (covgpu_marginal_covariance). The reference has no
+  // counterpart: it obtains the 6x6 covariance of a loop edge (LoopConstraint::cov_mat, optimization_be.cpp:922-923) from repeated 17-point
+  // solves (RelNonCentralPosSolver.cpp:187-292). Here: the map's own view after GBA.
+  // Joint covariance of the keyframes `ids` (id, client id; any order, distinct, none with a constant pose) at the map's estimate, on the problem
+  // the SECOND round of GlobalBundleAdjustment solves (loop constraints with their loss): [m][m] row-major, m = ids.size() * d in the order of
+  // `ids`, d = 6 (dtheta, dp: A.1's right perturbation) or — full_state on a visual-inertial problem — 15 (then dv, db_a, db_g). mu: damping
+  // of the factored system, 0 = the covariance proper. stats: covgpu_marginal_t::stats or nullptr. Throws std::invalid_argument for an id the
+  // problem does not hold and std::runtime_error with the library's message for a refused or failed call.
+  static std::vector<double> MarginalCovariance(const MapPtr& map, const std::vector<idpair>& ids, bool visual_only = false, bool full_state = false,
+                                                double mu = 0.0, int64_t* stats = nullptr) {
+    detail::Flat f; Index ix;
+    FlattenGBA(map, visual_only, true, f, ix);
+    std::map<idpair, int32_t> row;
+    for (size_t k = 0; k < ix.kfs.size(); ++k) row[ix.kfs[k]->id_] = (int32_t)k;
+    std::vector<int32_t> kf;
+    for (const idpair& id : ids) {
+      auto it = row.find(id);
+      if (it == row.end()) throw std::invalid_argument("MarginalCovariance: keyframe not in the problem");
+      kf.push_back(it->second);
+    }
+    const int d = (full_state && !visual_only) ? 15 : 6;
+    std::vector<double> cov((size_t)(kf.size() * d) * (kf.size() * d));
+    covgpu_marginal_t mg;
+    mg.num_kf = (int32_t)kf.size(); mg.kf = kf.data(); mg.block = full_state ? 1 : 0; mg.mu = mu; mg.cov = cov.data(); mg.stats = stats;
+    covgpu_problem p = f.view();
+    covgpu_options o = Options(1, visual_only);
+    if (covgpu_marginal_covariance(Context(), &o, &p, 0, &mg) != COVGPU_OK) throw std::runtime_error(covgpu_last_error());
+    return cov;
+  }
+  // Covariance of the relative pose T_s1_s2 of two keyframes from their joint pose covariance cov12 ([12][12]: MarginalCovariance(map, {id1,
+  // id2})): J cov12 J^T with J the 6x12 Jacobian of the between residual (R7) at zero residual and unit weight — [6][6] row-major, rotation
+  // first and translation second, the order of LoopConstraint::cov_mat.
+  static std::array<double, 36> RelativePoseCovariance(const std::vector<double>& cov12, const TransformType& Tws1, const TransformType& Tws2) {
+    if (cov12.size() != 144) throw std::invalid_argument("RelativePoseCovariance: cov12 must be 12x12");
+    double R1[9], R2[9], t[3], J[72] = {0};
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) { R1[3 * r + c] = Tws1(r, c); R2[3 * r + c] = Tws2(r, c); }
+    for (int r = 0; r < 3; ++r) { t[r] = 0; for (int c = 0; c < 3; ++c) t[r] += R1[3 * c + r] * (Tws2(c, 3) - Tws1(c, 3)); }   // R1^T (p2 - p1)
+    const double sk[9] = {0, -t[2], t[1], t[2], 0, -t[0], -t[1], t[0], 0};
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        double a = 0;
+        for (int k = 0; k < 3; ++k) a += R2[3 * k + r] * R1[3 * k + c];   // R2^T R1
+        J[12 * r + c] = -a; J[12 * r + 6 + c] = r == c ? 1.0 : 0.0;
+        J[12 * (3 + r) + c] = sk[3 * r + c]; J[12 * (3 + r) + 3 + c] = -R1[3 * c + r]; J[12 * (3 + r) + 9 + c] = R1[3 * c + r];
+      }
+    double JS[72];
+    for (int r = 0; r < 6; ++r) for (int c = 0; c < 12; ++c) { double a = 0; for (int k = 0; k < 12; ++k) a += J[12 * r + k] * cov12[12 * k + c]; JS[12 * r + c] = a; }
+    std::array<double, 36> out;
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c <= r; ++c) { double a = 0; for (int k = 0; k < 12; ++k) a += JS[12 * r + k] * J[12 * c + k]; out[6 * r + c] = out[6 * c + r] = a; }
+    return out;
   }
 
   // ---- optimization_be.cpp:56-618
