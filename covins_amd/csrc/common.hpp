@@ -373,7 +373,7 @@ struct CholAux {
 // batched form: n independent systems of identical shape; sM / sL / sR = elements between consecutive matrices, Linv
 // sets and right-hand sides. The same launches serve all of them (one more grid dimension).
 // multifrontal fronts: the backward substitution reads the given (ancestor) unknowns straight from the solution vector and
-// writes the front's own unknowns there — no separate gather / scatter launches (k_panel.hip: k_bwd_given, k_bwd_step_sub)
+// writes the front's own unknowns there — no separate gather / scatter launches (k_bwd.hip: k_bwd_given, k_bwd_step_sub)
 struct BwdXfer {
   const int* gidx = nullptr;                   // solution index of every own / border scalar of every front (nullptr: disabled)
   const int *own_g = nullptr, *st_g = nullptr, *own_dims = nullptr, *st_dims = nullptr;   // per front (level order)
@@ -392,7 +392,7 @@ struct DenseBatch {
   // pre_trsm: event the first panel's substitutions wait for (the caller's second-half extend-add of THIS batch's fronts).
   int split_ta = 0;
   hipEvent_t pre_trsm = nullptr;
-  int* bwd_cnt = nullptr;          // [n] zeroed ticket counters: whole-front backward substitution in one launch (k_panel.hip: k_bwd_front)
+  int* bwd_cnt = nullptr;          // [n] zeroed ticket counters: whole-front backward substitution in one launch (k_bwd.hip: k_bwd_front)
   double* bwd_scr = nullptr;       // its scratch: [n][interior tiles <= 4][row chunks][128]
   double* bwd_pipe = nullptr;      // k_bwd_pipe's sentinel-filled scratch (fronts of kBwdPipeMinTiles interior tiles and more); nullptr: launch per tile
   int *pipe_dead = nullptr, *pipe_dead_h = nullptr; double pipe_timeout_s = 3.0;   // CholAux::gate_dead / gate_dead_h / gate_timeout_s
@@ -429,7 +429,7 @@ void dense_cholesky_dist(double* S, double* b, double* Linv, int* flag, int npad
 // interior tiles one after the other). Measured in round 5 on the corrected 5-agent map, whose upper levels hold fronts of 5-6 tiles: the
 // serial part costs ~15 us per tile (dependent loads of one workgroup), a launch per tile 8.6 — 4: 212.8 it/s, 8: 211.8, 16: 200.0.
 constexpr int kBwdFrontMaxTiles = 4;
-// Fronts of at least this many interior tiles: one launch, one workgroup per tile, hand-overs inside the launch (k_panel.hip: k_bwd_pipe) —
+// Fronts of at least this many interior tiles: one launch, one workgroup per tile, hand-overs inside the launch (k_bwd.hip: k_bwd_pipe) —
 // unless COVGPU_BWD_PIPE=0 turns that form off (bwd_pipe_on, k_chol.hip).
 constexpr int kBwdPipeMinTiles = 2;
 bool bwd_pipe_on();
@@ -446,12 +446,12 @@ void launch_bwd_given(const double* S, size_t ld, int r0, int r1, double* y, dou
                       const long long* btab, const int* live, int tI, BwdXfer xf = BwdXfer());
 void launch_bwd_front(const double* S, int tI, int ntiles, int nchunk, double* y, const double* Linv, int nbt, size_t sL, size_t sR, hipStream_t st,
                       const long long* btab, const int* live, BwdXfer xf, int* cnt, double* scr);
-// fronts of many interior tiles: the whole backward substitution as one launch of cooperating workgroups (k_panel.hip: k_bwd_pipe). pipe: sentinel-filled
+// fronts of many interior tiles: the whole backward substitution as one launch of cooperating workgroups (k_bwd.hip: k_bwd_pipe). pipe: sentinel-filled
 // scratch of at least nbt * ntiles * (nchunk + 1) * 128 doubles (launch_pipe_fill once; the kernel leaves it as it found it)
 void launch_bwd_pipe(const double* S, int tI, int ntiles, int nchunk, double* y, const double* Linv, int nbt, size_t sL, size_t sR, hipStream_t st,
                      const long long* btab, const int* live, BwdXfer xf, double* pipe, int* dead, int* dead_h, double timeout_s);
 void launch_pipe_fill(double* buf, size_t n, hipStream_t st);
-// several (bottom) levels of the tree in ONE launch (k_panel.hip: k_bwd_tree); lev[0] is the HIGHEST of them. pipe: as above, at least the sum over the
+// several (bottom) levels of the tree in ONE launch (k_bwd.hip: k_bwd_tree); lev[0] is the HIGHEST of them. pipe: as above, at least the sum over the
 // levels of nbt * T * (nchunk + 1) * 128 doubles
 constexpr int kBwdTreeMax = 8;
 constexpr int kPipeChunk = 128;              // border rows per helper workgroup of the pipelined backward substitution

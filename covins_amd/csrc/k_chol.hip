@@ -1062,7 +1062,7 @@ void dense_cholesky_dist(double* S, double* b, double* Linv, int* flag, int npad
   }
 }
 
-// the pipelined backward substitution (k_panel.hip: k_bwd_pipe, k_bwd_tree); COVGPU_BWD_PIPE=0 disables it
+// the pipelined backward substitution (k_bwd.hip: k_bwd_pipe, k_bwd_tree); COVGPU_BWD_PIPE=0 disables it
 bool bwd_pipe_on() {
   static const bool v = env_int("COVGPU_BWD_PIPE", 1) != 0;
   return v;
@@ -1073,7 +1073,7 @@ void dense_backward_solve(double* S, double* b, double* Linv, int npad, hipStrea
   const int nbt = bt.n > 0 ? bt.n : 1;
   const size_t ld = (size_t)npad;
   {
-    // multifrontal front of few interior tiles: given rows and every interior tile in ONE launch (k_panel.hip: k_bwd_front)
+    // multifrontal front of few interior tiles: given rows and every interior tile in ONE launch (k_bwd.hip: k_bwd_front)
     const int nt_real = bt.own_max > 0 ? std::min(tfact, (bt.own_max + kTile - 1) / kTile) : tfact;
     if (bt.bwd_pipe != nullptr && bt.pipe_dead != nullptr && bt.xfer.gidx != nullptr && bt.tab != nullptr && bt.live != nullptr && bwd_pipe_on() && nt_real >= kBwdPipeMinTiles && nbt <= 65535) {
       launch_bwd_pipe(S, tfact, nt_real, ((tend - tfact) * kTile + kPipeChunk - 1) / kPipeChunk, b + npad, Linv, nbt, bt.sL, bt.sR, st, bt.tab, bt.live, bt.xfer, bt.bwd_pipe, bt.pipe_dead,
@@ -1087,7 +1087,7 @@ void dense_backward_solve(double* S, double* b, double* Linv, int npad, hipStrea
       return;
     }
   }
-  if (tend > tfact) {  // all given rows in one launch (k_panel.hip)
+  if (tend > tfact) {  // all given rows in one launch (k_bwd.hip)
     launch_bwd_given(S, ld, tfact * kTile, tend * kTile, b + npad, b, tfact * kTile, nbt, bt.sM, bt.sR, st, bt.tab, bt.live, bt.tI, bt.xfer);
     tend = tfact;
   }

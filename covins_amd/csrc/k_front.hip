@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void k_nd_zero(DevProblem P, NdZeroArgs z) {
 __global__ __launch_bounds__(256) void k_nd_assemble(DevProblem P, const int* __restrict__ rhs_off, double* __restrict__ x, const int* __restrict__ fill, int nfill,
                                                       unsigned long long empty, int part, int nleaf) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  // (the solution vector's entries of the levels whose backward substitution is ONE launch start a solve "empty": k_panel.hip, k_bwd_tree)
+  // (the solution vector's entries of the levels whose backward substitution is ONE launch start a solve "empty": k_bwd.hip, k_bwd_tree)
   if (t < nfill) reinterpret_cast<unsigned long long*>(x)[fill[t]] = empty;
   if (P.vi && part != 2) {
     const int pos = t / 324, e = t - 324 * pos;

@@ -333,7 +333,7 @@ struct FrontTables {
   // leaves the groups of levels whose backward substitution runs as one launch (tree_levels / tree_top0) and the solution indices of their
   // fronts' own unknowns (h_tree_fill)
   void backward_groups() {
-    // bottom levels (k_panel.hip: k_bwd_tree): while a level's fronts hold at most two interior tiles
+    // bottom levels (k_bwd.hip: k_bwd_tree): while a level's fronts hold at most two interior tiles
     int ls = 0;
     const int lmax = std::min(std::min(nlev, Hs), kBwdTreeMax);
     while (ls < lmax && dev.lev[ls].n > 0 && dev.lev[ls].n <= 65535 && (dev.lev[ls].own_max + kTile - 1) / kTile <= 2) ++ls;

@@ -483,7 +483,7 @@ static int solve_impl_dev(covgpu_context* c, const covgpu_options* opt, covgpu_r
 int solve_any(covgpu_context* c, const covgpu_options* opt, covgpu_result* out) {
   int rc = solve_impl_dev(c, opt, out);
   if (rc == COVGPU_ERR_GATE_TIMEOUT) {
-    if (c->chol.gate_dead_h[1] == -2)   // (k_panel.hip: pipe_take)
+    if (c->chol.gate_dead_h[1] == -2)   // (k_bwd.hip: pipe_take)
       std::fprintf(stderr, "[covgpu] warning: a hand-over inside the pipelined backward substitution timed out (workgroup %d of front %d of its level); repeating the solve with a launch per tile and HIP events (this context keeps them)\n",
                    c->chol.gate_dead_h[2], c->chol.gate_dead_h[3]);
     else

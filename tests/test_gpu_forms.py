@@ -1,6 +1,6 @@
 """Every kernel form of the multifrontal solve, at small sizes, against host solvers.
 
-Which kernel a launch of the multifrontal FP64 Cholesky takes (k_chol.hip, k_panel.hip, k_front.hip) is decided by the shape of the fronts: the
+Which kernel a launch of the multifrontal FP64 Cholesky takes (k_chol.hip, k_panel.hip, k_bwd.hip, k_front.hip) is decided by the shape of the fronts: the
 four-wave panel factorisation by the number of small fronts in a level, the width of k_trsm_sub4 by the real columns of a panel, full tiles or
 quadrants by the length of a tile list, the backward substitution by the interior tiles of a level, ... The default plans of the small maps reach
 few of them. Here ONE context runs a sweep of plan shapes (tests/forms_util.SWEEP: maps x leaf sizes x the two cuts of three agents; the host half

@@ -1,4 +1,4 @@
-// panel_probe.hip — correctness + phase timing of the 256-column panel chain kernels (k_panel.hip) on an idle GPU (dev tool):
+// panel_probe.hip — correctness + phase timing of the 256-column panel chain kernels (k_panel.hip, k_bwd.hip) on an idle GPU (dev tool):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DCOVGPU_PROBE tools/panel_probe.hip -o /tmp/panel_probe && /tmp/panel_probe
 // Checks k_potrf_panel (nb = 16 and 8, batched, with the right-hand side riding along), k_trsm_sub4<16|8> and
 // k_bwd_step_sub against a host Cholesky in double precision.
@@ -8,6 +8,7 @@
 #include <random>
 #include <vector>
 #include "../covins_amd/csrc/k_panel.hip"
+#include "../covins_amd/csrc/k_bwd.hip"
 
 using namespace covgpu;
 

@@ -4,7 +4,8 @@
 #include <cstdio>
 #include <vector>
 #include "../covins_amd/csrc/k_chol.hip"
-#include "../covins_amd/csrc/k_panel.hip"  // (k_chol.hip schedules its kernels)
+#include "../covins_amd/csrc/k_panel.hip"  // (k_chol.hip schedules its kernels
+#include "../covins_amd/csrc/k_bwd.hip"    //  and these)
 
 using namespace covgpu;
 
