@@ -162,6 +162,29 @@ def relative_pose_covariance(cov12, pose_i, pose_j):
     return 0.5 * (out + out.T)
 
 
+def selinv_limits():
+    """Host-only: {mfma_rows, panel_cols, block_rows} of Context.keyframe_covariances as the library was built (covgpu_selinv_limits)."""
+    out = (C.c_int32 * 4)()
+    lib().covgpu_selinv_limits(out)
+    return dict(zip(("mfma_rows", "panel_cols", "block_rows"), (int(v) for v in out)))
+
+
+def relative_pose_covariances(kf_cov, pair_cov, pairs, poses, pair_ok=None):
+    """Host-only: relative_pose_covariance of every served pair of Context.keyframe_covariances(.., block="pose", pairs=pairs): [P, 6, 6]
+    from the diagonal blocks kf_cov [K, 6, 6], the cross blocks pair_cov [P, 6, 6] (rows of i, columns of j) and the poses [K, 7]. A pair
+    that was not served (pair_ok[q] == 0) gives a block of NaN."""
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    out = np.full((len(pairs), 6, 6), np.nan)
+    for q, (i, j) in enumerate(pairs):
+        if pair_ok is not None and not pair_ok[q]:
+            continue
+        c = np.empty((12, 12))
+        c[:6, :6] = kf_cov[i][:6, :6]; c[6:, 6:] = kf_cov[j][:6, :6]
+        c[:6, 6:] = pair_cov[q][:6, :6]; c[6:, :6] = pair_cov[q][:6, :6].T
+        out[q] = relative_pose_covariance(c, poses[i], poses[j])
+    return out
+
+
 def kernel_form_names():
     """Names of the kernel forms Context.kernel_forms() counts, in the library's order."""
     n = lib().covgpu_get_kernel_forms(None, None, 0)
@@ -1011,6 +1034,43 @@ class Context:
         s, cov, stats, keep = self._marginal(kfs, block, mu, D)
         self._check(lib().covgpu_marginal_resident(self._h, C.byref(opt), C.byref(s)))
         return cov, dict(zip(capi.MARGINAL_STATS, (int(v) for v in stats)))
+
+    @staticmethod
+    def _selinv(K, D, block, mu, pairs):
+        """(Selinv, kf_cov, pair_cov, pair_ok, stats, keep-alive) of one selected-inverse call on K keyframes of D unknowns each."""
+        if block not in ("pose", "full"):
+            raise ValueError('block must be "pose" or "full"')
+        d = D if block == "full" else 6
+        pr = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        pi, pj = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        kf_cov = np.zeros((K, d, d)); pair_cov = np.zeros((len(pr), d, d)); ok = np.zeros(len(pr), np.uint8); stats = np.zeros(8, np.int64)
+        s = capi.Selinv()
+        s.block = 1 if block == "full" else 0; s.mu = float(mu); s.kf_cov = dptr(kf_cov); s.num_pairs = len(pr)
+        if len(pr):
+            s.pair_i = iptr(pi); s.pair_j = iptr(pj); s.pair_cov = dptr(pair_cov); s.pair_ok = ok.ctypes.data_as(capi._bp)
+        s.stats = stats.ctypes.data_as(capi._lp)
+        return s, kf_cov, pair_cov, ok, stats, (pi, pj)
+
+    def keyframe_covariances(self, prob, opt, block="pose", mu=0.0, pairs=None, pgo=False):
+        """Covariance of EVERY keyframe at the estimate in `prob`, and the cross blocks of the keyframe pairs `pairs` ([P, 2] problem indices)
+        that lie on the structure of the factor: the diagonal blocks, and the requested off-diagonal ones, of the inverse of the reduced
+        camera system at damping mu (covgpu_selected_inverse). block "pose": 6 rows per keyframe; "full": all 15 of a
+        visual-inertial problem. Returns (kf_cov [K, d, d] — zeros for a constant pose, pair_cov [P, d, d] = Sigma[rows of i][columns of j],
+        pair_ok [P] uint8 — 0: not stored, block zeroed, stats dict)."""
+        D = 6 if (pgo or opt.visual_only) else 15
+        s, kf_cov, pair_cov, ok, stats, keep = self._selinv(prob.K, D, block, mu, pairs)
+        ps = prob.as_struct()
+        self._keep = prob; self._keep_pgo = bool(pgo)
+        self._check(lib().covgpu_selected_inverse(self._h, C.byref(opt), C.byref(ps), 1 if pgo else 0, C.byref(s)))
+        return kf_cov, pair_cov, ok, dict(zip(capi.SELINV_STATS, (int(v) for v in stats)))
+
+    def keyframe_covariances_resident(self, opt, block="pose", mu=0.0, pairs=None):
+        """The same at the estimate the context holds (what download() returns), after upload() or a finished solve_resident()."""
+        D = 6 if (self._keep_pgo or opt.visual_only) else 15
+        K = self._keep.K if self._keep is not None else 1   # (nothing uploaded: the call refuses before it writes)
+        s, kf_cov, pair_cov, ok, stats, keep = self._selinv(K, D, block, mu, pairs)
+        self._check(lib().covgpu_selected_inverse_resident(self._h, C.byref(opt), C.byref(s)))
+        return kf_cov, pair_cov, ok, dict(zip(capi.SELINV_STATS, (int(v) for v in stats)))
 
     def solve_resident_traced(self, opt: Options, capacity: int = 64):
         """solve_resident that also returns the trust-region state at the end of every iteration, retry rounds included: (Result, trace

@@ -363,6 +363,15 @@ class Marginal(C.Structure):
 MARGINAL_STATS = ("columns", "fronts", "launches", "mfma_launches", "vector_launches", "scratch_bytes", "reserved6", "reserved7")
 
 
+class Selinv(C.Structure):
+    """covgpu_selinv_t (include/covgpu.h): covariance of every keyframe by selected inversion of the factor, DESIGN.md §4.20."""
+    _fields_ = [("block", C.c_int32), ("mu", C.c_double), ("kf_cov", _dp), ("num_pairs", C.c_int64), ("pair_i", _ip), ("pair_j", _ip),
+                ("pair_cov", _dp), ("pair_ok", _bp), ("stats", _lp)]
+
+
+SELINV_STATS = ("fronts", "levels", "launches", "mfma_launches", "vector_launches", "scratch_bytes", "pairs_served", "reserved7")
+
+
 PRUNE_ERASED, PRUNE_TIME_GATE, PRUNE_LOOP_KF, PRUNE_NOT_ERASE = 0, 1, 2, 3                       # round_action
 PRUNE_STOP_NO_CANDIDATES, PRUNE_STOP_THRESHOLD, PRUNE_STOP_MAX_KFS, PRUNE_STOP_MAX_ROUNDS = 0, 1, 2, 3   # stop_reason
 
@@ -447,6 +456,10 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("marginal_check", [PP, OP, C.POINTER(Marginal)])
         d("marginal_covariance", [C.c_void_p, OP, PP, C.c_int32, C.POINTER(Marginal)])
         d("marginal_resident", [C.c_void_p, OP, C.POINTER(Marginal)])
+        d("selinv_limits", [_ip], None)
+        d("selinv_check", [PP, OP, C.POINTER(Selinv)])
+        d("selected_inverse", [C.c_void_p, OP, PP, C.c_int32, C.POINTER(Selinv)])
+        d("selected_inverse_resident", [C.c_void_p, OP, C.POINTER(Selinv)])
         d("outlier_pass", [C.c_void_p, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])
         d("covisibility", [C.c_void_p, C.c_int32, C.c_int64, _ip, _ip, _ip, C.POINTER(C.c_int64)])
         d("gba_solve_multi", [OP, PP, RP, C.c_int32, _ip, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])

@@ -1061,6 +1061,42 @@ int covgpu_marginal_covariance(covgpu_context*, const covgpu_options*, const cov
  * covgpu_solve_resident returns the bits it would have returned without this call: every solve restarts from the uploaded estimate. */
 int covgpu_marginal_resident(covgpu_context*, const covgpu_options*, const covgpu_marginal_t*);
 
+/* ---- Covariance of every keyframe by selected inversion of the multifrontal factor ----
+ *
+ * Sigma = S^-1 on the structure of L (S = L L^T the matrix covgpu_schur / covgpu_schur_pgo return at the same mu; conventions as the
+ * marginal call above): the Takahashi recursion from the root of the elimination tree down. For a front with own unknowns O and border B
+ *   Sigma_BO = -Sigma_BB T,  Sigma_OO = W^T W - T^T Sigma_BO   with W = L_OO^-1, T = L_BO W,
+ * Sigma_BB gathered from the finished square of the deepest owner among the border rows (k_selinv.hip). The diagonal block of every
+ * keyframe is read out of it, and the cross block of every requested pair that lies on the structure of L: with block 0 every pair whose
+ * pose blocks are coupled in S (covisible pairs, IMU neighbours, loop edges), with block 1 every pair joined by an IMU factor; any other
+ * pair is served when the tree happens to hold it, else pair_ok = 0 and its block is zeroed (take it from covgpu_marginal_covariance).
+ * Refused with COVGPU_ERR_INVALID_ARG: block outside {0, 1}, mu negative or not finite, a NULL kf_cov, a negative num_pairs,
+ * num_pairs > 0 with a NULL pair array, a pair index out of range, equal indices, a keyframe with a constant pose in a pair; a sharded
+ * context; a context whose pose graph is off the elimination tree (COVGPU_PGO_ND=0). A non-positive pivot is COVGPU_ERR_NUMERIC, a
+ * scratch allocation that fails COVGPU_ERR_OUT_OF_MEMORY (nothing of the sweep is enqueued, the context stays usable).
+ * Scratch (stats[5]): two buffers laid out like the fronts (Sigma, and W / T of the level at work) and the tables. The factor is only read. */
+#define COVGPU_SELINV_MFMA_ROWS 128             /* a front with this many rows (own + border) or more takes the matrix-core form */
+typedef struct covgpu_selinv_t {
+  int32_t block;         /* 0: pose rows (d = 6); 1: all D rows of a keyframe, as covgpu_marginal_t::block */
+  double  mu;            /* >= 0, finite */
+  double* kf_cov;        /* out [K][d][d] row-major: diagonal block of every keyframe; a constant-pose keyframe: zeros */
+  int64_t num_pairs;     /* may be 0 */
+  const int32_t *pair_i, *pair_j;   /* [num_pairs] keyframe indices, i != j, both free */
+  double* pair_cov;      /* out [num_pairs][d][d]: Sigma[rows of i][columns of j] */
+  uint8_t* pair_ok;      /* out [num_pairs]: 1 = every requested sub-block lies on the structure of L; 0 = not stored, block zeroed */
+  int64_t* stats;        /* out [8], may be NULL: fronts, levels, launches, launches of the matrix-core form, of the vector form,
+                          * bytes of scratch, pairs served, 0 */
+} covgpu_selinv_t;
+/* {COVGPU_SELINV_MFMA_ROWS, own columns of a panel (128), rows of a block step (16), 0} as the library was built */
+void covgpu_selinv_limits(int32_t out[4]);
+/* The argument checks of covgpu_selected_inverse alone (no context, no device): COVGPU_OK or COVGPU_ERR_INVALID_ARG with the message. */
+int covgpu_selinv_check(const covgpu_problem*, const covgpu_options*, const covgpu_selinv_t*);
+/* Uploads `p` as covgpu_gn_step does (pgo != 0: as covgpu_upload_pgo), linearises at its estimate, builds and factors at mu, sweeps. */
+int covgpu_selected_inverse(covgpu_context*, const covgpu_options*, const covgpu_problem*, int32_t pgo, const covgpu_selinv_t*);
+/* The same at the estimate the context holds, after an upload or a finished solve. A following covgpu_solve_resident returns the bits
+ * it would have returned without this call. */
+int covgpu_selected_inverse_resident(covgpu_context*, const covgpu_options*, const covgpu_selinv_t*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -700,6 +700,45 @@ class OptimizationT {
     if (covgpu_marginal_covariance(Context(), &o, &p, 0, &mg) != COVGPU_OK) throw std::runtime_error(covgpu_last_error());
     return cov;
   }
+  // Covariance of EVERY keyframe of the map in one call, and the cross blocks of the keyframe pairs `pairs` that lie on the structure of the
+  // factor (covgpu_selected_inverse): covisible pairs, IMU neighbours and loop edges always do with the pose rows, IMU
+  // neighbours with the full state. Same problem, tangent, d and mu as MarginalCovariance. kf: per keyframe id its [d][d] block (a keyframe
+  // with a constant pose: zeros); pair: per entry of `pairs` its [d][d] block Sigma[rows of first][columns of second], zeroed where
+  // pair_ok is 0 (such a pair comes from MarginalCovariance). stats: covgpu_selinv_t::stats.
+  struct KeyframeCovarianceSet {
+    int d = 6;
+    std::map<idpair, std::vector<double>> kf;
+    std::vector<std::vector<double>> pair;
+    std::vector<uint8_t> pair_ok;
+    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  };
+  static KeyframeCovarianceSet KeyframeCovariances(const MapPtr& map, bool visual_only = false, bool full_state = false, double mu = 0.0,
+                                                   const std::vector<std::pair<idpair, idpair>>& pairs = {}) {
+    detail::Flat f; Index ix;
+    FlattenGBA(map, visual_only, true, f, ix);
+    std::map<idpair, int32_t> row;
+    for (size_t k = 0; k < ix.kfs.size(); ++k) row[ix.kfs[k]->id_] = (int32_t)k;
+    std::vector<int32_t> pi, pj;
+    for (const auto& pr : pairs) {
+      auto a = row.find(pr.first), b = row.find(pr.second);
+      if (a == row.end() || b == row.end()) throw std::invalid_argument("KeyframeCovariances: keyframe not in the problem");
+      pi.push_back(a->second); pj.push_back(b->second);
+    }
+    KeyframeCovarianceSet out;
+    out.d = (full_state && !visual_only) ? 15 : 6;
+    const size_t dd = (size_t)out.d * out.d, K = ix.kfs.size();
+    std::vector<double> kc(K * dd), pc(pairs.size() * dd);
+    out.pair_ok.assign(pairs.size(), 0);
+    covgpu_selinv_t s;
+    s.block = full_state ? 1 : 0; s.mu = mu; s.kf_cov = kc.data(); s.num_pairs = (int64_t)pairs.size();
+    s.pair_i = pi.data(); s.pair_j = pj.data(); s.pair_cov = pc.data(); s.pair_ok = out.pair_ok.data(); s.stats = out.stats;
+    covgpu_problem p = f.view();
+    covgpu_options o = Options(1, visual_only);
+    if (covgpu_selected_inverse(Context(), &o, &p, 0, &s) != COVGPU_OK) throw std::runtime_error(covgpu_last_error());
+    for (size_t k = 0; k < K; ++k) out.kf[ix.kfs[k]->id_] = std::vector<double>(kc.begin() + k * dd, kc.begin() + (k + 1) * dd);
+    for (size_t q = 0; q < pairs.size(); ++q) out.pair.emplace_back(pc.begin() + q * dd, pc.begin() + (q + 1) * dd);
+    return out;
+  }
   // Covariance of the relative pose T_s1_s2 of two keyframes from their joint pose covariance cov12 ([12][12]: MarginalCovariance(map, {id1,
   // id2})): J cov12 J^T with J the 6x12 Jacobian of the between residual (R7) at zero residual and unit weight — [6][6] row-major, rotation
   // first and translation second, the order of LoopConstraint::cov_mat.
