@@ -162,6 +162,13 @@ def relative_pose_covariance(cov12, pose_i, pose_j):
     return 0.5 * (out + out.T)
 
 
+def lmcov_limits():
+    """Host-only: {max_group, threads, block_doubles} of Context.landmark_covariances as the library was built (covgpu_lmcov_limits)."""
+    out = (C.c_int32 * 4)()
+    lib().covgpu_lmcov_limits(out)
+    return dict(max_group=int(out[0]), threads=int(out[1]), block_doubles=int(out[2]))
+
+
 def selinv_limits():
     """Host-only: {mfma_rows, panel_cols, block_rows} of Context.keyframe_covariances as the library was built (covgpu_selinv_limits)."""
     out = (C.c_int32 * 4)()
@@ -433,6 +440,7 @@ class Context:
         if kf_fixed_round2 is not None:
             fx = np.ascontiguousarray(kf_fixed_round2, np.uint8)
             tr.kf_fixed_round2 = fx.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._keep = prob; self._keep_pgo = False   # (the resident problem: prob's keyframes, the second round's observation set)
         self._check(lib().covgpu_gba_two_round(self._h, C.byref(opt), C.byref(s), C.byref(tr), erase.ctypes.data_as(capi._bp), iptr(left), cnt,
                                                C.byref(r1), C.byref(r2)))
         return q, r1, r2, erase[:prob.O].astype(bool), left[:prob.L], (int(cnt[0]), int(cnt[1]))
@@ -1071,6 +1079,40 @@ class Context:
         s, kf_cov, pair_cov, ok, stats, keep = self._selinv(K, D, block, mu, pairs)
         self._check(lib().covgpu_selected_inverse_resident(self._h, C.byref(opt), C.byref(s)))
         return kf_cov, pair_cov, ok, dict(zip(capi.SELINV_STATS, (int(v) for v in stats)))
+
+    @staticmethod
+    def _lmcov(L, K, mu, want_kf):
+        """(Lmcov, lm_cov, lm_ok, kf_cov or None, stats) of one landmark-covariance call on L landmarks and K keyframes."""
+        lm_cov = np.zeros((max(L, 1), 3, 3)); ok = np.zeros(max(L, 1), np.uint8); stats = np.zeros(8, np.int64)
+        kf_cov = np.zeros((K, 6, 6)) if want_kf else None
+        s = capi.Lmcov()
+        s.mu = float(mu); s.lm_cov = dptr(lm_cov); s.lm_ok = ok.ctypes.data_as(capi._bp)
+        if want_kf:
+            s.kf_cov = dptr(kf_cov)
+        s.stats = stats.ctypes.data_as(capi._lp)
+        return s, lm_cov, ok, kf_cov, stats
+
+    def landmark_covariances(self, prob, opt, mu=0.0, want_kf=False):
+        """Covariance of EVERY landmark at the estimate in `prob`: the 3x3 diagonal blocks, at the landmarks, of the inverse of the whole
+        system (poses, speed-biases, landmarks) at damping mu, from the selected inverse of the reduced camera system
+        (covgpu_landmark_covariance). Returns (lm_cov [L, 3, 3] world frame, lm_ok [L] uint8 — 0: H_ll not positive
+        definite, block zeroed, kf_cov [K, 6, 6] as keyframe_covariances(block="pose") or None, stats dict)."""
+        s, lm_cov, ok, kf_cov, stats = self._lmcov(prob.L, prob.K, mu, want_kf)
+        ps = prob.as_struct()
+        self._keep = prob; self._keep_pgo = False
+        self._check(lib().covgpu_landmark_covariance(self._h, C.byref(opt), C.byref(ps), C.byref(s)))
+        return lm_cov[:prob.L], ok[:prob.L], kf_cov, dict(zip(capi.LMCOV_STATS, (int(v) for v in stats)))
+
+    def landmark_covariances_resident(self, opt, mu=0.0, want_kf=False, num_lm=None):
+        """The same at the estimate and the observation set the context holds, after upload() or a finished solve. num_lm: the landmarks
+        of the resident observation set when it is not the uploaded one — after gba_two_round the landmarks with lm_left >= 2, in order."""
+        K = self._keep.K if self._keep is not None else 1   # (nothing uploaded: the call refuses before it writes)
+        L0 = self._keep.L if self._keep is not None else 1
+        L = int(num_lm) if num_lm is not None else L0
+        # (the library writes the resident set's landmarks, whatever num_lm says: never more than the uploaded problem's, so the buffers hold those)
+        s, lm_cov, ok, kf_cov, stats = self._lmcov(max(L, L0), K, mu, want_kf)
+        self._check(lib().covgpu_landmark_covariance_resident(self._h, C.byref(opt), C.byref(s)))
+        return lm_cov[:L], ok[:L], kf_cov, dict(zip(capi.LMCOV_STATS, (int(v) for v in stats)))
 
     def solve_resident_traced(self, opt: Options, capacity: int = 64):
         """solve_resident that also returns the trust-region state at the end of every iteration, retry rounds included: (Result, trace

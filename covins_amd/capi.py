@@ -372,6 +372,14 @@ class Selinv(C.Structure):
 SELINV_STATS = ("fronts", "levels", "launches", "mfma_launches", "vector_launches", "scratch_bytes", "pairs_served", "reserved7")
 
 
+class Lmcov(C.Structure):
+    """covgpu_lmcov_t (include/covgpu.h): covariance of every landmark from the selected inverse of the factor, DESIGN.md §4.21."""
+    _fields_ = [("mu", C.c_double), ("lm_cov", _dp), ("lm_ok", _bp), ("kf_cov", _dp), ("stats", _lp)]
+
+
+LMCOV_STATS = ("fronts", "levels", "sweep_launches", "landmark_launches", "group_width", "scratch_bytes", "pairs_resolved", "landmarks_not_ok")
+
+
 PRUNE_ERASED, PRUNE_TIME_GATE, PRUNE_LOOP_KF, PRUNE_NOT_ERASE = 0, 1, 2, 3                       # round_action
 PRUNE_STOP_NO_CANDIDATES, PRUNE_STOP_THRESHOLD, PRUNE_STOP_MAX_KFS, PRUNE_STOP_MAX_ROUNDS = 0, 1, 2, 3   # stop_reason
 
@@ -460,6 +468,10 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("selinv_check", [PP, OP, C.POINTER(Selinv)])
         d("selected_inverse", [C.c_void_p, OP, PP, C.c_int32, C.POINTER(Selinv)])
         d("selected_inverse_resident", [C.c_void_p, OP, C.POINTER(Selinv)])
+        d("lmcov_limits", [_ip], None)
+        d("lmcov_check", [PP, OP, C.POINTER(Lmcov)])
+        d("landmark_covariance", [C.c_void_p, OP, PP, C.POINTER(Lmcov)])
+        d("landmark_covariance_resident", [C.c_void_p, OP, C.POINTER(Lmcov)])
         d("outlier_pass", [C.c_void_p, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])
         d("covisibility", [C.c_void_p, C.c_int32, C.c_int64, _ip, _ip, _ip, C.POINTER(C.c_int64)])
         d("gba_solve_multi", [OP, PP, RP, C.c_int32, _ip, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])

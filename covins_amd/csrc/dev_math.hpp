@@ -126,6 +126,14 @@ COV_DEV double wave_sum(double v) {
   return v;
 }
 
+// sum over the G-lane group of the landmark-major kernels (k_visual.hip, k_lmcov.hip), result valid in every lane of the group
+template <int G>
+COV_DEV double group_sum(double v) {
+#pragma unroll
+  for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, G);
+  return v;
+}
+
 // R5 distortion of the normalised image point m = (x, y): RadTan or Equidistant, d = d(x', y') / d(x, y). The same arithmetic as inside
 // project_point, which keeps its own copy so that the pinhole kernels compile to the code they had before the unified model existed.
 COV_DEV void distort(double x, double y, const double* dist, int dist_type, double& xd, double& yd, double& dxx, double& dxy, double& dyx,

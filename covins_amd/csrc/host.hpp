@@ -60,6 +60,9 @@ struct covgpu_context {
   hipStream_t st = nullptr;
   covgpu::DevProblem P;
   bool have = false, pgo = false;
+  bool second_round = false; // a covgpu_gba_two_round that succeeded left the SECOND round's problem resident (compacted landmark / observation indexing) while
+                             // `have` is false for every call that scatters into the caller's first-round arrays; a call whose outputs are in the resident
+                             // indexing (covgpu_landmark_covariance_resident) may still use it. Cleared by the next upload.
   bool state_set = false;    // the working estimate (P.pose, P.sb, P.lm) holds the uploaded one or a solve's result (reset_state; cleared by an upload)
   std::vector<void*> allocs;
   size_t alloc_bytes = 0;  // device bytes behind `allocs` (the footprint covgpu_get_layout reports)

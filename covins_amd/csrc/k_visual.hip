@@ -43,13 +43,6 @@ COV_DEV void group_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
-template <int G>
-COV_DEV double group_sum(double v) {
-#pragma unroll
-  for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, G);
-  return v;
-}
-
 // symmetric 3x3 inverse; h = xx xy xz yy yz zz
 COV_DEV void inv3sym(const double* h, double* o) {
   const double c00 = h[3] * h[5] - h[4] * h[4], c01 = h[2] * h[4] - h[1] * h[5], c02 = h[1] * h[4] - h[2] * h[3];

@@ -2,7 +2,8 @@
 // k_selinv.hip. A call linearises, builds and factors through the product's own enqueue_build / enqueue_solve (as covgpu_marginal_covariance
 // does), plans the sweep on the host from the front tables the upload left in NdDev — every front's ancestor, the map of its border rows into
 // the ancestor's square, the steps per level, where every requested block lies — and runs it on the context's stream behind the solve. It
-// reads the factor and writes only its own scratch; nothing is kept per upload.
+// reads the factor and writes only its own scratch; nothing is kept per upload. A call is two named steps: sel_factor_and_sweep leaves Sigma in
+// the scratch (covgpu_landmark_covariance, lmcov.hip, starts with the same step), the read-out copies the requested entries out of it.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -13,28 +14,55 @@
 
 using namespace covgpu;
 
+static int bad_arg(const char* fn, const std::string& m) { g_err = std::string(fn) + ": " + m; return COVGPU_ERR_INVALID_ARG; }
+
+namespace covgpu {
+
+// The rule of the read-out, per pair of variables (the pose rows 0 .. 5 and the speed-bias rows 6 .. 14 of a keyframe may have different
+// owners): the block lies in the square of whichever of the two owners is lower in the tree, if the other variable is in its border.
+bool sel_want(const SelPlan& pl, int grow, int nrow, int gcol, int ncol, int sym, size_t out, std::vector<SelReq>& reqs) {
+  const int fa = pl.gnode[grow], fb = pl.gnode[gcol];
+  if (fa < 0 || fb < 0) return false;
+  if (fa != fb && pl.lev_of[fa] == pl.lev_of[fb]) return false;
+  reqs.push_back(SelReq{pl.lev_of[fa] <= pl.lev_of[fb] ? fa : fb, grow, nrow, gcol, ncol, sym, out, -1, 0});
+  return true;
+}
+
+// A variable's rows are contiguous in a front (nd_tables lays a front out variable by variable), which the resolution checks. The position of
+// a solution index in the square of front p goes through one scratch array that is filled and cleared per front.
+const char* sel_locate(const covgpu_context* c, const SelPlan& pl, std::vector<SelReq>& reqs) {
+  const NdDev& nd = c->nd;
+  std::vector<int> pos((size_t)c->P.n, -1);
+  auto fill = [&](int p, bool on) {
+    for (int t = 0; t < nd.h_own_dims[p]; ++t) pos[nd.h_gidx[nd.h_own_g[p] + t]] = on ? t : -1;
+    for (int t = 0; t < nd.h_st_dims[p]; ++t) pos[nd.h_gidx[nd.h_st_g[p] + t]] = on ? pl.fronts[p].nI + t : -1;
+  };
+  std::stable_sort(reqs.begin(), reqs.end(), [](const SelReq& a, const SelReq& b) { return a.front < b.front; });
+  for (size_t i = 0; i < reqs.size();) {
+    const int p = reqs[i].front;
+    const SelFront& f = pl.fronts[p];
+    fill(p, true);
+    for (; i < reqs.size() && reqs[i].front == p; ++i) {
+      SelReq& R = reqs[i];
+      const int r0 = pos[R.grow], q0 = pos[R.gcol];
+      if (r0 < 0 || q0 < 0) continue;
+      if (pos[R.grow + R.nrow - 1] != r0 + R.nrow - 1 || pos[R.gcol + R.ncol - 1] != q0 + R.ncol - 1) { fill(p, false); return "the rows of a variable are not contiguous in a front"; }
+      R.off = f.moff + (long long)r0 * f.ld + q0; R.ld = f.ld;
+    }
+    fill(p, false);
+  }
+  return nullptr;
+}
+
 namespace {
-
-struct SelLaunch { int first, count, kind; };   // kind 0: gather | 1 .. 4: matrix-core form | 5: vector form
-struct SelPlan {
-  int d = 0;
-  std::vector<SelFront> fronts;      // front order of NdDev (level order, leaves first)
-  std::vector<int> gmap;
-  std::vector<int4> items;
-  std::vector<SelLaunch> launches;   // stream order: root level first
-  std::vector<long long> src;        // [K d d | num_pairs d d] element of Sigma behind every output entry (-1: zero)
-  std::vector<uint8_t> pair_ok;
-  long long served = 0;
-};
-
 // Everything comes from the host tables of the upload: the own / border solution indices of every front (h_gidx) say who owns a border row;
 // the deepest owner among a front's border rows is its ancestor p, and struct(f) \ own(p) must lie in struct(p) (the fill property).
-const char* sel_plan(const covgpu_context* c, const covgpu_selinv_t* rq, const uint8_t* fixed, SelPlan& pl) {
+const char* sel_plan_tree(const covgpu_context* c, SelPlan& pl) {
   const NdDev& nd = c->nd;
   const DevProblem& P = c->P;
-  const int D = P.D, d = rq->block ? D : 6, nn = nd.nnodes, K = P.K;
-  pl.d = d;
-  std::vector<int> gnode((size_t)P.n, -1), goff((size_t)P.n, 0), lev_of(nn, 0);
+  const int nn = nd.nnodes;
+  std::vector<int>& gnode = pl.gnode; std::vector<int>& goff = pl.goff; std::vector<int>& lev_of = pl.lev_of;
+  gnode.assign((size_t)P.n, -1); goff.assign((size_t)P.n, 0); lev_of.assign(nn, 0);
   for (int i = 0; i < nn; ++i)
     for (int t = 0; t < nd.h_own_dims[i]; ++t) { const int g = nd.h_gidx[nd.h_own_g[i] + t]; gnode[g] = i; goff[g] = t; }
   for (size_t l = 0; l < nd.lev.size(); ++l) for (int k = 0; k < nd.lev[l].n; ++k) lev_of[nd.lev[l].first + k] = (int)l;
@@ -102,22 +130,24 @@ const char* sel_plan(const covgpu_context* c, const covgpu_selinv_t* rq, const u
       if (count > 0) pl.launches.push_back(SelLaunch{first, count, kind});
     }
   }
-  // read-out, per pair of variables (the pose rows 0 .. 5 and the speed-bias rows 6 .. 14 of a keyframe may have different owners): the
-  // block lies in the square of whichever of the two owners is lower in the tree, if the other variable is in its border. A variable's
-  // rows are contiguous in a front (nd_tables lays a front out variable by variable), which the resolution checks.
+  return nullptr;
+}
+}  // namespace
+
+// read-out of the keyframes' diagonal blocks and of the requested pairs, per pair of variables
+const char* sel_plan_readout(const covgpu_context* c, const covgpu_selinv_t* rq, const uint8_t* fixed, SelPlan& pl) {
+  const DevProblem& P = c->P;
+  const int D = P.D, d = rq->block ? D : 6, K = P.K;
+  pl.d = d;
   const int64_t np = rq->num_pairs;
   const size_t dd = (size_t)d * d;
   pl.src.assign(((size_t)K + (size_t)np) * dd, -1);
   pl.pair_ok.assign((size_t)np, 1);
-  struct Req { int front, grow, nrow, gcol, ncol, sym; size_t out; };   // sym: a diagonal block's part, stored at both places
-  std::vector<Req> reqs;
+  pl.served = 0;
+  std::vector<SelReq> reqs;   // sym: a diagonal block's part, stored at both places
   const int nparts = d > 6 ? 2 : 1, part0[2] = {0, 6}, partn[2] = {6, d - 6};
   auto want = [&](int ki, int a, int kj, int b, int sym, size_t base) -> bool {
-    const int ga = D * ki + part0[a], gb = D * kj + part0[b], fa = gnode[ga], fb = gnode[gb];
-    if (fa < 0 || fb < 0) return false;
-    if (fa != fb && lev_of[fa] == lev_of[fb]) return false;
-    reqs.push_back(Req{lev_of[fa] <= lev_of[fb] ? fa : fb, ga, partn[a], gb, partn[b], sym, base + (size_t)part0[a] * d + part0[b]});
-    return true;
+    return sel_want(pl, D * ki + part0[a], partn[a], D * kj + part0[b], partn[b], sym, base + (size_t)part0[a] * d + part0[b], reqs);
   };
   for (int k = 0; k < K; ++k) {
     if (fixed[k]) continue;
@@ -129,24 +159,15 @@ const char* sel_plan(const covgpu_context* c, const covgpu_selinv_t* rq, const u
     for (int a = 0; a < nparts && pl.pair_ok[e]; ++a)
       for (int b = 0; b < nparts; ++b)
         if (!want(rq->pair_i[e], a, rq->pair_j[e], b, 0, ((size_t)K + (size_t)e) * dd)) { pl.pair_ok[e] = 0; break; }
-  std::stable_sort(reqs.begin(), reqs.end(), [](const Req& a, const Req& b) { return a.front < b.front; });
-  for (size_t i = 0; i < reqs.size();) {
-    const int p = reqs[i].front;
-    const SelFront& f = pl.fronts[p];
-    fill(p, true);
-    for (; i < reqs.size() && reqs[i].front == p; ++i) {
-      const Req& R = reqs[i];
-      const int r0 = pos[R.grow], q0 = pos[R.gcol];
-      if (r0 < 0 || q0 < 0) continue;
-      if (pos[R.grow + R.nrow - 1] != r0 + R.nrow - 1 || pos[R.gcol + R.ncol - 1] != q0 + R.ncol - 1) return "the rows of a variable are not contiguous in a front";
-      for (int r = 0; r < R.nrow; ++r)
-        for (int q = 0; q < (R.sym && R.grow == R.gcol ? r + 1 : R.ncol); ++q) {
-          const long long s = f.moff + (long long)(r0 + r) * f.ld + q0 + q;
-          pl.src[R.out + (size_t)r * d + q] = s;
-          if (R.sym) pl.src[R.out - (size_t)(R.grow - R.gcol) * d + (R.grow - R.gcol) + (size_t)q * d + r] = s;
-        }
-    }
-    fill(p, false);
+  if (const char* e = sel_locate(c, pl, reqs)) return e;
+  for (const SelReq& R : reqs) {
+    if (R.off < 0) continue;
+    for (int r = 0; r < R.nrow; ++r)
+      for (int q = 0; q < (R.sym && R.grow == R.gcol ? r + 1 : R.ncol); ++q) {
+        const long long s = R.off + (long long)r * R.ld + q;
+        pl.src[R.out + (size_t)r * d + q] = s;
+        if (R.sym) pl.src[R.out - (size_t)(R.grow - R.gcol) * d + (R.grow - R.gcol) + (size_t)q * d + r] = s;
+      }
   }
   for (int k = 0; k < K; ++k)
     if (!fixed[k]) for (size_t e = 0; e < dd; ++e) if (pl.src[(size_t)k * dd + e] < 0) return "a diagonal block of a keyframe lies off the structure of L";
@@ -159,10 +180,7 @@ const char* sel_plan(const covgpu_context* c, const covgpu_selinv_t* rq, const u
   return nullptr;
 }
 
-int bad_arg(const char* fn, const std::string& m) { g_err = std::string(fn) + ": " + m; return COVGPU_ERR_INVALID_ARG; }
-
-// the refusals that depend on the context: the sweep reads the fronts of ONE device's elimination tree
-int context_check(const char* fn, const covgpu_context* c) {
+int sel_context_check(const char* fn, const covgpu_context* c) {
   if (c->sharded) return bad_arg(fn, "a sharded context holds one rank's share of the factor");
   if (!c->have) return bad_arg(fn, "no problem uploaded");
   if (!c->P.nd) return bad_arg(fn, "the pose graph of this context is off the elimination tree (COVGPU_PGO_ND=0)");
@@ -170,22 +188,22 @@ int context_check(const char* fn, const covgpu_context* c) {
 }
 
 // plan and scratch first (an allocation that fails leaves nothing enqueued), then linearise at the resident estimate, build and factor at mu
-// (the steps of covgpu_gn_step behind its upload), then the sweep and the read-out
-int factor_and_sweep(const char* fn, covgpu_context* c, const covgpu_selinv_t* rq, const uint8_t* fixed) {
-  SelPlan pl;
-  if (const char* e = sel_plan(c, rq, fixed, pl)) { g_err = std::string(fn) + ": " + e; return COVGPU_ERR_INVALID_ARG; }
-  const size_t mel = c->nd.M_elems, kel = (size_t)c->P.K * pl.d * pl.d, nout = pl.src.size();
-  DeviceScratch U(c->st);
-  SelArgs a;
+// (the steps of covgpu_gn_step behind its upload), then the sweep
+int sel_factor_and_sweep(const char* fn, covgpu_context* c, double mu, DeviceScratch& U, SelSweep& sw, const std::function<int(SelPlan&)>& prepare) {
+  SelPlan& pl = sw.pl;
+  if (const char* e = sel_plan_tree(c, pl)) { g_err = std::string(fn) + ": " + e; return COVGPU_ERR_INVALID_ARG; }
+  const size_t mel = c->nd.M_elems;
+  SelArgs& a = sw.a;
   a.M = c->P.nd_M; a.Linv = c->P.nd_Linv;
-  SelFront* fr = nullptr; int* gmap = nullptr; int4* items = nullptr; long long* src = nullptr; double* out = nullptr;
+  SelFront* fr = nullptr; int* gmap = nullptr; int4* items = nullptr;
   HIPCHK(U.alloc(&a.S, mel)); HIPCHK(U.alloc(&a.X, mel));
   HIPCHK(U.alloc(&fr, pl.fronts.size())); HIPCHK(U.alloc(&gmap, pl.gmap.size())); HIPCHK(U.alloc(&items, pl.items.size()));
-  HIPCHK(U.alloc(&src, nout)); HIPCHK(U.alloc(&out, nout));
   a.fr = fr; a.gmap = gmap; a.items = items;
+  sw.bytes = 2 * mel * sizeof(double) + pl.fronts.size() * sizeof(SelFront) + pl.items.size() * sizeof(int4) + pl.gmap.size() * sizeof(int);
+  RC(prepare(pl));
 
   launch_preintegrate(c->P, c->st);
-  enqueue_build(c, rq->mu);
+  enqueue_build(c, mu);
   enqueue_solve(c, c->P.gn);
   RC(read_scalars(c));
   if (chol_failed(c)) { g_err = std::string(fn) + ": reduced system is not positive definite"; return COVGPU_ERR_NUMERIC; }
@@ -194,13 +212,43 @@ int factor_and_sweep(const char* fn, covgpu_context* c, const covgpu_selinv_t* r
   HIPCHK(hipMemcpyAsync(fr, pl.fronts.data(), pl.fronts.size() * sizeof(SelFront), hipMemcpyHostToDevice, c->st));
   if (!pl.gmap.empty()) HIPCHK(hipMemcpyAsync(gmap, pl.gmap.data(), pl.gmap.size() * sizeof(int), hipMemcpyHostToDevice, c->st));
   HIPCHK(hipMemcpyAsync(items, pl.items.data(), pl.items.size() * sizeof(int4), hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(src, pl.src.data(), nout * sizeof(long long), hipMemcpyHostToDevice, c->st));
-  long long n_mfma = 0, n_vec = 0, n_gather = 0;
   for (const SelLaunch& L : pl.launches) {
-    if (L.kind == 0) { launch_selinv_gather(a, L.first, L.count, c->st); ++n_gather; }
-    else { launch_selinv_step(a, L.first, L.count, L.kind, c->st); ++(L.kind == 5 ? n_vec : n_mfma); }
+    if (L.kind == 0) { launch_selinv_gather(a, L.first, L.count, c->st); ++sw.n_gather; }
+    else { launch_selinv_step(a, L.first, L.count, L.kind, c->st); ++(L.kind == 5 ? sw.n_vec : sw.n_mfma); }
   }
-  launch_selinv_read(a.S, src, out, (long long)nout, c->st);
+  return COVGPU_OK;
+}
+
+int sel_read_out(covgpu_context* c, const SelSweep& sw, long long* src, double* out) {
+  const size_t nout = sw.pl.src.size();
+  HIPCHK(hipMemcpyAsync(src, sw.pl.src.data(), nout * sizeof(long long), hipMemcpyHostToDevice, c->st));
+  launch_selinv_read(sw.a.S, src, out, (long long)nout, c->st);
+  return COVGPU_OK;
+}
+
+int sel_fetch_fixed(covgpu_context* c, std::vector<uint8_t>& fixed) {
+  fixed.assign((size_t)std::max(c->P.K, 1), 0);
+  HIPCHK(hipMemcpy(fixed.data(), c->P.fixed, (size_t)c->P.K, hipMemcpyDeviceToHost));
+  return COVGPU_OK;
+}
+
+}  // namespace covgpu
+
+namespace {
+
+// the two steps of a call: Sigma into the sweep's scratch (with the read-out table planned and allocated before anything is enqueued), the read-out
+int factor_and_sweep(const char* fn, covgpu_context* c, const covgpu_selinv_t* rq, const uint8_t* fixed) {
+  DeviceScratch U(c->st);
+  SelSweep sw;
+  long long* src = nullptr; double* out = nullptr;
+  RC(sel_factor_and_sweep(fn, c, rq->mu, U, sw, [&](SelPlan& pl) -> int {
+    if (const char* e = sel_plan_readout(c, rq, fixed, pl)) { g_err = std::string(fn) + ": " + e; return COVGPU_ERR_INVALID_ARG; }
+    HIPCHK(U.alloc(&src, pl.src.size())); HIPCHK(U.alloc(&out, pl.src.size()));
+    return COVGPU_OK;
+  }));
+  const SelPlan& pl = sw.pl;
+  const size_t kel = (size_t)c->P.K * pl.d * pl.d, nout = pl.src.size();
+  RC(sel_read_out(c, sw, src, out));
   HIPCHK(U.fetch(rq->kf_cov, (const double*)out, kel));
   HIPCHK(U.fetch(rq->pair_cov, (const double*)(out + kel), nout - kel));
   HIPCHK(hipStreamSynchronize(c->st));
@@ -208,17 +256,10 @@ int factor_and_sweep(const char* fn, covgpu_context* c, const covgpu_selinv_t* r
   if (rq->num_pairs > 0) std::memcpy(rq->pair_ok, pl.pair_ok.data(), (size_t)rq->num_pairs);
   if (rq->stats) {
     int64_t* s = rq->stats;
-    s[0] = (int64_t)pl.fronts.size(); s[1] = (int64_t)c->nd.lev.size(); s[2] = n_mfma + n_vec + n_gather + 1; s[3] = n_mfma; s[4] = n_vec;
-    s[5] = (int64_t)((2 * mel + nout) * sizeof(double) + pl.fronts.size() * sizeof(SelFront) + pl.items.size() * sizeof(int4) +
-                     pl.gmap.size() * sizeof(int) + nout * sizeof(long long));
+    s[0] = (int64_t)pl.fronts.size(); s[1] = (int64_t)c->nd.lev.size(); s[2] = sw.n_mfma + sw.n_vec + sw.n_gather + 1; s[3] = sw.n_mfma; s[4] = sw.n_vec;
+    s[5] = (int64_t)(sw.bytes + nout * sizeof(double) + nout * sizeof(long long));
     s[6] = pl.served; s[7] = 0;
   }
-  return COVGPU_OK;
-}
-
-int fetch_fixed(covgpu_context* c, std::vector<uint8_t>& fixed) {
-  fixed.assign((size_t)std::max(c->P.K, 1), 0);
-  HIPCHK(hipMemcpy(fixed.data(), c->P.fixed, (size_t)c->P.K, hipMemcpyDeviceToHost));
   return COVGPU_OK;
 }
 
@@ -227,20 +268,20 @@ int inverse_impl(covgpu_context* c, const covgpu_options* opt, const covgpu_prob
   if (const char* e = selinv_check(p, opt, rq)) return bad_arg(fn, e);
   if (c->sharded) return bad_arg(fn, "a sharded context holds one rank's share of the factor");
   RC(upload_impl(c, opt, p, pgo != 0));
-  RC(context_check(fn, c));
+  RC(sel_context_check(fn, c));
   RC(reset_state(c));
   std::vector<uint8_t> fixed;
-  RC(fetch_fixed(c, fixed));
+  RC(sel_fetch_fixed(c, fixed));
   return factor_and_sweep(fn, c, rq, fixed.data());
 }
 
 int resident_impl(covgpu_context* c, const covgpu_options* opt, const covgpu_selinv_t* rq) {
   const char* fn = "covgpu_selected_inverse_resident";
   if (!opt) return bad_arg(fn, "NULL options");
-  RC(context_check(fn, c));
+  RC(sel_context_check(fn, c));
   HIPCHK(hipSetDevice(c->device));
   std::vector<uint8_t> fixed;
-  RC(fetch_fixed(c, fixed));
+  RC(sel_fetch_fixed(c, fixed));
   if (const char* e = selinv_request_check(c->P.K, fixed.data(), rq)) return bad_arg(fn, e);
   c->P.reproj_loss_a = opt->reproj_loss_a;   // (as every solve of the resident problem takes it)
   if (!c->state_set) RC(reset_state(c));     // an upload alone: the estimate is the uploaded one

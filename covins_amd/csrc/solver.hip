@@ -543,7 +543,7 @@ extern "C" int covgpu_pgo_solve(covgpu_context* c, const covgpu_options* opt, co
 extern "C" int covgpu_gba_two_round(covgpu_context* c, const covgpu_options* opt, covgpu_problem* p, const covgpu_two_round* tr, uint8_t* obs_erase,
                                     int32_t* lm_left, int64_t* counts, covgpu_result* round1, covgpu_result* round2) {
   const int rc = gba_two_round_impl(c, opt, p, tr, obs_erase, lm_left, counts, round1, round2);
-  if (c) { c->have = false; }
+  if (c) { c->second_round = rc == COVGPU_OK && c->have; c->have = false; }
   return rc;
 }
 int gba_two_round_impl(covgpu_context* c, const covgpu_options* opt, covgpu_problem* p, const covgpu_two_round* tr, uint8_t* obs_erase,

@@ -60,7 +60,7 @@ void free_problem(covgpu_context* c) {
   c->allocs.clear();
   c->alloc_bytes = 0;
   c->chol.tri_clear();
-  c->have = false; c->state_set = false;
+  c->have = false; c->second_round = false; c->state_set = false;
   c->pgo_plan.active = false;  // its device buffers were in `allocs`
   c->d_pairkey = nullptr;
   c->nd = NdDev();

@@ -1097,6 +1097,43 @@ int covgpu_selected_inverse(covgpu_context*, const covgpu_options*, const covgpu
  * it would have returned without this call. */
 int covgpu_selected_inverse_resident(covgpu_context*, const covgpu_options*, const covgpu_selinv_t*);
 
+/* ---- Covariance of every landmark from the selected inverse ----
+ *
+ * The 3x3 diagonal block of the inverse of the WHOLE damped system (poses, speed-biases and landmarks) at every landmark, by the Schur
+ * identity on what a build at mu leaves resident: with H_ll^-1 = R R^T and Z_a = (J_p^T J_l) R of observation a (k_visual.hip),
+ *   Sigma_l = H_ll^-1 + H_ll^-1 H_lp Sigma_pp H_pl H_ll^-1 = R (I + sum over a, b of Z_a^T Sigma_ab Z_b) R^T,
+ * a and b the observations of l by keyframes with a free pose, Sigma_ab the 6x6 pose-pose block of the selected inverse above: any two
+ * observers of a landmark are covisible, so the block lies on the structure of L. One landmark-major pass (k_lmcov.hip) behind the sweep
+ * of covgpu_selected_inverse; every sum in one fixed order, no atomics: two calls return the same bits, and lm_cov is symmetric bit for bit.
+ * A landmark no free keyframe observes gets H_ll^-1 = R R^T. A landmark whose damped H_ll the linearisation could not factor (not positive
+ * definite: fewer than three independent rows and mu = 0) gets lm_ok = 0 and a zero block, as does a landmark for which a block of
+ * Sigma between two of its observers was not found (never a block that is too small). The limit of lm_ok: it is the linearisation's own
+ * test (a determinant that is exactly zero, a pivot that is not positive). An H_ll that is rank deficient only up to rounding — two
+ * observations on nearly one ray, mu = 0 — can pass it and come back with lm_ok = 1 and a huge, meaningless block: judge such a landmark
+ * by the size of its block, or run at a small mu > 0.
+ * Refused with COVGPU_ERR_INVALID_ARG: a NULL lm_cov or lm_ok, mu negative or not finite, a problem without landmarks; a context that
+ * holds a pose graph; a sharded context; nothing uploaded (resident form). A non-positive pivot of the reduced system is
+ * COVGPU_ERR_NUMERIC, a scratch allocation that fails COVGPU_ERR_OUT_OF_MEMORY (nothing is enqueued, the context stays usable).
+ * Scratch (stats[5]): the sweep's two buffers and tables, 16 bytes per covisible pair and per keyframe, 4 (K + 1) bytes, the outputs. */
+typedef struct covgpu_lmcov_t {
+  double   mu;        /* >= 0, finite; 0 = the covariance proper */
+  double*  lm_cov;    /* out [L][3][3] row-major, world frame, landmark order of the problem (resident form: of the resident
+                         observation set — after covgpu_gba_two_round the second round's landmarks, those with lm_left >= 2, in order) */
+  uint8_t* lm_ok;     /* out [L]: 1 = served; 0 = H_ll not positive definite, block zeroed */
+  double*  kf_cov;    /* out [K][6][6], may be NULL: the pose diagonal blocks the sweep has anyway (covgpu_selinv_t::kf_cov at block 0) */
+  int64_t* stats;     /* out [8], may be NULL: fronts, levels, launches of the sweep, launches of the landmark pass,
+                         group width, bytes of scratch, covisible pairs resolved, landmarks with lm_ok = 0 */
+} covgpu_lmcov_t;
+/* {largest group width (16), threads of a workgroup of the landmark pass (256), doubles of a landmark's block (9), 0} as the library was built */
+void covgpu_lmcov_limits(int32_t out[4]);
+/* The argument checks of covgpu_landmark_covariance alone (no context, no device): COVGPU_OK or COVGPU_ERR_INVALID_ARG with the message. */
+int covgpu_lmcov_check(const covgpu_problem*, const covgpu_options*, const covgpu_lmcov_t*);
+/* Uploads `p` as covgpu_gn_step does, linearises at its estimate, builds and factors at mu, sweeps, runs the landmark pass. */
+int covgpu_landmark_covariance(covgpu_context*, const covgpu_options*, const covgpu_problem*, const covgpu_lmcov_t*);
+/* The same at the estimate and the observation set the context holds, after an upload or a finished solve. A following
+ * covgpu_solve_resident returns the bits it would have returned without this call. */
+int covgpu_landmark_covariance_resident(covgpu_context*, const covgpu_options*, const covgpu_lmcov_t*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -739,6 +739,31 @@ class OptimizationT {
     for (size_t q = 0; q < pairs.size(); ++q) out.pair.emplace_back(pc.begin() + q * dd, pc.begin() + (q + 1) * dd);
     return out;
   }
+  // Covariance of EVERY landmark of the map's problem in one call (covgpu_landmark_covariance): per landmark id its 3x3 block
+  // of the inverse of the whole system at damping mu, world frame. Same problem and mu as KeyframeCovariances. A landmark whose H_ll is not
+  // positive definite (lm_ok = 0) is left out of the map. Matrix3Type: any default-constructible 3x3 type written through operator()(r, c) —
+  // Eigen::Matrix3d in COVINS (this header stays Eigen-free, see the top). stats (optional): covgpu_lmcov_t::stats.
+  template <class Matrix3Type>
+  static std::map<idpair, Matrix3Type> LandmarkCovariances(const MapPtr& map, bool visual_only = false, double mu = 0.0, int64_t* stats = nullptr) {
+    detail::Flat f; Index ix;
+    FlattenGBA(map, visual_only, true, f, ix);
+    const size_t L = ix.lms.size();
+    std::vector<double> lc(9 * L + 9);
+    std::vector<uint8_t> ok(L + 1, 0);
+    covgpu_lmcov_t s;
+    s.mu = mu; s.lm_cov = lc.data(); s.lm_ok = ok.data(); s.kf_cov = nullptr; s.stats = stats;
+    covgpu_problem p = f.view();
+    covgpu_options o = Options(1, visual_only);
+    if (covgpu_landmark_covariance(Context(), &o, &p, &s) != COVGPU_OK) throw std::runtime_error(covgpu_last_error());
+    std::map<idpair, Matrix3Type> out;
+    for (size_t l = 0; l < L; ++l) {
+      if (!ok[l]) continue;
+      Matrix3Type m;
+      for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) m(r, c) = lc[9 * l + 3 * r + c];
+      out[ix.lms[l]->id_] = m;
+    }
+    return out;
+  }
   // Covariance of the relative pose T_s1_s2 of two keyframes from their joint pose covariance cov12 ([12][12]: MarginalCovariance(map, {id1,
   // id2})): J cov12 J^T with J the 6x12 Jacobian of the between residual (R7) at zero residual and unit weight — [6][6] row-major, rotation
   // first and translation second, the order of LoopConstraint::cov_mat.
