@@ -169,6 +169,14 @@ def lmcov_limits():
     return dict(max_group=int(out[0]), threads=int(out[1]), block_doubles=int(out[2]))
 
 
+def obscov_limits():
+    """Host-only: {max_group, threads, cross_doubles, block_doubles} of Context.observation_covariances as the library was built
+    (covgpu_obscov_limits)."""
+    out = (C.c_int32 * 4)()
+    lib().covgpu_obscov_limits(out)
+    return dict(max_group=int(out[0]), threads=int(out[1]), cross_doubles=int(out[2]), block_doubles=int(out[3]))
+
+
 def selinv_limits():
     """Host-only: {mfma_rows, panel_cols, block_rows} of Context.keyframe_covariances as the library was built (covgpu_selinv_limits)."""
     out = (C.c_int32 * 4)()
@@ -1113,6 +1121,59 @@ class Context:
         s, lm_cov, ok, kf_cov, stats = self._lmcov(max(L, L0), K, mu, want_kf)
         self._check(lib().covgpu_landmark_covariance_resident(self._h, C.byref(opt), C.byref(s)))
         return lm_cov[:L], ok[:L], kf_cov, dict(zip(capi.LMCOV_STATS, (int(v) for v in stats)))
+
+    @staticmethod
+    def _obscov(O, L, K, mu, want_cross, want_res, want_lm, want_kf):
+        """(Obscov, outputs dict, stats) of one observation-covariance call on O observations, L landmarks and K keyframes."""
+        O, L = max(O, 1), max(L, 1)
+        out = dict(obs_cov=np.zeros((O, 2, 2)), obs_ok=np.zeros(O, np.uint8), cross_cov=np.zeros((O, 6, 3)) if want_cross else None,
+                   obs_res=np.zeros((O, 2)) if want_res else None, lm_cov=np.zeros((L, 3, 3)) if want_lm else None,
+                   lm_ok=np.zeros(L, np.uint8) if want_lm else None, kf_cov=np.zeros((K, 6, 6)) if want_kf else None)
+        stats = np.zeros(8, np.int64)
+        s = capi.Obscov()
+        s.mu = float(mu)
+        for f in ("obs_cov", "cross_cov", "obs_res", "lm_cov", "kf_cov"):
+            if out[f] is not None:
+                setattr(s, f, dptr(out[f]))
+        for f in ("obs_ok", "lm_ok"):
+            if out[f] is not None:
+                setattr(s, f, out[f].ctypes.data_as(capi._bp))
+        s.stats = stats.ctypes.data_as(capi._lp)
+        return s, out, stats
+
+    @staticmethod
+    def _obscov_result(out, stats, O, L):
+        cut = dict(obs_cov=O, obs_ok=O, cross_cov=O, obs_res=O, lm_cov=L, lm_ok=L)
+        res = {f: (v if v is None or f not in cut else v[:cut[f]]) for f, v in out.items()}
+        res["stats"] = dict(zip(capi.OBSCOV_STATS, (int(v) for v in stats)))
+        return res
+
+    def observation_covariances(self, prob, opt, mu=0.0, want_cross=True, want_res=True, want_lm=False, want_kf=False):
+        """Covariance of EVERY observation o = (a, l) at the estimate in `prob` (covgpu_observation_covariance), in the
+        landmark-major observation order of the problem: obs_cov [O, 2, 2] = J_o Sigma J_o^T (the block of the hat matrix, Sigma the inverse
+        of the whole system at damping mu), cross_cov [O, 6, 3] = Sigma_al (pose rows of the observer by the landmark's coordinates), obs_res
+        [O, 2] the whitened, loss-corrected residual, obs_ok [O] uint8 (0: the landmark is not served, blocks zeroed); lm_cov, lm_ok and
+        kf_cov as landmark_covariances returns them. Returns a dict of these (None where not asked for) and "stats"."""
+        s, out, stats = self._obscov(prob.O, prob.L, prob.K, mu, want_cross, want_res, want_lm, want_kf)
+        ps = prob.as_struct()
+        self._keep = prob; self._keep_pgo = False
+        self._check(lib().covgpu_observation_covariance(self._h, C.byref(opt), C.byref(ps), C.byref(s)))
+        return self._obscov_result(out, stats, prob.O, prob.L)
+
+    def observation_covariances_resident(self, opt, mu=0.0, want_cross=True, want_res=True, want_lm=False, want_kf=False, num_obs=None,
+                                         num_lm=None):
+        """The same at the estimate and the observation stream the context holds, after upload() or a finished solve. num_obs / num_lm: the
+        observations and landmarks of the resident stream when it is not the uploaded one — after gba_two_round the kept observations of
+        the landmarks with lm_left >= 2, in order."""
+        K = self._keep.K if self._keep is not None else 1   # (nothing uploaded: the call refuses before it writes)
+        L0 = self._keep.L if self._keep is not None else 1
+        O0 = self._keep.O if self._keep is not None else 1
+        L = int(num_lm) if num_lm is not None else L0
+        O = int(num_obs) if num_obs is not None else O0
+        # (the library writes the resident stream, whatever the counts say: never more than the uploaded problem's, so the buffers hold those)
+        s, out, stats = self._obscov(max(O, O0), max(L, L0), K, mu, want_cross, want_res, want_lm, want_kf)
+        self._check(lib().covgpu_observation_covariance_resident(self._h, C.byref(opt), C.byref(s)))
+        return self._obscov_result(out, stats, O, L)
 
     def solve_resident_traced(self, opt: Options, capacity: int = 64):
         """solve_resident that also returns the trust-region state at the end of every iteration, retry rounds included: (Result, trace

@@ -380,6 +380,16 @@ class Lmcov(C.Structure):
 LMCOV_STATS = ("fronts", "levels", "sweep_launches", "landmark_launches", "group_width", "scratch_bytes", "pairs_resolved", "landmarks_not_ok")
 
 
+class Obscov(C.Structure):
+    """covgpu_obscov_t (include/covgpu.h): covariance of every observation and its pose-landmark cross block, DESIGN.md §4.22."""
+    _fields_ = [("mu", C.c_double), ("obs_cov", _dp), ("cross_cov", _dp), ("obs_res", _dp), ("obs_ok", _bp), ("lm_cov", _dp), ("lm_ok", _bp),
+                ("kf_cov", _dp), ("stats", _lp)]
+
+
+OBSCOV_STATS = ("fronts", "levels", "sweep_launches", "observation_launches", "group_width", "scratch_bytes", "observations_not_ok",
+                "constant_observers")
+
+
 PRUNE_ERASED, PRUNE_TIME_GATE, PRUNE_LOOP_KF, PRUNE_NOT_ERASE = 0, 1, 2, 3                       # round_action
 PRUNE_STOP_NO_CANDIDATES, PRUNE_STOP_THRESHOLD, PRUNE_STOP_MAX_KFS, PRUNE_STOP_MAX_ROUNDS = 0, 1, 2, 3   # stop_reason
 
@@ -472,6 +482,10 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("lmcov_check", [PP, OP, C.POINTER(Lmcov)])
         d("landmark_covariance", [C.c_void_p, OP, PP, C.POINTER(Lmcov)])
         d("landmark_covariance_resident", [C.c_void_p, OP, C.POINTER(Lmcov)])
+        d("obscov_limits", [_ip], None)
+        d("obscov_check", [PP, OP, C.POINTER(Obscov)])
+        d("observation_covariance", [C.c_void_p, OP, PP, C.POINTER(Obscov)])
+        d("observation_covariance_resident", [C.c_void_p, OP, C.POINTER(Obscov)])
         d("outlier_pass", [C.c_void_p, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])
         d("covisibility", [C.c_void_p, C.c_int32, C.c_int64, _ip, _ip, _ip, C.POINTER(C.c_int64)])
         d("gba_solve_multi", [OP, PP, RP, C.c_int32, _ip, C.c_double, _bp, _ip, C.POINTER(C.c_int64)])

@@ -16,8 +16,8 @@
 // transposed (the sweep stores both halves of Sigma from one computed value, so that IS Sigma_ji bit for bit). A diagonal block is read
 // through its lower triangle. A block that is not found (the list is built from the same observation stream, and the host plan resolves every
 // entry of it: it does not happen) is not skipped in silence: the landmark gets lm_ok = 0 and a zero block, never a covariance that is too small.
-#include "dev_math.hpp"
-#include "lmcov.hpp"
+// The sum over the observer pairs and the landmark's block are in lmcov_dev.hpp, which k_obscov.hip shares.
+#include "lmcov_dev.hpp"
 
 namespace covgpu {
 using namespace covdev;
@@ -39,59 +39,10 @@ __global__ __launch_bounds__(kLmcovThreads) void k_lmcov(DevProblem P, LmcovArgs
   for (int a = lane; a < nobs; a += G) {
     const int ka = P.obs_kf[o0 + a];
     if (P.fixed[ka]) continue;   // a constant pose has no rows in Sigma
-    const int pa = P.perm[ka];
     double Za[18], V[18];
-    {
-      const double2* z = Zrec + 9 * (size_t)P.obs_zpos[o0 + a];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) { const double2 t = z[k]; Za[2 * k] = t.x; Za[2 * k + 1] = t.y; }
-    }
-#pragma unroll
-    for (int k = 0; k < 18; ++k) V[k] = 0.0;
-    for (int b = 0; b < nobs; ++b) {
-      const int kb = P.obs_kf[o0 + b];
-      if (P.fixed[kb]) continue;
-      const int pb = P.perm[kb];
-      LmcovBlock B;
-      int sr, sc;             // strides of Sigma_ab's rows and columns in the stored block
-      const bool diag = pa == pb;
-      if (diag) { B = A.kf_blk[ka]; sr = B.ld; sc = 1; }
-      else {
-        const int hi = pa > pb ? pa : pb, lo = pa > pb ? pb : pa;
-        int e0 = A.row_ptr[hi], e1 = A.row_ptr[hi + 1];
-        while (e0 < e1) { const int m = (e0 + e1) >> 1; if (P.pair_j[m] < lo) e0 = m + 1; else e1 = m; }
-        if (e0 >= A.row_ptr[hi + 1] || P.pair_j[e0] != lo) { missing = 1; continue; }   // (two observers of a landmark are a pair of the list: not taken)
-        B = A.pair_blk[e0];
-        sr = pa > pb ? B.ld : 1; sc = pa > pb ? 1 : B.ld;
-      }
-      if (B.off < 0) { missing = 1; continue; }   // (the host plan resolves every entry: not taken)
-      const double* Sb = A.S + B.off;
-      double Zb[18];
-      {
-        const double2* z = Zrec + 9 * (size_t)P.obs_zpos[o0 + b];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { const double2 t = z[k]; Zb[2 * k] = t.x; Zb[2 * k + 1] = t.y; }
-      }
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        double s[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-          const bool up = diag && c > r;   // a diagonal block through its lower triangle
-          s[c] = Sb[(size_t)(up ? c : r) * sr + (size_t)(up ? r : c) * sc];
-        }
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-          V[3 * r] += s[c] * Zb[3 * c]; V[3 * r + 1] += s[c] * Zb[3 * c + 1]; V[3 * r + 2] += s[c] * Zb[3 * c + 2];
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        M[3 * p] += Za[3 * r + p] * V[3 * r]; M[3 * p + 1] += Za[3 * r + p] * V[3 * r + 1]; M[3 * p + 2] += Za[3 * r + p] * V[3 * r + 2];
-      }
+    lmcov_load_z(Zrec, P.obs_zpos[o0 + a], Za);
+    lmcov_gather_v(P, A, Zrec, o0, nobs, ka, P.perm[ka], V, missing);
+    lmcov_add_m(Za, V, M);
   }
 #pragma unroll
   for (int k = 0; k < 9; ++k) M[k] = group_sum<G>(M[k]);
@@ -99,29 +50,8 @@ __global__ __launch_bounds__(kLmcovThreads) void k_lmcov(DevProblem P, LmcovArgs
   for (int off = G / 2; off >= 1; off >>= 1) missing |= __shfl_xor(missing, off, G);
   if (!live || lane != 0) return;
 
-  // Sigma_l = R T R^T, T = I + (M + M^T) / 2 (M is symmetric up to rounding), R = (r00 r10 r11 r20 r21 r22) lower: one triangle, stored twice
-  const double* rt = P.lmRT + 9 * (size_t)l;
-  const double R[3][3] = {{rt[0], 0.0, 0.0}, {rt[1], rt[2], 0.0}, {rt[3], rt[4], rt[5]}};
-  double T[3][3];
-#pragma unroll
-  for (int p = 0; p < 3; ++p)
-#pragma unroll
-    for (int q = 0; q <= p; ++q) { const double t = 0.5 * (M[3 * p + q] + M[3 * q + p]) + (p == q ? 1.0 : 0.0); T[p][q] = t; T[q][p] = t; }
-  double Y[3][3], out[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) Y[r][q] = R[r][0] * T[0][q] + R[r][1] * T[1][q] + R[r][2] * T[2][q];
-  // k_lm_lin leaves a zero pivot in R (chol3) for an H_ll it could not accept as positive definite: no covariance
-  bool ok = R[0][0] > 0.0 && R[1][1] > 0.0 && R[2][2] > 0.0 && missing == 0;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c <= r; ++c) {
-      const double v = Y[r][0] * R[c][0] + Y[r][1] * R[c][1] + Y[r][2] * R[c][2];
-      ok = ok && isfinite(v);
-      out[3 * r + c] = v; out[3 * c + r] = v;
-    }
+  double out[9];
+  const bool ok = lmcov_block(P.lmRT + 9 * (size_t)l, M, missing, out);
   double* dst = A.lm_cov + 9 * (size_t)l;
 #pragma unroll
   for (int k = 0; k < 9; ++k) dst[k] = ok ? out[k] : 0.0;

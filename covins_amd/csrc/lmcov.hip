@@ -2,7 +2,8 @@
 // landmark pass of k_lmcov.hip. A call starts with step one of covgpu_selected_inverse (selinv.hip: sel_factor_and_sweep leaves Sigma in its
 // scratch), with its own plan and scratch made before anything is enqueued: where the 6x6 pose-pose block of Sigma lies for every entry of
 // the resident covisible pair list and for every free keyframe. The blocks are found by the rule of the selected inverse's read-out
-// (sel_want / sel_locate); nothing is kept per upload.
+// (sel_want / sel_locate); nothing is kept per upload. The tables and the context's refusals are exported through lmcov.hpp: the
+// observation pass (obscov.hip) runs on the same ones.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -20,16 +21,10 @@ int bad_arg(const char* fn, const std::string& m) { g_err = std::string(fn) + ":
 
 // The tables of the landmark pass. Two numberings meet: sel_want / sel_locate work in SOLUTION indices (D * keyframe of the problem + component),
 // the covisible pair list (pair_i, pair_j) in chain-major POSITIONS (perm[keyframe]).
-struct LmcovPlan {
-  std::vector<LmcovBlock> kf_blk;     // [K] by keyframe
-  std::vector<LmcovBlock> pair_blk;   // [npairs] by entry of the pair list (positions)
-  std::vector<int> row_ptr;           // [K + 1] by position
-};
-
-// pair_i / pair_j: the resident pair list (positions, sorted by (i, j), i > j); pos_kf: position -> keyframe
-const char* lmcov_plan(const covgpu_context* c, const SelPlan& pl, const uint8_t* fixed, const std::vector<int>& pair_i, const std::vector<int>& pair_j,
-                       const std::vector<int>& pos_kf, LmcovPlan& lp) {
+const char* lmcov_plan(const covgpu_context* c, const SelPlan& pl, LmcovTables& lp) {
   const int K = c->P.K, D = c->P.D;
+  const uint8_t* fixed = lp.fixed.data();
+  const std::vector<int>&pair_i = lp.pair_i, &pair_j = lp.pair_j, &pos_kf = lp.pos_kf;
   const size_t np = pair_i.size();
   lp.kf_blk.assign((size_t)K, LmcovBlock{-1, 0, 0});
   lp.pair_blk.assign(np, LmcovBlock{-1, 0, 0});
@@ -54,47 +49,82 @@ const char* lmcov_plan(const covgpu_context* c, const SelPlan& pl, const uint8_t
   return nullptr;
 }
 
-int sweep_and_pass(const char* fn, covgpu_context* c, const covgpu_lmcov_t* rq) {
+}  // namespace
+
+namespace covgpu {
+
+int lmcov_lists(const char* fn, covgpu_context* c, LmcovTables& t) {
   const DevProblem& P = c->P;
-  const int K = P.K, L = P.L;
-  std::vector<uint8_t> fixed;
-  RC(sel_fetch_fixed(c, fixed));
-  std::vector<int> pair_i((size_t)P.npairs), pair_j((size_t)P.npairs), pos_kf((size_t)K, 0);
+  const int K = P.K;
+  RC(sel_fetch_fixed(c, t.fixed));
+  t.pair_i.assign((size_t)P.npairs, 0); t.pair_j.assign((size_t)P.npairs, 0); t.pos_kf.assign((size_t)K, 0);
   if (P.npairs > 0) {
-    HIPCHK(hipMemcpy(pair_i.data(), P.pair_i, (size_t)P.npairs * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(pair_j.data(), P.pair_j, (size_t)P.npairs * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(t.pair_i.data(), P.pair_i, (size_t)P.npairs * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(t.pair_j.data(), P.pair_j, (size_t)P.npairs * sizeof(int), hipMemcpyDeviceToHost));
   }
   if ((int)c->h_perm.size() != K) return bad_arg(fn, "the context holds no chain-major order");
   for (int k = 0; k < K; ++k) {
     if (c->h_perm[k] < 0 || c->h_perm[k] >= K) return bad_arg(fn, "the chain-major order is not a permutation");
-    pos_kf[c->h_perm[k]] = k;
+    t.pos_kf[c->h_perm[k]] = k;
   }
+  return COVGPU_OK;
+}
 
-  LmcovPlan lp;
+int lmcov_prepare(const char* fn, const covgpu_context* c, const SelPlan& pl, ::DeviceScratch& U, LmcovTables& t, size_t& bytes) {
+  const int L = c->P.L;
+  if (const char* m = lmcov_plan(c, pl, t)) return bad_arg(fn, m);
+  HIPCHK(U.alloc(&t.d_kf, t.kf_blk.size())); HIPCHK(U.alloc(&t.d_pair, t.pair_blk.size())); HIPCHK(U.alloc(&t.d_row, t.row_ptr.size()));
+  HIPCHK(U.alloc(&t.d_lm_cov, (size_t)9 * L)); HIPCHK(U.alloc(&t.d_lm_ok, (size_t)L));
+  bytes += (t.kf_blk.size() + t.pair_blk.size()) * sizeof(LmcovBlock) + t.row_ptr.size() * sizeof(int) + (size_t)L * (9 * sizeof(double) + 1);
+  return COVGPU_OK;
+}
+
+int lmcov_upload(covgpu_context* c, const LmcovTables& t, LmcovArgs& a) {
+  HIPCHK(hipMemcpyAsync(t.d_kf, t.kf_blk.data(), t.kf_blk.size() * sizeof(LmcovBlock), hipMemcpyHostToDevice, c->st));
+  if (!t.pair_blk.empty()) HIPCHK(hipMemcpyAsync(t.d_pair, t.pair_blk.data(), t.pair_blk.size() * sizeof(LmcovBlock), hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipMemcpyAsync(t.d_row, t.row_ptr.data(), t.row_ptr.size() * sizeof(int), hipMemcpyHostToDevice, c->st));
+  a.kf_blk = t.d_kf; a.pair_blk = t.d_pair; a.row_ptr = t.d_row; a.lm_cov = t.d_lm_cov; a.lm_ok = t.d_lm_ok;
+  return COVGPU_OK;
+}
+
+// the refusals that depend on the context
+int lmcov_context_check(const char* fn, const covgpu_context* c) {
+  if (c->sharded) return bad_arg(fn, "a sharded context holds one rank's share of the factor");
+  if (!c->have && !c->second_round) return bad_arg(fn, "no problem uploaded");   // (second_round: what covgpu_gba_two_round left, host.hpp)
+  if (c->pgo) return bad_arg(fn, "the context holds a pose graph: it has no landmarks");
+  if (!c->P.nd) return bad_arg(fn, "the problem of this context is off the elimination tree");
+  if (c->P.L <= 0 || c->P.O <= 0) return bad_arg(fn, "a problem without landmarks");
+  return COVGPU_OK;
+}
+
+}  // namespace covgpu
+
+namespace {
+
+int sweep_and_pass(const char* fn, covgpu_context* c, const covgpu_lmcov_t* rq) {
+  const DevProblem& P = c->P;
+  const int L = P.L;
+  LmcovTables lp;
+  RC(lmcov_lists(fn, c, lp));
+
   DeviceScratch U(c->st);
   SelSweep sw;
   LmcovArgs a{};
-  LmcovBlock *d_kf = nullptr, *d_pair = nullptr; int* d_row = nullptr;
   long long* src = nullptr; double* kf_out = nullptr;
   size_t own_bytes = 0;
   covgpu_selinv_t diag{};   // the read-out of kf_cov: the pose diagonal blocks as covgpu_selected_inverse at block 0 returns them
   diag.block = 0; diag.mu = rq->mu; diag.kf_cov = rq->kf_cov; diag.num_pairs = 0;
   RC(sel_factor_and_sweep(fn, c, rq->mu, U, sw, [&](SelPlan& pl) -> int {
-    if (const char* m = lmcov_plan(c, pl, fixed.data(), pair_i, pair_j, pos_kf, lp)) return bad_arg(fn, m);
+    RC(lmcov_prepare(fn, c, pl, U, lp, own_bytes));
     if (rq->kf_cov) {
-      if (const char* m = sel_plan_readout(c, &diag, fixed.data(), pl)) return bad_arg(fn, m);
+      if (const char* m = sel_plan_readout(c, &diag, lp.fixed.data(), pl)) return bad_arg(fn, m);
       HIPCHK(U.alloc(&src, pl.src.size())); HIPCHK(U.alloc(&kf_out, pl.src.size()));
       own_bytes += pl.src.size() * (sizeof(long long) + sizeof(double));
     }
-    HIPCHK(U.alloc(&d_kf, lp.kf_blk.size())); HIPCHK(U.alloc(&d_pair, lp.pair_blk.size())); HIPCHK(U.alloc(&d_row, lp.row_ptr.size()));
-    HIPCHK(U.alloc(&a.lm_cov, (size_t)9 * L)); HIPCHK(U.alloc(&a.lm_ok, (size_t)L));
-    own_bytes += (lp.kf_blk.size() + lp.pair_blk.size()) * sizeof(LmcovBlock) + lp.row_ptr.size() * sizeof(int) + (size_t)L * (9 * sizeof(double) + 1);
     return COVGPU_OK;
   }));
-  HIPCHK(hipMemcpyAsync(d_kf, lp.kf_blk.data(), lp.kf_blk.size() * sizeof(LmcovBlock), hipMemcpyHostToDevice, c->st));
-  if (!lp.pair_blk.empty()) HIPCHK(hipMemcpyAsync(d_pair, lp.pair_blk.data(), lp.pair_blk.size() * sizeof(LmcovBlock), hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(d_row, lp.row_ptr.data(), lp.row_ptr.size() * sizeof(int), hipMemcpyHostToDevice, c->st));
-  a.S = sw.a.S; a.kf_blk = d_kf; a.pair_blk = d_pair; a.row_ptr = d_row;
+  RC(lmcov_upload(c, lp, a));
+  a.S = sw.a.S;
   launch_lmcov(P, a, c->st);
   if (rq->kf_cov) {
     RC(sel_read_out(c, sw, src, kf_out));
@@ -115,15 +145,7 @@ int sweep_and_pass(const char* fn, covgpu_context* c, const covgpu_lmcov_t* rq) 
   return COVGPU_OK;
 }
 
-// the refusals that depend on the context
-int context_check(const char* fn, const covgpu_context* c) {
-  if (c->sharded) return bad_arg(fn, "a sharded context holds one rank's share of the factor");
-  if (!c->have && !c->second_round) return bad_arg(fn, "no problem uploaded");   // (second_round: what covgpu_gba_two_round left, host.hpp)
-  if (c->pgo) return bad_arg(fn, "the context holds a pose graph: it has no landmarks");
-  if (!c->P.nd) return bad_arg(fn, "the problem of this context is off the elimination tree");
-  if (c->P.L <= 0 || c->P.O <= 0) return bad_arg(fn, "a problem without landmarks");
-  return COVGPU_OK;
-}
+int context_check(const char* fn, const covgpu_context* c) { return lmcov_context_check(fn, c); }
 
 int covariance_impl(covgpu_context* c, const covgpu_options* opt, const covgpu_problem* p, const covgpu_lmcov_t* rq) {
   const char* fn = "covgpu_landmark_covariance";

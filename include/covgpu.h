@@ -1134,6 +1134,52 @@ int covgpu_landmark_covariance(covgpu_context*, const covgpu_options*, const cov
  * covgpu_solve_resident returns the bits it would have returned without this call. */
 int covgpu_landmark_covariance_resident(covgpu_context*, const covgpu_options*, const covgpu_lmcov_t*);
 
+/* ---- Covariance of every observation and its pose-landmark cross block ----
+ *
+ * For every observation o = (a, l) of the observation stream, at damping mu (conventions of the three calls above: S whitened and
+ * loss-corrected as covgpu_schur returns it, A.1's tangent, world frame):
+ *   obs_cov   C_o = J_o Sigma J_o^T, the 2x2 block of the hat matrix: J_o = [J_p J_l] the whitened, loss-corrected 2x9 Jacobian of the
+ *             observation, Sigma the inverse of the WHOLE damped system restricted to (pose of a, landmark l). 0 <= C_o <= I in exact
+ *             arithmetic at any mu >= 0; the normalised residual of the observation is r^T (I - C_o)^-1 r with r = obs_res.
+ *   cross_cov Sigma_al, pose rows of the observer (dtheta, dp) by the landmark's coordinates.
+ * With H_ll^-1 = R R^T, Z_b = (J_p^T J_l) R of observation b of l, V_a = sum_b Sigma_ab Z_b, M = sum_a Z_a^T V_a and Y = J_l R:
+ *   Sigma_al = -V_a R^T,   C_o = [J_p -Y] [[Sigma_aa, V_a], [V_a^T, (M + M^T) / 2]] [J_p -Y]^T + Y Y^T,
+ * one landmark-major pass (k_obscov.hip) behind the sweep of covgpu_selected_inverse: pass 1 is the landmark call's sum, pass 2 evaluates
+ * the observation again. Every sum in one fixed order, no atomics: two calls return the same bits; obs_cov is symmetric bit for bit (the
+ * off-diagonal entry is computed once and stored twice). lm_cov, lm_ok and kf_cov are covgpu_landmark_covariance's, bit for bit.
+ * Edges: an observer with a constant pose has J_p = 0 — its cross_cov is zeros, C_o = J_l Sigma_l J_l^T, obs_ok = 1. An observation that
+ * does not project (r = 0, J = 0) has C_o = 0 and obs_ok = 1. An observation of a landmark that is not served (lm_ok = 0 by the landmark
+ * call's rule, "a block of Sigma was not found" included) has obs_ok = 0 and zero blocks.
+ * Order of the outputs: the landmark-major observation order of the problem (lm_obs_ptr). Resident form: of the resident observation
+ * stream — after covgpu_gba_two_round the compacted second-round stream, the kept observations of the landmarks with lm_left >= 2, in order
+ * (as lm_cov: the second round's landmarks).
+ * With reproj_loss_a > 0 every block is in loss-corrected units (the Jacobians and the residual carry the loss's scale).
+ * Refused with COVGPU_ERR_INVALID_ARG: a NULL obs_cov or obs_ok, mu negative or not finite, a problem without observations, lm_cov given
+ * without lm_ok; a context that holds a pose graph; a sharded context; nothing uploaded (resident form). A non-positive pivot of the
+ * reduced system is COVGPU_ERR_NUMERIC, a scratch allocation that fails COVGPU_ERR_OUT_OF_MEMORY (nothing is enqueued, the context
+ * stays usable). Scratch (stats[5]): the landmark call's, and 8 (18 + 4 + 2) + 1 bytes per observation. */
+typedef struct covgpu_obscov_t {
+  double   mu;         /* >= 0, finite; 0 = the covariance proper */
+  double*  obs_cov;    /* out [O][2][2] row-major */
+  double*  cross_cov;  /* out [O][6][3] row-major, may be NULL */
+  double*  obs_res;    /* out [O][2], may be NULL: the whitened, loss-corrected residual of the same evaluation */
+  uint8_t* obs_ok;     /* out [O]: 1 = served; 0 = the landmark is not served, blocks zeroed */
+  double*  lm_cov;     /* out [L][3][3], may be NULL: covgpu_lmcov_t::lm_cov */
+  uint8_t* lm_ok;      /* out [L], may be NULL unless lm_cov is given */
+  double*  kf_cov;     /* out [K][6][6], may be NULL: covgpu_lmcov_t::kf_cov */
+  int64_t* stats;      /* out [8], may be NULL: fronts, levels, launches of the sweep, launches of the observation pass, group width,
+                          bytes of scratch, observations with obs_ok = 0, observations whose observer has a constant pose */
+} covgpu_obscov_t;
+/* {largest group width (16), threads of a workgroup of the observation pass (256), doubles of a cross block (18), of an obs block (4)} */
+void covgpu_obscov_limits(int32_t out[4]);
+/* The argument checks of covgpu_observation_covariance alone (no context, no device): COVGPU_OK or COVGPU_ERR_INVALID_ARG with the message. */
+int covgpu_obscov_check(const covgpu_problem*, const covgpu_options*, const covgpu_obscov_t*);
+/* Uploads `p` as covgpu_gn_step does, linearises at its estimate, builds and factors at mu, sweeps, runs the observation pass. */
+int covgpu_observation_covariance(covgpu_context*, const covgpu_options*, const covgpu_problem*, const covgpu_obscov_t*);
+/* The same at the estimate and the observation stream the context holds, after an upload or a finished solve. A following
+ * covgpu_solve_resident returns the bits it would have returned without this call. */
+int covgpu_observation_covariance_resident(covgpu_context*, const covgpu_options*, const covgpu_obscov_t*);
+
 #ifdef __cplusplus
 }
 #endif

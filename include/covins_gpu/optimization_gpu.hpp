@@ -764,6 +764,39 @@ class OptimizationT {
     }
     return out;
   }
+  // Covariance of EVERY observation of the map's problem in one call (covgpu_observation_covariance), in the landmark-major
+  // observation order of the problem: the 2x2 block C_o = J_o Sigma J_o^T of the hat matrix (row-major; the normalised residual of the
+  // observation is r^T (I - C_o)^-1 r) and the 6x3 block Sigma_al, pose rows of the observer (dtheta, dp) by the landmark's world
+  // coordinates. Same problem and mu as LandmarkCovariances; with a robust loss the blocks are in loss-corrected units. ok = 0: the
+  // landmark is not served (LandmarkCovariances leaves it out), the blocks are zeros. stats (optional): covgpu_obscov_t::stats.
+  struct ObservationCovariance {
+    idpair lm, kf;
+    double cov[4] = {0, 0, 0, 0};
+    double cross[18] = {};
+    uint8_t ok = 0;
+  };
+  static std::vector<ObservationCovariance> ObservationCovariances(const MapPtr& map, bool visual_only = false, double mu = 0.0, int64_t* stats = nullptr) {
+    detail::Flat f; Index ix;
+    FlattenGBA(map, visual_only, true, f, ix);
+    const size_t L = ix.lms.size(), O = f.obs_kf.size();
+    std::vector<double> oc(4 * O + 4), cc(18 * O + 18);
+    std::vector<uint8_t> ok(O + 1, 0);
+    covgpu_obscov_t s;
+    s.mu = mu; s.obs_cov = oc.data(); s.cross_cov = cc.data(); s.obs_res = nullptr; s.obs_ok = ok.data();
+    s.lm_cov = nullptr; s.lm_ok = nullptr; s.kf_cov = nullptr; s.stats = stats;
+    covgpu_problem p = f.view();
+    covgpu_options o = Options(1, visual_only);
+    if (covgpu_observation_covariance(Context(), &o, &p, &s) != COVGPU_OK) throw std::runtime_error(covgpu_last_error());
+    std::vector<ObservationCovariance> out(O);
+    for (size_t l = 0; l < L; ++l)
+      for (size_t i = (size_t)f.obs_ptr[l]; i < (size_t)f.obs_ptr[l + 1]; ++i) {
+        ObservationCovariance& r = out[i];
+        r.lm = ix.lms[l]->id_; r.kf = ix.kfs[f.obs_kf[i]]->id_; r.ok = ok[i];
+        for (int k = 0; k < 4; ++k) r.cov[k] = oc[4 * i + k];
+        for (int k = 0; k < 18; ++k) r.cross[k] = cc[18 * i + k];
+      }
+    return out;
+  }
   // Covariance of the relative pose T_s1_s2 of two keyframes from their joint pose covariance cov12 ([12][12]: MarginalCovariance(map, {id1,
   // id2})): J cov12 J^T with J the 6x12 Jacobian of the between residual (R7) at zero residual and unit weight — [6][6] row-major, rotation
   // first and translation second, the order of LoopConstraint::cov_mat.
