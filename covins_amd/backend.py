@@ -177,6 +177,43 @@ def obscov_limits():
     return dict(max_group=int(out[0]), threads=int(out[1]), cross_doubles=int(out[2]), block_doubles=int(out[3]))
 
 
+def fivept_limits():
+    """Host-only: {stage_cap, hypotheses, sample, max_iterations} of Context.fivept_ransac_batch as the library was built
+    (covgpu_fivept_limits): correspondences staged in LDS, hypotheses per pass, correspondences per draw, the largest max_iterations."""
+    out = (C.c_int32 * 4)()
+    lib().covgpu_fivept_limits(out)
+    return dict(zip(("stage_cap", "hypotheses", "sample", "max_iterations"), (int(v) for v in out)))
+
+
+def _fivept_args(bt: dict, opts: dict):
+    """The structures of a five-point call and the arrays they point into (kept alive by the caller)."""
+    o = capi.FiveptOpts()
+    lib().covgpu_default_fivept_opts(C.byref(o))
+    _set_opts(o, [name for name, _ in capi.FiveptOpts._fields_], opts, "five-point")
+    ptr = _opt(_i32, bt.get("ptr"))
+    B = len(ptr) - 1 if ptr is not None else int(bt.get("num", 0))
+    Cn = int(ptr[-1]) if ptr is not None and len(ptr) else 0
+    f1 = _opt(lambda a: _f64(a).reshape(-1, 3), bt.get("bearing1"))
+    f2 = _opt(lambda a: _f64(a).reshape(-1, 3), bt.get("bearing2"))
+    seed = _opt(lambda a: np.ascontiguousarray(a, dtype=np.uint64), bt.get("seed"))
+    T = np.array(bt["T0"], dtype=np.float64, order="C").reshape(-1, 7) if bt.get("T0") is not None else np.zeros((max(B, 1), 7))
+    mask = np.zeros(max(Cn, 1), np.uint8)
+    inl, st, its, bd = (np.zeros(max(B, 1), np.int32) for _ in range(4))
+    keep = dict(ptr=ptr, f1=f1, f2=f2, seed=seed, T=T, mask=mask, inl=inl, st=st, its=its, bd=bd, B=B, C=max(Cn, 0))
+    s = capi.FiveptBatch(B, _opt(iptr, ptr), _opt(dptr, f1), _opt(dptr, f2), None if seed is None else seed.ctypes.data_as(C.POINTER(C.c_uint64)),
+                         dptr(T), _bp(mask), iptr(inl), iptr(st), iptr(its), iptr(bd))
+    return s, o, keep
+
+
+def fivept_check(bt: dict, **opts):
+    """Host-only: the argument check of Context.fivept_ransac_batch alone (covgpu_fivept_check); raises CovGpuError with the message
+    of the first violation. A key of `bt` that is absent is passed as a NULL array."""
+    s, o, _keep = _fivept_args(bt, opts)
+    rc = lib().covgpu_fivept_check(C.byref(s), C.byref(o))
+    if rc != 0:
+        raise CovGpuError(f"covgpu error {rc}: {lib().covgpu_last_error().decode()}")
+
+
 def selinv_limits():
     """Host-only: {mfma_rows, panel_cols, block_rows} of Context.keyframe_covariances as the library was built (covgpu_selinv_limits)."""
     out = (C.c_int32 * 4)()
@@ -560,6 +597,30 @@ class Context:
                               dptr(T), _bp(mask), iptr(inl), iptr(its), iptr(bd))
         self._check(lib().covgpu_abspose_ransac_batch(self._h, C.byref(s), C.byref(o)))
         return dict(T_wc=T[:max(B, 0)], inlier=mask[:Cn].astype(bool), inliers=inl[:max(B, 0)], iterations=its[:max(B, 0)], best_draw=bd[:max(B, 0)])
+
+    def fivept_ransac_batch(self, bt: dict, **opts):
+        """Batched five-point relative-pose RANSAC of COVINS-G (covgpu_fivept_ransac_batch). `bt`: dict with ptr [num+1],
+        bearing1 [C,3] (frame 1, the query side), bearing2 [C,3], optionally seed [num] (uint64; absent = opts seed + b) and T0 [num,7]
+        (what untouched rows hold). `opts`: min_inliers, max_iterations, probability, threshold, sigma, seed (defaults:
+        covgpu_default_fivept_opts). Returns dict(T_12 [num,7], inlier [C] bool, inliers [num], status [num], iterations [num],
+        best_draw [num])."""
+        s, o, k = _fivept_args(bt, opts)
+        self._check(lib().covgpu_fivept_ransac_batch(self._h, C.byref(s), C.byref(o)))
+        B = max(k["B"], 0)
+        return dict(T_12=k["T"][:B], inlier=k["mask"][:k["C"]].astype(bool), inliers=k["inl"][:B], status=k["st"][:B], iterations=k["its"][:B],
+                    best_draw=k["bd"][:B])
+
+    def fivept_solve_batch(self, f1, f2):
+        """Test entry point (covgpu_fivept_solve_batch): the five-point problem of every 8-tuple f1, f2 [n,8,3] on its slots 0..4. Returns
+        dict(E [n,10,3,3] (rows past nsol zero), nsol [n], T [n,7] (zero where no pose), chosen [n] (-1: none))."""
+        f1 = _f64(f1).reshape(-1, 8, 3); f2 = _f64(f2).reshape(-1, 8, 3)
+        n = len(f1)
+        if len(f2) != n:
+            raise ValueError("f1 and f2 differ in length")
+        E = np.zeros((max(n, 1), 10, 3, 3)); T = np.zeros((max(n, 1), 7))
+        ns = np.zeros(max(n, 1), np.int32); ch = np.zeros(max(n, 1), np.int32)
+        self._check(lib().covgpu_fivept_solve_batch(self._h, n, dptr(f1), dptr(f2), dptr(E), iptr(ns), dptr(T), iptr(ch)))
+        return dict(E=E[:n], nsol=ns[:n], T=T[:n], chosen=ch[:n])
 
     def match_batch(self, sets: dict, set_a, set_b, mode: str = "dense", **opts):
         """Batched ORB descriptor matching of loop candidates (covgpu_match_batch). `sets`: dict with row_ptr

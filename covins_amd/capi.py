@@ -222,6 +222,18 @@ class RansacOpts(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class FiveptBatch(C.Structure):
+    _fields_ = [("num", C.c_int32), ("corr_ptr", _ip), ("bearing1", _dp), ("bearing2", _dp), ("seed", C.POINTER(C.c_uint64)),
+                ("T_12", _dp), ("inlier", _bp), ("inliers", _ip), ("status", _ip), ("iterations", _ip), ("best_draw", _ip)]
+
+
+class FiveptOpts(C.Structure):
+    _fields_ = [("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("probability", C.c_double), ("threshold", C.c_double),
+                ("sigma", C.c_double), ("seed", C.c_uint64)]
+
+
+FIVEPT_FOUND, FIVEPT_TOO_FEW, FIVEPT_NO_MODEL, FIVEPT_FEW_INLIERS, FIVEPT_MAX_ITERATIONS = range(5)   # include/covgpu.h
+
 MATCH_DENSE, MATCH_KNN2, MATCH_MAX_ROWS = 0, 1, 4096   # include/covgpu.h
 
 
@@ -433,6 +445,11 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("default_ransac_opts", [C.POINTER(RansacOpts)], None)
         d("abspose_ransac_batch", [C.c_void_p, C.POINTER(AbsposeBatch), C.POINTER(RansacOpts)])
         d("p3p_batch", [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _ip])
+        d("default_fivept_opts", [C.POINTER(FiveptOpts)], None)
+        d("fivept_limits", [_ip], None)
+        d("fivept_check", [C.POINTER(FiveptBatch), C.POINTER(FiveptOpts)])
+        d("fivept_ransac_batch", [C.c_void_p, C.POINTER(FiveptBatch), C.POINTER(FiveptOpts)])
+        d("fivept_solve_batch", [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _dp, _ip])
         d("default_match_opts", [C.POINTER(MatchOpts), C.c_int32], None)
         d("match_batch", [C.c_void_p, C.POINTER(MatchBatch), C.POINTER(MatchOpts)])
         d("default_match_float_opts", [C.POINTER(MatchOpts)], None)

@@ -619,6 +619,12 @@ void launch_abspose(int num, const int* ptr, const double* f, const double* P, c
                     unsigned char* inlier, int* inliers, int* iterations, int* best_draw, int min_inliers, int max_iterations, double probability,
                     double threshold, int max_n, hipStream_t st);
 void launch_p3p(int num, const double* F, const double* P, double* T, int* nsol, int* chosen, hipStream_t st);
+// k_fivept.hip: batched five-point relative-pose RANSAC of COVINS-G (one 256-thread workgroup per job, 16 lanes per hypothesis)
+void fivept_limits(int out[4]);   // LDS staging cap, hypotheses per pass, sample size, largest max_iterations
+hipError_t launch_fivept(int num, const int* ptr, const double* f1, const double* f2, const unsigned long long* seed, double* T, unsigned char* inlier,
+                   int* inliers, int* status, int* iterations, int* best_draw, int min_inliers, int max_iterations, double probability,
+                   double threshold, double sigma, int max_n, hipStream_t st);
+hipError_t launch_fivept_solve(int num, const double* f1, const double* f2, double* E, int* nsol, double* T, int* chosen, hipStream_t st);
 // k_match.hip: batched ORB descriptor matching of loop candidates (DENSE: scan + assignbest replay; KNN2: scan only)
 size_t match_assign_lds_bytes(int maxA, int maxB);
 void launch_match(int mode, int num_jobs, int maxA, int maxB, const unsigned char* desc, const unsigned char* skip, const int* row_ptr,

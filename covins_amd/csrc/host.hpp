@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "batch_check.hpp"
+#include "fivept_check.hpp"
 #include "common.hpp"
 #include "nd_plan.hpp"
 

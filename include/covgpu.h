@@ -527,6 +527,48 @@ int  covgpu_p3p_batch(covgpu_context*, int32_t n, const double* f /*[n][4][3]*/,
                       double* T /*[n][4][7]*/, int32_t* nsol /*[n]*/, int32_t* chosen /*[n]*/);
 
 
+/* ---------------------------------------------------------------- COVINS-G five-point relative-pose RANSAC
+ * Batched RelNonCentralPosSolver::computePose (RelNonCentralPosSolver.cpp:343-377): per job b an opengv-style RANSAC (central
+ * relative pose, five-point solver on slots 0..4 of a draw of 8, all 8 pick the pose) over the correspondences
+ * [corr_ptr[b], corr_ptr[b+1]): unit bearings f1_i (frame 1, the query side) and f2_i (frame 2). Model T_12 = [R | t], frame 2 in
+ * frame 1 (x1 = R x2 + t, ||t|| = 1). Score: the midpoint p of the two rays (triangulate2), r1 = p/||p||, r2 = q/||q|| with
+ * q = R^T p - R^T t, score = 0.5 ||r1 - f1||^2 / sigma + 0.5 ||r2 - f2||^2 / sigma, inlier iff score < threshold. Among the up to 40
+ * poses of a draw the smallest sum over its 8 correspondences of (1 - f1.r1) + (1 - f2.r2) wins, the first on a tie. Draw d, slot k
+ * uses splitmix64(seed_b + 8 d + k) in a partial Fisher-Yates over [0, n). The loop is §4.10's with sample size 8. One workgroup
+ * per job, one launch per call; a job's result does not depend on its batch. max_iterations must lie in 1..100000 (a job makes at
+ * most 11 max_iterations + 1 draws). All arguments are checked on the host before any device work (covgpu_fivept_check is that check
+ * alone); it reads every bearing once, and a non-finite bearing refuses the whole batch. */
+typedef struct covgpu_fivept_batch_t {
+  int32_t num;              const int32_t* corr_ptr;     /* [num+1] */
+  const double* bearing1;   /* [C][3] */   const double* bearing2; /* [C][3] */
+  const uint64_t* seed;     /* [num] or NULL = opts seed + b */
+  double*  T_12;            /* [num][7] out, qx qy qz qw x y z; untouched unless status[b] == 0 */
+  uint8_t* inlier;          /* [C] out: all 0 unless status[b] == 0 */
+  int32_t* inliers;         /* [num] out: the best model's inlier count, whatever the status */
+  int32_t* status;          /* [num] out: COVGPU_FIVEPT_* */
+  int32_t* iterations;      /* [num] out or NULL */
+  int32_t* best_draw;       /* [num] out or NULL: draw index of the model (for parity tests) */
+} covgpu_fivept_batch_t;
+#define COVGPU_FIVEPT_FOUND 0
+#define COVGPU_FIVEPT_TOO_FEW 1        /* n < 8 */
+#define COVGPU_FIVEPT_NO_MODEL 2       /* every draw failed */
+#define COVGPU_FIVEPT_FEW_INLIERS 3    /* fewer than min_inliers */
+#define COVGPU_FIVEPT_MAX_ITERATIONS 4 /* iterations >= max_iterations (RelNonCentralPosSolver.cpp:368-369) */
+typedef struct { int32_t min_inliers; int32_t max_iterations; double probability; double threshold; double sigma; uint64_t seed; } covgpu_fivept_opts;
+void covgpu_default_fivept_opts(covgpu_fivept_opts*);   /* 20, 200, 0.99, 16.0, 4.5e-6, 0 (config_backend.yaml:100-102) */
+/* out[0] correspondences staged in LDS (longer jobs read global memory), out[1] hypotheses per pass, out[2] the sample size,
+ * out[3] the largest max_iterations */
+void covgpu_fivept_limits(int32_t out[4]);
+/* the argument check of covgpu_fivept_ransac_batch alone; needs no context and no device */
+int  covgpu_fivept_check(const covgpu_fivept_batch_t*, const covgpu_fivept_opts*);
+int  covgpu_fivept_ransac_batch(covgpu_context*, const covgpu_fivept_batch_t*, const covgpu_fivept_opts*);
+/* test entry point: the five-point problem of every 8-tuple on its slots 0..4: every real E (||E||_F = sqrt 2, the largest-magnitude
+ * entry positive, row-major, order unspecified; rows past nsol are zero), the pose that the 8 points pick (untouched if none) and the
+ * index of its E (-1: none) */
+int  covgpu_fivept_solve_batch(covgpu_context*, int32_t n, const double* f1 /*[n][8][3]*/, const double* f2 /*[n][8][3]*/,
+                               double* E /*[n][10][9]*/, int32_t* nsol /*[n]*/, double* T /*[n][7]*/, int32_t* chosen /*[n]*/);
+
+
 /* ---------------------------------------------------------------- loop-candidate descriptor matching
  * Brute-force Hamming matching of 32-byte ORB descriptors (distance = popcount of eight 32-bit XORs, feature_matcher_be.cpp:49-64),
  * job j matching the rows of set set_a[j] (query, "A") against those of set set_b[j] (candidate, "B"). Two modes:

@@ -224,9 +224,32 @@ inline uint64_t abspose_seed(const K* query, const K* cand) {
   return id(query) * 0x9E3779B97F4A7C15ull + id(cand);
 }
 
+// seed of cell `cell` of the five-point grid of a (query, candidate) keyframe pair: the pair's seed, moved by the cell
+template <class K>
+inline uint64_t fivept_seed(const K* kf1, const K* kf2, uint64_t cell) {
+  return abspose_seed(kf1, kf2) + cell * 0xD1B54A32D192ED03ull;
+}
+
 inline void fatal(const char* msg) {  // the reference prints COUTFATAL and exit(-1) (e.g. optimization_be.cpp:113-114)
   std::fprintf(stderr, "[covins_gpu] FATAL: %s\n", msg);
   std::exit(-1);
+}
+
+// unit bearing of additional feature i of a keyframe (COVINS-G: bearings_add_, frame-relative-adapter.cpp:27-38) through the optional
+// trait Types::bearing_add(keyframe, i, out3); without it kf.bearings_add_[i], read by [0..2]. Normalised here, as the adapter does.
+template <class Types, class K>
+inline auto bearing_add_raw(K& kf, size_t i, double* out, int) -> decltype(Types::bearing_add(kf, i, out), void()) { Types::bearing_add(kf, i, out); }
+template <class Types, class K>
+inline void bearing_add_raw(K& kf, size_t i, double* out, long) {
+  if (i >= kf.bearings_add_.size()) fatal("five-point: a match indexes past bearings_add_");
+  const auto& b = kf.bearings_add_[i];
+  out[0] = b[0]; out[1] = b[1]; out[2] = b[2];
+}
+template <class Types, class K>
+inline void bearing_add(K& kf, size_t i, double* out) {
+  bearing_add_raw<Types>(kf, i, out, 0);
+  const double n = std::sqrt(out[0] * out[0] + out[1] * out[1] + out[2] * out[2]);
+  out[0] /= n; out[1] /= n; out[2] /= n;
 }
 
 // float descriptor matrix of a keyframe (COVINS-G with feat.type SIFT: descriptors_add_ as `dim`-float rows) through the optional trait
@@ -1625,6 +1648,192 @@ class LoopMatcherT {
     return out;
   }
 };
+
+// ---- RelNonCentralPosSolver's five-point stage (RelNonCentralPosSolver.cpp:82-144, 343-377): the 2D-2D RANSAC between a query and
+//      a candidate keyframe, batched (covgpu_fivept_ransac_batch). computePose has the reference's signature and
+//      return value; ComputePoseBatch runs many of them in ONE library call per distinct threshold; ComputePoseGrid does what
+//      computeNonCentralRelPose does in front of its 17-point stage, for ALL candidates of a query: the two predecessor chains, ONE
+//      MatchImagePairsBatch, the mImgMatches test and ALL cells of ALL candidates in ONE covgpu_fivept_ransac_batch.
+template <class Types>
+class RelPoseSolverT {
+ public:
+  using Keyframe = typename Types::Keyframe;
+  using KeyframePtr = std::shared_ptr<Keyframe>;
+  using TransformType = typename Types::TransformType;
+  using Matcher = LoopMatcherT<Types>;
+  using Matches = typename Matcher::Matches;
+
+  // the reference's defaults (RelNonCentralPosSolver.hpp:47-48); min_img_matches is covins_params::placerec::rel_pose::min_img_matches
+  RelPoseSolverT(const size_t minInliers = 50, const double ransacProb = 0.99, const size_t maxIter = 300, const size_t minImgMatches = 0)
+      : mMinInliers(minInliers), mRansacProb(ransacProb), mMaxIter(maxIter), mImgMatches(minImgMatches) {}
+  void setRansacParams(const int minInliers, const double ransacProb, const int maxIter) {
+    mMinInliers = (size_t)minInliers; mRansacProb = ransacProb; mMaxIter = (size_t)maxIter;
+  }
+  void setMinImgMatches(size_t n) { mImgMatches = n; }
+  // what findMatches reads (RelNonCentralPosSolver.cpp:303-340): covins_params::features::type, img_match_thres, ratio_thres
+  void setMatchParams(const std::string& feature_type, float img_match_thres, float ratio_thres = 0.8f) {
+    mFeatureType = feature_type; mImgMatchThres = img_match_thres; mRatioThres = ratio_thres;
+  }
+
+  // one RANSAC: matches between kf1 (idxA) and kf2 (idxB). cell only moves the seed (0 for a call of its own).
+  struct PoseJob {
+    KeyframePtr kf1, kf2;
+    const Matches* matches = nullptr;
+    double threshold = 16.0;
+    uint64_t cell = 0;
+    TransformType* Tc1c2 = nullptr;          // written iff found (:373-374)
+    std::vector<int>* inlierInd = nullptr;   // the model's inliers, ascending (opengv's inliers_); empty unless found
+    bool found = false;                      // out: computePose's return value
+    int status = 0;                          // out: COVGPU_FIVEPT_*
+  };
+
+  void ComputePoseBatch(std::vector<PoseJob>& jobs) const {
+    std::vector<double> ths;
+    for (const PoseJob& j : jobs) if (std::find(ths.begin(), ths.end(), j.threshold) == ths.end()) ths.push_back(j.threshold);
+    for (double th : ths) run(jobs, th);
+  }
+
+  bool computePose(const KeyframePtr KfPtr1, const KeyframePtr KfPtr2, Matches& ImgMatches, const double threshold, TransformType& Tc1c2,
+                   std::vector<int>& inlierInd) const {
+    std::vector<PoseJob> jobs(1);
+    jobs[0].kf1 = KfPtr1; jobs[0].kf2 = KfPtr2; jobs[0].matches = &ImgMatches; jobs[0].threshold = threshold; jobs[0].Tc1c2 = &Tc1c2;
+    jobs[0].inlierInd = &inlierInd;
+    ComputePoseBatch(jobs);
+    return jobs[0].found;
+  }
+
+  // what FrameNoncentralRelativeAdapter is constructed from (:146-147), per candidate; ok = false is the reference's early `return false`
+  // (a cell with fewer than mImgMatches matches, a failed cell, or a predecessor chain that ends early) and leaves the rest unspecified.
+  struct GridResult {
+    bool ok = false;
+    std::vector<KeyframePtr> view_A, view_B;
+    std::vector<std::vector<Matches>> match_vect;                  // [n_qkfs][n_ckfs]
+    std::vector<std::vector<std::vector<int>>> inliers_vect;       // [n_qkfs][n_ckfs], indices ascending
+    std::vector<int> inliers_size;                                 // query-major
+    TransformType T_init;                                          // cell (0, 0)
+    std::vector<std::vector<TransformType>> TF_vect;               // [0]: T_QKF_cw * T_wc of its chain, [1]: the candidate's (:94, 113)
+  };
+
+  template <class Binding = Types>
+  std::vector<GridResult> ComputePoseGrid(const KeyframePtr& kf_query, const std::vector<KeyframePtr>& candidates, const double threshold,
+                                          size_t n_qkfs = 2, size_t n_ckfs = 3) const {
+    const std::string& feature_type = mFeatureType;
+    const float img_match_thres = mImgMatchThres, ratio_thres = mRatioThres;
+    const size_t NC = candidates.size(), cells = n_qkfs * n_ckfs;
+    std::vector<GridResult> out(NC);
+    std::vector<KeyframePtr> qs;
+    for (KeyframePtr k = kf_query; k && qs.size() < n_qkfs; k = k->GetPredecessor()) qs.push_back(k);
+    std::vector<std::pair<KeyframePtr, KeyframePtr>> pairs;
+    std::vector<size_t> first(NC, (size_t)-1);
+    for (size_t c = 0; c < NC; ++c) {
+      GridResult& g = out[c];
+      for (KeyframePtr k = candidates[c]; k && g.view_B.size() < n_ckfs; k = k->GetPredecessor()) g.view_B.push_back(k);
+      if (qs.size() < n_qkfs || g.view_B.size() < n_ckfs) continue;
+      g.view_A = qs;
+      first[c] = pairs.size();
+      for (const KeyframePtr& a : qs) for (const KeyframePtr& b : g.view_B) pairs.emplace_back(a, b);
+    }
+    std::vector<Matches> lists = Matcher::template MatchImagePairsBatch<Binding>(pairs, feature_type, img_match_thres, ratio_thres);
+    std::vector<PoseJob> jobs;
+    std::vector<TransformType> T(pairs.size());
+    std::vector<std::vector<int>> inl(pairs.size());
+    std::vector<size_t> job0(NC, (size_t)-1);
+    for (size_t c = 0; c < NC; ++c) {
+      if (first[c] == (size_t)-1) continue;
+      bool enough = true;
+      for (size_t q = 0; q < cells; ++q) enough = enough && lists[first[c] + q].size() >= mImgMatches;    // :119
+      if (!enough) continue;
+      job0[c] = jobs.size();
+      for (size_t q = 0; q < cells; ++q) {
+        PoseJob j;
+        j.kf1 = pairs[first[c] + q].first; j.kf2 = pairs[first[c] + q].second; j.matches = &lists[first[c] + q]; j.threshold = threshold;
+        j.cell = q; j.Tc1c2 = &T[first[c] + q]; j.inlierInd = &inl[first[c] + q];
+        jobs.push_back(j);
+      }
+    }
+    ComputePoseBatch(jobs);
+    for (size_t c = 0; c < NC; ++c) {
+      if (job0[c] == (size_t)-1) continue;
+      GridResult& g = out[c];
+      bool ok = true;
+      for (size_t q = 0; q < cells; ++q) ok = ok && jobs[job0[c] + q].found;                               // :137-139
+      if (!ok) continue;
+      g.ok = true;
+      g.match_vect.assign(n_qkfs, std::vector<Matches>(n_ckfs));
+      g.inliers_vect.assign(n_qkfs, std::vector<std::vector<int>>(n_ckfs));
+      for (size_t q = 0; q < cells; ++q) {
+        g.match_vect[q / n_ckfs][q % n_ckfs] = lists[first[c] + q];
+        g.inliers_vect[q / n_ckfs][q % n_ckfs] = inl[first[c] + q];
+        g.inliers_size.push_back((int)inl[first[c] + q].size());
+      }
+      g.T_init = T[first[c]];
+      g.TF_vect.assign(2, std::vector<TransformType>());
+      for (const KeyframePtr& k : g.view_A) g.TF_vect[0].push_back(mul4(kf_query->GetPoseTcw(), k->GetPoseTwc()));
+      for (const KeyframePtr& k : g.view_B) g.TF_vect[1].push_back(mul4(candidates[c]->GetPoseTcw(), k->GetPoseTwc()));
+    }
+    return out;
+  }
+
+ private:
+  size_t mMinInliers;
+  double mRansacProb;   // stored, not used: see Params::ransac_probability (the reference never passes it to opengv either)
+  size_t mMaxIter, mImgMatches;
+  std::string mFeatureType = "ORB";
+  float mImgMatchThres = 40.0f, mRatioThres = 0.8f;
+
+  static TransformType mul4(TransformType A, TransformType B) {
+    TransformType Cm = A;
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) {
+        double s = 0.0;
+        for (int k = 0; k < 4; ++k) s += A(r, k) * B(k, c);
+        Cm(r, c) = s;
+      }
+    return Cm;
+  }
+
+  void run(std::vector<PoseJob>& jobs, double th) const {
+    std::vector<size_t> sel;
+    for (size_t b = 0; b < jobs.size(); ++b) if (jobs[b].threshold == th) sel.push_back(b);
+    const size_t B = sel.size();
+    if (B == 0) return;
+    std::vector<int32_t> ptr(1, 0);
+    std::vector<double> f1, f2, T(7 * B, 0.0);
+    std::vector<uint64_t> seed(B);
+    for (size_t s = 0; s < B; ++s) {
+      PoseJob& j = jobs[sel[s]];
+      for (const auto& m : *j.matches) {                             // frame-relative-adapter.cpp:27-38
+        double a[3], b[3];
+        detail::bearing_add<Types>(*j.kf1, m.idxA, a);
+        detail::bearing_add<Types>(*j.kf2, m.idxB, b);
+        f1.insert(f1.end(), a, a + 3); f2.insert(f2.end(), b, b + 3);
+      }
+      ptr.push_back((int32_t)(f1.size() / 3));
+      seed[s] = detail::fivept_seed(j.kf1.get(), j.kf2.get(), j.cell);
+    }
+    std::vector<uint8_t> mask(f1.size() / 3 + 1);
+    std::vector<int32_t> inl(B), st(B);
+    f1.reserve(1); f2.reserve(1);
+    covgpu_fivept_batch_t bt{};
+    bt.num = (int32_t)B; bt.corr_ptr = ptr.data(); bt.bearing1 = f1.data(); bt.bearing2 = f2.data(); bt.seed = seed.data();
+    bt.T_12 = T.data(); bt.inlier = mask.data(); bt.inliers = inl.data(); bt.status = st.data();
+    covgpu_fivept_opts o;
+    covgpu_default_fivept_opts(&o);
+    o.min_inliers = (int32_t)mMinInliers; o.max_iterations = (int32_t)mMaxIter; o.threshold = th;
+    o.probability = OptimizationT<Types>::params().ransac_probability;
+    if (covgpu_fivept_ransac_batch(OptimizationT<Types>::Context(), &bt, &o) != COVGPU_OK) detail::fatal(covgpu_last_error());
+    for (size_t s = 0; s < B; ++s) {
+      PoseJob& j = jobs[sel[s]];
+      j.status = st[s]; j.found = st[s] == COVGPU_FIVEPT_FOUND;
+      if (j.inlierInd) {
+        j.inlierInd->clear();
+        for (int32_t c = ptr[s]; c < ptr[s + 1]; ++c) if (mask[c]) j.inlierInd->push_back(c - ptr[s]);
+      }
+      if (j.found && j.Tc1c2) detail::pose_to_transform(&T[7 * s], *j.Tc1c2);
+    }
+  }
+};
+
 
 // ---- KeyframeDatabase with the reference's method names, the query batched on the GPU (covgpu_detect_candidates_batch, DESIGN.md
 // §4.13), plus the bag-of-words transform of arriving keyframes (keyframe_be.cpp:159-183) and the covisibility-consistency groups of
