@@ -205,6 +205,53 @@ def _fivept_args(bt: dict, opts: dict):
     return s, o, keep
 
 
+def ncrelpose_limits():
+    """Host-only: {stage_cap, hypotheses, sample, max_iterations, max_cells, max_cov_iters, max_rows, polish_steps} of
+    Context.ncrelpose_batch as the library was built (covgpu_ncrelpose_limits)."""
+    out = (C.c_int32 * 8)()
+    lib().covgpu_ncrelpose_limits(out)
+    return dict(zip(("stage_cap", "hypotheses", "sample", "max_iterations", "max_cells", "max_cov_iters", "max_rows", "polish_steps"), (int(v) for v in out)))
+
+
+def _ncrelpose_args(bt: dict, opts: dict):
+    """The structures of a 17-point call and the arrays they point into (kept alive by the caller)."""
+    o = capi.NcrelposeOpts()
+    lib().covgpu_default_ncrelpose_opts(C.byref(o))
+    _set_opts(o, [name for name, _ in capi.NcrelposeOpts._fields_], opts, "17-point")
+    ptr = _opt(_i32, bt.get("ptr"))
+    B = len(ptr) - 1 if ptr is not None else int(bt.get("num", 0))
+    Cn = int(ptr[-1]) if ptr is not None and len(ptr) else 0
+    cell = _opt(_i32, bt.get("cell_ptr"))
+    cells = int(bt["cells"]) if "cells" in bt else (cell.reshape(max(B, 1), -1).shape[1] - 1 if cell is not None and B > 0 else 0)
+    f1 = _opt(lambda a: _f64(a).reshape(-1, 3), bt.get("bearing1"))
+    f2 = _opt(lambda a: _f64(a).reshape(-1, 3), bt.get("bearing2"))
+    c1, c2, cp = (_opt(_i32, bt.get(k)) for k in ("cam1", "cam2", "cam_ptr"))
+    cam = _opt(lambda a: _f64(a).reshape(-1, 12), bt.get("cam"))
+    Tq = _opt(lambda a: _f64(a).reshape(-1, 7), bt.get("T_sc_q"))
+    Tc = _opt(lambda a: _f64(a).reshape(-1, 7), bt.get("T_sc_c"))
+    seed = _opt(lambda a: np.ascontiguousarray(a, dtype=np.uint64), bt.get("seed"))
+    fill = float(bt.get("fill", 0.0))                        # what untouched outputs hold
+    T, Tr, Ts = (np.full((max(B, 1), 7), fill) for _ in range(3))
+    cov = np.full((max(B, 1), 36), fill)
+    mask = np.zeros(max(Cn, 1), np.uint8)
+    inl, st, its, bd, cr, cd = (np.zeros(max(B, 1), np.int32) for _ in range(6))
+    keep = dict(ptr=ptr, cell=cell, f1=f1, f2=f2, c1=c1, c2=c2, cp=cp, cam=cam, Tq=Tq, Tc=Tc, seed=seed, T=T, Tr=Tr, Ts=Ts, cov=cov, mask=mask,
+                inl=inl, st=st, its=its, bd=bd, cr=cr, cd=cd, B=B, C=max(Cn, 0))
+    s = capi.NcrelposeBatch(B, cells, _opt(iptr, ptr), _opt(iptr, cell), _opt(dptr, f1), _opt(dptr, f2), _opt(iptr, c1), _opt(iptr, c2), _opt(iptr, cp),
+                            _opt(dptr, cam), _opt(dptr, Tq), _opt(dptr, Tc), None if seed is None else seed.ctypes.data_as(C.POINTER(C.c_uint64)),
+                            dptr(T), dptr(Tr), dptr(Ts), dptr(cov), _bp(mask), iptr(inl), iptr(st), iptr(its), iptr(bd), iptr(cr), iptr(cd))
+    return s, o, keep
+
+
+def ncrelpose_check(bt: dict, **opts):
+    """Host-only: the argument check of Context.ncrelpose_batch alone (covgpu_ncrelpose_check); raises CovGpuError with the message of
+    the first violation. A key of `bt` that is absent is passed as a NULL array."""
+    s, o, _keep = _ncrelpose_args(bt, opts)
+    rc = lib().covgpu_ncrelpose_check(C.byref(s), C.byref(o))
+    if rc != 0:
+        raise CovGpuError(f"covgpu error {rc}: {lib().covgpu_last_error().decode()}")
+
+
 def fivept_check(bt: dict, **opts):
     """Host-only: the argument check of Context.fivept_ransac_batch alone (covgpu_fivept_check); raises CovGpuError with the message
     of the first violation. A key of `bt` that is absent is passed as a NULL array."""
@@ -621,6 +668,30 @@ class Context:
         ns = np.zeros(max(n, 1), np.int32); ch = np.zeros(max(n, 1), np.int32)
         self._check(lib().covgpu_fivept_solve_batch(self._h, n, dptr(f1), dptr(f2), dptr(E), iptr(ns), dptr(T), iptr(ch)))
         return dict(E=E[:n], nsol=ns[:n], T=T[:n], chosen=ch[:n])
+
+    def ncrelpose_batch(self, bt: dict, **opts):
+        """Batched 17-point stage of COVINS-G's loop verification with the polish and the sampled loop covariance
+        (covgpu_ncrelpose_batch). `bt`: dict with ptr [num+1], cell_ptr [num,cells+1] (relative to the job), bearing1,
+        bearing2 [C,3], cam1, cam2 [C] (into the job's cameras), cam_ptr [num+1], cam [M,12] (R_c row-major | o_c), T_sc_q, T_sc_c [num,7],
+        optionally seed [num] (uint64; absent = opts seed + b) and fill (what untouched outputs hold, default 0). `opts`: rp_error,
+        rp_error_cov, min_inliers, max_iterations, cov_thres, cov_iters, cov_max_iters, probability, seed, stage_cap (defaults:
+        covgpu_default_ncrelpose_opts). Returns dict(T_c1c2, T_c1c2_ransac, T_s1s2 [num,7], cov [num,6,6], inlier [C] bool, inliers,
+        status, iterations, best_draw, cov_rows, cov_draws [num])."""
+        s, o, k = _ncrelpose_args(bt, opts)
+        self._check(lib().covgpu_ncrelpose_batch(self._h, C.byref(s), C.byref(o)))
+        B = max(k["B"], 0)
+        return dict(T_c1c2=k["T"][:B], T_c1c2_ransac=k["Tr"][:B], T_s1s2=k["Ts"][:B], cov=k["cov"][:B].reshape(-1, 6, 6),
+                    inlier=k["mask"][:k["C"]].astype(bool), inliers=k["inl"][:B], status=k["st"][:B], iterations=k["its"][:B],
+                    best_draw=k["bd"][:B], cov_rows=k["cr"][:B], cov_draws=k["cd"][:B])
+
+    def ncrelpose_solve_batch(self, ray1, ray2):
+        """Test entry point (covgpu_ncrelpose_solve_batch): the 17-point linear solve alone on the tuples ray1, ray2 [n,N,6] (g | o),
+        N = 17..64. Returns dict(T [n,7] (zero where not ok), ok [n], sv [n,3] (sigma_1, sigma_17, sigma_18))."""
+        ray1 = _f64(ray1); ray2 = _f64(ray2)
+        n, N = ray1.shape[0], ray1.shape[1]
+        T = np.zeros((max(n, 1), 7)); ok = np.zeros(max(n, 1), np.int32); sv = np.zeros((max(n, 1), 3))
+        self._check(lib().covgpu_ncrelpose_solve_batch(self._h, n, N, dptr(ray1), dptr(ray2), dptr(T), iptr(ok), dptr(sv)))
+        return dict(T=T[:n], ok=ok[:n], sv=sv[:n])
 
     def match_batch(self, sets: dict, set_a, set_b, mode: str = "dense", **opts):
         """Batched ORB descriptor matching of loop candidates (covgpu_match_batch). `sets`: dict with row_ptr

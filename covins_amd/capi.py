@@ -227,6 +227,19 @@ class FiveptBatch(C.Structure):
                 ("T_12", _dp), ("inlier", _bp), ("inliers", _ip), ("status", _ip), ("iterations", _ip), ("best_draw", _ip)]
 
 
+class NcrelposeBatch(C.Structure):
+    _fields_ = [("num", C.c_int32), ("cells", C.c_int32), ("corr_ptr", _ip), ("cell_ptr", _ip), ("bearing1", _dp), ("bearing2", _dp),
+                ("cam1", _ip), ("cam2", _ip), ("cam_ptr", _ip), ("cam", _dp), ("T_sc_q", _dp), ("T_sc_c", _dp), ("seed", C.POINTER(C.c_uint64)),
+                ("T_c1c2", _dp), ("T_c1c2_ransac", _dp), ("T_s1s2", _dp), ("cov", _dp), ("inlier", _bp), ("inliers", _ip), ("status", _ip),
+                ("iterations", _ip), ("best_draw", _ip), ("cov_rows", _ip), ("cov_draws", _ip)]
+
+
+class NcrelposeOpts(C.Structure):
+    _fields_ = [("rp_error", C.c_double), ("rp_error_cov", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32),
+                ("cov_thres", C.c_double), ("cov_iters", C.c_int32), ("cov_max_iters", C.c_int32), ("probability", C.c_double),
+                ("seed", C.c_uint64), ("stage_cap", C.c_int32)]
+
+
 class FiveptOpts(C.Structure):
     _fields_ = [("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("probability", C.c_double), ("threshold", C.c_double),
                 ("sigma", C.c_double), ("seed", C.c_uint64)]
@@ -450,6 +463,11 @@ def declare(lib: C.CDLL, prefix: str) -> None:
         d("fivept_check", [C.POINTER(FiveptBatch), C.POINTER(FiveptOpts)])
         d("fivept_ransac_batch", [C.c_void_p, C.POINTER(FiveptBatch), C.POINTER(FiveptOpts)])
         d("fivept_solve_batch", [C.c_void_p, C.c_int32, _dp, _dp, _dp, _ip, _dp, _ip])
+        d("default_ncrelpose_opts", [C.POINTER(NcrelposeOpts)], None)
+        d("ncrelpose_limits", [_ip], None)
+        d("ncrelpose_check", [C.POINTER(NcrelposeBatch), C.POINTER(NcrelposeOpts)])
+        d("ncrelpose_batch", [C.c_void_p, C.POINTER(NcrelposeBatch), C.POINTER(NcrelposeOpts)])
+        d("ncrelpose_solve_batch", [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, _ip, _dp])
         d("default_match_opts", [C.POINTER(MatchOpts), C.c_int32], None)
         d("match_batch", [C.c_void_p, C.POINTER(MatchBatch), C.POINTER(MatchOpts)])
         d("default_match_float_opts", [C.POINTER(MatchOpts)], None)

@@ -569,6 +569,62 @@ int  covgpu_fivept_solve_batch(covgpu_context*, int32_t n, const double* f1 /*[n
                                double* E /*[n][10][9]*/, int32_t* nsol /*[n]*/, double* T /*[n][7]*/, int32_t* chosen /*[n]*/);
 
 
+/* ---------------------------------------------------------------- COVINS-G 17-point stage and loop covariance
+ * Batched back half of RelNonCentralPosSolver::computeNonCentralRelPose (RelNonCentralPosSolver.cpp:149-301): per job b the
+ * non-central 17-point RANSAC over the correspondences [corr_ptr[b], corr_ptr[b+1]) of all cells, the non-linear polish of its
+ * model on its inliers, and the sampled 6x6 covariance of the loop edge in the IMU frames. Correspondence i has unit bearings f1_i,
+ * f2_i and cameras cam1_i, cam2_i, indices into the job's camera table [cam_ptr[b], cam_ptr[b+1]) of (R_c row-major [9], o_c [3]),
+ * the camera in its viewpoint (viewpoint 1 the query keyframe, 2 the candidate): ray direction g = R_c f, origin o_c. The cells of
+ * a job are the ranges [cell_ptr[b][j], cell_ptr[b][j+1]) relative to the job, cell_ptr[b][0] = 0, cell_ptr[b][cells] = n_b.
+ * Model T_12 = [R | t], x1 = R x2 + t, metric t. Draw d, slot k of the RANSAC uses splitmix64(seed_b + 17 d + k) in a partial
+ * Fisher-Yates over [0, n); covariance draw e, cell j, slot k uses splitmix64(seed_b' + (e cells + j) 4 + k) over the cell's
+ * ascending inlier list, seed_b' = splitmix64(seed_b ^ 0x17C0F17C0F17C0F1). T_s1s2 = T_sc_q T_c1c2 T_sc_c^-1. One workgroup per
+ * job, one launch per call; a job's result does not depend on its batch. Outputs up to the failing stage are written, later ones
+ * are untouched. All arguments are checked on the host before any device work (covgpu_ncrelpose_check is that check alone). */
+typedef struct covgpu_ncrelpose_batch_t {
+  int32_t num;              int32_t cells;               /* cells per job, 1..16 (the reference has 6, query-major) */
+  const int32_t* corr_ptr;  /* [num+1] */  const int32_t* cell_ptr; /* [num][cells+1] */
+  const double* bearing1;   /* [C][3] */   const double* bearing2; /* [C][3] */
+  const int32_t* cam1;      /* [C] */      const int32_t* cam2;    /* [C] */
+  const int32_t* cam_ptr;   /* [num+1] */  const double* cam;      /* [M][12] */
+  const double* T_sc_q;     /* [num][7] qx qy qz qw x y z */       const double* T_sc_c; /* [num][7] */
+  const uint64_t* seed;     /* [num] or NULL = opts seed + b */
+  double*  T_c1c2;          /* [num][7] out: the polished pose; written from status 4 on and at 0 */
+  double*  T_c1c2_ransac;   /* [num][7] out: the RANSAC model; written unless status is 1 or 2 */
+  double*  T_s1s2;          /* [num][7] out: with T_c1c2 */
+  double*  cov;             /* [num][36] out, rotation first; written at status 0 and 6 */
+  uint8_t* inlier;          /* [C] out: the RANSAC model's inliers (all 0 at status 1 and 2) */
+  int32_t* inliers;         /* [num] out */
+  int32_t* status;          /* [num] out: COVGPU_NCRELPOSE_* */
+  int32_t* iterations;      /* [num] out */
+  int32_t* best_draw;       /* [num] out: draw index of the model, -1: none */
+  int32_t* cov_rows;        /* [num] out: accepted covariance draws */
+  int32_t* cov_draws;       /* [num] out: covariance draws made */
+} covgpu_ncrelpose_batch_t;
+#define COVGPU_NCRELPOSE_FOUND 0
+#define COVGPU_NCRELPOSE_TOO_FEW 1        /* n < 17 */
+#define COVGPU_NCRELPOSE_NO_MODEL 2       /* every draw failed */
+#define COVGPU_NCRELPOSE_FEW_INLIERS 3    /* fewer than min_inliers (:165) */
+#define COVGPU_NCRELPOSE_THIN_CELL 4      /* a cell with fewer than 8 inliers (:222-227) */
+#define COVGPU_NCRELPOSE_COV_INCOMPLETE 5 /* the draws ran out before cov_iters rows existed */
+#define COVGPU_NCRELPOSE_COV_TRACE 6      /* trace(cov) >= cov_thres (:294) */
+typedef struct {
+  double rp_error; double rp_error_cov; int32_t min_inliers; int32_t max_iterations; double cov_thres; int32_t cov_iters; int32_t cov_max_iters;
+  double probability; uint64_t seed;
+  int32_t stage_cap;        /* 0: the library's LDS staging cap; > 0: the smaller of the two (tests force the global-memory path) */
+} covgpu_ncrelpose_opts;
+void covgpu_default_ncrelpose_opts(covgpu_ncrelpose_opts*);   /* 1.5, 10, 100, 4000, 10, 30, 300, 0.99, 0, 0 (config_backend.yaml:91-97) */
+/* out[0] correspondences staged in LDS, out[1] draws per pass, out[2] the sample size, out[3] the largest max_iterations, out[4] the
+ * most cells, out[5] the largest cov_iters, out[6] the most rows of a linear solve, out[7] the step cap of the polish */
+void covgpu_ncrelpose_limits(int32_t out[8]);
+int  covgpu_ncrelpose_check(const covgpu_ncrelpose_batch_t*, const covgpu_ncrelpose_opts*);
+int  covgpu_ncrelpose_batch(covgpu_context*, const covgpu_ncrelpose_batch_t*, const covgpu_ncrelpose_opts*);
+/* test entry point: the linear solve alone on n tuples of N (17..64) ray pairs, ray = (g [3], o [3]): the pose (untouched where ok is
+ * 0), whether the solve succeeded, and sigma_1, sigma_17, sigma_18 of the N x 18 system */
+int  covgpu_ncrelpose_solve_batch(covgpu_context*, int32_t n, int32_t N, const double* ray1 /*[n][N][6]*/, const double* ray2 /*[n][N][6]*/,
+                                  double* T /*[n][7]*/, int32_t* ok /*[n]*/, double* sv /*[n][3]*/);
+
+
 /* ---------------------------------------------------------------- loop-candidate descriptor matching
  * Brute-force Hamming matching of 32-byte ORB descriptors (distance = popcount of eight 32-bit XORs, feature_matcher_be.cpp:49-64),
  * job j matching the rows of set set_a[j] (query, "A") against those of set set_b[j] (candidate, "B"). Two modes:

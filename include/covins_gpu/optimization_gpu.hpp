@@ -230,6 +230,12 @@ inline uint64_t fivept_seed(const K* kf1, const K* kf2, uint64_t cell) {
   return abspose_seed(kf1, kf2) + cell * 0xD1B54A32D192ED03ull;
 }
 
+// seed of the 17-point job of a (query, candidate) keyframe pair: the pair's seed, moved off every cell of its five-point grid
+template <class K>
+inline uint64_t ncrelpose_seed(const K* kf_query, const K* kf_cand) {
+  return abspose_seed(kf_query, kf_cand) ^ 0x17D1B54A32D192EDull;
+}
+
 inline void fatal(const char* msg) {  // the reference prints COUTFATAL and exit(-1) (e.g. optimization_be.cpp:113-114)
   std::fprintf(stderr, "[covins_gpu] FATAL: %s\n", msg);
   std::exit(-1);
@@ -1774,7 +1780,104 @@ class RelPoseSolverT {
     return out;
   }
 
+  // ---- the 17-point stage and the loop covariance (RelNonCentralPosSolver.cpp:149-301, covgpu_ncrelpose_batch)
+  struct NonCentralParams {               // covins_params::placerec::nc_rel_pose (config_backend.yaml:91-97)
+    double rp_error = 1.5, rp_error_cov = 10.0;
+    int min_inliers = 100, max_iters = 4000;
+    double cov_thres = 10.0;
+    int cov_iters = 30, cov_max_iters = 300;
+  };
+  void setNonCentralParams(const NonCentralParams& p) { mNc = p; }
+
+  struct NonCentralResult {
+    bool found = false;                   // computeNonCentralRelPose's return value
+    int status = -1;                      // COVGPU_NCRELPOSE_*, -1: the five-point grid ended early (GridResult::ok false)
+    int inliers = 0;
+    TransformType Tc1c2, Ts1s2;           // the polished pose and the loop edge's measurement; written from status 4 on and at 0
+    double cov_loop[36];                  // row-major, rotation first: LoopConstraint::cov_mat; the identity unless status is 0 or 6 (:73)
+  };
+
+  // computeNonCentralRelPose for ALL candidates of a query: ComputePoseGrid, then every GridResult with ok in ONE library call
+  template <class Binding = Types>
+  std::vector<NonCentralResult> ComputeNonCentralRelPoseBatch(const KeyframePtr& kf_query, const std::vector<KeyframePtr>& candidates,
+                                                              const double threshold, size_t n_qkfs = 2, size_t n_ckfs = 3) const {
+    const std::vector<GridResult> grid = ComputePoseGrid<Binding>(kf_query, candidates, threshold, n_qkfs, n_ckfs);
+    const size_t NC = candidates.size(), cells = n_qkfs * n_ckfs;
+    std::vector<NonCentralResult> out(NC);
+    for (NonCentralResult& r : out)
+      for (int i = 0; i < 36; ++i) r.cov_loop[i] = i % 7 == 0 ? 1.0 : 0.0;
+    std::vector<size_t> sel;
+    for (size_t c = 0; c < NC; ++c) if (grid[c].ok) sel.push_back(c);
+    const size_t B = sel.size();
+    if (B == 0) return out;
+    std::vector<int32_t> ptr(1, 0), cell, cam1, cam2, cam_ptr(1, 0);
+    std::vector<double> f1, f2, cam, Tq(7 * B), Tc(7 * B);
+    std::vector<uint64_t> seed(B);
+    for (size_t s = 0; s < B; ++s) {
+      const GridResult& g = grid[sel[s]];
+      const int32_t o0 = ptr.back();
+      for (size_t i = 0; i < n_qkfs; ++i)                              // FrameNoncentralRelativeAdapter.cpp:83-105
+        for (size_t j = 0; j < n_ckfs; ++j) {
+          cell.push_back((int32_t)(f1.size() / 3) - o0);
+          for (int k : g.inliers_vect[i][j]) {
+            double a[3], b[3];
+            detail::bearing_add<Types>(*g.view_A[i], g.match_vect[i][j][(size_t)k].idxA, a);
+            detail::bearing_add<Types>(*g.view_B[j], g.match_vect[i][j][(size_t)k].idxB, b);
+            f1.insert(f1.end(), a, a + 3); f2.insert(f2.end(), b, b + 3);
+            cam1.push_back((int32_t)i); cam2.push_back((int32_t)(n_qkfs + j));
+          }
+        }
+      cell.push_back((int32_t)(f1.size() / 3) - o0);
+      ptr.push_back((int32_t)(f1.size() / 3));
+      for (int side = 0; side < 2; ++side)                             // :111-118: first the query side's cameras, then the candidate's
+        for (const TransformType& T : g.TF_vect[side]) {
+          for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) cam.push_back(T(r, c));
+          for (int r = 0; r < 3; ++r) cam.push_back(T(r, 3));
+        }
+      cam_ptr.push_back((int32_t)(cam.size() / 12));
+      detail::transform_to_pose(kf_query->GetStateExtrinsics(), &Tq[7 * s]);
+      detail::transform_to_pose(candidates[sel[s]]->GetStateExtrinsics(), &Tc[7 * s]);
+      seed[s] = detail::ncrelpose_seed(kf_query.get(), candidates[sel[s]].get());
+    }
+    std::vector<double> T(7 * B, 0.0), Tr(7 * B, 0.0), Ts(7 * B, 0.0), cov(36 * B, 0.0);
+    std::vector<uint8_t> mask(f1.size() / 3 + 1);
+    std::vector<int32_t> inl(B), st(B), it(B), bd(B), cr(B), cd(B);
+    f1.reserve(1); f2.reserve(1); cam1.reserve(1); cam2.reserve(1); cam.reserve(1);
+    covgpu_ncrelpose_batch_t bt{};
+    bt.num = (int32_t)B; bt.cells = (int32_t)cells; bt.corr_ptr = ptr.data(); bt.cell_ptr = cell.data(); bt.bearing1 = f1.data(); bt.bearing2 = f2.data();
+    bt.cam1 = cam1.data(); bt.cam2 = cam2.data(); bt.cam_ptr = cam_ptr.data(); bt.cam = cam.data(); bt.T_sc_q = Tq.data(); bt.T_sc_c = Tc.data();
+    bt.seed = seed.data(); bt.T_c1c2 = T.data(); bt.T_c1c2_ransac = Tr.data(); bt.T_s1s2 = Ts.data(); bt.cov = cov.data(); bt.inlier = mask.data();
+    bt.inliers = inl.data(); bt.status = st.data(); bt.iterations = it.data(); bt.best_draw = bd.data(); bt.cov_rows = cr.data(); bt.cov_draws = cd.data();
+    covgpu_ncrelpose_opts o;
+    covgpu_default_ncrelpose_opts(&o);
+    o.rp_error = mNc.rp_error; o.rp_error_cov = mNc.rp_error_cov; o.min_inliers = mNc.min_inliers; o.max_iterations = mNc.max_iters;
+    o.cov_thres = mNc.cov_thres; o.cov_iters = mNc.cov_iters; o.cov_max_iters = mNc.cov_max_iters;
+    o.probability = OptimizationT<Types>::params().ransac_probability;
+    if (covgpu_ncrelpose_batch(OptimizationT<Types>::Context(), &bt, &o) != COVGPU_OK) detail::fatal(covgpu_last_error());
+    for (size_t s = 0; s < B; ++s) {
+      NonCentralResult& r = out[sel[s]];
+      r.status = st[s]; r.found = st[s] == COVGPU_NCRELPOSE_FOUND; r.inliers = inl[s];
+      if (st[s] == COVGPU_NCRELPOSE_FOUND || st[s] >= COVGPU_NCRELPOSE_THIN_CELL) {
+        detail::pose_to_transform(&T[7 * s], r.Tc1c2);
+        detail::pose_to_transform(&Ts[7 * s], r.Ts1s2);
+      }
+      if (st[s] == COVGPU_NCRELPOSE_FOUND || st[s] == COVGPU_NCRELPOSE_COV_TRACE)
+        for (int i = 0; i < 36; ++i) r.cov_loop[i] = cov[36 * s + i];
+    }
+    return out;
+  }
+
+  // the reference's signature and return value; cov_loop is anything indexed (r, c) (an Eigen::Matrix<double, 6, 6>)
+  template <class Cov, class Binding = Types>
+  bool computeNonCentralRelPose(const KeyframePtr QKF, const KeyframePtr CKF, const double threshold, TransformType& Tc1c2, Cov& cov_loop) const {
+    const std::vector<NonCentralResult> r = ComputeNonCentralRelPoseBatch<Binding>(QKF, std::vector<KeyframePtr>(1, CKF), threshold);
+    for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) cov_loop(i, j) = r[0].cov_loop[6 * i + j];
+    if (r[0].status == COVGPU_NCRELPOSE_FOUND || r[0].status >= COVGPU_NCRELPOSE_THIN_CELL) Tc1c2 = r[0].Tc1c2;
+    return r[0].found;
+  }
+
  private:
+  NonCentralParams mNc;
   size_t mMinInliers;
   double mRansacProb;   // stored, not used: see Params::ransac_probability (the reference never passes it to opengv either)
   size_t mMaxIter, mImgMatches;
